@@ -77,7 +77,13 @@ def parse_args(argv=None):
                         help="frames/s instead of rays/s: every rank optimises its shard of synthetic frames in the reference's native mode; "
                              "every other argument goes to vsrd_amd.launcher.main (--gpus, --frames, --frames-in-flight, --num-steps, --views, "
                              "... -- see python -m vsrd_amd.launcher -h)")
-    return parser.parse_args(argv)
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last timed step computed -- the loss, every parameter's gradient and every "
+                             "parameter after the Adam update -- as DIR/<name>.npy (rank 0's frame), for output-for-output comparisons of two builds")
+    args = parser.parse_args(argv)
+    if args.dump_outputs and args.launcher_selftest:
+        parser.error("--dump-outputs needs the render step: --launcher-selftest computes nothing")
+    return args
 
 
 def schedule_values(fraction):
@@ -387,6 +393,7 @@ def run_rank(args):
         # one frame per rank, and every rank a replica of the same synthetic frame (the scaling curve then isolates the
         # launcher; frames of a real shard differ in cost, which is load imbalance, not scaling); the Philox streams differ by rank
         frame = synthetic_frame(seed=0, num_views=V, height=H, width=W, num_instances=N)
+        torch.manual_seed(rank)                 # BoxParameters3D draws its embeddings at construction: the same inputs on every run
         K, E, raw_loc, raw_dim, raw_ori = frame
         # ---- resident inputs (untimed) -------------------------------------------------------------------------------
         cam, dirs = rendering.ray_casting((H, W), K.to(dev), E.to(dev))                 # [V,3], [V,H,W,3]
@@ -404,12 +411,14 @@ def run_rank(args):
             targets = rendering.render_hierarchical(build_union(perturbed, 0.1), origins, directions, (0.0, 100.0), S, 0.1, 1.0,
                                                     seed=99, skip_exact_misses=True)["labels"].clamp(0.0, 1.0).contiguous()
         params = [detector.locations, detector.dimensions, detector.orientations]
+        named_params = [("locations", detector.locations), ("dimensions", detector.dimensions), ("orientations", detector.orientations)]
         hyper = None
         hyper_state = None
         if args.residual:
             torch.manual_seed(rank)
             hyper = models.HyperDistanceField(48, [16, 16, 16, 16], 256, [256, 256, 256, 256]).to(dev)
             params += [detector.embeddings, *hyper.parameters()]
+            named_params += [("embeddings", detector.embeddings), *(("hyper." + name, p) for name, p in hyper.named_parameters())]
             hyper_state = dict(hyper={k: v.detach().cpu().clone() for k, v in hyper.state_dict().items()},
                                embeddings=detector.embeddings.detach().cpu().clone())
         optimizer = torch.optim.Adam(params, lr=1e-2)
@@ -455,6 +464,8 @@ def run_rank(args):
             fence()
             elapsed = time.perf_counter() - t0
         kernels = timer.summary()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, loss, named_params)
     per_rank_ms = [own / args.steps * 1e3]
     ranks_through = 1
     if distributed:
@@ -506,6 +517,28 @@ def run_rank(args):
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, loss, named_params):
+    """What the last timed step handed its caller, as float32 .npy files (float64 where the step computed in float64): `loss` (the step's scalar), `<parameter>.grad` (its gradient)
+    and `<parameter>` (the value after the optimiser's update).  Written after the timed region, so the timing does not see it."""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss.detach()}
+    for name, param in named_params:
+        if param.grad is not None:
+            arrays[name + ".grad"] = param.grad.detach()
+        arrays[name] = param.detach()
+    arrays = {name: (t if t.dtype == torch.float64 else t.float()).cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(directory, exist_ok=True)
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
 
 
 def step_kernel_symbols(args, fused):

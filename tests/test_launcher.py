@@ -22,7 +22,7 @@ def _worker(rank, world, port, tmp):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from vsrd_amd import launcher
     r, w, device = launcher.init_process_group(backend="gloo")
-    assert (r, w) == (rank, world) and device.type == "cpu"
+    assert (r, w) == (rank, world) and device.type == ("cuda" if torch.cuda.is_available() else "cpu")     # the rank's GPU where there is one
     manifest = launcher.broadcast_manifest({"frames": list(range(11)), "seed": 3} if rank == 0 else None)
     assert manifest == {"frames": list(range(11)), "seed": 3}
     mine = launcher.shard_frames(manifest["frames"], rank, world, seed=manifest["seed"])
@@ -181,6 +181,43 @@ def test_bench_two_ranks_with_the_real_step_on_one_gpu():
     assert abs(line["value"] - 2 * rays / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]     # whole-job rays/s = both ranks' rays / slowest time
     assert line["ms_per_step"] >= max(line["per_rank_ms_per_step"]) - 0.05
     assert line["config"]["rays_per_gpu"] == rays and math.isfinite(line["config"]["final_loss"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("residual", [False, True], ids=["box", "residual"])
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path, residual):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed -- the loss, every parameter's gradient and every parameter after
+    the update -- as float32 .npy files: the dumped loss is the line's final_loss, the step count is --steps, and a second run with the same
+    arguments starts from the same inputs (seeded frame, targets, parameters and Philox streams), so its outputs agree with the first run's."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    bench = os.path.join(ROOT, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    sizes = ["--views", "2", "--height", "94", "--width", "352", "--instances", "4", "--samples", "32"] + (["--residual"] if residual else [])
+    runs = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, bench, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *sizes, "--dump-outputs", str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=900, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0.0
+        arrays = {f[:-len(".npy")]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        expected = {"loss"} | {p + suffix for p in ("locations", "dimensions", "orientations") for suffix in ("", ".grad")}
+        assert expected <= set(arrays) and (residual == ("embeddings.grad" in arrays))
+        assert arrays["locations"].shape == (1, 4, 3) and arrays["orientations.grad"].shape == (1, 4, 2)
+        assert float(arrays["loss"]) == line["config"]["final_loss"]
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        runs.append(arrays)
+    first, second = runs
+    assert set(first) == set(second)
+    for key in first:
+        scale = max(float(np.abs(first[key]).max()), 1e-6)
+        assert np.abs(first[key] - second[key]).max() <= 1e-3 * scale, key
 
 
 @pytest.mark.gpu

@@ -162,7 +162,14 @@ def _check_render_case(name, tol_labels, tol_grad):
     moved = (moved[:, :-1] | moved[:, 1:]).unsqueeze(-1).expand_as(got_g)                                # (gradients live at the midpoints)
     error = (got_g - want_g).abs().detach()
     tight = error <= 1e-4 + 1e-3 * want_g.abs()
-    assert bool(tight[~moved].all()), (int((~tight & ~moved).sum()), float(error[~moved].max()))          # every sample that stayed: tight
+    # (a sample that stayed may still sit an ulp or two from the golden's -- the sampler's last bit differs between CPUs -- and next to an
+    #  edge of a box the field gradient changes that fast: such a sample passes when the field, evaluated at the golden's own positions, is tight)
+    nudged = got_d != want_d
+    nudged = (nudged[:, :-1] | nudged[:, 1:]).unsqueeze(-1).expand_as(got_g)
+    at_golden = rendering.render_given_distances(union, g["origins"], g["directions"], g["fine_distances"].t(), std, ratio).gradients[~miss]
+    tight_at_golden = (at_golden - want_g).abs().detach() <= 1e-4 + 1e-3 * want_g.abs()
+    stayed_tight = tight | (nudged & tight_at_golden)
+    assert bool(stayed_tight[~moved].all()), (int((~stayed_tight & ~moved).sum()), float(error[~moved].max()))   # every sample that stayed: tight
     assert moved.float().mean() <= 5e-2 and (~tight).float().mean() <= 1e-3 and float(error.max()) < 5e-3, \
         (float(moved.float().mean()), int((~tight).sum()), float(error.max()))
     # losses and parameter gradients

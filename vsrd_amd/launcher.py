@@ -36,7 +36,12 @@ def init_process_group(backend=None, ranks_per_device=1):
 
 def barrier():
     if dist.is_available() and dist.is_initialized():
-        dist.barrier()
+        if dist.get_backend() == "gloo":
+            # (dist.barrier() asks the HIP runtime for devices before it settles on gloo's host barrier: on a GPU node that opens the
+            #  device in every rank, the GPU-free selftest ranks included.  A one-element host all_reduce is the same barrier without it.)
+            dist.all_reduce(torch.zeros(1))
+        else:
+            dist.barrier()
 
 
 def ordered(action: Callable[[int], None]):
