@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define VSRD_ABI_VERSION 8
+#define VSRD_ABI_VERSION 9
 
 #define VSRD_OK 0
 #define VSRD_E_INVALID_ARGUMENT (-1) /* null pointer, non-positive size, unsupported N / S */
@@ -58,7 +58,27 @@ extern "C" {
  * The fields sit at the end of vsrd_render_config, vsrd_frame_config and vsrd_hypernetwork.  Entry points that accept B >= 2:
  * vsrd_frame_prologue, vsrd_frame_prologue_sample, vsrd_frame_epilogue, vsrd_hypernetwork_forward, vsrd_hypernetwork_backward_step,
  * vsrd_render_silhouette_step (gathered launches in the split-ray form: at most 2048 rays per frame) and vsrd_render_residual_step
- * (two-kernel form, one chunk of rays per frame); every other entry point returns VSRD_E_UNSUPPORTED for B >= 2. */
+ * (two-kernel form, one chunk of rays per frame); every other entry point returns VSRD_E_UNSUPPORTED for B >= 2.
+ *
+ * Mixed batches (ABI 9): frames whose instance counts differ.  The batch keeps ONE layout for all of its rows, sized for a CAPACITY
+ * N_cap, and every frame carries its own count 1 <= n_f <= N_cap in a vsrd_frame_header in device memory.  The entry points that take
+ * a header are the *_with_header twins below; frame_header addresses frame 0's header and frame f's lies f * frame_stride bytes behind
+ * it, like every other buffer of the call (a header for one frame is accepted too).  With a header set:
+ *   - the by-value N (vsrd_field::num_instances, vsrd_frame_config::num_boxes) is the capacity: the stride of every per-instance array
+ *     ([N,16] instances, [V,N,4] ground-truth boxes, [V,N] visibility, rows of targets with target_stride = N, ...);
+ *   - each kernel reads the frame's count once, as a wave-uniform scalar, clamps it to [1, N] and loops, matches, reduces and
+ *     normalises over that count only; instances n_f .. N_cap - 1 of a row are never read and never written;
+ *   - loss_scale (the silhouette normaliser 1 / (R n_f)) is the header's, not the by-value argument.
+ * Frame f then computes, bit for bit, what the same call computes on a frame of its own with N = n_f.  The old entry points are the
+ * twins with frame_header = NULL: every frame has the by-value N, the by-value loss_scale applies.  A header on a launch form that does
+ * not batch (the dense multi-ray kernels of vsrd_render_silhouette_step) is answered with VSRD_E_UNSUPPORTED, as B >= 2 is.
+ * Twins: vsrd_frame_prologue, vsrd_frame_prologue_sample, vsrd_frame_epilogue, vsrd_render_silhouette_step (split-ray form),
+ * vsrd_render_residual_step (two-kernel form with the ray split over a pair of waves, both MLP product forms), vsrd_hypernetwork_forward,
+ * vsrd_hypernetwork_backward_step (N = vsrd_hypernetwork::num_instances is the capacity: the stride of the embeddings and the workspace). */
+typedef struct vsrd_frame_header {
+    int32_t num_instances;      /* n_f, 1..N_cap (clamped)                                                      */
+    float loss_scale;           /* the silhouette loss normaliser of the frame: 1 / (R * n_f) as float32        */
+} vsrd_frame_header;
 
 /* Field = temperature soft-min union of N oriented boxes (+ optional residual MLP).
  * Replaces the closure tree scripts/main.py:525-618 builds from
@@ -219,6 +239,16 @@ int32_t vsrd_render_residual_step(const vsrd_field* field, const vsrd_render_con
                                   float* losses /* [2] */, float* grad_instances, float* grad_mlp_weights, float* labels /* [R,N] or NULL */,
                                   void* stream);
 
+/* vsrd_render_residual_step with a per-frame header (mixed batches, "frame batches" above): the two-kernel form whose front kernel splits
+ * a ray over a pair of waves (launches of <= 2048 rays per frame, or S > 64), one chunk of rays, no sample outputs; VSRD_E_UNSUPPORTED
+ * otherwise.  The MLP adjoint's work items of instances >= n_f find no seeds and do nothing; its item geometry depends on the capacity only. */
+int32_t vsrd_render_residual_step_with_header(const vsrd_field* field, const vsrd_render_config* config,
+                                              const float* origins, const float* directions, const float* u_coarse, const float* u_fine,
+                                              const float* targets, const float* instance_weights, float loss_scale,
+                                              float eikonal_ratio, void* workspace, size_t workspace_bytes,
+                                              float* losses, float* grad_instances, float* grad_mlp_weights, float* labels,
+                                              const vsrd_frame_header* frame_header, void* stream);
+
 /* Hungarian matching of predicted to ground-truth 2-D boxes of the target view (scripts/main.py:374-386:
  * scipy.optimize.linear_sum_assignment(-torchvision.ops.distance_box_iou(pd, gt).cpu())), on the device -- no host
  * synchronisation, capturable in a hipGraph.  pd_boxes [P,4], gt_boxes [G,4] (x1,y1,x2,y2), 1 <= P,G <= 64.
@@ -358,6 +388,13 @@ int32_t vsrd_render_silhouette_step(const vsrd_field* field, const vsrd_render_c
                                     void* workspace, size_t workspace_bytes,
                                     float* loss, float* grad_instances, float* labels, void* stream);
 
+/* vsrd_render_silhouette_step with a per-frame header (mixed batches, "frame batches" above): the split-ray form only. */
+int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const vsrd_render_config* config,
+                                                const float* origins, const float* directions, const float* u_coarse, const float* u_fine,
+                                                const float* targets, const float* instance_weights, float loss_scale,
+                                                void* workspace, size_t workspace_bytes,
+                                                float* loss, float* grad_instances, float* labels, const vsrd_frame_header* frame_header, void* stream);
+
 /* Multi-view projection of N boxes (8 corners each, world frame) into V cameras and reduction to clipped 2-D boxes:
  * scripts/main.py:339-362 = einsum with E + divide by w, vsrd.operations.project_box_3d / clip_lines_to_front
  * (geometric_operations.py:343-389) per box, torchvision.ops.clip_boxes_to_image.  One launch for all V*N boxes.
@@ -423,6 +460,21 @@ int32_t vsrd_frame_prologue_sample(const vsrd_frame_config* config, const float*
                                    float* schedule, float* projection_losses, float* grad_raw,
                                    void* ray_table, int64_t count, int32_t num_rays, uint64_t seed, const int64_t* remap, int64_t* ray_indices, void* stream);
 
+/* The two prologues with a per-frame header (mixed batches, "frame batches" above): num_boxes is the capacity, the stride of gt_boxes
+ * [V,N,4] and visible [V,N]; decode, projection, the matching (an n_f x n_f problem) and the projection losses cover the frame's n_f boxes. */
+int32_t vsrd_frame_prologue_with_header(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions,
+                                        const float* raw_orientations, const float* extrinsics, const float* intrinsics, const float* gt_boxes,
+                                        const uint8_t* visible, const int64_t* step, void* scratch, size_t scratch_bytes,
+                                        float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
+                                        float* schedule, float* projection_losses, float* grad_raw, const vsrd_frame_header* frame_header, void* stream);
+int32_t vsrd_frame_prologue_sample_with_header(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions,
+                                               const float* raw_orientations, const float* extrinsics, const float* intrinsics, const float* gt_boxes,
+                                               const uint8_t* visible, const int64_t* step, void* scratch, size_t scratch_bytes,
+                                               float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
+                                               float* schedule, float* projection_losses, float* grad_raw,
+                                               void* ray_table, int64_t count, int32_t num_rays, uint64_t seed, const int64_t* remap, int64_t* ray_indices,
+                                               const vsrd_frame_header* frame_header, void* stream);
+
 /* torch.optim.Adam(capturable=True) state of one parameter tensor: all device memory, updated in place. */
 typedef struct vsrd_adam_tensors {
     float* parameter;
@@ -442,6 +494,13 @@ int32_t vsrd_frame_epilogue(const vsrd_frame_config* config, const float* grad_i
                             const vsrd_adam_tensors* locations, const vsrd_adam_tensors* dimensions, const vsrd_adam_tensors* orientations,
                             float* other_learning_rate_0, float* other_learning_rate_1, int64_t* step,
                             float* record, float* raw_gradients, void* stream);
+
+/* vsrd_frame_epilogue with a per-frame header (mixed batches, "frame batches" above): Adam on the frame's n_f boxes. */
+int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const float* grad_instances, const float* grad_raw_projection,
+                                        const float* projection_losses, const float* render_losses, float eikonal_ratio,
+                                        const vsrd_adam_tensors* locations, const vsrd_adam_tensors* dimensions, const vsrd_adam_tensors* orientations,
+                                        float* other_learning_rate_0, float* other_learning_rate_1, int64_t* step,
+                                        float* record, float* raw_gradients, const vsrd_frame_header* frame_header, void* stream);
 
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]
@@ -477,6 +536,13 @@ int32_t vsrd_hypernetwork_forward(const vsrd_hypernetwork* net, void* workspace,
  * every tensor of `net` (in place, torch's update), step counters + 1, both learning rates * lr_gamma.  Deterministic. */
 int32_t vsrd_hypernetwork_backward_step(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
                                         const float* grad_mlp_weights, float grad_scale, void* stream);
+
+/* The two with a per-frame header (mixed batches, "frame batches" above): the forward, the weight gradients (summed over the frame's
+ * n_f instances in the order of the one-frame call) and Adam on the frame's n_f embedding rows. */
+int32_t vsrd_hypernetwork_forward_with_header(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
+                                              float* mlp_weights, float* centred, const vsrd_frame_header* frame_header, void* stream);
+int32_t vsrd_hypernetwork_backward_step_with_header(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
+                                                    const float* grad_mlp_weights, float grad_scale, const vsrd_frame_header* frame_header, void* stream);
 
 /* The centred copy of per-instance MLP weights [N,1617] that VSRD_FLAG_MLP_WEIGHTS_CENTRED announces: in the four linears that feed a
  * LayerNorm (hyper_distance_field.py:57-73) every column, bias column included, has its mean over the 16 output channels removed.

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VSRD_HIP_LIBRARY: an experiment build of the same ABI (tools/phase_timers.py, A/B macros); the product path is the in-tree default
 LIBRARY_PATH = os.environ.get("VSRD_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libvsrd_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_INSTANCES = 64
 MAX_SAMPLES = 256
 INSTANCE_STRIDE = 16
@@ -134,6 +134,14 @@ class Hypernetwork(ctypes.Structure):
 
 
 # symbol -> (restype, argtypes); mirrors include/vsrd_hip.h one to one
+class FrameHeader(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_frame_header (ABI 9, mixed batches): one frame's own instance count and silhouette normaliser."""
+    _fields_ = [
+        ("num_instances", ctypes.c_int32),
+        ("loss_scale", ctypes.c_float),
+    ]
+
+
 SIGNATURES = {
     "vsrd_abi_version": (ctypes.c_int32, []),
     "vsrd_error_string": (ctypes.c_char_p, [ctypes.c_int32]),
@@ -190,6 +198,29 @@ SIGNATURES = {
     "vsrd_frame_epilogue": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float,
                                              ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors),
                                              c_float_p, c_float_p, ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_void_p]),
+    # ABI 9: the twins of the batched entry points with a per-frame header (the header pointer before the stream)
+    "vsrd_frame_prologue_with_header": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p]),
+    "vsrd_frame_prologue_sample_with_header": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                                                c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "vsrd_frame_epilogue_with_header": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float,
+                                                         ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors),
+                                                         c_float_p, c_float_p, ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "vsrd_render_silhouette_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
+                                                                 c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
+                                                                 c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "vsrd_render_residual_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
+                                                               c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
+                                                               ctypes.c_size_t, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "vsrd_hypernetwork_forward_with_header": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "vsrd_hypernetwork_backward_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p,
+                                                                     ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
     "vsrd_hypernetwork_forward": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_backward_step": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_float,

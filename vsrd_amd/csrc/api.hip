@@ -638,6 +638,15 @@ int32_t vsrd_render_silhouette_step(const vsrd_field* field, const vsrd_render_c
                                     const float* targets, const float* instance_weights, float loss_scale,
                                     void* workspace, size_t workspace_bytes,
                                     float* loss, float* grad_instances, float* labels, void* stream) {
+    return vsrd_render_silhouette_step_with_header(field, config, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, workspace,
+                                                   workspace_bytes, loss, grad_instances, labels, nullptr, stream);
+}
+
+int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const vsrd_render_config* config,
+                                                const float* origins, const float* directions, const float* u_coarse, const float* u_fine,
+                                                const float* targets, const float* instance_weights, float loss_scale,
+                                                void* workspace, size_t workspace_bytes,
+                                                float* loss, float* grad_instances, float* labels, const vsrd_frame_header* frame_header, void* stream) {
     if (!valid_field(field) || !valid_config(config, true, true) || !workspace || !loss || !grad_instances) return VSRD_E_INVALID_ARGUMENT;
     if (field->mlp_weights != nullptr) return VSRD_E_UNSUPPORTED;            // box-only fast path
     const int N = field->num_instances;
@@ -646,7 +655,8 @@ int32_t vsrd_render_silhouette_step(const vsrd_field* field, const vsrd_render_c
     const int row = N * kGradStride;
     Frames frames;
     frames_of(config->num_frames, config->frame_stride, &frames);           // (validated by valid_config)
-    if (frames.count > 1 && (config->num_rays == 0 || wants_samples(config))) return VSRD_E_UNSUPPORTED;
+    if ((frames.count > 1 || frame_header) && (config->num_rays == 0 || wants_samples(config))) return VSRD_E_UNSUPPORTED;
+    const FrameHeader* header = reinterpret_cast<const FrameHeader*>(frame_header);
     if (config->num_rays == 0) {
         if (hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) return VSRD_E_LAUNCH;
         return hipMemsetAsync(grad_instances, 0, row * sizeof(float), s) == hipSuccess ? VSRD_OK : VSRD_E_LAUNCH;
@@ -684,17 +694,17 @@ int32_t vsrd_render_silhouette_step(const vsrd_field* field, const vsrd_render_c
         do {                                                                                                                      \
             if (opt_in_lds(render_silhouette_split_kernel<K, FRAMES>, lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH;               \
             hipLaunchKernelGGL((render_silhouette_split_kernel<K, FRAMES>), dim3(blocks, frames.count), dim3(kPairWaves * kWave), lds_bytes, s, f, field->instances, c, \
-                               origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials, loss_partials); \
+                               origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials, loss_partials, header); \
         } while (0)
-        if (frames.count > 1) { if (rounds == 2) VSRD_LAUNCH_SPLIT(2, true); else VSRD_LAUNCH_SPLIT(4, true); }
+        if (frames.count > 1 || header) { if (rounds == 2) VSRD_LAUNCH_SPLIT(2, true); else VSRD_LAUNCH_SPLIT(4, true); }
         else if (rounds == 2) VSRD_LAUNCH_SPLIT(2, false); else VSRD_LAUNCH_SPLIT(4, false);
 #undef VSRD_LAUNCH_SPLIT
         if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
         hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 1, frames.count), dim3(256), 0, s, partials, num_waves, row, grad_instances, nullptr, loss_partials, 1, loss,
-                           frames.stride);
+                           frames.stride, header);
         return launch_status();
     }
-    if (frames.count > 1) return VSRD_E_UNSUPPORTED;     // a batch of frames runs in the split-ray form only (gathered launches of at most 2048 rays per frame)
+    if (frames.count > 1 || header) return VSRD_E_UNSUPPORTED;     // a batch of frames runs in the split-ray form only (gathered launches of at most 2048 rays per frame)
     const int lanes = quad ? kRowLanes : 32, rays_per_wave = kWave / lanes;
     // a launch that fills its shape (S = lanes x rounds of the shape, more than half of its instance slots: BASELINE configs 2 and 5)
     // runs the hot kernel instantiated for that S with the instance tables padded to the shape's count (quad_step.h: kFull)
@@ -1014,6 +1024,16 @@ int32_t vsrd_render_residual_step(const vsrd_field* field, const vsrd_render_con
                                   const float* targets, const float* instance_weights, float loss_scale, float eikonal_ratio,
                                   void* workspace, size_t workspace_bytes,
                                   float* losses, float* grad_instances, float* grad_mlp_weights, float* labels, void* stream) {
+    return vsrd_render_residual_step_with_header(field, config, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, eikonal_ratio,
+                                                 workspace, workspace_bytes, losses, grad_instances, grad_mlp_weights, labels, nullptr, stream);
+}
+
+int32_t vsrd_render_residual_step_with_header(const vsrd_field* field, const vsrd_render_config* config,
+                                              const float* origins, const float* directions, const float* u_coarse, const float* u_fine,
+                                              const float* targets, const float* instance_weights, float loss_scale, float eikonal_ratio,
+                                              void* workspace, size_t workspace_bytes,
+                                              float* losses, float* grad_instances, float* grad_mlp_weights, float* labels,
+                                              const vsrd_frame_header* frame_header, void* stream) {
     if (!valid_field(field) || !valid_config(config, true, true) || !workspace || !losses || !grad_instances || !grad_mlp_weights) return VSRD_E_INVALID_ARGUMENT;
     if (field->mlp_weights == nullptr) return VSRD_E_INVALID_ARGUMENT;       // box-only fields: vsrd_render_silhouette_step
     const int N = field->num_instances, S = config->num_samples;
@@ -1028,6 +1048,9 @@ int32_t vsrd_render_residual_step(const vsrd_field* field, const vsrd_render_con
                             !plan_residual_step(N, S, config->num_rays, allow_pair, &p, config->adjoint_slots_per_item);
     // a batch of frames: the two-kernel form with every frame's rays in ONE chunk (each frame its own seeds, item counter and rows, frame_stride apart)
     if (frames.count > 1 && (one_kernel || p.chunk < config->num_rays || static_cast<long long>(p.total_bytes) > frames.stride)) return VSRD_E_UNSUPPORTED;
+    // a per-frame header (mixed batches): the forms that batch -- two kernels, the ray split over a pair of waves, one chunk, no sample outputs
+    const FrameHeader* header = reinterpret_cast<const FrameHeader*>(frame_header);
+    if (header && (one_kernel || !p.pair || p.chunk < config->num_rays || wants_samples(config))) return VSRD_E_UNSUPPORTED;
     if (one_kernel && wants_samples(config)) return VSRD_E_UNSUPPORTED;
     if (one_kernel)
         return residual_step_single_kernel(field, config, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, eikonal_ratio,
@@ -1061,7 +1084,7 @@ int32_t vsrd_render_residual_step(const vsrd_field* field, const vsrd_render_con
     const float* front_weights = field->mlp_weights;
     if (split) {
         unsigned* images = reinterpret_cast<unsigned*>(base + p.images);
-        if (vsrd_split_front::pack_images(field->mlp_weights, N, (config->flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? 1 : 0, images, frames.count, frames.stride, s) != vsrd_split_front::kOk)
+        if (vsrd_split_front::pack_images(field->mlp_weights, N, (config->flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? 1 : 0, images, frames.count, frames.stride, header, s) != vsrd_split_front::kOk)
             return VSRD_E_LAUNCH;
         front_weights = reinterpret_cast<const float*>(images);
     }
@@ -1079,17 +1102,19 @@ int32_t vsrd_render_residual_step(const vsrd_field* field, const vsrd_render_con
         if (wants_samples(config)) return VSRD_E_UNSUPPORTED; /* (the samples are written by the two-round instantiation below) */                      \
         hipLaunchKernelGGL(residual_step_front_kernel<K>, dim3(p.front_blocks), dim3(kBlockThreads), p.front_lds, s, VSRD_FRONT_ARGS)
 #define VSRD_LAUNCH_PAIR(K)                                                                                                              \
-        if (frames.count > 1) {                                                                                                          \
+        if (frames.count > 1 || header) {                                                                                                \
             if (opt_in_lds(residual_step_pair_kernel<K, true>, p.front_lds) != VSRD_OK) return VSRD_E_LAUNCH;                            \
-            hipLaunchKernelGGL((residual_step_pair_kernel<K, true>), dim3(p.front_blocks, frames.count), dim3(kPairWaves * kWave), p.front_lds, s, VSRD_FRONT_ARGS); \
+            hipLaunchKernelGGL((residual_step_pair_kernel<K, true>), dim3(p.front_blocks, frames.count), dim3(kPairWaves * kWave), p.front_lds, s, VSRD_FRONT_ARGS, \
+                               header);                                                                                                  \
         } else {                                                                                                                         \
             if (opt_in_lds(residual_step_pair_kernel<K>, p.front_lds) != VSRD_OK) return VSRD_E_LAUNCH;                                  \
-            hipLaunchKernelGGL(residual_step_pair_kernel<K>, dim3(p.front_blocks), dim3(kPairWaves * kWave), p.front_lds, s, VSRD_FRONT_ARGS); \
+            hipLaunchKernelGGL(residual_step_pair_kernel<K>, dim3(p.front_blocks), dim3(kPairWaves * kWave), p.front_lds, s, VSRD_FRONT_ARGS, nullptr); \
         }
         if (split) {
             vsrd_split_front::FrontLaunch launch = {&f, sizeof f, &c, sizeof c, field->instances, front_weights, origins, directions, u_coarse, u_fine, targets, instance_weights,
                                                     loss_scale, eikonal_scale, eikonal_norm, labels, box_partials, jets, loss_partials, seeds, masks, p.slots_per_instance,
-                                                    first, rays, chunk_index > 0 ? 1 : 0, p.pair, p.rounds, p.front_blocks, p.front_lds, wants_samples(config), frames.count};
+                                                    first, rays, chunk_index > 0 ? 1 : 0, p.pair, p.rounds, p.front_blocks, p.front_lds, wants_samples(config), frames.count,
+                                                    frame_header};
             const int code = vsrd_split_front::launch_front(launch, s);
             if (code != vsrd_split_front::kOk) return code == vsrd_split_front::kUnsupported ? VSRD_E_UNSUPPORTED : VSRD_E_LAUNCH;
         } else if (p.pair) {
@@ -1122,14 +1147,14 @@ int32_t vsrd_render_residual_step(const vsrd_field* field, const vsrd_render_con
                                counter, item_rows, item_flags, frames.stride);
         }
         hipLaunchKernelGGL(reduce_item_rows_kernel, dim3(N, (kItemRowFloats + 255) / 256, kItemSegments * frames.count), dim3(256), 0, s, item_rows, item_flags,
-                           p.items_per_instance, segment_sums, frames.stride);
+                           p.items_per_instance, segment_sums, frames.stride, header);
         hipLaunchKernelGGL(reduce_item_segments_kernel, dim3(N, (kItemRowFloats + 255) / 256, frames.count), dim3(256), 0, s, segment_sums, grad_mlp_weights, box_extra,
-                           chunk_index > 0 ? 1 : 0, frames.stride);
+                           chunk_index > 0 ? 1 : 0, frames.stride, header);
         if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
     }
     (void)mlp_row;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 2, frames.count), dim3(256), 0, s, box_partials, p.front_waves, row, grad_instances, box_extra, loss_partials, 2, losses,
-                       frames.stride);
+                       frames.stride, header);
     return launch_status();
 }
 
@@ -1154,6 +1179,7 @@ static bool frame_args(const vsrd_frame_config* c, FrameStepArgs* a) {
     Frames frames;
     if (!frames_of(c->num_frames, c->frame_stride, &frames)) return false;
     a->frame_stride = frames.stride;
+    a->header = nullptr;
     return true;
 }
 }  // namespace
@@ -1163,8 +1189,19 @@ int32_t vsrd_frame_prologue(const vsrd_frame_config* config, const float* raw_lo
                             const uint8_t* visible, const int64_t* step, void* scratch, size_t scratch_bytes,
                             float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
                             float* schedule, float* projection_losses, float* grad_raw, void* stream) {
+    return vsrd_frame_prologue_with_header(config, raw_locations, raw_dimensions, raw_orientations, extrinsics, intrinsics, gt_boxes, visible, step, scratch,
+                                           scratch_bytes, instances, pd_indices, gt_indices, target_columns, instance_weights, schedule, projection_losses,
+                                           grad_raw, nullptr, stream);
+}
+
+int32_t vsrd_frame_prologue_with_header(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions,
+                                        const float* raw_orientations, const float* extrinsics, const float* intrinsics, const float* gt_boxes,
+                                        const uint8_t* visible, const int64_t* step, void* scratch, size_t scratch_bytes,
+                                        float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
+                                        float* schedule, float* projection_losses, float* grad_raw, const vsrd_frame_header* frame_header, void* stream) {
     FrameStepArgs a;
     if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
+    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible || !step || !instances ||
         !pd_indices || !gt_indices || !target_columns || !instance_weights || !schedule || !projection_losses || !grad_raw)
         return VSRD_E_INVALID_ARGUMENT;
@@ -1187,8 +1224,21 @@ int32_t vsrd_frame_prologue_sample(const vsrd_frame_config* config, const float*
                                    float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
                                    float* schedule, float* projection_losses, float* grad_raw,
                                    void* ray_table, int64_t count, int32_t num_rays, uint64_t seed, const int64_t* remap, int64_t* ray_indices, void* stream) {
+    return vsrd_frame_prologue_sample_with_header(config, raw_locations, raw_dimensions, raw_orientations, extrinsics, intrinsics, gt_boxes, visible, step,
+                                                  scratch, scratch_bytes, instances, pd_indices, gt_indices, target_columns, instance_weights, schedule,
+                                                  projection_losses, grad_raw, ray_table, count, num_rays, seed, remap, ray_indices, nullptr, stream);
+}
+
+int32_t vsrd_frame_prologue_sample_with_header(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions,
+                                               const float* raw_orientations, const float* extrinsics, const float* intrinsics, const float* gt_boxes,
+                                               const uint8_t* visible, const int64_t* step, void* scratch, size_t scratch_bytes,
+                                               float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
+                                               float* schedule, float* projection_losses, float* grad_raw,
+                                               void* ray_table, int64_t count, int32_t num_rays, uint64_t seed, const int64_t* remap, int64_t* ray_indices,
+                                               const vsrd_frame_header* frame_header, void* stream) {
     FrameStepArgs a;
     if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
+    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible || !step || !instances ||
         !pd_indices || !gt_indices || !target_columns || !instance_weights || !schedule || !projection_losses || !grad_raw)
         return VSRD_E_INVALID_ARGUMENT;
@@ -1216,8 +1266,18 @@ int32_t vsrd_frame_epilogue(const vsrd_frame_config* config, const float* grad_i
                             const vsrd_adam_tensors* locations, const vsrd_adam_tensors* dimensions, const vsrd_adam_tensors* orientations,
                             float* other_learning_rate_0, float* other_learning_rate_1, int64_t* step,
                             float* record, float* raw_gradients, void* stream) {
+    return vsrd_frame_epilogue_with_header(config, grad_instances, grad_raw_projection, projection_losses, render_losses, eikonal_ratio, locations, dimensions,
+                                           orientations, other_learning_rate_0, other_learning_rate_1, step, record, raw_gradients, nullptr, stream);
+}
+
+int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const float* grad_instances, const float* grad_raw_projection,
+                                        const float* projection_losses, const float* render_losses, float eikonal_ratio,
+                                        const vsrd_adam_tensors* locations, const vsrd_adam_tensors* dimensions, const vsrd_adam_tensors* orientations,
+                                        float* other_learning_rate_0, float* other_learning_rate_1, int64_t* step,
+                                        float* record, float* raw_gradients, const vsrd_frame_header* frame_header, void* stream) {
     FrameStepArgs a;
     if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
+    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     if (!grad_instances || !grad_raw_projection || !projection_losses || !render_losses || !locations || !dimensions || !orientations || !step || !record)
         return VSRD_E_INVALID_ARGUMENT;
     const vsrd_adam_tensors* groups[3] = {locations, dimensions, orientations};
@@ -1278,7 +1338,13 @@ size_t vsrd_hypernetwork_workspace_bytes(int32_t num_instances) {
 
 int32_t vsrd_hypernetwork_forward(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
                                   float* mlp_weights, float* centred, void* stream) {
+    return vsrd_hypernetwork_forward_with_header(net, workspace, workspace_bytes, mlp_weights, centred, nullptr, stream);
+}
+
+int32_t vsrd_hypernetwork_forward_with_header(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
+                                              float* mlp_weights, float* centred, const vsrd_frame_header* frame_header, void* stream) {
     if (!valid_hypernetwork(net) || !mlp_weights) return VSRD_E_INVALID_ARGUMENT;
+    const FrameHeader* header = reinterpret_cast<const FrameHeader*>(frame_header);
     Frames frames;
     if (!frames_of(net->num_frames, net->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
     const int N = net->num_instances;
@@ -1297,24 +1363,30 @@ int32_t vsrd_hypernetwork_forward(const vsrd_hypernetwork* net, void* workspace,
         hidden.inv_norm[l] = ws + p.inv_norm + l * kHyperWidth;
         if (l + 1 < kLast) { hidden.gamma[l] = net->norm_weight[l].parameter; hidden.beta[l] = net->norm_bias[l].parameter; }
     }
-    hipLaunchKernelGGL(hyper_hidden_forward_kernel, dim3(N, frames.count), dim3(kHyperChainThreads), 0, s, net->embeddings.parameter, hidden, frames.stride);
+    hipLaunchKernelGGL(hyper_hidden_forward_kernel, dim3(N, frames.count), dim3(kHyperChainThreads), 0, s, net->embeddings.parameter, hidden, frames.stride, header);
     hipLaunchKernelGGL(hyper_linear_forward_kernel, dim3((kMlpWeights + kHyperWaves - 1) / kHyperWaves, frames.count), dim3(kHyperThreads), lds, s,
                        ws + p.activations + (kLast - 1) * slab, net->norm_weight[kLast - 1].parameter, net->norm_bias[kLast - 1].parameter,
                        net->weight_v[kLast].parameter, net->weight_g[kLast].parameter, net->bias[kLast].parameter, kMlpWeights, N, mlp_weights,
-                       ws + p.inv_norm + kLast * kHyperWidth, frames.stride);
-    if (centred) hipLaunchKernelGGL(hyper_centre_kernel, dim3(N, frames.count), dim3(128), 0, s, mlp_weights, N, centred, frames.stride);
+                       ws + p.inv_norm + kLast * kHyperWidth, frames.stride, header);
+    if (centred) hipLaunchKernelGGL(hyper_centre_kernel, dim3(N, frames.count), dim3(128), 0, s, mlp_weights, N, centred, frames.stride, header);
     return launch_status();
 }
 
 int32_t vsrd_centre_mlp_weights(const float* mlp_weights, int32_t num_instances, float* centred, void* stream) {
     if (!mlp_weights || !centred || num_instances < 1 || num_instances > VSRD_MAX_INSTANCES) return VSRD_E_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(hyper_centre_kernel, dim3(num_instances), dim3(128), 0, static_cast<hipStream_t>(stream), mlp_weights, num_instances, centred);
+    hipLaunchKernelGGL(hyper_centre_kernel, dim3(num_instances), dim3(128), 0, static_cast<hipStream_t>(stream), mlp_weights, num_instances, centred, 0ll, nullptr);
     return launch_status();
 }
 
 int32_t vsrd_hypernetwork_backward_step(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
                                         const float* grad_mlp_weights, float grad_scale, void* stream) {
+    return vsrd_hypernetwork_backward_step_with_header(net, workspace, workspace_bytes, grad_mlp_weights, grad_scale, nullptr, stream);
+}
+
+int32_t vsrd_hypernetwork_backward_step_with_header(const vsrd_hypernetwork* net, void* workspace, size_t workspace_bytes,
+                                                    const float* grad_mlp_weights, float grad_scale, const vsrd_frame_header* frame_header, void* stream) {
     if (!valid_hypernetwork(net) || !grad_mlp_weights) return VSRD_E_INVALID_ARGUMENT;
+    const FrameHeader* header = reinterpret_cast<const FrameHeader*>(frame_header);
     Frames frames;
     if (!frames_of(net->num_frames, net->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
     const int N = net->num_instances;
@@ -1334,9 +1406,9 @@ int32_t vsrd_hypernetwork_backward_step(const vsrd_hypernetwork* net, void* work
     const int final_blocks = (kMlpWeights + kHyperWaves - 1) / kHyperWaves;
     hipLaunchKernelGGL(hyper_linear_backward_kernel, dim3(final_blocks, frames.count), dim3(kHyperThreads), lds, s, z(kLast - 1), net->norm_weight[kLast - 1].parameter,
                        net->norm_bias[kLast - 1].parameter, grad_mlp_weights, grad_scale, inv_norm(kLast), kMlpWeights, N, adam_tensors(net->weight_v[kLast]),
-                       adam_tensors(net->weight_g[kLast]), adam_tensors(net->bias[kLast]), adam, ws + p.partials, frames.stride);
+                       adam_tensors(net->weight_g[kLast]), adam_tensors(net->bias[kLast]), adam, ws + p.partials, frames.stride, header);
     hipLaunchKernelGGL(hyper_norm_backward_kernel, dim3(N, frames.count), dim3(kHyperNormThreads * kHyperNormSplit), 0, s, ws + p.partials, final_blocks, z(kLast - 1), N,
-                       net->norm_weight[kLast - 1].parameter, net->norm_bias[kLast - 1].parameter, gz(kLast - 1), norm_shares(kLast - 1), frames.stride);
+                       net->norm_weight[kLast - 1].parameter, net->norm_bias[kLast - 1].parameter, gz(kLast - 1), norm_shares(kLast - 1), frames.stride, header);
     // the chain through the hidden blocks (one workgroup per instance), then every hidden linear's own update
     HyperHiddenBackward chain;
     HyperHiddenUpdate update;
@@ -1363,10 +1435,10 @@ int32_t vsrd_hypernetwork_backward_step(const vsrd_hypernetwork* net, void* work
         update.v[l] = adam_tensors(net->weight_v[l]); update.g[l] = adam_tensors(net->weight_g[l]); update.b[l] = adam_tensors(net->bias[l]);
     }
     chain.embedding_bar = gz(kLast);
-    hipLaunchKernelGGL(hyper_hidden_backward_kernel, dim3(N, frames.count), dim3(kHyperChainThreads), 0, s, chain, frames.stride);
-    hipLaunchKernelGGL(hyper_hidden_update_kernel, dim3(kHyperHidden * (kHyperWidth / kHyperWaves), frames.count), dim3(kHyperThreads), lds, s, update, N, adam, frames.stride);
+    hipLaunchKernelGGL(hyper_hidden_backward_kernel, dim3(N, frames.count), dim3(kHyperChainThreads), 0, s, chain, frames.stride, header);
+    hipLaunchKernelGGL(hyper_hidden_update_kernel, dim3(kHyperHidden * (kHyperWidth / kHyperWaves), frames.count), dim3(kHyperThreads), lds, s, update, N, adam, frames.stride, header);
     hipLaunchKernelGGL(hyper_finish_kernel, dim3(1, frames.count), dim3(kHyperChainThreads), 0, s, norms, ws + p.norm_partials, adam_tensors(net->embeddings), gz(kLast), N, adam,
-                       counters, net->embeddings.learning_rate, net->weight_v[0].learning_rate, net->lr_gamma, frames.stride);
+                       counters, net->embeddings.learning_rate, net->weight_v[0].learning_rate, net->lr_gamma, frames.stride, header);
     return launch_status();
 }
 

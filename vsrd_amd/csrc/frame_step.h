@@ -36,6 +36,7 @@ struct FrameStepArgs {
     float weight_iou, weight_l1, weight_silhouette;
     float beta1, beta2, adam_epsilon, lr_gamma;
     long long frame_stride;            // vsrd_frame_config::frame_stride (bytes; wave.h: frame batches), 0 for one frame
+    const FrameHeader* header;         // the frame's own count (wave.h: mixed batches), or null: num_boxes is every frame's count
 };
 
 // scratch (global, one per frame): boxes_2d [V,N,4], selection [V,N,4] (int), grad_boxes [V,N,4], grad_world [V,N,8,3]
@@ -137,7 +138,9 @@ __device__ __forceinline__ void frame_prologue_body(const FrameStepArgs& a, cons
     __shared__ int match_gt[kFrameMaxBoxes];          // gt column of prediction n (every prediction is matched: the problem is square)
     __shared__ float partial[kThreads / kWave][3];
     const int tid = static_cast<int>(threadIdx.x);
-    const int N = a.num_boxes, V = a.num_views;
+    // N: the boxes this frame has; NS: the stride of the [V, NS] ground-truth tables (the capacity of a mixed batch, else N)
+    const int NS = a.num_boxes, V = a.num_views;
+    const int N = a.header ? frame_count(a.header, NS) : NS;
 #ifdef VSRD_PHASE_TIMERS
     const unsigned long long t_start = wall_clock64();                 // 100 MHz; mark k = time of the k-th barrier (tools/prologue_timers.py)
     int mark = 8;
@@ -269,11 +272,11 @@ __device__ __forceinline__ void frame_prologue_body(const FrameStepArgs& a, cons
     for (int idx = tid; idx < V * N; idx += kThreads) {
         const int v = idx / N, n = idx - v * N;
         const int g = match_gt[n];
-        const bool keep = b.visible[v * N + g] != 0;
+        const bool keep = b.visible[v * NS + g] != 0;
         float gi[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (keep) {
             const float* pd = boxes_2d + idx * 4;
-            const float* gt = b.gt_boxes + (static_cast<size_t>(v) * N + g) * 4;
+            const float* gt = b.gt_boxes + (static_cast<size_t>(v) * NS + g) * 4;
             iou_sum += diou_loss(pd, gt, gi);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                 // smooth_l1_loss, beta = 1
@@ -426,7 +429,7 @@ __device__ __forceinline__ void shift_frame(FrameBuffers& b, long long shift) {
 }
 
 __global__ __launch_bounds__(kFrameThreads) void frame_prologue_kernel(FrameStepArgs a, FrameBuffers b) {
-    if (a.frame_stride != 0) shift_frame(b, frame_shift(a.frame_stride, blockIdx.y));
+    if (a.frame_stride != 0) { shift_frame(b, frame_shift(a.frame_stride, blockIdx.y)); a.header = of_frame(a.header, frame_shift(a.frame_stride, blockIdx.y)); }
     frame_prologue_body<kFrameThreads>(a, b);
 }
 
@@ -438,6 +441,7 @@ __global__ __launch_bounds__(kTableThreads) void frame_prologue_sample_kernel(Fr
     if (a.frame_stride != 0) {             // a batch of frames (wave.h): two workgroups per frame, frame blockIdx.y
         const long long shift = frame_shift(a.frame_stride, blockIdx.y);
         shift_frame(b, shift);
+        a.header = of_frame(a.header, shift);
         VSRD_OF_FRAME(table, shift); VSRD_OF_FRAME(device_step, shift); VSRD_OF_FRAME(remap, shift); VSRD_OF_FRAME(ray_indices, shift);
     }
     if (blockIdx.x == 0) frame_prologue_body<kTableThreads>(a, b);
@@ -489,9 +493,12 @@ __device__ __forceinline__ void shift_frame(EpilogueBuffers& e, long long shift)
 }
 
 __global__ __launch_bounds__(kFrameMaxBoxes) void frame_epilogue_kernel(FrameStepArgs a, EpilogueBuffers e) {
-    if (a.frame_stride != 0) shift_frame(e, frame_shift(a.frame_stride, blockIdx.y));      // a batch of frames (wave.h): one workgroup per frame
+    if (a.frame_stride != 0) {             // a batch of frames (wave.h): one workgroup per frame
+        shift_frame(e, frame_shift(a.frame_stride, blockIdx.y));
+        a.header = of_frame(a.header, frame_shift(a.frame_stride, blockIdx.y));
+    }
     const int tid = static_cast<int>(threadIdx.x);
-    const int N = a.num_boxes;
+    const int N = a.header ? frame_count(a.header, a.num_boxes) : a.num_boxes;
     // every thread reads the scalars before anyone updates them -- and with them everything else it will need (its box's raw
     // parameters, their Adam moments, the two gradient rows; thread 0 the step counter, the losses, the other groups' rates): ONE global
     // round trip of ~2 us for this lone workgroup instead of four in a row

@@ -98,7 +98,8 @@ __device__ __forceinline__ void stage_hyper_input(const float* __restrict__ x, c
 __global__ __launch_bounds__(kHyperThreads) void hyper_linear_forward_kernel(
     const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ v,
     const float* __restrict__ g, const float* __restrict__ b, int num_rows, int num_instances, float* __restrict__ z, float* __restrict__ inv_norm,
-    long long frame_stride) {
+    long long frame_stride, const FrameHeader* __restrict__ frame_header) {
+    num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances);      // (a mixed batch: the frame's own count, wave.h)
     if (frame_stride != 0) {               // a batch of frames (wave.h): frame blockIdx.y, every frame its own hypernetwork
         const long long shift = frame_shift(frame_stride, blockIdx.y);
         VSRD_OF_FRAME(x, shift); VSRD_OF_FRAME(gamma, shift); VSRD_OF_FRAME(beta, shift); VSRD_OF_FRAME(v, shift); VSRD_OF_FRAME(g, shift); VSRD_OF_FRAME(b, shift);
@@ -137,7 +138,9 @@ struct HyperHiddenForward {
 
 // (Frame batches, wave.h: the pointer tables of these kernels are indexed by run-time layer numbers and therefore stay where they are, in
 //  the kernel arguments -- a modified copy would live in scratch memory; every pointer is moved to the workgroup's frame where it is read.)
-__global__ __launch_bounds__(kHyperChainThreads) void hyper_hidden_forward_kernel(const float* __restrict__ embeddings, HyperHiddenForward net, long long frame_stride) {
+__global__ __launch_bounds__(kHyperChainThreads) void hyper_hidden_forward_kernel(const float* __restrict__ embeddings, HyperHiddenForward net, long long frame_stride,
+                                                                                  const FrameHeader* __restrict__ frame_header) {
+    if (static_cast<int>(blockIdx.x) >= frame_count_of(frame_header, frame_stride, blockIdx.y, static_cast<int>(gridDim.x))) return;   // (a mixed batch's pad instance)
     const long long shift = frame_shift(frame_stride, blockIdx.y);      // this workgroup's frame (0 for one frame)
     VSRD_OF_FRAME(embeddings, shift);
     __shared__ __attribute__((aligned(16))) float h[kHyperWidth];
@@ -224,7 +227,9 @@ __global__ __launch_bounds__(kHyperChainThreads) void hyper_hidden_forward_kerne
 
 // Centre the generated weights for the render kernels (VSRD_FLAG_MLP_WEIGHTS_CENTRED; rendering/renderers.py::_centre_mlp): in the
 // four linears of the per-instance MLP that feed a LayerNorm, remove each column's mean over the 16 output channels.
-__global__ __launch_bounds__(128) void hyper_centre_kernel(const float* __restrict__ weights, int num_instances, float* __restrict__ centred, long long frame_stride = 0) {
+__global__ __launch_bounds__(128) void hyper_centre_kernel(const float* __restrict__ weights, int num_instances, float* __restrict__ centred, long long frame_stride = 0,
+                                                           const FrameHeader* __restrict__ frame_header = nullptr) {
+    if (static_cast<int>(blockIdx.x) >= frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances)) return;       // (a mixed batch's pad instance)
     if (frame_stride != 0) { const long long shift = frame_shift(frame_stride, blockIdx.y); VSRD_OF_FRAME(weights, shift); VSRD_OF_FRAME(centred, shift); }
     const int n = blockIdx.x;
     const float* src = weights + static_cast<size_t>(n) * kMlpWeights;
@@ -320,7 +325,8 @@ __device__ __forceinline__ void hyper_rows_backward(
 __global__ __launch_bounds__(kHyperThreads) void hyper_linear_backward_kernel(
     const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ gz, float grad_scale,
     const float* __restrict__ inv_norm, int num_rows, int num_instances, AdamTensors v, AdamTensors g, AdamTensors b, HyperAdam adam,
-    float* __restrict__ partial_gh, long long frame_stride) {
+    float* __restrict__ partial_gh, long long frame_stride, const FrameHeader* __restrict__ frame_header) {
+    num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances);      // (a mixed batch: the frame's own count, wave.h)
     if (frame_stride != 0) {
         const long long shift = frame_shift(frame_stride, blockIdx.y);
         VSRD_OF_FRAME(x, shift); VSRD_OF_FRAME(gamma, shift); VSRD_OF_FRAME(beta, shift); VSRD_OF_FRAME(gz, shift); VSRD_OF_FRAME(inv_norm, shift); VSRD_OF_FRAME(partial_gh, shift);
@@ -337,7 +343,9 @@ struct HyperHiddenUpdate {
     AdamTensors v[4], g[4], b[4];
 };
 
-__global__ __launch_bounds__(kHyperThreads) void hyper_hidden_update_kernel(HyperHiddenUpdate u, int num_instances, HyperAdam adam, long long frame_stride) {
+__global__ __launch_bounds__(kHyperThreads) void hyper_hidden_update_kernel(HyperHiddenUpdate u, int num_instances, HyperAdam adam, long long frame_stride,
+                                                                            const FrameHeader* __restrict__ frame_header) {
+    num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances);      // (a mixed batch: the frame's own count, wave.h)
     const long long shift = frame_shift(frame_stride, blockIdx.y);      // this workgroup's frame (0 for one frame)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int kBlocksPerLayer = kHyperWidth / kHyperWaves;
@@ -363,7 +371,10 @@ __device__ __forceinline__ float block_sum_256(float value, float* scratch) {   
 // them at the end of the step).  Used behind the final linear, whose 203 workgroups' shares have to be summed across workgroups.
 __global__ __launch_bounds__(kHyperNormThreads * kHyperNormSplit) void hyper_norm_backward_kernel(
     const float* __restrict__ partial_gh, int num_partials, const float* __restrict__ z_prev, int num_instances,
-    const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ gz_out, float* __restrict__ norm_partials, long long frame_stride) {
+    const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ gz_out, float* __restrict__ norm_partials, long long frame_stride,
+    const FrameHeader* __restrict__ frame_header) {
+    num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances);      // (the stride of the shares: as hyper_rows_backward wrote them)
+    if (static_cast<int>(blockIdx.x) >= num_instances) return;                                   // (a mixed batch's pad instance)
     if (frame_stride != 0) {
         const long long shift = frame_shift(frame_stride, blockIdx.y);
         VSRD_OF_FRAME(partial_gh, shift); VSRD_OF_FRAME(z_prev, shift); VSRD_OF_FRAME(gamma, shift); VSRD_OF_FRAME(beta, shift); VSRD_OF_FRAME(gz_out, shift);
@@ -413,7 +424,8 @@ struct HyperHiddenBackward {
     float* embedding_bar;                     // [N][256]
 };
 
-__global__ __launch_bounds__(kHyperChainThreads) void hyper_hidden_backward_kernel(HyperHiddenBackward net, long long frame_stride) {
+__global__ __launch_bounds__(kHyperChainThreads) void hyper_hidden_backward_kernel(HyperHiddenBackward net, long long frame_stride, const FrameHeader* __restrict__ frame_header) {
+    if (static_cast<int>(blockIdx.x) >= frame_count_of(frame_header, frame_stride, blockIdx.y, static_cast<int>(gridDim.x))) return;   // (a mixed batch's pad instance)
     const long long shift = frame_shift(frame_stride, blockIdx.y);      // this workgroup's frame (0 for one frame)
     constexpr int kWorkers = kHyperChainWaves - kHyperHidden;      // waves 4 .. 15 hold the weights: rows o = (wave - 4) + 12 r, 4 input channels per lane
     constexpr int kRows = (kHyperWidth + kWorkers - 1) / kWorkers; // 22 (the last ones of some waves fall off the end)
@@ -518,7 +530,10 @@ struct HyperStepCounters { float* step[32]; int count; };
 __global__ __launch_bounds__(kHyperChainThreads) void hyper_finish_kernel(HyperNorms norms, const float* __restrict__ norm_partials, AdamTensors embeddings,
                                                                           const float* __restrict__ embedding_bar, int num_instances, HyperAdam adam,
                                                                           HyperStepCounters counters, float* embedding_lr, float* hyper_lr, float gamma,
-                                                                          long long frame_stride) {
+                                                                          long long frame_stride, const FrameHeader* __restrict__ frame_header) {
+    // (a mixed batch, wave.h: the layers' shares lie `capacity` instances apart, the frame's own count is summed and stepped)
+    const int capacity = num_instances;
+    num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances);
     const long long shift = frame_shift(frame_stride, blockIdx.y);      // a batch of frames (wave.h): one workgroup per frame (0 for one frame)
     VSRD_OF_FRAME(norm_partials, shift); shift_frame(embeddings, shift); VSRD_OF_FRAME(embedding_bar, shift);
     VSRD_OF_FRAME(embedding_lr, shift); VSRD_OF_FRAME(hyper_lr, shift);
@@ -541,7 +556,7 @@ __global__ __launch_bounds__(kHyperChainThreads) void hyper_finish_kernel(HyperN
         e_v[it] = in ? embeddings.exp_avg_sq[idx] : 0.0f;
         e_p[it] = in ? embeddings.parameter[idx] : 0.0f;
     }
-    const float* src = norm_partials + static_cast<size_t>(k) * num_instances * 2 * kHyperWidth;
+    const float* src = norm_partials + static_cast<size_t>(k) * capacity * 2 * kHyperWidth;
     float dgamma = 0.0f, dbeta = 0.0f;
     for (int n = 0; n < num_instances; ++n) {
         dgamma += src[(static_cast<size_t>(n) * 2 + 0) * kHyperWidth + c];

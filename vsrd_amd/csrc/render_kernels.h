@@ -92,6 +92,13 @@ __device__ __forceinline__ float load_target(const RenderArgs& c, const float* _
     const int column = c.target_columns[lane];
     return (column >= 0) ? targets[row * c.target_stride + column] : 0.0f;
 }
+// ... for a mixed batch's frame (wave.h): N instances of rows `pitch` (the capacity) wide
+__device__ __forceinline__ float load_target_pitched(const RenderArgs& c, const float* __restrict__ targets, long long row, int lane, int N, int pitch) {
+    if (lane >= N) return 0.0f;
+    if (c.target_columns == nullptr) return targets[row * pitch + lane];
+    const int column = c.target_columns[lane];
+    return (column >= 0) ? targets[row * c.target_stride + column] : 0.0f;
+}
 
 // Phase clocks (experiments only: -DVSRD_PHASE_TIMERS, tools/phase_timers.py): every wave adds the s_memtime ticks it spends in each
 // phase of the fused step kernels to a global table that vsrd_debug_phase_cycles reads back.  Compiled out by default.
@@ -1221,8 +1228,12 @@ __global__ __launch_bounds__(kPairWaves * kWave) __attribute__((amdgpu_waves_per
     const float* __restrict__ origins, const float* __restrict__ directions, const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale, float eikonal_scale, float eikonal_norm,
     float* __restrict__ labels_out, float* __restrict__ partials, float4* __restrict__ residual_cache, float* __restrict__ loss_partials,
-    float* __restrict__ seed_table, unsigned char* __restrict__ mask_table, long long slots_per_instance, int chunk_base, int chunk_rays, int accumulate) {
+    float* __restrict__ seed_table, unsigned char* __restrict__ mask_table, long long slots_per_instance, int chunk_base, int chunk_rays, int accumulate,
+    const FrameHeader* __restrict__ frame_header) {
     static_assert(kRounds % kPairWaves == 0, "a wave takes kRounds / 2 rounds of pass 2");
+    // N: the instances this frame has; NS: the stride of the per-instance rows (a mixed batch's capacity, wave.h; N for one frame)
+    int N = f.num_instances;
+    const int NS = f.num_instances;
     if constexpr (kFrames) {               // a batch of frames (wave.h): this workgroup's frame is blockIdx.y
         const long long shift = frame_shift(c.frame_stride, blockIdx.y);
         shift_frame(c, shift);
@@ -1230,6 +1241,11 @@ __global__ __launch_bounds__(kPairWaves * kWave) __attribute__((amdgpu_waves_per
         VSRD_OF_FRAME(u_coarse, shift); VSRD_OF_FRAME(u_fine, shift); VSRD_OF_FRAME_NONNULL(targets, shift); VSRD_OF_FRAME(instance_weights, shift);
         VSRD_OF_FRAME(labels_out, shift); VSRD_OF_FRAME_NONNULL(partials, shift); VSRD_OF_FRAME_NONNULL(residual_cache, shift); VSRD_OF_FRAME_NONNULL(loss_partials, shift);
         VSRD_OF_FRAME_NONNULL(seed_table, shift); VSRD_OF_FRAME_NONNULL(mask_table, shift);
+        if (frame_header != nullptr) {
+            VSRD_OF_FRAME_NONNULL(frame_header, shift);
+            N = frame_count(frame_header, NS);
+            loss_scale = frame_header->loss_scale;
+        }
     }
     apply_device_schedule(f, c);
     constexpr int kRoundsS = (kRounds + 1) / 2;                               // rounds of pass 1 (all of them staged and merged by wave 0)
@@ -1239,7 +1255,6 @@ __global__ __launch_bounds__(kPairWaves * kWave) __attribute__((amdgpu_waves_per
     const int wave = wave_in_block();
     const int lane = lane_id();
     const int S = c.num_samples;
-    const int N = f.num_instances;
     // shared by the two waves: the ray's sample arrays, the exchange scalars, the label halves
     WaveLds l = carve_lds(lds, S, 0);
     float* xchg = lds + ((7 * S + 3) & ~3);                                   // [0..1] pass-1 products, [2..3] pass-2 products, [4..5] suffix sums
@@ -1250,7 +1265,7 @@ __global__ __launch_bounds__(kPairWaves * kWave) __attribute__((amdgpu_waves_per
     float* lam = l.cull + cull_coef_floats(N);
     float* G = lam + N;
     const size_t wave_global = static_cast<size_t>(blockIdx.x) * kPairWaves + wave;
-    float* out = partials + wave_global * (N * kGradStride);
+    float* out = partials + wave_global * (NS * kGradStride);
     for (int idx = lane; idx < N * kGradStride; idx += kWave) G[idx] = accumulate ? out[idx] : 0.0f;
     float4* rcache = residual_cache + wave_global * jet_wave_float4s(kRounds, N);
     const bool sorted_input = (u_fine != nullptr) && (c.flags & 1u);
@@ -1274,7 +1289,7 @@ __global__ __launch_bounds__(kPairWaves * kWave) __attribute__((amdgpu_waves_per
         block_lds_barrier();                                                      // the previous ray's arrays are no longer read
         const long long row = source_row(c, ray);
         const Ray r = load_ray_gathered(c, origins, directions, row);
-        const float target = load_target(c, targets, row, lane, N);
+        const float target = load_target_pitched(c, targets, row, lane, N, NS);
         const RayCull rc = cull_ray_setup(instances, N, r.ox, r.oy, r.oz, r.rx, r.ry, r.rz, l.cull, lane);
         if (wave == 0) stage_ray_samples<kRoundsS>(l, c, S, ray, u_coarse, u_fine, nullptr, nullptr, sorted_input, lane);
         block_lds_barrier();
@@ -1316,7 +1331,7 @@ __global__ __launch_bounds__(kPairWaves * kWave) __attribute__((amdgpu_waves_per
         label_half[wave * kWave + lane] = label;
         block_lds_barrier();
         label = label_half[lane] + label_half[kWave + lane];
-        if (wave == 0 && labels_out != nullptr && lane < N) labels_out[static_cast<size_t>(ray) * N + lane] = label;
+        if (wave == 0 && labels_out != nullptr && lane < N) labels_out[static_cast<size_t>(ray) * NS + lane] = label;
         // silhouette BCE and its gradient (as render_silhouette_kernel); the loss is counted by wave 0
         const float p = fminf(fmaxf(label, 1.0e-6f), 1.0f - 1.0e-6f);
         const float bce = -(target * logf(p) + (1.0f - target) * logf(1.0f - p));
@@ -1378,14 +1393,22 @@ __global__ __launch_bounds__(kPairWaves * kWave) void render_silhouette_split_ke
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
     const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale,
-    float* __restrict__ labels_out, float* __restrict__ partials, float* __restrict__ loss_partials) {
+    float* __restrict__ labels_out, float* __restrict__ partials, float* __restrict__ loss_partials, const FrameHeader* __restrict__ frame_header) {
     static_assert(kRounds % kPairWaves == 0, "a wave takes kRounds / 2 rounds of pass 2");
+    // N: the instances this frame has; NS: the stride of the per-instance rows (a mixed batch's capacity, wave.h; N for one frame)
+    int N = f.num_instances;
+    const int NS = f.num_instances;
     if constexpr (kFrames) {               // a batch of frames (wave.h): this workgroup's frame is blockIdx.y
         const long long shift = frame_shift(c.frame_stride, blockIdx.y);
         shift_frame(c, shift);
         VSRD_OF_FRAME_NONNULL(instances, shift); VSRD_OF_FRAME_NONNULL(origins, shift); VSRD_OF_FRAME_NONNULL(directions, shift);
         VSRD_OF_FRAME(u_coarse, shift); VSRD_OF_FRAME(u_fine, shift); VSRD_OF_FRAME_NONNULL(targets, shift); VSRD_OF_FRAME(instance_weights, shift);
         VSRD_OF_FRAME(labels_out, shift); VSRD_OF_FRAME_NONNULL(partials, shift); VSRD_OF_FRAME_NONNULL(loss_partials, shift);
+        if (frame_header != nullptr) {
+            VSRD_OF_FRAME_NONNULL(frame_header, shift);
+            N = frame_count(frame_header, NS);
+            loss_scale = frame_header->loss_scale;
+        }
     }
     apply_device_schedule(f, c);
     constexpr int kRoundsS = (kRounds + 1) / 2;                               // rounds of pass 1 (all of them staged and merged by wave 0)
@@ -1395,7 +1418,6 @@ __global__ __launch_bounds__(kPairWaves * kWave) void render_silhouette_split_ke
     const int wave = wave_in_block();
     const int lane = lane_id();
     const int S = c.num_samples;
-    const int N = f.num_instances;
     WaveLds l = carve_lds(lds, S, 0);                                         // shared by the two waves: the ray's sample arrays
     float* xchg = lds + ((7 * S + 3) & ~3);                                   // [0..1] pass-1 products, [2..3] pass-2 products, [4..5] suffix sums, [6..7] pass-1 weight sums
     float* label_half = xchg + 16;                                            // [2][64]
@@ -1420,7 +1442,7 @@ __global__ __launch_bounds__(kPairWaves * kWave) void render_silhouette_split_ke
         block_lds_barrier();                                                  // the previous ray's arrays are no longer read
         const long long row = source_row(c, ray);
         const Ray r = load_ray_gathered(c, origins, directions, row);
-        const float target = load_target(c, targets, row, lane, N);
+        const float target = load_target_pitched(c, targets, row, lane, N, NS);
         const RayCull rc = cull_ray_setup(instances, N, r.ox, r.oy, r.oz, r.rx, r.ry, r.rz, l.cull, lane);
         if (wave == 0) stage_ray_samples<kRoundsS>(l, c, S, ray, u_coarse, u_fine, nullptr, nullptr, sorted_input, lane);
         block_lds_barrier();
@@ -1468,7 +1490,7 @@ __global__ __launch_bounds__(kPairWaves * kWave) void render_silhouette_split_ke
             block_lds_barrier();
             label = label_half[lane] + label_half[kWave + lane];
         }
-        if (wave == 0 && labels_out != nullptr && lane < N) labels_out[static_cast<size_t>(ray) * N + lane] = label;
+        if (wave == 0 && labels_out != nullptr && lane < N) labels_out[static_cast<size_t>(ray) * NS + lane] = label;
         // silhouette BCE and its gradient (as render_silhouette_kernel); the loss is counted by wave 0
         const float p = fminf(fmaxf(label, 1.0e-6f), 1.0f - 1.0e-6f);
         const float bce = -(target * logf(p) + (1.0f - target) * logf(1.0f - p));
@@ -1498,7 +1520,7 @@ __global__ __launch_bounds__(kPairWaves * kWave) void render_silhouette_split_ke
     }
     wave_lds_sync();
     const size_t wave_global = static_cast<size_t>(blockIdx.x) * kPairWaves + wave;
-    float* out = partials + wave_global * (N * kGradStride);
+    float* out = partials + wave_global * (NS * kGradStride);
     for (int idx = lane; idx < N * kGradStride; idx += kWave) out[idx] = G[idx];
     const float loss_total = wave_sum(loss_acc);
     if (lane == 0) loss_partials[wave_global] = loss_total * loss_scale;
@@ -1690,7 +1712,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 // VSRD_FLAG_MLP_SPLIT_BF16: the operand images of a launch's instances (residual.h: pack_mlp_image), one workgroup per instance, once per
 // vsrd_render_residual_step call (N x 9.4 KB: the front kernels stage an instance's image where they staged its 6.5 KB of weights).
 #ifdef VSRD_SPLIT_BF16      // (csrc/split_front.hip only)
-__global__ __launch_bounds__(256) void pack_mlp_images_kernel(const float* __restrict__ weights, int centred, unsigned* __restrict__ images, long long frame_stride) {
+__global__ __launch_bounds__(256) void pack_mlp_images_kernel(const float* __restrict__ weights, int centred, unsigned* __restrict__ images, long long frame_stride,
+                                                              const FrameHeader* __restrict__ frame_header) {
+    if (static_cast<int>(blockIdx.x) >= frame_count_of(frame_header, frame_stride, blockIdx.y, static_cast<int>(gridDim.x))) return;   // (a mixed batch's pad instance)
     if (frame_stride != 0) { const long long shift = frame_shift(frame_stride, blockIdx.y); VSRD_OF_FRAME(weights, shift); VSRD_OF_FRAME(images, shift); }
     __shared__ __attribute__((aligned(16))) float staged[kMlpWbarFloats];
     const int n = blockIdx.x;
@@ -1706,8 +1730,10 @@ __global__ __launch_bounds__(256) void pack_mlp_images_kernel(const float* __res
 constexpr int kItemSegments = 32;
 
 __global__ __launch_bounds__(256) void reduce_item_rows_kernel(const float* __restrict__ item_rows, const unsigned char* __restrict__ item_flags,
-                                                               int rows_per_instance, float* __restrict__ segment_sums, long long frame_stride) {
+                                                               int rows_per_instance, float* __restrict__ segment_sums, long long frame_stride,
+                                                               const FrameHeader* __restrict__ frame_header = nullptr) {
     const int i = blockIdx.x, segment = blockIdx.z % kItemSegments;
+    if (i >= frame_count_of(frame_header, frame_stride, blockIdx.z / kItemSegments, static_cast<int>(gridDim.x))) return;   // (a mixed batch's pad instance)
     if (frame_stride != 0) {               // a batch of frames (wave.h): the grid's z extent is frames x segments
         const long long shift = frame_shift(frame_stride, blockIdx.z / kItemSegments);
         VSRD_OF_FRAME(item_rows, shift); VSRD_OF_FRAME(item_flags, shift); VSRD_OF_FRAME(segment_sums, shift);
@@ -1733,7 +1759,9 @@ __global__ __launch_bounds__(256) void reduce_item_rows_kernel(const float* __re
 
 // grad_mlp [N,1617] (+)= the segment sums of instance i; box_extra [N,16] likewise (the MLP's dL/dp chained into t and R).
 __global__ __launch_bounds__(256) void reduce_item_segments_kernel(const float* __restrict__ segment_sums, float* __restrict__ grad_mlp,
-                                                                   float* __restrict__ box_extra, int accumulate, long long frame_stride) {
+                                                                   float* __restrict__ box_extra, int accumulate, long long frame_stride,
+                                                                   const FrameHeader* __restrict__ frame_header = nullptr) {
+    if (static_cast<int>(blockIdx.x) >= frame_count_of(frame_header, frame_stride, blockIdx.z, static_cast<int>(gridDim.x))) return;   // (a mixed batch's pad instance)
     if (frame_stride != 0) { const long long shift = frame_shift(frame_stride, blockIdx.z); VSRD_OF_FRAME(segment_sums, shift); VSRD_OF_FRAME(grad_mlp, shift); VSRD_OF_FRAME(box_extra, shift); }
     const int i = blockIdx.x;
     const int idx = blockIdx.y * blockDim.x + threadIdx.x;
@@ -1754,14 +1782,17 @@ __global__ __launch_bounds__(256) void reduce_item_segments_kernel(const float* 
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partials, int num_waves, int row, float* __restrict__ out,
                                                               const float* __restrict__ extra = nullptr,
                                                               const float* __restrict__ partials2 = nullptr, int row2 = 0, float* __restrict__ out2 = nullptr,
-                                                              long long frame_stride = 0) {
+                                                              long long frame_stride = 0, const FrameHeader* __restrict__ frame_header = nullptr) {
     if (frame_stride != 0) {               // a batch of frames (wave.h): frame blockIdx.y
         const long long shift = frame_shift(frame_stride, blockIdx.y);
         VSRD_OF_FRAME(partials, shift); VSRD_OF_FRAME(out, shift); VSRD_OF_FRAME(extra, shift); VSRD_OF_FRAME(partials2, shift); VSRD_OF_FRAME(out2, shift);
+        VSRD_OF_FRAME(frame_header, shift);
     }
     __shared__ float scratch[256 / kWave];
     const bool second = static_cast<int>(blockIdx.x) >= row;
     const int idx = second ? static_cast<int>(blockIdx.x) - row : static_cast<int>(blockIdx.x);
+    // a mixed batch (wave.h): the rows are [capacity][kGradStride] and the frame's own instances come first; the rest is not touched
+    if (frame_header != nullptr && !second && idx >= frame_count(frame_header, row / kGradStride) * kGradStride) return;
     const float* table = second ? partials2 : partials;
     const int pitch = second ? row2 : row;
     float acc = 0.0f;

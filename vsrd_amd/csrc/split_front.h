@@ -23,11 +23,13 @@ struct FrontLaunch {
     size_t lds_bytes;
     bool export_samples;                                   // vsrd_render_config::out_* set: the instantiation that writes the step's samples (two rounds only)
     int frames;                                            // frame batch (include/vsrd_hip.h, ABI 8): the grid's y extent; the stride travels in RenderArgs
+    const void* frame_header;                              // mixed batch (ABI 9): frame 0's vsrd_frame_header, or null
 };
 
 enum { kOk = 0, kLdsRefused = 1, kUnsupported = 2, kLaunchFailed = 3 };
 
-int pack_images(const float* weights, int num_instances, int centred, unsigned* images, int frames, long long frame_stride, hipStream_t stream);
+int pack_images(const float* weights, int num_instances, int centred, unsigned* images, int frames, long long frame_stride, const void* frame_header,
+                hipStream_t stream);
 int launch_front(const FrontLaunch& launch, hipStream_t stream);
 // residual_mlp_adjoint_split_kernel: the arguments of residual_mlp_adjoint_kernel with the image table in the place of the weights
 int launch_adjoint(int blocks, const float* instances, const float* images, int num_instances, const float* seeds, const unsigned char* masks,

@@ -11,8 +11,10 @@
 
 namespace vsrd_split_front {
 
-int pack_images(const float* weights, int num_instances, int centred, unsigned* images, int frames, long long frame_stride, hipStream_t stream) {
-    hipLaunchKernelGGL(vsrd_split::pack_mlp_images_kernel, dim3(num_instances, frames), dim3(256), 0, stream, weights, centred, images, frame_stride);
+int pack_images(const float* weights, int num_instances, int centred, unsigned* images, int frames, long long frame_stride, const void* frame_header,
+                hipStream_t stream) {
+    hipLaunchKernelGGL(vsrd_split::pack_mlp_images_kernel, dim3(num_instances, frames), dim3(256), 0, stream, weights, centred, images, frame_stride,
+                       static_cast<const vsrd_split::FrameHeader*>(frame_header));
     return hipGetLastError() == hipSuccess ? kOk : kLaunchFailed;
 }
 
@@ -42,12 +44,13 @@ int launch_front(const FrontLaunch& a, hipStream_t stream) {
     } while (0)
 #define VSRD_PAIR(K)                                                                                                                          \
     do {                                                                                                                                      \
-        if (a.frames > 1) {                                                                                                                   \
+        if (a.frames > 1 || a.frame_header) {                                                                                                 \
             if (!opt_in(residual_step_pair_kernel<K, true>, a.lds_bytes)) return kLdsRefused;                                                 \
-            hipLaunchKernelGGL((residual_step_pair_kernel<K, true>), dim3(a.blocks, a.frames), dim3(kPairWaves * kWave), a.lds_bytes, stream, VSRD_ARGS); \
+            hipLaunchKernelGGL((residual_step_pair_kernel<K, true>), dim3(a.blocks, a.frames), dim3(kPairWaves * kWave), a.lds_bytes, stream, VSRD_ARGS, \
+                               static_cast<const FrameHeader*>(a.frame_header));                                                               \
         } else {                                                                                                                              \
             if (!opt_in(residual_step_pair_kernel<K>, a.lds_bytes)) return kLdsRefused;                                                       \
-            hipLaunchKernelGGL(residual_step_pair_kernel<K>, dim3(a.blocks), dim3(kPairWaves * kWave), a.lds_bytes, stream, VSRD_ARGS);       \
+            hipLaunchKernelGGL(residual_step_pair_kernel<K>, dim3(a.blocks), dim3(kPairWaves * kWave), a.lds_bytes, stream, VSRD_ARGS, nullptr); \
         }                                                                                                                                     \
     } while (0)
     if (a.pair) {

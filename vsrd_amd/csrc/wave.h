@@ -38,6 +38,23 @@ __device__ __forceinline__ T* of_frame_nonnull(T* p, long long shift) {
 }
 #define VSRD_OF_FRAME_NONNULL(p, shift) p = of_frame_nonnull(p, shift)
 
+// Mixed batches (ABI 9: vsrd_frame_header): the by-value instance count of a batched launch is the CAPACITY -- the stride of every
+// per-instance array -- and each frame's own count sits in its header (device memory, frame_stride apart like every other buffer).
+// Read once per workgroup as a wave-uniform scalar and clamped to [1, capacity]; instances count .. capacity - 1 of a frame are
+// never read and never written.
+struct FrameHeader {
+    int num_instances;
+    float loss_scale;
+};
+__device__ __forceinline__ int frame_count(const FrameHeader* header, int capacity) {
+    const int n = __builtin_amdgcn_readfirstlane(header->num_instances);
+    return n < 1 ? 1 : (n > capacity ? capacity : n);
+}
+// The count of frame `frame` of a launch whose header pointer addresses frame 0's (null: every frame has `capacity`).
+__device__ __forceinline__ int frame_count_of(const FrameHeader* header, long long frame_stride, unsigned frame, int capacity) {
+    return header ? frame_count(of_frame(header, frame_shift(frame_stride, frame)), capacity) : capacity;
+}
+
 __device__ __forceinline__ float uniform(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }

@@ -332,7 +332,7 @@ class _RenderWork:
         if frame in self.inputs:
             return self.inputs[frame]
         args = self.args
-        return synthetic_frame_inputs(self.device, frame, args.views, args.instances, args.height, args.width)
+        return synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts), args.height, args.width)
 
     def optimization_config(self, **more):
         from . import optimization
@@ -347,7 +347,8 @@ class _RenderWork:
         from . import optimization
         args = self.args
         mine = [] if self.queue.dynamic else [frame for frame in self.queue.mine if not os.path.exists(self.path_of(frame))]
-        self.inputs = {frame: synthetic_frame_inputs(self.device, frame, args.views, args.instances, args.height, args.width) for frame in mine}
+        self.inputs = {frame: synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts), args.height, args.width)
+                       for frame in mine}
         self.slots, self.batch = queue.Queue(), None
         self.setup_seconds, self.graphs_per_slot, self.unsuitable_founders = 0.0, 0, []
         # the frames a slot or batch may be founded on: this rank's own (static), or the head of the job's queue (dynamic: built here, once)
@@ -358,7 +359,9 @@ class _RenderWork:
                 founders = [self.inputs_of(f) for f in candidates[:args.frame_batch]]
                 founders += [founders[-1]] * (args.frame_batch - len(founders))           # (fewer frames than rows: the shape is what matters)
                 try:
-                    self.batch = optimization.FrameBatch(founders, self.optimization_config(), self.device)
+                    mixed = len(set(args.instance_counts)) > 1           # (a mixed list: rows of capacity max(list), each frame its own count)
+                    self.batch = optimization.FrameBatch(founders, self.optimization_config(), self.device,
+                                                         max_instances=max(args.instance_counts) if mixed else None)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
                     tail = len(mine) % args.frame_batch if mine else 0                   # a static queue's last group is known now: capture it too
                     self.graphs_per_slot = self.batch.capture_all(actives=sorted({args.frame_batch, tail} - {0}, reverse=True))
@@ -407,7 +410,9 @@ class _RenderWork:
         def optimise(frame):
             slot = self.slots.get() if self._have_slots else None      # (--fresh-loops, or no frame could found a slot)
             try:
-                if slot is None or not slot.reset(self.inputs_of(frame), init_seed=self.init_seed(frame)):
+                inputs = self.inputs_of(frame)
+                # (a slot serves frames of its founder's shape: a frame of another instance count runs in a loop of its own)
+                if slot is None or int(inputs.soft_masks.shape[-1]) != slot.num_instances or not slot.reset(inputs, init_seed=self.init_seed(frame)):
                     fallbacks.append(int(frame))
                     losses[frame], payload = self._own_loop(frame)
                     return payload
@@ -532,6 +537,22 @@ def effective_frame_batch(requested: int, total_frames: int, world_size: int) ->
     return max(1, min(int(requested), share))
 
 
+def parse_instances(text):
+    """--instances: one count (every frame) or a comma list -- frame j has list[j % len(list)] instances (instances_of)."""
+    try:
+        counts = [int(x) for x in str(text).split(",")]
+    except ValueError:
+        raise SystemExit(f"--instances: an integer or a comma list of integers, got {text!r}")
+    if not counts or any(not 1 <= n <= 64 for n in counts):
+        raise SystemExit(f"--instances: counts of 1..64, got {text!r}")
+    return counts
+
+
+def instances_of(frame, counts):
+    """The instance count of frame number `frame`: a pure function of the frame number (the same on every rank and after a restart)."""
+    return int(counts[int(frame) % len(counts)])
+
+
 def main(argv=None):
     """Optimise K synthetic frames, sharded over the ranks, each rank keeping `--frames-in-flight` frames on its GPU at a time with
     ``FrameOptimizer(graph=True)``; checkpoints through formats.checkpoint_payload (atomic, restartable: a frame whose final checkpoint
@@ -568,7 +589,9 @@ def main(argv=None):
                              "a batch picks FrameBatch.item_slots).  A frame's trajectory is bit-identical alone and in a batch for equal numbers")
     parser.add_argument("--fp32-mlp", action="store_true", help="the residual MLP's products on the exact-fp32 matrix instruction instead of split bf16")
     parser.add_argument("--views", type=int, default=17)
-    parser.add_argument("--instances", type=int, default=8)
+    parser.add_argument("--instances", type=str, default="8",
+                        help="instances per frame: one count, or a comma list (frame j gets list[j %% len(list)]); with --frame-batch > 1 a mixed "
+                             "list runs in batches of capacity max(list) (optimization.FrameBatch(max_instances=...))")
     parser.add_argument("--rays", type=int, default=1000)
     parser.add_argument("--samples", type=int, default=100)
     parser.add_argument("--num-steps", type=int, default=3000)
@@ -600,6 +623,8 @@ def main(argv=None):
     parser.add_argument("--selftest-hang", default="", help="RANK:FRAMES -- on attempt 0 that rank hangs (sleeps for ever) once it has finished FRAMES frames")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parser.parse_args(argv)
+    args.instance_counts = parse_instances(args.instances)
+    args.instances = args.instance_counts[0] if len(args.instance_counts) == 1 else args.instances
     if not 1 <= args.frames_in_flight <= (4 if args.fresh_loops else 8):
         # (round 4, a new loop per frame: five and more frames on one device ended in a memory fault or a segmentation fault inside torch / HIP
         #  within seconds -- construction and eager warm-up steps of that many threads next to a capture.  Frame slots capture nothing once
@@ -728,6 +753,11 @@ def _rank_main(args):
                 "frames_per_s_per_gpu": frames_done / slowest / n_gpus,
                 "ranks": len(gathered), "procs_per_gpu": procs, "frames_in_flight_per_process": args.frames_in_flight, "rank_devices": [r["device"] for r in gathered],
                 "frame_batch": args.frame_batch,        # frames one process steps together, one launch of every kernel for all of them (optimization.FrameBatch)
+                # instances per frame (frame j: instance_list[j % len]); frames done per count; the rows' capacity of a mixed batch (None: one shape)
+                "instance_list": list(args.instance_counts),
+                "frames_per_instances": {str(n): sum(1 for r in gathered for f in r["final_losses"] if instances_of(f, args.instance_counts) == n)
+                                         for n in sorted(set(args.instance_counts))},
+                "batch_capacity": max(args.instance_counts) if args.frame_batch > 1 and len(set(args.instance_counts)) > 1 else None,
                 "control_plane": "gloo" if share else "RCCL",
                 "queue": "dynamic (TCPStore counter on rank 0; inputs built when a frame is taken, inside the clock)" if dynamic else
                          "static (frame j of the seeded permutation to rank j mod world; inputs resident before the clock)",

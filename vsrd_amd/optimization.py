@@ -277,15 +277,25 @@ class FrameRow:
         return view
 
 
-def adam_state_tensors(optimizer, parameter, group, row=None):
+def _instance_prefix(tensor, count):
+    """The first `count` instances of a [1, capacity, ...] buffer of a mixed batch's row, as a contiguous [1, count, ...] view."""
+    return tensor.as_strided((tensor.shape[0], int(count), *tensor.shape[2:]), tensor.stride(), tensor.storage_offset())
+
+
+def adam_state_tensors(optimizer, parameter, group, row=None, capacity=None):
     """`parameter`'s torch.optim.Adam(capturable=True) state as the C ABI's pointer block, created now if the optimiser has not
     stepped yet (torch creates it lazily): the kernels update the moments, the counter and the parameter in place.  `row`: the frame's
-    row of a batch's arena (FrameRow) -- the state is created there."""
+    row of a batch's arena (FrameRow) -- the state is created there.  `capacity`: the parameter is [1, N, ...] and its moments are the
+    first N instances of [1, capacity, ...] buffers (a mixed batch's row, FrameBatch(max_instances=...))."""
     state = optimizer.state[parameter]
     if not state:
         if row is not None:
             state["step"] = row.new((), torch.float32, fill=0.0)
-            state["exp_avg"], state["exp_avg_sq"] = row.new(parameter.shape, torch.float32, fill=0.0), row.new(parameter.shape, torch.float32, fill=0.0)
+            shape = parameter.shape if capacity is None else (parameter.shape[0], int(capacity), *parameter.shape[2:])
+            state["exp_avg"], state["exp_avg_sq"] = row.new(shape, torch.float32, fill=0.0), row.new(shape, torch.float32, fill=0.0)
+            if capacity is not None:
+                state["exp_avg"] = _instance_prefix(state["exp_avg"], parameter.shape[1])
+                state["exp_avg_sq"] = _instance_prefix(state["exp_avg_sq"], parameter.shape[1])
         else:
             state["step"] = torch.zeros((), dtype=torch.float32, device=parameter.device)
             state["exp_avg"], state["exp_avg_sq"] = torch.zeros_like(parameter), torch.zeros_like(parameter)
@@ -293,16 +303,16 @@ def adam_state_tensors(optimizer, parameter, group, row=None):
                             group["lr"].data_ptr())
 
 
-def hypernetwork_tensors(hyper_distance_field, embeddings, optimizer, lr_gamma, row=None):
+def hypernetwork_tensors(hyper_distance_field, embeddings, optimizer, lr_gamma, row=None, capacity=None):
     """include/vsrd_hip.h::vsrd_hypernetwork over the torch module's own parameters and the optimiser's own state.  `optimizer`'s
     groups: the one holding `embeddings` and the one holding the hypernetwork, learning rates as device tensors."""
     def group_of(p):
         return next(g for g in optimizer.param_groups if any(q is p for q in g["params"]))
     net = _lib.Hypernetwork()
-    net.num_instances, net.num_outputs = int(embeddings.shape[-2]), _lib.MLP_WEIGHTS
+    net.num_instances, net.num_outputs = int(embeddings.shape[-2] if capacity is None else capacity), _lib.MLP_WEIGHTS
     betas = group_of(embeddings)["betas"]
     net.beta1, net.beta2, net.adam_epsilon, net.lr_gamma = float(betas[0]), float(betas[1]), float(group_of(embeddings)["eps"]), float(lr_gamma)
-    net.embeddings = adam_state_tensors(optimizer, embeddings, group_of(embeddings), row)
+    net.embeddings = adam_state_tensors(optimizer, embeddings, group_of(embeddings), row, capacity)
     blocks = list(hyper_distance_field.hypernetwork)
     if len(blocks) != _lib.HYPER_LAYERS or embeddings.shape[-1] != 256 or not all(p.is_contiguous() for p in hyper_distance_field.parameters()):
         raise ValueError("csrc/hypernetwork.h is built for config.json:143-156: 256-d embeddings, four hidden blocks of 256")
@@ -323,14 +333,20 @@ class FrameOptimizer:
     frame-resident tensors by index; in the residual phase the hypernetwork, its backward and its Adam are csrc/hypernetwork.h
     (``fused_hypernetwork = False`` keeps them with torch: the A/B reference)."""
 
-    def __init__(self, inputs: FrameInputs, config: OptimizationConfig, device, graph=False, fused_glue=None, persistent=False, row=None):
+    def __init__(self, inputs: FrameInputs, config: OptimizationConfig, device, graph=False, fused_glue=None, persistent=False, row=None,
+                 capacity=None):
         """``persistent``: the loop will be given other frames of the same shape through ``reset()`` (a frame SLOT, launcher.py): it then
         owns every buffer a captured graph holds the address of -- in particular a copy of the soft masks instead of the caller's tensor.
         ``row`` (a ``FrameRow``): the loop is one frame of a ``FrameBatch`` and keeps EVERY device buffer its kernels touch -- parameters,
-        Adam's state, rates, counters, rays, masks, sampling table, scratch -- in that row of the batch's arena."""
+        Adam's state, rates, counters, rays, masks, sampling table, scratch -- in that row of the batch's arena.  ``capacity`` (with
+        ``row``): the row of a MIXED batch (FrameBatch(max_instances=...)): every per-instance buffer is laid out for ``capacity``
+        instances, the frame's own N fill the first rows, and the row's header (include/vsrd_hip.h, vsrd_frame_header) carries N."""
         self._graphs = {}
         self.persistent = bool(persistent)
         self._row = row
+        self._capacity = None if capacity is None else int(capacity)
+        if self._capacity is not None and row is None:
+            raise ValueError("a capacity belongs to a frame of a FrameBatch (row=...)")
         if row is not None and not (graph and persistent and fused_glue in (None, True)):
             raise ValueError("a frame of a batch is a persistent graph-mode loop with the fused glue")
         # the whole construction stays out of other frames' captures: it copies modules to the device, reads ranges back (.item()), runs
@@ -349,6 +365,9 @@ class FrameOptimizer:
             raise ValueError("fused_glue keeps the learning rates and Adam's counters on the device: it needs graph=True")
         V, H, W, N = inputs.soft_masks.shape
         self.num_views, self.num_instances = V, N
+        self.capacity = N if self._capacity is None else self._capacity
+        if not 1 <= N <= self.capacity:
+            raise ValueError(f"a row of capacity {self.capacity} serves frames of 1..{self.capacity} instances, got {N}")
         with _initial_draw:
             if config.init_seed is not None:
                 torch.default_generator.manual_seed(int(config.init_seed))      # (the CPU generator: the modules are built on the host; the device generators, which captured graphs register, stay untouched)
@@ -357,8 +376,9 @@ class FrameOptimizer:
             field = models.HyperDistanceField(48, [16, 16, 16, 16], 256, [256, 256, 256, 256])
         self.detector, self.hyper_distance_field = detector.to(self.device), field.to(self.device)
         if self._row is not None:          # the parameters move into the frame's row (module order: the same in every frame of the batch)
+            per_instance = set(self.detector.parameters()) if self._capacity is not None else set()     # ([1, N, ...]: laid out for the capacity)
             for p in [*self.detector.parameters(), *self.hyper_distance_field.parameters()]:
-                p.data = self._row.adopt(p.data)
+                p.data = self._adopt_instances(p.data, 1, prefix=True) if p in per_instance else self._row.adopt(p.data)
         def rate(value):   # graph mode: learning rates are device tensors decayed in place inside the captured step
             if self._row is not None:
                 return self._row.new((), torch.float32, fill=value)
@@ -376,7 +396,7 @@ class FrameOptimizer:
         self.workspace = rendering.Workspace(allocate=None if self._row is None else self._row.bytes)
         if self.graph:
             self.workspace.keep_outgrown = True          # a captured graph holds the buffer's address: an outgrown buffer must outlive it
-            self.workspace.reserve(self.device, N, residual=True, step_shape=(config.num_samples, config.num_rays))
+            self.workspace.reserve(self.device, self.capacity, residual=True, step_shape=(config.num_samples, config.num_rays))
         self._graphs = {}
         self._capture_stream = None
         self._eager_graph_steps = {}
@@ -398,17 +418,34 @@ class FrameOptimizer:
         """`tensor` as a buffer of this loop: a copy in the frame's row of the batch's arena, or the tensor itself."""
         return tensor if self._row is None else self._row.adopt(tensor)
 
+    def _adopt_instances(self, tensor, dim, prefix=False):
+        """A mixed batch's row: `tensor` (N instances along `dim`) copied into the first N of a buffer of `capacity` instances.  Returns
+        the FULL buffer (the kernels stride by the capacity), or with `prefix` the [1, N, ...] view of a [1, capacity, ...] parameter."""
+        shape = list(tensor.shape)
+        shape[dim] = self.capacity
+        full = self._row.new(shape, tensor.dtype, fill=0)
+        full.narrow(dim, 0, tensor.shape[dim]).copy_(tensor)
+        return _instance_prefix(full, tensor.shape[dim]) if prefix else full
+
+    def _write_header(self):
+        """A mixed batch's row: the frame's own count and silhouette normaliser (the float32 the one-frame path passes by value)."""
+        header = self._glue["header"]
+        header.view(torch.int32)[0] = self.num_instances
+        header.view(torch.float32)[1] = 1.0 / (self.config.num_rays * self.num_instances)
+
     def _prepare_rays(self, inputs, config, H, W, N):
         # rays of every view, once per frame (main.py:267-296)
         cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
         self.camera_positions = self._own(cam)                              # [V,3]
         self.ray_directions = self._own(dirs.reshape(-1, 3).contiguous())   # [V*H*W,3]
         self.flat_masks = inputs.soft_masks.reshape(-1, N)
-        if self._row is not None:
+        if self._capacity is not None:               # [pixels, capacity]: the kernels read the targets with target_stride = capacity
+            self.flat_masks = self._adopt_instances(self.flat_masks.to(torch.float32), 1)
+        elif self._row is not None:
             self.flat_masks = self._row.adopt(self.flat_masks.to(torch.float32))
         elif self.persistent:                                               # (a slot's graphs read the masks through this address for every later frame)
             self.flat_masks = self.flat_masks.to(torch.float32).clone(memory_format=torch.contiguous_format)
-        self.sampling_weights = self._own(self.flat_masks.max(dim=-1).values.to(torch.float32).contiguous())          # main.py:620-624
+        self.sampling_weights = self._own(self.flat_masks[:, :N].max(dim=-1).values.to(torch.float32).contiguous())          # main.py:620-624
         self.ray_table = self.ray_remap = None
         if not self._prepare_sampler(config):
             raise UnsuitableFrameError("this frame's importance weights do not suit the table sampler (too much of the weight in fewer pixels "
@@ -449,7 +486,7 @@ class FrameOptimizer:
     # ---- fused glue (csrc/frame_step.h) ---------------------------------------------------------------------------------
     def _init_fused_glue(self):
         cfg, inp, dev = self.config, self.inputs, self.device
-        V, N = self.num_views, self.num_instances
+        V, N = self.num_views, self.capacity          # (a mixed batch's row: every per-instance buffer is laid out for the capacity)
         lib = _lib.load()
         det = self.detector
         w = cfg.loss_weights
@@ -470,9 +507,13 @@ class FrameOptimizer:
         b = self._glue = {}
         b["extrinsics"] = inp.extrinsic_matrices.to(**f32).reshape(V, 16).contiguous()
         b["intrinsics"] = inp.intrinsic_matrices.to(**f32).reshape(V, 9).contiguous()
-        b["gt_boxes"] = inp.boxes_2d.to(**f32).reshape(V, N, 4).contiguous()
+        b["gt_boxes"] = inp.boxes_2d.to(**f32).reshape(V, self.num_instances, 4).contiguous()
         b["visible"] = inp.visible_masks.to(device=dev, dtype=torch.uint8).contiguous()
-        if self.persistent:       # a slot OWNS what reset() overwrites: float32 contiguous inputs would otherwise be these very tensors -- the
+        if self._capacity is not None:
+            b["gt_boxes"], b["visible"] = self._adopt_instances(b["gt_boxes"], 1), self._adopt_instances(b["visible"], 1)
+            for name in ("extrinsics", "intrinsics"):
+                b[name] = self._row.adopt(b[name])
+        elif self.persistent:       # a slot OWNS what reset() overwrites: float32 contiguous inputs would otherwise be these very tensors -- the
             for name in ("extrinsics", "intrinsics", "gt_boxes", "visible"):      # caller's, and every other slot's built from the same frame
                 b[name] = b[name].clone() if self._row is None else self._row.adopt(b[name])
         new = self._new            # (a frame of a batch: everything below lives in the frame's row of the arena)
@@ -486,6 +527,9 @@ class FrameOptimizer:
         b["grad_instances"], b["grad_mlp"] = new((N, 16), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
         b["record"] = new(5, fill=0.0)
         b["masks"] = self.flat_masks.to(**f32).contiguous()        # (persistent: _prepare_rays made this the slot's own copy)
+        if self._capacity is not None:
+            b["header"] = new(8, torch.uint8, fill=0)              # vsrd_frame_header: int32 num_instances, float32 loss_scale
+            self._write_header()
         self.fused_hypernetwork = True
         self.rebind()
         b["hyper_workspace"] = new(lib.vsrd_hypernetwork_workspace_bytes(N), torch.uint8)
@@ -538,11 +582,11 @@ class FrameOptimizer:
                 state = self.optimizer.state.get(p)
                 if state and not (isinstance(state.get("step"), torch.Tensor) and state["step"].device == self.device and state["step"].dtype == torch.float32):
                     state["step"] = torch.as_tensor(float(state["step"]), dtype=torch.float32, device=self.device).clone()
-        self._adam = [adam_state_tensors(self.optimizer, p, group, self._row)
+        self._adam = [adam_state_tensors(self.optimizer, p, group, self._row, self._capacity)
                       for group, p in zip(self.optimizer.param_groups[:3], (det.locations, det.dimensions, det.orientations))]
         # the hypernetwork and the embeddings (residual phase) run through csrc/hypernetwork.h on the same footing: torch's module
         # owns the parameters, torch.optim.Adam owns the moments and counters, the kernels update both in place
-        self._hypernetwork = hypernetwork_tensors(self.hyper_distance_field, det.embeddings, self.optimizer, cfg.lr_gamma, self._row)
+        self._hypernetwork = hypernetwork_tensors(self.hyper_distance_field, det.embeddings, self.optimizer, cfg.lr_gamma, self._row, self._capacity)
         _destroy_graphs(self._graphs)
         # references keep every bound tensor alive until the next rebind: a replaced tensor's memory is not handed to somebody else
         # while a graph that writes through its address may still be replayed
@@ -576,8 +620,9 @@ class FrameOptimizer:
         frame.num_frames, frame.frame_stride = batch
         self._hypernetwork.num_frames, self._hypernetwork.frame_stride = batch
         det = self.detector
-        N = self.num_instances
+        N = self.capacity               # (the stride of every per-instance buffer; a mixed batch's row carries its own count in its header)
         residual = self.step_index >= cfg.warmup_steps
+        header = b.get("header")            # a mixed batch's row (FrameBatch(max_instances=...)): every launch takes the *_with_header twin
         main = torch.cuda.current_stream(self.device)
         stream = _lib.stream()
         rays_branch, net_branch = self._branches
@@ -599,14 +644,23 @@ class FrameOptimizer:
             if joins[0]:                # (inside a several-step graph the branch simply continues behind the hypernetwork backward of the step
                 net_branch.wait_stream(main)     # before: nothing on the main stream concerns it until this step's render adjoint)
             with torch.cuda.stream(net_branch):
-                _lib.check(lib.vsrd_hypernetwork_forward(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["mlp_weights"]),
-                                                         _lib.ptr(b["mlp_centred"]), _lib.stream()))
+                if header is not None:
+                    _lib.check(lib.vsrd_hypernetwork_forward_with_header(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["mlp_weights"]),
+                                                                         _lib.ptr(b["mlp_centred"]), header.data_ptr(), _lib.stream()))
+                else:
+                    _lib.check(lib.vsrd_hypernetwork_forward(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["mlp_weights"]),
+                                                             _lib.ptr(b["mlp_centred"]), _lib.stream()))
         prologue_args = (frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data),
                          _lib.ptr(b["extrinsics"]), _lib.ptr(b["intrinsics"]), _lib.ptr(b["gt_boxes"]), b["visible"].data_ptr(),
                          self.step_tensor.data_ptr(), b["scratch"].data_ptr(), b["scratch"].numel(), _lib.ptr(b["instances"]),
                          b["pd_indices"].data_ptr(), b["gt_indices"].data_ptr(), b["target_columns"].data_ptr(),
                          _lib.ptr(b["instance_weights"]), _lib.ptr(self.schedule), _lib.ptr(b["projection_losses"]), _lib.ptr(b["grad_raw"]))
-        if with_prologue:
+        if with_prologue and header is not None:
+            table = self.ray_table
+            code = lib.vsrd_frame_prologue_sample_with_header(*prologue_args, table.table.data_ptr(), table.count, cfg.num_rays,
+                                                              (cfg.seed + 1) & 0xFFFFFFFFFFFFFFFF, None, b["ray_indices"].data_ptr(), header.data_ptr(), stream)
+            _lib.check(code)
+        elif with_prologue:
             table = self.ray_table
             code = lib.vsrd_frame_prologue_sample(*prologue_args, table.table.data_ptr(), table.count, cfg.num_rays, (cfg.seed + 1) & 0xFFFFFFFFFFFFFFFF,
                                                   None, b["ray_indices"].data_ptr(), stream)          # (the table covers every pixel: no remap)
@@ -622,6 +676,8 @@ class FrameOptimizer:
                 self._draw_rays(b["ray_indices"], b["picks"])
             else:
                 _lib.check(code)
+        elif header is not None:
+            _lib.check(lib.vsrd_frame_prologue_with_header(*prologue_args, header.data_ptr(), stream))
         else:
             _lib.check(lib.vsrd_frame_prologue(*prologue_args, stream))
         if sampled and not with_prologue:
@@ -652,12 +708,22 @@ class FrameOptimizer:
         config = _lib.make_config(R, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, seed=cfg.seed, stream_offset=self.step_tensor, flags=flags,
                                   schedule=self.schedule, gather=(ray_indices, self.pixels_per_view, b["target_columns"], N), frames=frames,
                                   adjoint_slots_per_item=cfg.mlp_adjoint_item_slots if residual else 0)
-        loss_scale = 1.0 / (R * N)
-        if residual:
+        loss_scale = 1.0 / (R * self.num_instances)
+        if residual and header is not None:
+            _lib.check(lib.vsrd_render_residual_step_with_header(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
+                                                                 _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale, float(eikonal_ratio),
+                                                                 workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]),
+                                                                 _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_mlp"]), None, header.data_ptr(), stream))
+        elif residual:
             _lib.check(lib.vsrd_render_residual_step(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
                                                      _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale, float(eikonal_ratio),
                                                      workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]), _lib.ptr(b["grad_instances"]),
                                                      _lib.ptr(b["grad_mlp"]), None, stream))
+        elif header is not None:
+            _lib.check(lib.vsrd_render_silhouette_step_with_header(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
+                                                                   _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale,
+                                                                   workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]),
+                                                                   _lib.ptr(b["grad_instances"]), None, header.data_ptr(), stream))
         else:
             _lib.check(lib.vsrd_render_silhouette_step(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
                                                        _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale,
@@ -666,16 +732,23 @@ class FrameOptimizer:
         if fused_net:     # branch: backward through the hypernetwork, Adam on it and on the embeddings, both rates decayed (next to the epilogue)
             net_branch.wait_stream(main)
             with torch.cuda.stream(net_branch):
-                _lib.check(lib.vsrd_hypernetwork_backward_step(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["grad_mlp"]),
-                                                               float(weights["silhouette_loss"]), _lib.stream()))
+                if header is not None:
+                    _lib.check(lib.vsrd_hypernetwork_backward_step_with_header(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["grad_mlp"]),
+                                                                               float(weights["silhouette_loss"]), header.data_ptr(), _lib.stream()))
+                else:
+                    _lib.check(lib.vsrd_hypernetwork_backward_step(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["grad_mlp"]),
+                                                                   float(weights["silhouette_loss"]), _lib.stream()))
         groups = self.optimizer.param_groups
         # ExponentialLR decays every group's rate AFTER the optimiser step: the epilogue does it for the groups it steps itself (and, in
         # the box-only phase, for the two that have nothing to step); in the residual phase those two are decayed after torch's step
         others = (None, None) if residual else (_lib.ptr(groups[3]["lr"]), _lib.ptr(groups[4]["lr"]))
-        _lib.check(lib.vsrd_frame_epilogue(frame, _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_raw"]), _lib.ptr(b["projection_losses"]),
-                                           _lib.ptr(b["render_losses"]), float(eikonal_ratio), self._adam[0], self._adam[1], self._adam[2],
-                                           others[0], others[1], self.step_tensor.data_ptr(),
-                                           _lib.ptr(b["record"]), _lib.ptr(b["raw_gradients"]), stream))
+        epilogue_args = (frame, _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_raw"]), _lib.ptr(b["projection_losses"]), _lib.ptr(b["render_losses"]),
+                         float(eikonal_ratio), self._adam[0], self._adam[1], self._adam[2], others[0], others[1], self.step_tensor.data_ptr(),
+                         _lib.ptr(b["record"]), _lib.ptr(b["raw_gradients"]))
+        if header is not None:
+            _lib.check(lib.vsrd_frame_epilogue_with_header(*epilogue_args, header.data_ptr(), stream))
+        else:
+            _lib.check(lib.vsrd_frame_epilogue(*epilogue_args, stream))
         if residual and not fused_net:    # autograd + torch.optim.Adam (the box tensors have no .grad: skipped)
             mlp_weights.backward(b["grad_mlp"] * weights["silhouette_loss"])
             self.optimizer.step()
@@ -685,7 +758,7 @@ class FrameOptimizer:
             main.wait_stream(net_branch)
         if count:
             self.step_index += 1
-        record, raw = b["record"], b["raw_gradients"]
+        record, raw = b["record"], b["raw_gradients"][:self.num_instances]
         result = dict(iou_projection_loss=record[0], l1_projection_loss=record[1], silhouette_loss=record[2], loss=record[4],
                       raw_gradients=[raw[:, 0:3].unsqueeze(0), raw[:, 3:6].unsqueeze(0), raw[:, 6:8].unsqueeze(0)])
         if residual:
@@ -927,7 +1000,13 @@ class FrameOptimizer:
             raise ValueError("reset() belongs to a persistent graph-mode loop (FrameOptimizer(..., graph=True, persistent=True))")
         cfg, dev, b = self.config, self.device, self._glue
         V, N = self.num_views, self.num_instances
-        if tuple(inputs.soft_masks.shape) != (V, *[int(x) for x in self.inputs.image_size], N) or tuple(inputs.image_size) != tuple(self.inputs.image_size):
+        if self._capacity is not None:       # a mixed batch's row: any frame of its views and image size with 1..capacity instances
+            N = int(inputs.soft_masks.shape[-1])
+            if (tuple(inputs.soft_masks.shape[:-1]) != (V, *[int(x) for x in self.inputs.image_size]) or tuple(inputs.image_size) != tuple(self.inputs.image_size)
+                    or not 1 <= N <= self._capacity):
+                raise ValueError(f"a row of capacity {self._capacity} serves frames of shape {tuple(self.inputs.soft_masks.shape[:-1])} with 1..{self._capacity} "
+                                 f"instances, got {tuple(inputs.soft_masks.shape)}")
+        elif tuple(inputs.soft_masks.shape) != (V, *[int(x) for x in self.inputs.image_size], N) or tuple(inputs.image_size) != tuple(self.inputs.image_size):
             raise ValueError(f"a slot serves frames of ONE shape: {tuple(self.inputs.soft_masks.shape)}, got {tuple(inputs.soft_masks.shape)}")
         with _capture_lock, torch.no_grad():
             main = torch.cuda.current_stream(dev)
@@ -937,15 +1016,25 @@ class FrameOptimizer:
             cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
             self.camera_positions.copy_(cam)
             self.ray_directions.copy_(dirs.reshape(-1, 3))
-            self.flat_masks.copy_(inputs.soft_masks.reshape(-1, N))
+            self.flat_masks[:, :N].copy_(inputs.soft_masks.reshape(-1, N))
             if b["masks"].data_ptr() != self.flat_masks.data_ptr():
                 b["masks"].copy_(self.flat_masks)
-            torch.amax(self.flat_masks, dim=-1, out=self.sampling_weights)
+            torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)
             b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
             b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
-            b["gt_boxes"].copy_(inputs.boxes_2d.reshape(V, N, 4))
-            b["visible"].copy_(inputs.visible_masks)
+            b["gt_boxes"][:, :N].copy_(inputs.boxes_2d.reshape(V, N, 4))
+            b["visible"][:, :N].copy_(inputs.visible_masks)
             self.inputs = inputs
+            if self._capacity is not None and N != self.num_instances:
+                # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
+                # addresses: the pointer blocks and the captured graphs stay valid)
+                for param in (self.detector.locations, self.detector.dimensions, self.detector.orientations, self.detector.embeddings):
+                    param.data = _instance_prefix(param.data, N)
+                    state = self.optimizer.state.get(param)
+                    if state:
+                        state["exp_avg"], state["exp_avg_sq"] = _instance_prefix(state["exp_avg"], N), _instance_prefix(state["exp_avg_sq"], N)
+                self.num_instances = N
+                self._bound = self._bound_tensors()
             # ---- parameters, optimiser, counters ----
             with _initial_draw:                                   # (OptimizationConfig.init_seed, for THIS frame: seed and draw as one step -- the generator is the process's,
                 if init_seed is not None:                         #  and the capture gate lets several frames' threads in here at once)
@@ -967,6 +1056,8 @@ class FrameOptimizer:
             self.step_index = 0
             for name in ("record", "raw_gradients", "grad_raw", "grad_instances", "grad_mlp", "projection_losses", "render_losses"):
                 b[name].zero_()
+            if self._capacity is not None:
+                self._write_header()
             suits = self._prepare_sampler(cfg)
             main.synchronize()
         return suits
@@ -1051,13 +1142,27 @@ class FrameBatch:
     Like a frame slot, a batch is built and captured once (``capture_all``) and then serves group after group of frames through
     ``reset(f, inputs, init_seed)``; a last group of fewer than B frames runs with ``active < B`` (the first ``active`` rows)."""
 
-    def __init__(self, inputs, config, device, init_seeds=None):
+    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None):
+        """``max_instances`` None: every frame has ONE shape (views, height, width, instances).  An integer: a MIXED batch -- the frames
+        share (views, height, width) and have 1..max_instances instances each; every row is laid out for ``max_instances`` (the capacity)
+        and carries its frame's own count in a header (include/vsrd_hip.h, vsrd_frame_header), and frame f still walks, bit for bit, the
+        trajectory it walks in a slot of its own N, through both phases."""
         inputs = list(inputs)
         if not inputs:
             raise ValueError("FrameBatch needs at least one frame")
         shape = tuple(inputs[0].soft_masks.shape)
-        if any(tuple(i.soft_masks.shape) != shape or tuple(i.image_size) != tuple(inputs[0].image_size) for i in inputs):
-            raise ValueError("the frames of a batch share ONE shape (views, height, width, instances)")
+        self.max_instances = None if max_instances is None else int(max_instances)
+        if self.max_instances is None:
+            if any(tuple(i.soft_masks.shape) != shape or tuple(i.image_size) != tuple(inputs[0].image_size) for i in inputs):
+                raise ValueError("the frames of a batch share ONE shape (views, height, width, instances)")
+        else:
+            if not 1 <= self.max_instances <= _lib.MAX_INSTANCES:
+                raise ValueError(f"max_instances: 1..{_lib.MAX_INSTANCES}, got {self.max_instances}")
+            if any(tuple(i.soft_masks.shape[:-1]) != shape[:-1] or tuple(i.image_size) != tuple(inputs[0].image_size) for i in inputs):
+                raise ValueError("the frames of a mixed batch share (views, height, width)")
+            if any(not 1 <= int(i.soft_masks.shape[-1]) <= self.max_instances for i in inputs):
+                raise ValueError(f"the frames of a mixed batch have 1..max_instances = {self.max_instances} instances")
+            shape = (*shape[:-1], self.max_instances)
         self.size = len(inputs)
         import dataclasses
         if config.mlp_adjoint_item_slots == 0:
@@ -1079,7 +1184,7 @@ class FrameBatch:
             for position, frame_inputs in enumerate(candidates):
                 row.cursor, row.layout = 0, []                           # (a founder that failed had begun to fill the row)
                 try:
-                    member = FrameOptimizer(frame_inputs, cfg, self.device, graph=True, persistent=True, row=row)
+                    member = FrameOptimizer(frame_inputs, cfg, self.device, graph=True, persistent=True, row=row, capacity=self.max_instances)
                 except UnsuitableFrameError:
                     if position == 0:
                         self.unsuitable_founders.append(f)
@@ -1152,7 +1257,7 @@ class FrameBatch:
     def outputs(self, f):
         """Frame f's record of its last step: the dictionary ``FrameOptimizer.step`` returns (device tensors, rewritten by every step)."""
         m = self.frames[f]
-        record, raw = m._glue["record"], m._glue["raw_gradients"]
+        record, raw = m._glue["record"], m._glue["raw_gradients"][:m.num_instances]
         result = dict(iou_projection_loss=record[0], l1_projection_loss=record[1], silhouette_loss=record[2], loss=record[4],
                       raw_gradients=[raw[:, 0:3].unsqueeze(0), raw[:, 3:6].unsqueeze(0), raw[:, 6:8].unsqueeze(0)])
         if m.step_index > self.config.warmup_steps:
@@ -1251,7 +1356,8 @@ class FrameBatch:
         return len(self._graphs)
 
     def reset(self, f, inputs, init_seed=None):
-        """Row f starts another frame (``FrameOptimizer.reset``).  False: the frame does not suit the table sampler -- optimise it in a loop of its own."""
+        """Row f starts another frame (``FrameOptimizer.reset``; a mixed batch's row takes any frame of its views and image size with 1..max_instances
+        instances, ValueError otherwise).  False: the frame does not suit the table sampler -- optimise it in a loop of its own."""
         return self.frames[f].reset(inputs, init_seed=init_seed)
 
     def close(self):
