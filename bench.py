@@ -6,7 +6,12 @@ One step = one pass of the hot path over one dense frame: the fused two-pass ren
 backward through the box decode (and the hypernetwork) to the raw parameters, Adam update.  Inputs are resident in HBM
 before the timed region.  Defaults = BASELINE.json config 2 (9 views x 376x1408, 16 instances, 64 samples/ray).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--residual] [--schedule start|mid|end] [--no-culling] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--residual] [--schedule start|mid|end] [--no-culling] ... [--full]
+
+A plain run does only what its headline figure needs: it sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints
+the line (with ``roofline`` / ``roofline_valu``, computed from the timed steps' own launch timings and the committed counters).
+``--full`` also measures, after the headline and on one rank only, the CPU baseline (``cpu_baseline``) and, for the default workload,
+config 3, config 5 and the reference's native mode as ``extra_regimes`` (child processes of their own).
 
 Multi-GPU: target frames are independent optimisation problems (README.md:128) -- every rank renders its own frame, there is no
 data-path collective ("scaling": "weak"); RCCL carries the barriers and the max-reduce of the timing.  Either the driver starts
@@ -62,12 +67,14 @@ def parse_args(argv=None):
     parser.add_argument("--no-skip-misses", action="store_true")
     parser.add_argument("--wave-per-ray", action="store_true",
                         help="VSRD_FLAG_STEP_WAVE_PER_RAY: one ray per wave for the fused box-only step (A/B against four rays per wave)")
-    parser.add_argument("--cpu-rays", type=int, default=0, help="rays of the CPU-baseline sample (default 16384; 1408 with --residual)")
-    parser.add_argument("--cpu-chunk", type=int, default=0, help="rays per oracle call (default: one image row; 352 with --residual)")
+    parser.add_argument("--full", action="store_true",
+                        help="after the headline, also measure the CPU baseline (`cpu_baseline`) and, for the default workload, the `extra_regimes` "
+                             "object (config 3 / config 5 at full size and the reference's native mode); a plain run measures the headline only")
+    parser.add_argument("--cpu-rays", type=int, default=0, help="with --full: rays of the CPU-baseline sample (default 16384; 1408 with --residual)")
+    parser.add_argument("--cpu-chunk", type=int, default=0, help="with --full: rays per oracle call (default: one image row; 352 with --residual)")
     parser.add_argument("--cpu-threads", type=int, default=16)   # best of {8,16,32,64} on the 2x64-core EPYC 9575F GPU host (r01)
-    parser.add_argument("--no-cpu-baseline", action="store_true")
-    parser.add_argument("--no-extra-regimes", action="store_true",
-                        help="default run only: skip the `extra_regimes` object (config 3 / config 5 at full size and the reference's native mode, measured after the headline)")
+    parser.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` object")
+    parser.add_argument("--no-extra-regimes", action="store_true", help="with --full: skip the `extra_regimes` object")
     parser.add_argument("--launcher-selftest", action="store_true", help="no rendering: exercise the N-rank launch/report path (gloo, CPU)")
     parser.add_argument("--ranks-share-gpu", action="store_true",
                         help="TEST ONLY: all ranks render on cuda:0 and rendezvous over gloo -- runs the real step under the multi-rank "
@@ -504,12 +511,12 @@ def run_rank(args):
             if share:
                 result["metric"] = "ranks share ONE GPU (--ranks-share-gpu): a test of the multi-rank path, NOT a scaling measurement; " + result["metric"]
             result.update(rooflines(args, kernels, R, fused))
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 result["cpu_baseline"] = cpu_baseline(args, sched, frame, lambda a, b: targets[a:b].cpu(), hyper_state,
                                                       min(args.cpu_threads, os.cpu_count() or 1))
             default_workload = (V, H, W, N, S) == (9, 376, 1408, 16, 64) and not args.residual and fused and args.schedule == "mid" \
                 and not args.no_culling and not args.no_skip_misses and not args.wave_per_ray
-            if world == 1 and default_workload and not args.no_extra_regimes:
+            if world == 1 and args.full and default_workload and not args.no_extra_regimes:
                 del targets, directions, origins
                 torch.cuda.empty_cache()
                 result["extra_regimes"] = extra_regimes()
@@ -614,7 +621,7 @@ def rooflines(args, kernels, R, fused):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# extra regimes of the default run: measured AFTER the headline, each in a child process
+# extra regimes of a --full run: measured AFTER the headline, each in a child process
 # ---------------------------------------------------------------------------------------------------------------------
 
 def extra_regimes():
@@ -655,7 +662,7 @@ def extra_regimes():
     frames = ["value", "unit", "n_gpus", "frames", "seconds", "frames_per_s_per_gpu", "per_rank_seconds", "seconds_per_frame_per_gpu", "capture_seconds_per_frame",
               "restarts", "max_restarts", "mean_final_loss", "ranks", "procs_per_gpu", "frames_in_flight_per_process", "control_plane", "frame_batch", "queue",
               "mlp_products", "slot_setup_seconds", "graphs_per_slot", "frames_outside_slots", "frames_with_unhealthy_draws"]
-    base = ["bench.py", "--no-cpu-baseline", "--no-extra-regimes"]
+    base = ["bench.py"]                     # plain runs: each child measures its own headline only
     tool = os.path.join("tools", "native_mode_bench.py")
     regimes = {
         "note": "measured after the headline's timed region, one child process each; config 2 above stays the metric's workload",

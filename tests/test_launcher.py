@@ -221,6 +221,31 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path, residual):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain `bench.py` run reports the headline with its roofline objects and measures nothing else; `--full` adds the CPU baseline
+    of the same frame after it (`extra_regimes` belong to the default full-size workload only, minutes of child runs: not tested here)."""
+    import json
+    import subprocess
+    import sys
+    bench = os.path.join(ROOT, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    sizes = ["--steps", "2", "--warmup", "1", "--views", "2", "--height", "94", "--width", "352", "--instances", "4", "--samples", "32"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--cpu-rays", "704"])):
+        out = subprocess.run([sys.executable, bench, *sizes, *extra], capture_output=True, text=True, timeout=900, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        found = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1
+        lines[name] = json.loads(found[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == 2 and line["ms_per_step"] > 0.0 and line["unit"] == "rays/s" and line["dtype"] == "f32"
+        assert line["roofline"]["launch_ms"] > 0.0 and "roofline_valu" in line
+    assert "cpu_baseline" not in plain and "extra_regimes" not in plain
+    assert full["cpu_baseline"]["kind"] == "port" and full["cpu_baseline"]["value"] > 0.0 and "extra_regimes" not in full
+
+
+@pytest.mark.gpu
 def test_native_frames_entry_point_two_ranks_on_one_gpu(tmp_path):
     """The frames/s entry point: `python bench.py --native --gpus 2` = vsrd_amd.launcher.main -- two ranks spawned
     by the launcher itself (both on cuda:0: --ranks-share-gpu, gloo), manifest broadcast, ordered start-up barrier, every rank
