@@ -261,7 +261,7 @@ def test_config3_full_size_fused_step(dev):
 
 def test_chunked_residual_step_adds_up(dev):
     """A residual step whose MLP-adjoint seeds exceed the 6 GiB budget is cut into chunks of rays that accumulate into the same
-    partial rows (api.hip: plan_residual_step).  At the reference's S = 100 (four rounds: residual_step_pair_kernel<4>) and N = 16 a
+    partial rows (api.hip: plan_residual_step, laid out by lay_out).  At the reference's S = 100 (four rounds: residual_step_pair_kernel<4>) and N = 16 a
     chunk is 39 321 rays, so 45 056 rays run as two chunks; the one-kernel form (VSRD_FLAG_RESIDUAL_SINGLE_KERNEL) takes them in
     one piece.  Loss, labels and every gradient of the two must agree."""
     import bench

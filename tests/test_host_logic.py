@@ -42,6 +42,99 @@ def test_header_symbols_are_exported(lib):
     assert lib.vsrd_error_string(-1) == b"invalid argument"
 
 
+def test_workspace_sizes_are_the_parents(lib, monkeypatch):
+    """The sizing contract of the C ABI, pinned.  Hosts size frame rows and arenas from these functions, so a change of the launch plans
+    must not move a byte.  Every number below was recorded from the library of the commit BEFORE the launch planning was collapsed into
+    plan_rows / lay_out (csrc/api.hip), not from the code under test.
+    The sizing functions return the larger of the one-kernel floor (vsrd_workspace_bytes) and the split form's plan, so a plan's branch
+    shows here only where its total exceeds the floor (some 41 000 ray-rounds per launch).  Above the floor: one, two and four rounds and
+    the refused eight (S = 16 .. 129; distances 32 .. 258), a launch cut into chunks (N = 16, S = 64, R = 200000 against the 6 GiB seed
+    budget), and each clamp of the item size: 4 (N = 1, one round, R = 60000: 60000 / 16384 = 3 -> 4, in both plans), 32 (N = 16,
+    R = 30000: 58 -> 32) and 64 (N = 16, R = 100000: 195 -> 64).  NOT visible through these functions, and pinned only as the floor: the
+    pair kernel on and off at two rounds (R = 2048 / 2049: 7 MB of seeds per instance against a floor of 74 MB), and the front kernels' LDS
+    refusal at N = 64, S = 128 (the one-wave-per-ray plan is refused, the pair plan is taken and has the size the refused one would have).
+    R = 0, N = 1 at one ray and the invalid arguments (0) complete the table."""
+    forced = [name for name in ("VSRD_PAIR_MAX_RAYS", "VSRD_SLOTS_PER_ITEM") if os.environ.get(name) is not None]
+    for name in forced:
+        monkeypatch.delenv(name)
+    if forced:
+        pytest.skip(f"{forced} set: the library froze its switches at the first call, the plans below are the defaults'")
+    expected = {
+        "vsrd_workspace_bytes": [
+            ((1, 0), 4194304),
+            ((1, 1), 73748480),
+            ((16, 0), 67108864),
+            ((16, 1), 1179975680),
+            ((64, 1), 4719902720),
+            ((0, 0), 0),
+            ((65, 1), 0),
+        ],
+        "vsrd_residual_step_workspace_bytes": [
+            ((1, 16, 60000), 208973008),
+            ((16, 16, 60000), 1958398784),
+            ((16, 32, 60000), 1958398784),
+            ((16, 33, 30000), 1992084288),
+            ((16, 64, 30000), 1992084288),
+            ((16, 65, 15000), 2059455296),
+            ((16, 100, 15000), 2059455296),
+            ((16, 128, 15000), 2059455296),
+            ((16, 129, 60000), 1179975680),
+            ((16, 64, 2048), 1179975680),
+            ((16, 64, 2049), 1179975680),
+            ((16, 64, 200000), 6889404128),
+            ((1, 16, 1), 73748480),
+            ((16, 64, 100000), 6140264288),
+            ((64, 128, 15000), 7377815184),
+            ((64, 128, 1000), 4719902720),
+            ((64, 100, 15000), 7377815184),
+            ((3, 100, 132352), 3201244976),
+            ((16, 64, 0), 1179975680),
+            ((1, 100, 132352), 1067092592),
+            ((0, 64, 100), 0),
+            ((65, 64, 100), 0),
+            ((16, 1, 100), 0),
+            ((16, 257, 100), 0),
+            ((16, 64, -1), 0),
+        ],
+        "vsrd_render_backward_workspace_bytes": [
+            ((16, 0, 128, 60000), 67108864),
+            ((1, 1, 32, 60000), 208947040),
+            ((16, 1, 32, 60000), 1958228816),
+            ((16, 1, 65, 60000), 1958228816),
+            ((16, 1, 66, 30000), 1991914320),
+            ((16, 1, 200, 20000), 2698975328),
+            ((16, 1, 257, 20000), 2698975328),
+            ((16, 1, 258, 20000), 1179975680),
+            ((64, 1, 256, 20000), 7747658272),
+            ((16, 1, 128, 200000), 7259602528),
+            ((16, 1, 128, 0), 1179975680),
+            ((1, 1, 2, 1), 73748480),
+            ((0, 1, 128, 10), 0),
+            ((16, 1, 1, 10), 0),
+            ((16, 1, 513, 10), 0),
+            ((16, 1, 128, -1), 0),
+        ],
+        "vsrd_hypernetwork_workspace_bytes": [
+            ((1,), 235904),
+            ((8,), 1812864),
+            ((64,), 14428544),
+            ((0,), 0),
+            ((65,), 0),
+        ],
+        "vsrd_frame_scratch_bytes": [
+            ((1, 1), 144),
+            ((4, 8), 4608),
+            ((32, 64), 294912),
+            ((0, 1), 0),
+            ((33, 1), 0),
+            ((1, 65), 0),
+        ],
+    }
+    for name, rows in expected.items():
+        for args, size in rows:
+            assert getattr(lib, name)(*args) == size, (name, args)
+
+
 def test_struct_layout_matches_header(tmp_path):
     """The ctypes structures against the C compiler's view of include/vsrd_hip.h itself (gcc: sizeof / offsetof of every member that
     matters), not against numbers copied into the test."""

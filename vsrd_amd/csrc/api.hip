@@ -11,7 +11,7 @@
 #include "projection.h"
 #include "frame_step.h"
 #include "hypernetwork.h"
-#include "split_front.h"
+#include "launch.h"
 
 namespace {
 
@@ -46,9 +46,6 @@ const Switches& switches() {
     }();
     return frozen;
 }
-int grid_cap() { return switches().grid_blocks; }
-constexpr size_t kLdsLimit = 160 * 1024;     // gfx950 LDS per CU
-constexpr size_t kLdsDefault = 64 * 1024;    // dynamic LDS without opting in
 
 struct Geometry {
     int blocks;
@@ -65,7 +62,7 @@ bool plan(int num_rays, size_t floats_per_wave, Geometry* g) {
     g->threads = waves * kWave;
     g->lds_bytes = per_wave * waves;
     const long long want = (static_cast<long long>(num_rays) + waves - 1) / waves;
-    const int cap = grid_cap();
+    const int cap = switches().grid_blocks;
     g->blocks = static_cast<int>(want < 1 ? 1 : (want > cap ? cap : want));
     return true;
 }
@@ -75,6 +72,10 @@ bool plan(int num_rays, size_t floats_per_wave, Geometry* g) {
 // = 1.33 phases cost 2).  Performance only -- correctness never depends on residency (no inter-workgroup communication).
 template <typename Kernel>
 void fit_to_residency(Kernel kernel, Geometry* g) {
+    // Measured on C2 (r01): capping the grid at `resident` (one phase) is 5 % SLOWER than 2048 workgroups -- rays differ a lot in
+    // cost (culling, early outs) and the extra workgroups act as dynamic load balancing -- so the grid is left alone unless the
+    // experiment switch asks for it.
+    if (!switches().cap_to_residency) return;
     static int num_cus = 0;
     if (num_cus == 0) {
         int device = 0;
@@ -85,19 +86,12 @@ void fit_to_residency(Kernel kernel, Geometry* g) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), g->threads, g->lds_bytes) != hipSuccess || per_cu < 1)
         return;
-    const int resident = per_cu * num_cus;
-    // Measured on C2 (r01): capping the grid at `resident` (one phase) is 5 % SLOWER than 2048 workgroups -- rays differ a lot in
-    // cost (culling, early outs) and the extra workgroups act as dynamic load balancing -- so the grid is left alone unless the
-    // experiment switch asks for it.
-    if (switches().cap_to_residency && g->blocks > resident) g->blocks = resident;
+    if (g->blocks > per_cu * num_cus) g->blocks = per_cu * num_cus;
 }
 
 template <typename Kernel>
 int opt_in_lds(Kernel kernel, size_t bytes) {
-    if (bytes <= kLdsDefault) return VSRD_OK;
-    const hipError_t error = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (error != hipSuccess && switches().debug) fprintf(stderr, "libvsrd_hip: LDS opt-in of %zu bytes failed: %s\n", bytes, hipGetErrorString(error));
-    return error == hipSuccess ? VSRD_OK : VSRD_E_LAUNCH;
+    return opt_in(kernel, bytes, switches().debug) ? VSRD_OK : VSRD_E_LAUNCH;
 }
 
 int launch_status() {
@@ -218,6 +212,247 @@ size_t partial_floats(int num_instances, bool residual) {
     return box + mlp + residual_cache_floats(num_instances, residual);
 }
 
+
+// The workspace of the one-kernel forms (vsrd_workspace_bytes): the box partials of the largest grid, then -- residual fields -- the MLP
+// partials, the jets and the seeds of kMaxBlocksResidual x kResidualWaves waves (partial_floats).
+struct OneKernelWorkspace {
+    float* partials; float* mlp_partials; float4* jets; float* seeds;
+};
+OneKernelWorkspace one_kernel_workspace(void* workspace, int num_instances, bool residual) {
+    OneKernelWorkspace w;
+    w.partials = static_cast<float*>(workspace);
+    w.mlp_partials = w.partials + static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * num_instances * kGradStride;
+    float* jets = w.mlp_partials + (residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * num_instances * kMlpWeights : 0);
+    w.jets = reinterpret_cast<float4*>(jets);
+    w.seeds = jets + residual_jet_floats(num_instances, residual);
+    return w;
+}
+
+// The multi-ray ("rows") mappings of quad_step.h, box-only fields: four neighbouring rays per wave, 16 lanes each (quad: N <= 16,
+// S <= 64), or two, 32 lanes each (pair: N <= 64, S <= 128: BASELINE config 5).  A launch that fills its shape (S = 4 x lanes, more than half
+// of the shape's instance slots: BASELINE configs 2 and 5) runs the hot kernel instantiated for that S with the instance tables padded
+// to the shape's count (quad_step.h: kFull).
+struct RowsPlan {
+    bool rows;                  // one of the two mappings takes the launch
+    bool quad, full;            // (pair: rows && !quad)
+    int lanes, rays_per_wave, shape_instances;
+    int rounds;                 // rounds of `lanes` samples of a pass, rounded up to the instantiated {1, 2, 4} (pair: {2, 4}); only the silhouette step is instantiated by it
+    size_t lds_floats;          // per wave
+    size_t num_groups;          // groups of rays_per_wave rays, one per wave and turn
+    size_t flag_bytes;          // behind the waves' partial rows: two summary words + one byte per group, "the hot kernel could not serve this group"
+};
+// num_distances: a ray's merged samples, 2 S (vsrd_render_backward is handed that number, and it may be odd: only 8 x lanes is `full`)
+RowsPlan plan_rows(int num_instances, int num_distances, int num_rays, uint32_t flags, bool allowed) {
+    RowsPlan r = {};
+    r.rows = allowed && !(flags & VSRD_FLAG_STEP_WAVE_PER_RAY) && num_instances <= kPairMaxInstances && num_distances <= 2 * kPairMaxSamples;
+    if (!r.rows) return r;
+    const int S = (num_distances + 1) / 2;
+    r.quad = num_instances <= kQuadMaxInstances && num_distances <= 2 * kQuadMaxSamples;
+    r.lanes = r.quad ? kRowLanes : 32;
+    r.rays_per_wave = kWave / r.lanes;
+    r.shape_instances = r.quad ? kQuadMaxInstances : kPairMaxInstances;
+    r.full = num_distances == 8 * r.lanes && 2 * num_instances > r.shape_instances && !switches().no_full_shape;
+    r.rounds = (r.quad && S <= r.lanes) ? 1 : (S <= 2 * r.lanes ? 2 : 4);
+    r.lds_floats = static_cast<size_t>(quad_lds_floats(S, r.full ? r.shape_instances : num_instances, r.lanes));
+    r.num_groups = (static_cast<size_t>(num_rays) + r.rays_per_wave - 1) / r.rays_per_wave;
+    r.flag_bytes = 16 + ((r.num_groups + 15) & ~static_cast<size_t>(15));
+    return r;
+}
+
+// The partial buffer holds one row of `width` floats per wave (a gradient row; + 1: the wave's loss partial, in the tail of the same
+// budget) and behind the rows `flag_bytes` (RowsPlan): cap the grid to what `bytes` hold.  False: not even one workgroup's rows fit.
+bool cap_to_workspace(size_t bytes, int width, size_t flag_bytes, Geometry* g) {
+    const int waves_per_block = g->threads / kWave;
+    if (flag_bytes + static_cast<size_t>(waves_per_block) * width * sizeof(float) > bytes) return false;
+    const int max_waves = static_cast<int>((bytes - flag_bytes) / sizeof(float) / width);
+    if (g->blocks * waves_per_block > max_waves) g->blocks = max_waves / waves_per_block;
+    return true;
+}
+
+// two kernels on one grid (quad_step.h): the hot body (rotations about y, fixed soft-min shift), then everything it left over
+template <typename Kernel, typename... Args>
+void launch_hot_then_rest(Kernel hot, Kernel rest, const Geometry& g, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(hot, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, args...);
+    hipLaunchKernelGGL(rest, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, args...);
+}
+
+// ---- the split form of the residual step and of vsrd_render_backward on residual fields (render_kernels.h: a front kernel +
+// residual_mlp_adjoint_kernel), the default --------------------------------------------------------------------------------------
+constexpr size_t kSeedBudgetBytes = size_t(6) << 30;     // seeds of one chunk of rays: N x chunk x rounds x 1792 B (a launch is cut into chunks that fit)
+constexpr int kFrontBlocks = 512;                        // x 4 waves = two waves on each of the 1024 SIMDs
+constexpr int kMlpAdjointBlocks = 4096;                  // single-wave workgroups, dynamic item fetch (two per SIMD are resident)
+constexpr int kPairBlocks = 1024;                        // residual_step_pair_kernel: x 2 waves = two waves on each of the 1024 SIMDs
+
+struct ResidualStepPlan {
+    int rounds, chunk, front_blocks, front_waves, slots_per_item, items_per_instance;
+    bool pair;                     // few rays: residual_step_pair_kernel (a ray split over the two waves of a workgroup)
+    long long slots_per_instance;
+    size_t front_lds;
+    // workspace layout, in floats from the base
+    size_t box_partials, loss_partials, jets, box_extra, counter, segment_sums, seeds, item_rows, masks, item_flags, images, total_bytes;
+};
+
+// a chunk's front grid (one wave per ray) and its slots; returns the item size that balances it, before the caller's clamps: enough
+// items to balance ~2000 waves, few enough that an item amortises its partial row (6.6 KB written and read once)
+long long size_chunk(ResidualStepPlan* p, long long chunk, int N) {
+    p->chunk = static_cast<int>(chunk);
+    const long long want = (chunk + kMaxWavesPerBlock - 1) / kMaxWavesPerBlock;
+    p->front_blocks = static_cast<int>(want > kFrontBlocks ? kFrontBlocks : want);
+    p->front_waves = p->front_blocks * kMaxWavesPerBlock;
+    p->slots_per_instance = chunk * p->rounds;
+    return (p->slots_per_instance * N) / 16384;
+}
+
+// The regions of the workspace, from the plan's front_waves, rounds, slots and items.  loss_floats: the front waves' loss partials.
+void lay_out(ResidualStepPlan* p, int N, long long per_item, size_t loss_floats, bool with_images) {
+    p->slots_per_item = static_cast<int>(per_item);
+    p->items_per_instance = static_cast<int>((p->slots_per_instance + per_item - 1) / per_item);
+    size_t at = 0;
+    auto take = [&](size_t floats) { const size_t here = at; at += (floats + 3) & ~size_t(3); return here; };
+    p->box_partials = take(static_cast<size_t>(p->front_waves) * N * kGradStride);
+    p->loss_partials = take(loss_floats);
+    p->jets = take(static_cast<size_t>(p->front_waves) * jet_wave_float4s(p->rounds, N) * 4);
+    p->box_extra = take(static_cast<size_t>(N) * kGradStride);
+    p->segment_sums = take(static_cast<size_t>(N) * kItemSegments * kItemRowFloats);
+    p->seeds = take(static_cast<size_t>(N) * p->slots_per_instance * kSeedFloats * kWave);
+    p->item_rows = take(static_cast<size_t>(N) * p->items_per_instance * kItemRowFloats);
+    p->masks = take((static_cast<size_t>(N) * p->slots_per_instance + 3) / 4);
+    p->counter = take(4);                                // right behind the masks: one memset clears both
+    p->item_flags = take((static_cast<size_t>(N) * p->items_per_instance + 3) / 4);
+    p->images = with_images ? take(static_cast<size_t>(N) * kMlpImageWords) : at;       // VSRD_FLAG_MLP_SPLIT_BF16: the instances' operand images (residual.h)
+    p->total_bytes = at * sizeof(float);
+}
+
+bool plan_residual_step(int N, int S, int num_rays, bool allow_pair, ResidualStepPlan* p, int slots_per_item = 0) {
+    p->rounds = rounds_for(2 * S - 1);
+    if (p->rounds < 1 || p->rounds > 4) return false;
+    // four rounds (S in (64, 128]): the one-wave-per-ray kernel needs 308 registers (one wave per SIMD), the pair kernel 256 -- the pair
+    // kernel wins at every launch size (132 k rays, S = 100: 90.3 against 97.9 ms); two rounds: only while a launch cannot fill the SIMDs
+    // (VSRD_PAIR_MAX_RAYS = 0 turns the pair kernel off for them)
+    p->pair = allow_pair && num_rays >= 1 && (p->rounds == 4 || (p->rounds == 2 && num_rays <= switches().pair_max_rays));
+    p->front_lds = p->pair ? static_cast<size_t>(residual_pair_lds_floats(S, N)) * sizeof(float)
+                           : static_cast<size_t>(residual_front_lds_floats(S, N)) * sizeof(float) * kMaxWavesPerBlock;
+    if (p->front_lds > kLdsLimit / 2) return false;     // two workgroups per CU = two waves per SIMD (one wave per ray at N = 64, S = 128: 93 KB -> the single-kernel form)
+    const size_t per_ray = static_cast<size_t>(N) * p->rounds * kSeedFloats * kWave * sizeof(float);
+    long long chunk = static_cast<long long>(kSeedBudgetBytes / per_ray);
+    if (chunk < 256) chunk = 256;
+    if (chunk > num_rays) chunk = num_rays < 1 ? 1 : num_rays;
+    long long per_item = size_chunk(p, chunk, N);
+    if (p->pair) {
+        p->front_blocks = static_cast<int>(chunk > kPairBlocks ? kPairBlocks : chunk);
+        p->front_waves = p->front_blocks * kPairWaves;
+    }
+    // (round 6: launches that leave >= 32 k items even at the largest item -- config 3's chunks of 110 k rays -- take 64 slots per item: same
+    //  speed as 32 or 48 (3.66-3.70 Mrays/s, tools/gpu_r06q.sh), half the partial rows written and reduced: 35 -> 17 GB per config-3 step)
+    per_item = per_item < 4 ? 4 : (per_item >= 128 ? 64 : (per_item > 32 ? 32 : per_item));
+    const int forced = switches().slots_per_item;                        // experiment switch
+    if (forced >= 1 && forced <= 64) per_item = forced;
+    if (slots_per_item >= 1 && slots_per_item <= 64) per_item = slots_per_item;      // vsrd_render_config::adjoint_slots_per_item
+    lay_out(p, N, per_item, static_cast<size_t>(p->front_waves) * 2, true);
+    return true;
+}
+
+// vsrd_render_backward on residual fields in the split form.  The plan is the residual step's, with the chunk of rays sized to what the
+// caller's workspace holds (at least min(num_rays, 64) rays, else the caller falls back to render_backward_kernel<K, true>).
+bool plan_backward_split(int N, int num_distances, int num_rays, size_t budget_bytes, ResidualStepPlan* p) {
+    p->rounds = rounds_for(num_distances - 1);
+    if (p->rounds < 1 || p->rounds > 4) return false;
+    p->pair = false;
+    p->front_lds = static_cast<size_t>(backward_front_lds_floats(num_distances, N)) * sizeof(float) * kMaxWavesPerBlock;
+    if (p->front_lds > kLdsDefault) return false;
+    const size_t per_ray = static_cast<size_t>(N) * p->rounds * kSeedFloats * kWave * sizeof(float);
+    long long chunk = static_cast<long long>(kSeedBudgetBytes / per_ray);
+    if (chunk > num_rays) chunk = num_rays < 1 ? 1 : num_rays;
+    for (;; chunk = chunk * 3 / 4) {                                       // the largest chunk whose whole layout fits the budget
+        if (chunk < (num_rays < 64 ? num_rays : 64)) return false;
+        const long long per_item = size_chunk(p, chunk, N);
+        lay_out(p, N, per_item < 4 ? 4 : (per_item > 32 ? 32 : per_item), 4, false);
+        if (p->total_bytes <= budget_bytes) return true;
+        if (chunk <= 1) return false;
+    }
+}
+
+// the regions of a planned workspace as pointers
+struct SplitWorkspace {
+    float* box_partials; float* loss_partials; float4* jets; float* box_extra; unsigned* counter; float* segment_sums; float* seeds; float* item_rows;
+    unsigned char* masks; unsigned char* item_flags; unsigned* images;
+    size_t clear_bytes;         // tile masks + the item counter's 16-byte slot (a multiple of 16 bytes: one fill kernel, not two)
+};
+SplitWorkspace split_workspace(void* workspace, const ResidualStepPlan& p) {
+    float* base = static_cast<float*>(workspace);
+    SplitWorkspace w;
+    w.box_partials = base + p.box_partials;
+    w.loss_partials = base + p.loss_partials;
+    w.jets = reinterpret_cast<float4*>(base + p.jets);
+    w.box_extra = base + p.box_extra;
+    w.counter = reinterpret_cast<unsigned*>(base + p.counter);
+    w.segment_sums = base + p.segment_sums;
+    w.seeds = base + p.seeds;
+    w.item_rows = base + p.item_rows;
+    w.masks = reinterpret_cast<unsigned char*>(base + p.masks);
+    w.item_flags = reinterpret_cast<unsigned char*>(base + p.item_flags);
+    w.images = reinterpret_cast<unsigned*>(base + p.images);
+    w.clear_bytes = (p.counter - p.masks + 4) * sizeof(float);
+    return w;
+}
+
+// A chunk's tail, behind its front kernel: the MLP adjoint by instance over the chunk's seeds (images: its split-bf16 form, which reads
+// the operand images the front kernel read), then the two deterministic reductions of its item rows into grad_mlp_weights and box_extra.
+int32_t launch_adjoint_tail(const vsrd_field* field, const unsigned* images, uint32_t flags, const ResidualStepPlan& p, const SplitWorkspace& w, int rays,
+                            bool accumulate, float* grad_mlp_weights, const Frames& frames, const FrameHeader* header, hipStream_t s) {
+    const int N = field->num_instances;
+    const long long used_slots = static_cast<long long>(rays) * p.rounds;
+    if (images != nullptr) {
+        if (vsrd_split_front::launch_adjoint(kMlpAdjointBlocks, field->instances, reinterpret_cast<const float*>(images), N, w.seeds, w.masks, p.slots_per_instance,
+                                             used_slots, p.items_per_instance, p.slots_per_item, w.counter, w.item_rows, w.item_flags, frames.count, frames.stride, s) !=
+            vsrd_split_front::kOk)
+            return VSRD_E_LAUNCH;
+    } else {
+        const unsigned mlp_bits = (flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? kMlpCentredBit : 0u;
+        const size_t adjoint_lds = (static_cast<size_t>(kMlpWbarFloats) + static_cast<size_t>(kMlpStashTiles) * kTileFloats) * sizeof(float);
+        hipLaunchKernelGGL(residual_mlp_adjoint_kernel, dim3(kMlpAdjointBlocks, frames.count), dim3(kWave), adjoint_lds, s, field->instances, field->mlp_weights, N,
+                           mlp_bits, w.seeds, w.masks, p.slots_per_instance, used_slots, p.items_per_instance, p.slots_per_item, w.counter, w.item_rows, w.item_flags,
+                           frames.stride);
+    }
+    hipLaunchKernelGGL(reduce_item_rows_kernel, dim3(N, (kItemRowFloats + 255) / 256, kItemSegments * frames.count), dim3(256), 0, s, w.item_rows, w.item_flags,
+                       p.items_per_instance, w.segment_sums, frames.stride, header);
+    hipLaunchKernelGGL(reduce_item_segments_kernel, dim3(N, (kItemRowFloats + 255) / 256, frames.count), dim3(256), 0, s, w.segment_sums, grad_mlp_weights, w.box_extra,
+                       accumulate ? 1 : 0, frames.stride, header);
+    return launch_status();
+}
+
+int32_t render_backward_split(const vsrd_field* field, const vsrd_render_config* config, const float* origins, const float* directions,
+                              const float* distances, int32_t num_distances, const float* grad_labels, const float* grad_gradients,
+                              const float* grad_weights, void* workspace, size_t workspace_bytes, float* grad_instances, float* grad_mlp_weights,
+                              void* stream, bool* taken) {
+    const int N = field->num_instances;
+    ResidualStepPlan p;
+    *taken = plan_backward_split(N, num_distances, config->num_rays, workspace_bytes, &p);
+    if (!*taken) return VSRD_OK;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const int row = N * kGradStride;
+    const FieldArgs f = field_args(field);
+    RenderArgs c = render_args(config);
+    c.sh.inv_t = f.inv_t;
+    const SplitWorkspace w = split_workspace(workspace, p);
+    const Frames one_frame = {1, 0};
+    int chunk_index = 0;
+    for (int first = 0; first < config->num_rays; first += p.chunk, ++chunk_index) {
+        const int rays = std::min(p.chunk, config->num_rays - first);
+        if (hipMemsetAsync(w.masks, 0, w.clear_bytes, s) != hipSuccess) return VSRD_E_LAUNCH;
+        const bool known = for_rounds<1, 2, 4>(p.rounds, [&](auto k) {
+            hipLaunchKernelGGL(render_backward_front_kernel<decltype(k)::value>, dim3(p.front_blocks), dim3(kBlockThreads), p.front_lds, s, f, field->instances,
+                               field->mlp_weights, c, origins, directions, distances, num_distances, grad_labels, grad_gradients, grad_weights, w.box_partials, w.jets,
+                               w.seeds, w.masks, p.slots_per_instance, first, rays, chunk_index > 0 ? 1 : 0);
+        });
+        if (!known) return VSRD_E_UNSUPPORTED;
+        const int32_t status = launch_adjoint_tail(field, nullptr, config->flags, p, w, rays, chunk_index > 0, grad_mlp_weights, one_frame, nullptr, s);
+        if (status != VSRD_OK) return status;
+    }
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, w.box_partials, p.front_waves, row, grad_instances, w.box_extra);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -256,12 +491,10 @@ int32_t vsrd_field_eval(const vsrd_field* field, const float* positions, int64_t
     if (hard_union && labels) return VSRD_E_INVALID_ARGUMENT;
     if (num_points == 0) return VSRD_OK;
     const int blocks = static_cast<int>(std::min<int64_t>((num_points + 255) / 256, 8192));
-    if (field->mlp_weights != nullptr)
-        hipLaunchKernelGGL(field_eval_kernel<true>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), field_args(field),
+    for_bool(field->mlp_weights != nullptr, [&](auto residual) {
+        hipLaunchKernelGGL(field_eval_kernel<decltype(residual)::value>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), field_args(field),
                            field->instances, field->mlp_weights, positions, static_cast<long long>(num_points), distances, gradients, labels, hard_union);
-    else
-        hipLaunchKernelGGL(field_eval_kernel<false>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), field_args(field),
-                           field->instances, field->mlp_weights, positions, static_cast<long long>(num_points), distances, gradients, labels, hard_union);
+    });
     return launch_status();
 }
 
@@ -286,20 +519,17 @@ int32_t vsrd_field_eval_backward(const vsrd_field* field, const float* positions
     if (!plan(static_cast<int>(std::min<int64_t>((num_points + kWave - 1) / kWave, 1 << 30)), per_wave, &g)) return VSRD_E_UNSUPPORTED;
     if (residual && g.threads > kResidualWaves * kWave) return VSRD_E_UNSUPPORTED;
     g.blocks = std::min(g.blocks, residual ? kMaxBlocksResidual : 2048);
-    float* partials = static_cast<float*>(workspace);
-    float* mlp_partials = partials + static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * row;
+    const OneKernelWorkspace w = one_kernel_workspace(workspace, N, residual);
     const FieldArgs f = field_args(field);
-    if (residual)
-        hipLaunchKernelGGL(field_eval_backward_kernel<true>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights,
-                           positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union, grad_positions, partials, mlp_partials);
-    else
-        hipLaunchKernelGGL(field_eval_backward_kernel<false>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights,
-                           positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union, grad_positions, partials, mlp_partials);
+    for_bool(residual, [&](auto res) {
+        hipLaunchKernelGGL(field_eval_backward_kernel<decltype(res)::value>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights,
+                           positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union, grad_positions, w.partials, w.mlp_partials);
+    });
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
     const int num_waves = g.blocks * (g.threads / kWave);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, partials, num_waves, row, grad_instances);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, w.partials, num_waves, row, grad_instances);
     if (residual)
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, mlp_partials, num_waves, mlp_row, grad_mlp_weights);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, w.mlp_partials, num_waves, mlp_row, grad_mlp_weights);
     return launch_status();
 }
 
@@ -312,14 +542,11 @@ int32_t vsrd_sphere_trace(const vsrd_field* field, const float* origins, int32_t
     if (!origins || !directions || !positions || !converged) return VSRD_E_INVALID_ARGUMENT;
     const int blocks = static_cast<int>(std::min<int64_t>((num_rays + 255) / 256, 16384));
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (field->mlp_weights != nullptr)
-        hipLaunchKernelGGL(sphere_trace_kernel<true>, dim3(blocks), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights,
+    for_bool(field->mlp_weights != nullptr, [&](auto residual) {
+        hipLaunchKernelGGL(sphere_trace_kernel<decltype(residual)::value>, dim3(blocks), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights,
                            origins, origin_stride, directions, foreground, static_cast<long long>(num_rays), num_iterations,
                            convergence_criteria, bounding_radius, initialise, hard_union, positions, converged);
-    else
-        hipLaunchKernelGGL(sphere_trace_kernel<false>, dim3(blocks), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights,
-                           origins, origin_stride, directions, foreground, static_cast<long long>(num_rays), num_iterations,
-                           convergence_criteria, bounding_radius, initialise, hard_union, positions, converged);
+    });
     return launch_status();
 }
 
@@ -358,17 +585,11 @@ int32_t vsrd_sample_importance(const vsrd_render_config* config, const float* co
     if (!plan(config->num_rays, wave_lds_floats(config->num_samples, 0), &g)) return VSRD_E_UNSUPPORTED;
     const RenderArgs c = render_args(config);
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rounds = rounds_for(config->num_samples);
-#define VSRD_LAUNCH(K)                                                                                                  \
-    hipLaunchKernelGGL(sample_importance_kernel<K>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, c, coarse_distances, \
-                       coarse_weights, u_fine, merged, fine)
-    switch (rounds) {
-        case 1: VSRD_LAUNCH(1); break;
-        case 2: VSRD_LAUNCH(2); break;
-        case 4: VSRD_LAUNCH(4); break;
-        default: return VSRD_E_UNSUPPORTED;
-    }
-#undef VSRD_LAUNCH
+    const bool known = for_rounds<1, 2, 4>(rounds_for(config->num_samples), [&](auto k) {
+        hipLaunchKernelGGL(sample_importance_kernel<decltype(k)::value>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, c, coarse_distances,
+                           coarse_weights, u_fine, merged, fine);
+    });
+    if (!known) return VSRD_E_UNSUPPORTED;
     return launch_status();
 }
 
@@ -388,40 +609,20 @@ int32_t vsrd_render_forward(const vsrd_field* field, const vsrd_render_config* c
     RenderArgs c = render_args(config);
     c.sh.inv_t = f.inv_t;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-#define VSRD_LAUNCH(K, RES)                                                                                                  \
-    do {                                                                                                                       \
-        if (opt_in_lds(render_forward_kernel<K, RES>, g.lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH;                         \
-        fit_to_residency(render_forward_kernel<K, RES>, &g);                                                                  \
-        hipLaunchKernelGGL((render_forward_kernel<K, RES>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, \
-                           field->mlp_weights, c, origins, directions, distances, num_distances, labels, gradients, weights);   \
-    } while (0)
+    int32_t status = VSRD_OK;
+    auto launch = [&](auto k, auto res) {
+        constexpr auto kernel = render_forward_kernel<decltype(k)::value, decltype(res)::value>;
+        if ((status = opt_in_lds(kernel, g.lds_bytes)) != VSRD_OK) return;
+        fit_to_residency(kernel, &g);
+        hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights, c, origins, directions, distances,
+                           num_distances, labels, gradients, weights);
+    };
     const int rounds = rounds_for(num_distances - 1);
-    if (residual) {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1, true); break;
-            case 2: VSRD_LAUNCH(2, true); break;
-            case 4: VSRD_LAUNCH(4, true); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-    } else {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1, false); break;
-            case 2: VSRD_LAUNCH(2, false); break;
-            case 4: VSRD_LAUNCH(4, false); break;
-            case 8: VSRD_LAUNCH(8, false); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-    }
-#undef VSRD_LAUNCH
+    const bool known = residual ? for_rounds<1, 2, 4>(rounds, [&](auto k) { launch(k, std::true_type{}); })
+                                : for_rounds<1, 2, 4, 8>(rounds, [&](auto k) { launch(k, std::false_type{}); });
+    if (!known) return VSRD_E_UNSUPPORTED;
+    if (status != VSRD_OK) return status;
     return launch_status();
-}
-
-namespace {
-// (defined with the residual step's launch plan, below)
-int32_t render_backward_split(const vsrd_field* field, const vsrd_render_config* config, const float* origins, const float* directions,
-                              const float* distances, int32_t num_distances, const float* grad_labels, const float* grad_gradients,
-                              const float* grad_weights, void* workspace, size_t workspace_bytes, float* grad_instances, float* grad_mlp_weights,
-                              void* stream, bool* taken);
 }
 
 int32_t vsrd_render_backward(const vsrd_field* field, const vsrd_render_config* config,
@@ -454,80 +655,50 @@ int32_t vsrd_render_backward(const vsrd_field* field, const vsrd_render_config* 
         return hipMemsetAsync(grad_instances, 0, row * sizeof(float), s) == hipSuccess ? VSRD_OK : VSRD_E_LAUNCH;
     }
     Geometry g;
-    // box-only fields, label adjoints only: the mappings of the fused step (quad_step.h) -- four rays per wave for N <= 16 and <= 128
-    // distances, two for N <= 64 and <= 256
-    if (!residual && !grad_gradients && !grad_weights && !(config->flags & VSRD_FLAG_STEP_WAVE_PER_RAY) && N <= kPairMaxInstances &&
-        num_distances <= 2 * kPairMaxSamples) {
-        const bool quad = N <= kQuadMaxInstances && num_distances <= 2 * kQuadMaxSamples;
-        const int lanes = quad ? kRowLanes : 32, rays_per_wave = kWave / lanes, half = (num_distances + 1) / 2;
-        const int shape_instances = quad ? kQuadMaxInstances : kPairMaxInstances;
-        const bool full = num_distances == 8 * lanes && 2 * N > shape_instances && !switches().no_full_shape;      // (2 S = 8 x lanes: BASELINE configs 2 and 5)
-        if (!plan((config->num_rays + rays_per_wave - 1) / rays_per_wave, static_cast<size_t>(quad_lds_floats(half, full ? shape_instances : N, lanes)), &g))
-            return VSRD_E_UNSUPPORTED;
-        const FieldArgs f = field_args(field);
-        RenderArgs c = render_args(config);
-        c.sh.inv_t = f.inv_t;
+    const FieldArgs f = field_args(field);
+    RenderArgs c = render_args(config);
+    c.sh.inv_t = f.inv_t;
+    // box-only fields, label adjoints only: the mappings of the fused step (quad_step.h), two kernels on one grid (backward_rows_kernel_body)
+    // (allowed: a box-only field and no adjoints but the labels' -- the rows kernels carry neither the MLP nor per-sample adjoints)
+    const RowsPlan r = plan_rows(N, num_distances, config->num_rays, config->flags, !residual && !grad_gradients && !grad_weights);
+    if (r.rows) {
+        if (!plan(static_cast<int>(r.num_groups), r.lds_floats, &g)) return VSRD_E_UNSUPPORTED;
+        if (!cap_to_workspace(workspace_bytes, row, r.flag_bytes, &g)) return VSRD_E_WORKSPACE;
+        const int num_waves = g.blocks * (g.threads / kWave);
         float* partials = static_cast<float*>(workspace);
-        // two kernels on one grid (quad_step.h: backward_rows_kernel_body): behind the waves' partial rows, two summary words and one byte per group of rays
-        const size_t num_groups = (static_cast<size_t>(config->num_rays) + rays_per_wave - 1) / rays_per_wave;
-        const size_t flag_bytes = 16 + ((num_groups + 15) & ~static_cast<size_t>(15));
-        const int waves_per_block = g.threads / kWave;
-        if (flag_bytes + static_cast<size_t>(waves_per_block) * row * sizeof(float) > workspace_bytes) return VSRD_E_WORKSPACE;
-        const int max_waves = static_cast<int>((workspace_bytes - flag_bytes) / sizeof(float) / row);
-        if (g.blocks * waves_per_block > max_waves) g.blocks = max_waves / waves_per_block;
-        unsigned char* redo_flags = reinterpret_cast<unsigned char*>(partials + static_cast<size_t>(g.blocks) * waves_per_block * row);
+        unsigned char* redo_flags = reinterpret_cast<unsigned char*>(partials + static_cast<size_t>(num_waves) * row);
         if (hipMemsetAsync(redo_flags, 0, 16, s) != hipSuccess) return VSRD_E_LAUNCH;
-#define VSRD_LAUNCH_BACKWARD_ROWS(KERNEL, FULL)                                                                                           \
-        hipLaunchKernelGGL((KERNEL<true, FULL>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c, origins, directions,   \
-                           distances, num_distances, grad_labels, partials, redo_flags);                                                \
-        hipLaunchKernelGGL((KERNEL<false, false>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c, origins, directions, \
-                           distances, num_distances, grad_labels, partials, redo_flags)
-        if (quad) { if (full) { VSRD_LAUNCH_BACKWARD_ROWS(render_backward_quad_kernel, true); } else { VSRD_LAUNCH_BACKWARD_ROWS(render_backward_quad_kernel, false); } }
-        else { if (full) { VSRD_LAUNCH_BACKWARD_ROWS(render_backward_pair_kernel, true); } else { VSRD_LAUNCH_BACKWARD_ROWS(render_backward_pair_kernel, false); } }
-#undef VSRD_LAUNCH_BACKWARD_ROWS
+        for_bool(r.full, [&](auto full) {
+            auto launch = [&](auto hot, auto rest) {
+                launch_hot_then_rest(hot, rest, g, s, f, field->instances, c, origins, directions, distances, num_distances, grad_labels, partials, redo_flags);
+            };
+            if (r.quad) launch(render_backward_quad_kernel<true, decltype(full)::value>, render_backward_quad_kernel<false, false>);
+            else launch(render_backward_pair_kernel<true, decltype(full)::value>, render_backward_pair_kernel<false, false>);
+        });
         if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, partials, g.blocks * (g.threads / kWave), row, grad_instances);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, partials, num_waves, row, grad_instances);
         return launch_status();
     }
     if (!plan(config->num_rays, static_cast<size_t>(backward_lds_floats(num_distances, N, residual)), &g)) return VSRD_E_UNSUPPORTED;
     if (residual && g.threads > kResidualWaves * kWave) return VSRD_E_UNSUPPORTED;      // cannot happen (LDS per wave), but the scratch is sized for it
     if (residual && g.blocks > kMaxBlocksResidual) g.blocks = kMaxBlocksResidual;
-    const FieldArgs f = field_args(field);
-    RenderArgs c = render_args(config);
-    c.sh.inv_t = f.inv_t;
-    float* partials = static_cast<float*>(workspace);
-    float* mlp_partials = partials + static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * row;
-    float* jets = mlp_partials + (residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * mlp_row : 0);
-    float4* residual_cache = reinterpret_cast<float4*>(jets);
-    float* seed_cache = jets + residual_jet_floats(N, residual);
-#define VSRD_LAUNCH(K, RES)                                                                                                    \
-    fit_to_residency(render_backward_kernel<K, RES>, &g);                                                                        \
-    if (residual && g.blocks > kMaxBlocksResidual) g.blocks = kMaxBlocksResidual;                                                \
-    hipLaunchKernelGGL((render_backward_kernel<K, RES>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances,    \
-                       field->mlp_weights, c, origins, directions, distances, num_distances, grad_labels, grad_gradients,         \
-                       grad_weights, partials, mlp_partials, residual_cache, seed_cache)
-    const int rounds = rounds_for(num_distances - 1);
-    if (residual) {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1, true); break;
-            case 2: VSRD_LAUNCH(2, true); break;
-            case 4: VSRD_LAUNCH(4, true); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-    } else {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1, false); break;
-            case 2: VSRD_LAUNCH(2, false); break;
-            case 4: VSRD_LAUNCH(4, false); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-    }
-#undef VSRD_LAUNCH
+    const OneKernelWorkspace w = one_kernel_workspace(workspace, N, residual);
+    bool known = false;
+    for_bool(residual, [&](auto res) {
+        known = for_rounds<1, 2, 4>(rounds_for(num_distances - 1), [&](auto k) {
+            constexpr auto kernel = render_backward_kernel<decltype(k)::value, decltype(res)::value>;
+            fit_to_residency(kernel, &g);
+            if (residual && g.blocks > kMaxBlocksResidual) g.blocks = kMaxBlocksResidual;
+            hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights, c, origins, directions, distances,
+                               num_distances, grad_labels, grad_gradients, grad_weights, w.partials, w.mlp_partials, w.jets, w.seeds);
+        });
+    });
+    if (!known) return VSRD_E_UNSUPPORTED;
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
     const int num_waves = g.blocks * (g.threads / kWave);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, partials, num_waves, row, grad_instances);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, w.partials, num_waves, row, grad_instances);
     if (residual)
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, mlp_partials, num_waves, mlp_row, grad_mlp_weights);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, w.mlp_partials, num_waves, mlp_row, grad_mlp_weights);
     return launch_status();
 }
 
@@ -549,54 +720,34 @@ int32_t vsrd_render_hierarchical_forward(const vsrd_field* field, const vsrd_ren
     c.sh.inv_t = f.inv_t;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     // labels, distances, pass 1's weights and the uniforms only (no per-sample gradients / weights of pass 2), box-only field: the forward
-    // in the mappings of the fused step (quad_step.h) -- four rays per wave for N <= 16 and S <= 64, two for N <= 64 and S <= 128
-    if (!residual && !gradients && !weights && !(config->flags & VSRD_FLAG_STEP_WAVE_PER_RAY) &&
-        S <= kPairMaxSamples && field->num_instances <= kPairMaxInstances) {
-        const bool quad = S <= kQuadMaxSamples && field->num_instances <= kQuadMaxInstances;
-        const int lanes = quad ? kRowLanes : 32, rays_per_wave = kWave / lanes;
-        // two kernels on one grid, the hot one instantiated for a full shape (quad_step.h: hierarchical_rows_kernel_body), as in vsrd_render_silhouette_step
-        const int shape_instances = quad ? kQuadMaxInstances : kPairMaxInstances;
-        const bool full = S == 4 * lanes && 2 * field->num_instances > shape_instances && !switches().no_full_shape;
-        if (!plan((config->num_rays + rays_per_wave - 1) / rays_per_wave,
-                  static_cast<size_t>(quad_lds_floats(S, full ? shape_instances : field->num_instances, lanes)), &g))
-            return VSRD_E_UNSUPPORTED;
-#define VSRD_LAUNCH_FORWARD_ROWS(KERNEL, FULL)                                                                                            \
-        hipLaunchKernelGGL((KERNEL<true, FULL>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c, origins,         \
-                           directions, u_coarse, u_fine, labels, distances, coarse_weights, u_coarse_out, u_fine_out);                   \
-        hipLaunchKernelGGL((KERNEL<false, false>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c, origins,       \
-                           directions, u_coarse, u_fine, labels, distances, coarse_weights, u_coarse_out, u_fine_out)
-        if (quad) { if (full) { VSRD_LAUNCH_FORWARD_ROWS(render_hierarchical_quad_kernel, true); } else { VSRD_LAUNCH_FORWARD_ROWS(render_hierarchical_quad_kernel, false); } }
-        else { if (full) { VSRD_LAUNCH_FORWARD_ROWS(render_hierarchical_pair_kernel, true); } else { VSRD_LAUNCH_FORWARD_ROWS(render_hierarchical_pair_kernel, false); } }
-#undef VSRD_LAUNCH_FORWARD_ROWS
+    // in the mappings of the fused step (quad_step.h), two kernels on one grid (hierarchical_rows_kernel_body)
+    // (allowed: a box-only field and no per-sample outputs of pass 2, which the rows kernels do not write)
+    const RowsPlan r = plan_rows(field->num_instances, 2 * S, config->num_rays, config->flags, !residual && !gradients && !weights);
+    if (r.rows) {
+        if (!plan(static_cast<int>(r.num_groups), r.lds_floats, &g)) return VSRD_E_UNSUPPORTED;
+        for_bool(r.full, [&](auto full) {
+            auto launch = [&](auto hot, auto rest) {
+                launch_hot_then_rest(hot, rest, g, s, f, field->instances, c, origins, directions, u_coarse, u_fine, labels, distances, coarse_weights, u_coarse_out, u_fine_out);
+            };
+            if (r.quad) launch(render_hierarchical_quad_kernel<true, decltype(full)::value>, render_hierarchical_quad_kernel<false, false>);
+            else launch(render_hierarchical_pair_kernel<true, decltype(full)::value>, render_hierarchical_pair_kernel<false, false>);
+        });
         return launch_status();
     }
     if (!plan(config->num_rays, static_cast<size_t>(hierarchical_lds_floats(S, field->num_instances, residual)), &g)) return VSRD_E_UNSUPPORTED;
-#define VSRD_LAUNCH(K, RES)                                                                                                  \
-    do {                                                                                                                       \
-        if (opt_in_lds(render_hierarchical_kernel<K, RES>, g.lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH;                    \
-        fit_to_residency(render_hierarchical_kernel<K, RES>, &g);                                                             \
-        hipLaunchKernelGGL((render_hierarchical_kernel<K, RES>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f,            \
-                           field->instances, field->mlp_weights, c, origins, directions, u_coarse, u_fine, labels, distances,   \
-                           gradients, weights, coarse_weights, u_coarse_out, u_fine_out);                                                     \
-    } while (0)
+    int32_t status = VSRD_OK;
+    auto launch = [&](auto k, auto res) {
+        constexpr auto kernel = render_hierarchical_kernel<decltype(k)::value, decltype(res)::value>;
+        if ((status = opt_in_lds(kernel, g.lds_bytes)) != VSRD_OK) return;
+        fit_to_residency(kernel, &g);
+        hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights, c, origins, directions, u_coarse, u_fine,
+                           labels, distances, gradients, weights, coarse_weights, u_coarse_out, u_fine_out);
+    };
     const int rounds = rounds_for(2 * S - 1);
-    if (residual) {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1, true); break;
-            case 2: VSRD_LAUNCH(2, true); break;
-            case 4: VSRD_LAUNCH(4, true); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-    } else {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1, false); break;
-            case 2: VSRD_LAUNCH(2, false); break;
-            case 4: VSRD_LAUNCH(4, false); break;
-            case 8: VSRD_LAUNCH(8, false); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-    }
-#undef VSRD_LAUNCH
+    const bool known = residual ? for_rounds<1, 2, 4>(rounds, [&](auto k) { launch(k, std::true_type{}); })
+                                : for_rounds<1, 2, 4, 8>(rounds, [&](auto k) { launch(k, std::false_type{}); });
+    if (!known) return VSRD_E_UNSUPPORTED;
+    if (status != VSRD_OK) return status;
     return launch_status();
 }
 
@@ -630,7 +781,6 @@ int32_t vsrd_project_boxes_backward(const float* world_corners, const float* ext
 
 namespace {
 constexpr int kSplitBlocks = 1024;                       // render_silhouette_split_kernel: x 2 waves = two waves on each of the 1024 SIMDs
-int split_max_rays() { return switches().split_max_rays; }   // box-only step: launches of at most this many rays split every ray over two waves (0: never)
 }  // namespace
 
 int32_t vsrd_render_silhouette_step(const vsrd_field* field, const vsrd_render_config* config,
@@ -669,15 +819,15 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
     // importance-sampled rays per step) are neither neighbours nor enough to fill the chip four to a wave.
     const bool force_split = (config->flags & VSRD_FLAG_STEP_SPLIT_RAY) && !(config->flags & VSRD_FLAG_STEP_WAVE_PER_RAY);
     // (dense = rays AND targets read row by row: the multi-ray kernels know neither ray_indices nor the target column map)
-    const bool dense = config->ray_indices == nullptr && config->target_columns == nullptr && !(config->flags & VSRD_FLAG_STEP_WAVE_PER_RAY) && !force_split;
-    const bool quad = dense && S <= kQuadMaxSamples && N <= kQuadMaxInstances;
-    // ... and for more instances or samples than that (BASELINE config 5: N = 64, S = 128) two rays per wave, 32 lanes each
-    const bool pair = dense && !quad && S <= kPairMaxSamples && N <= kPairMaxInstances;
+    // (allowed: a dense launch that was not asked to split its rays)
+    const RowsPlan r = plan_rows(N, 2 * S, config->num_rays, config->flags,
+                                 config->ray_indices == nullptr && config->target_columns == nullptr && !(config->flags & VSRD_FLAG_STEP_SPLIT_RAY));
+    // ... and for more instances or samples than a quad takes (BASELINE config 5: N = 64, S = 128) two rays per wave, 32 lanes each (plan_rows)
     // ... and for launches too small to put two waves on every SIMD one ray per wave (the reference's 1000 sampled rays per step: 1000
     // waves on 1024 SIMDs, pure latency), a ray split over the two waves of a workgroup (render_silhouette_split_kernel)
     // (a step that writes its samples out -- vsrd_render_config::out_* -- keeps one ray per wave: the split form has no such outputs)
-    const bool split = !quad && !pair && !(config->flags & VSRD_FLAG_STEP_WAVE_PER_RAY) && !wants_samples(config) && (rounds == 2 || rounds == 4) &&
-                       (force_split || config->num_rays <= split_max_rays()) &&
+    const bool split = !r.rows && !(config->flags & VSRD_FLAG_STEP_WAVE_PER_RAY) && !wants_samples(config) && (rounds == 2 || rounds == 4) &&
+                       (force_split || config->num_rays <= switches().split_max_rays) &&
                        static_cast<size_t>(split_lds_floats(S, N)) * sizeof(float) <= kLdsLimit / 2;
     if (split) {
         const int blocks = config->num_rays < kSplitBlocks ? config->num_rays : kSplitBlocks;
@@ -690,40 +840,30 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
         c.sh.inv_t = f.inv_t;
         float* partials = static_cast<float*>(workspace);
         float* loss_partials = partials + static_cast<size_t>(num_waves) * row;
-#define VSRD_LAUNCH_SPLIT(K, FRAMES)                                                                                            \
-        do {                                                                                                                      \
-            if (opt_in_lds(render_silhouette_split_kernel<K, FRAMES>, lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH;               \
-            hipLaunchKernelGGL((render_silhouette_split_kernel<K, FRAMES>), dim3(blocks, frames.count), dim3(kPairWaves * kWave), lds_bytes, s, f, field->instances, c, \
-                               origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials, loss_partials, header); \
-        } while (0)
-        if (frames.count > 1 || header) { if (rounds == 2) VSRD_LAUNCH_SPLIT(2, true); else VSRD_LAUNCH_SPLIT(4, true); }
-        else if (rounds == 2) VSRD_LAUNCH_SPLIT(2, false); else VSRD_LAUNCH_SPLIT(4, false);
-#undef VSRD_LAUNCH_SPLIT
+        int32_t status = VSRD_OK;
+        for_rounds<2, 4>(rounds, [&](auto k) {
+            for_bool(frames.count > 1 || header, [&](auto batch) {
+                constexpr auto kernel = render_silhouette_split_kernel<decltype(k)::value, decltype(batch)::value>;
+                if ((status = opt_in_lds(kernel, lds_bytes)) != VSRD_OK) return;
+                hipLaunchKernelGGL(kernel, dim3(blocks, frames.count), dim3(kPairWaves * kWave), lds_bytes, s, f, field->instances, c, origins, directions, u_coarse,
+                                   u_fine, targets, instance_weights, loss_scale, labels, partials, loss_partials, header);
+            });
+        });
+        if (status != VSRD_OK) return status;
         if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
         hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 1, frames.count), dim3(256), 0, s, partials, num_waves, row, grad_instances, nullptr, loss_partials, 1, loss,
                            frames.stride, header);
         return launch_status();
     }
     if (frames.count > 1 || header) return VSRD_E_UNSUPPORTED;     // a batch of frames runs in the split-ray form only (gathered launches of at most 2048 rays per frame)
-    const int lanes = quad ? kRowLanes : 32, rays_per_wave = kWave / lanes;
-    // a launch that fills its shape (S = lanes x rounds of the shape, more than half of its instance slots: BASELINE configs 2 and 5)
-    // runs the hot kernel instantiated for that S with the instance tables padded to the shape's count (quad_step.h: kFull)
-    const int shape_instances = quad ? kQuadMaxInstances : kPairMaxInstances;
-    // (exactly the launches the dispatch below gives a <4, true, true> kernel: S = 4 x lanes)
-    const bool full = (quad || pair) && S == 4 * lanes && 2 * N > shape_instances && !switches().no_full_shape;
     Geometry g;
-    const size_t per_wave = (quad || pair) ? static_cast<size_t>(quad_lds_floats(S, full ? shape_instances : N, lanes)) : static_cast<size_t>(wave_lds_floats(S, N)) + N + row;
-    if (!plan((quad || pair) ? (config->num_rays + rays_per_wave - 1) / rays_per_wave : config->num_rays, per_wave, &g)) return VSRD_E_UNSUPPORTED;
+    if (!plan(r.rows ? static_cast<int>(r.num_groups) : config->num_rays, r.rows ? r.lds_floats : static_cast<size_t>(wave_lds_floats(S, N)) + N + row, &g))
+        return VSRD_E_UNSUPPORTED;
 #ifdef VSRD_INSTANCE_LDS
-    if (quad && full) g.lds_bytes += static_cast<size_t>(N) * kInstanceStride * sizeof(float);      // experiment: the instance block next to the waves' partitions
+    if (r.quad && r.full) g.lds_bytes += static_cast<size_t>(N) * kInstanceStride * sizeof(float);      // experiment: the instance block next to the waves' partitions
 #endif
-    // the partial buffer holds one gradient row per wave; the loss partials live in the tail of the same row budget, and behind them
-    // (multi-ray mappings) one byte per group of rays: "the hot kernel could not serve this group" (quad_step.h)
-    const size_t num_groups = (quad || pair) ? (static_cast<size_t>(config->num_rays) + rays_per_wave - 1) / rays_per_wave : 0;
-    const size_t flag_bytes = (quad || pair) ? 16 + ((num_groups + 15) & ~static_cast<size_t>(15)) : 0;      // summary words + one byte per group
-    if (flag_bytes + static_cast<size_t>(g.threads / kWave) * (row + 1) * sizeof(float) > vsrd_workspace_bytes(N, 0)) return VSRD_E_WORKSPACE;
-    const int max_waves_for_loss = static_cast<int>((vsrd_workspace_bytes(N, 0) - flag_bytes) / sizeof(float) / (row + 1));
-    if (g.blocks * (g.threads / kWave) > max_waves_for_loss) g.blocks = max_waves_for_loss / (g.threads / kWave);
+    // one gradient row and one loss partial per wave, and behind them (multi-ray mappings) the groups' flags
+    if (!cap_to_workspace(vsrd_workspace_bytes(N, 0), row + 1, r.flag_bytes, &g)) return VSRD_E_WORKSPACE;
     const FieldArgs f = field_args(field);
     RenderArgs c = render_args(config);
     c.sh.inv_t = f.inv_t;
@@ -731,48 +871,32 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
     float* partials = static_cast<float*>(workspace);
     float* loss_partials = partials + static_cast<size_t>(num_waves) * row;
     unsigned char* redo_flags = reinterpret_cast<unsigned char*>(loss_partials + num_waves);
-#define VSRD_LAUNCH(K)                                                                                                          \
-    do {                                                                                                                          \
-        if (opt_in_lds(render_silhouette_kernel<K>, g.lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH;                               \
-        hipLaunchKernelGGL(render_silhouette_kernel<K>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c,    \
-                           origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials,        \
-                           loss_partials);                                                                                       \
-    } while (0)
-// two kernels on one grid: the hot body (rotations about y, fixed soft-min shift), then everything it left over (quad_step.h)
-#define VSRD_LAUNCH_ROWS(KERNEL, K, FULL)                                                                                         \
-    do {                                                                                                                          \
-        if (opt_in_lds(KERNEL<K, true, FULL>, g.lds_bytes) != VSRD_OK || opt_in_lds(KERNEL<K, false, false>, g.lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH; \
-        if (hipMemsetAsync(redo_flags, 0, 16, s) != hipSuccess) return VSRD_E_LAUNCH;                                               \
-        hipLaunchKernelGGL((KERNEL<K, true, FULL>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c,        \
-                           origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials,        \
-                           loss_partials, redo_flags);                                                                           \
-        hipLaunchKernelGGL((KERNEL<K, false, false>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c,      \
-                           origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials,        \
-                           loss_partials, redo_flags);                                                                           \
-    } while (0)
-#define VSRD_LAUNCH_QUAD(K) VSRD_LAUNCH_ROWS(render_silhouette_quad_kernel, K, false)
-#define VSRD_LAUNCH_PAIR(K) VSRD_LAUNCH_ROWS(render_silhouette_pair_kernel, K, false)
-    if (quad) {
-        if (S <= 16) VSRD_LAUNCH_QUAD(1);
-        else if (S <= 32) VSRD_LAUNCH_QUAD(2);
-        else if (full) VSRD_LAUNCH_ROWS(render_silhouette_quad_kernel, 4, true);
-        else VSRD_LAUNCH_QUAD(4);
-    } else if (pair) {
-        if (S <= 64) VSRD_LAUNCH_PAIR(2);
-        else if (full) VSRD_LAUNCH_ROWS(render_silhouette_pair_kernel, 4, true);
-        else VSRD_LAUNCH_PAIR(4);
+    int32_t status = VSRD_OK;
+    bool known = true;
+    if (r.rows) {
+        // (exactly the launches that fill their shape get a <4, true, true> kernel: S = 4 x lanes)
+        auto launch = [&](auto hot, auto rest) {
+            if ((status = opt_in_lds(hot, g.lds_bytes)) != VSRD_OK || (status = opt_in_lds(rest, g.lds_bytes)) != VSRD_OK) return;
+            if (hipMemsetAsync(redo_flags, 0, 16, s) != hipSuccess) { status = VSRD_E_LAUNCH; return; }
+            launch_hot_then_rest(hot, rest, g, s, f, field->instances, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials,
+                                 loss_partials, redo_flags);
+        };
+        if (r.quad && r.full) launch(render_silhouette_quad_kernel<4, true, true>, render_silhouette_quad_kernel<4, false, false>);
+        else if (r.full) launch(render_silhouette_pair_kernel<4, true, true>, render_silhouette_pair_kernel<4, false, false>);
+        else if (r.quad) known = for_rounds<1, 2, 4>(r.rounds, [&](auto k) {
+            launch(render_silhouette_quad_kernel<decltype(k)::value, true, false>, render_silhouette_quad_kernel<decltype(k)::value, false, false>); });
+        else known = for_rounds<2, 4>(r.rounds, [&](auto k) {
+            launch(render_silhouette_pair_kernel<decltype(k)::value, true, false>, render_silhouette_pair_kernel<decltype(k)::value, false, false>); });
     } else {
-        switch (rounds) {
-            case 1: VSRD_LAUNCH(1); break;
-            case 2: VSRD_LAUNCH(2); break;
-            case 4: VSRD_LAUNCH(4); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
+        known = for_rounds<1, 2, 4>(rounds, [&](auto k) {
+            constexpr auto kernel = render_silhouette_kernel<decltype(k)::value>;
+            if ((status = opt_in_lds(kernel, g.lds_bytes)) != VSRD_OK) return;
+            hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, c, origins, directions, u_coarse, u_fine, targets,
+                               instance_weights, loss_scale, labels, partials, loss_partials);
+        });
     }
-#undef VSRD_LAUNCH
-#undef VSRD_LAUNCH_QUAD
-#undef VSRD_LAUNCH_PAIR
-#undef VSRD_LAUNCH_ROWS
+    if (!known) return VSRD_E_UNSUPPORTED;
+    if (status != VSRD_OK) return status;
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 1), dim3(256), 0, s, partials, num_waves, row, grad_instances, nullptr, loss_partials, 1, loss);
     return launch_status();
@@ -806,201 +930,26 @@ static int32_t residual_step_single_kernel(const vsrd_field* field, const vsrd_r
     RenderArgs c = render_args(config);
     c.sh.inv_t = f.inv_t;
     const int num_waves = g.blocks * (g.threads / kWave);
-    float* partials = static_cast<float*>(workspace);
-    float* loss_partials = partials + static_cast<size_t>(num_waves) * row;             // inside the (much larger) box-partial region
-    float* mlp_partials = partials + static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * row;
-    float* jets = mlp_partials + static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * mlp_row;
-    float4* residual_cache = reinterpret_cast<float4*>(jets);
-    float* seed_cache = jets + residual_jet_floats(N, true);
+    const OneKernelWorkspace w = one_kernel_workspace(workspace, N, true);
+    float* loss_partials = w.partials + static_cast<size_t>(num_waves) * row;           // inside the (much larger) box-partial region
     // d/dg of  eikonal_ratio * mean over [R, 2S-1] of (|g| - 1)^2 ;  the reported eikonal term is the plain mean
     const float eikonal_norm = 1.0f / (static_cast<float>(config->num_rays) * static_cast<float>(num_points));
     const float eikonal_scale = eikonal_ratio * eikonal_norm;
-#define VSRD_LAUNCH(K)                                                                                                             \
-    do {                                                                                                                             \
-        if (opt_in_lds(render_residual_step_kernel<K>, g.lds_bytes) != VSRD_OK) return VSRD_E_LAUNCH;                                \
-        hipLaunchKernelGGL(render_residual_step_kernel<K>, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances,       \
-                           field->mlp_weights, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale,       \
-                           eikonal_scale, eikonal_norm, labels, partials, mlp_partials, residual_cache, seed_cache, loss_partials);  \
-    } while (0)
-    switch (rounds) {
-        case 1: VSRD_LAUNCH(1); break;
-        case 2: VSRD_LAUNCH(2); break;
-        case 4: VSRD_LAUNCH(4); break;
-        default: return VSRD_E_UNSUPPORTED;
-    }
-#undef VSRD_LAUNCH
+    int32_t status = VSRD_OK;
+    const bool known = for_rounds<1, 2, 4>(rounds, [&](auto k) {
+        constexpr auto kernel = render_residual_step_kernel<decltype(k)::value>;
+        if ((status = opt_in_lds(kernel, g.lds_bytes)) != VSRD_OK) return;
+        hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights, c, origins, directions, u_coarse, u_fine,
+                           targets, instance_weights, loss_scale, eikonal_scale, eikonal_norm, labels, w.partials, w.mlp_partials, w.jets, w.seeds, loss_partials);
+    });
+    if (!known) return VSRD_E_UNSUPPORTED;
+    if (status != VSRD_OK) return status;
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, partials, num_waves, row, grad_instances);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, mlp_partials, num_waves, mlp_row, grad_mlp_weights);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, w.partials, num_waves, row, grad_instances);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, w.mlp_partials, num_waves, mlp_row, grad_mlp_weights);
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(2), dim3(256), 0, s, loss_partials, num_waves, 2, losses);
     return launch_status();
 }
-
-
-// ---- the split form (render_kernels.h: residual_step_front_kernel + residual_mlp_adjoint_kernel), the default ---------------------
-namespace {
-
-constexpr size_t kSeedBudgetBytes = size_t(6) << 30;     // seeds of one chunk of rays: N x chunk x rounds x 2560 B (a launch is cut into chunks that fit)
-constexpr int kFrontBlocks = 512;                        // x 4 waves = two waves on each of the 1024 SIMDs
-constexpr int kMlpAdjointBlocks = 4096;                  // single-wave workgroups, dynamic item fetch (two per SIMD are resident)
-constexpr int kPairBlocks = 1024;                        // residual_step_pair_kernel: x 2 waves = two waves on each of the 1024 SIMDs
-constexpr int kPairMaxRays = 2048;                       // two-round launches of at most this many rays split each ray over two waves
-
-int pair_max_rays() { return switches().pair_max_rays; }    // experiment switch: 0 turns the pair kernel off
-
-struct ResidualStepPlan {
-    int rounds, chunk, front_blocks, front_waves, slots_per_item, items_per_instance;
-    bool pair;                     // few rays: residual_step_pair_kernel (a ray split over the two waves of a workgroup)
-    long long slots_per_instance;
-    size_t front_lds;
-    // workspace layout, in floats from the base
-    size_t box_partials, loss_partials, jets, box_extra, counter, segment_sums, seeds, item_rows, masks, item_flags, images, total_bytes;
-};
-
-static bool plan_residual_step(int N, int S, int num_rays, bool allow_pair, ResidualStepPlan* p, int slots_per_item = 0) {
-    p->rounds = rounds_for(2 * S - 1);
-    if (p->rounds < 1 || p->rounds > 4) return false;
-    // four rounds (S in (64, 128]): the one-wave-per-ray kernel needs 308 registers (one wave per SIMD), the pair kernel 256 -- the pair
-    // kernel wins at every launch size (132 k rays, S = 100: 90.3 against 97.9 ms); two rounds: only while a launch cannot fill the SIMDs
-    p->pair = allow_pair && num_rays >= 1 && (p->rounds == 4 || (p->rounds == 2 && num_rays <= pair_max_rays()));
-    p->front_lds = p->pair ? static_cast<size_t>(residual_pair_lds_floats(S, N)) * sizeof(float)
-                           : static_cast<size_t>(residual_front_lds_floats(S, N)) * sizeof(float) * kMaxWavesPerBlock;
-    if (p->front_lds > kLdsLimit / 2) return false;     // two workgroups per CU = two waves per SIMD (one wave per ray at N = 64, S = 128: 93 KB -> the single-kernel form)
-    const size_t per_ray = static_cast<size_t>(N) * p->rounds * kSeedFloats * kWave * sizeof(float);
-    long long chunk = static_cast<long long>(kSeedBudgetBytes / per_ray);
-    if (chunk < 256) chunk = 256;
-    if (chunk > num_rays) chunk = num_rays < 1 ? 1 : num_rays;
-    p->chunk = static_cast<int>(chunk);
-    const long long want = (chunk + kMaxWavesPerBlock - 1) / kMaxWavesPerBlock;
-    p->front_blocks = static_cast<int>(want > kFrontBlocks ? kFrontBlocks : want);
-    p->front_waves = p->front_blocks * kMaxWavesPerBlock;
-    if (p->pair) {
-        p->front_blocks = static_cast<int>(chunk > kPairBlocks ? kPairBlocks : chunk);
-        p->front_waves = p->front_blocks * kPairWaves;
-    }
-    p->slots_per_instance = chunk * p->rounds;
-    // items: enough of them to balance ~2000 waves, few enough that an item amortises its partial row (6.6 KB written and read once)
-    long long per_item = (p->slots_per_instance * N) / 16384;
-    // (round 6: launches that leave >= 32 k items even at the largest item -- config 3's chunks of 110 k rays -- take 64 slots per item: same
-    //  speed as 32 or 48 (3.66-3.70 Mrays/s, tools/gpu_r06q.sh), half the partial rows written and reduced: 35 -> 17 GB per config-3 step)
-    per_item = per_item < 4 ? 4 : (per_item >= 128 ? 64 : (per_item > 32 ? 32 : per_item));
-    const int forced = switches().slots_per_item;                        // experiment switch
-    if (forced >= 1 && forced <= 64) per_item = forced;
-    if (slots_per_item >= 1 && slots_per_item <= 64) per_item = slots_per_item;      // vsrd_render_config::adjoint_slots_per_item
-    p->slots_per_item = static_cast<int>(per_item);
-    p->items_per_instance = static_cast<int>((p->slots_per_instance + per_item - 1) / per_item);
-    size_t at = 0;
-    auto take = [&](size_t floats) { const size_t here = at; at += (floats + 3) & ~size_t(3); return here; };
-    p->box_partials = take(static_cast<size_t>(p->front_waves) * N * kGradStride);
-    p->loss_partials = take(static_cast<size_t>(p->front_waves) * 2);
-    p->jets = take(static_cast<size_t>(p->front_waves) * jet_wave_float4s(p->rounds, N) * 4);
-    p->box_extra = take(static_cast<size_t>(N) * kGradStride);
-    p->segment_sums = take(static_cast<size_t>(N) * kItemSegments * kItemRowFloats);
-    p->seeds = take(static_cast<size_t>(N) * p->slots_per_instance * kSeedFloats * kWave);
-    p->item_rows = take(static_cast<size_t>(N) * p->items_per_instance * kItemRowFloats);
-    p->masks = take((static_cast<size_t>(N) * p->slots_per_instance + 3) / 4);
-    p->counter = take(4);                                // right behind the masks: one memset clears both
-    p->item_flags = take((static_cast<size_t>(N) * p->items_per_instance + 3) / 4);
-    p->images = take(static_cast<size_t>(N) * kMlpImageWords);       // VSRD_FLAG_MLP_SPLIT_BF16: the instances' operand images (residual.h)
-    p->total_bytes = at * sizeof(float);
-    return true;
-}
-
-// vsrd_render_backward on residual fields in the split form.  The plan is the residual step's, with the chunk of rays sized to what the
-// caller's workspace holds (at least min(num_rays, 64) rays, else the caller falls back to render_backward_kernel<K, true>).
-bool plan_backward_split(int N, int num_distances, int num_rays, size_t budget_bytes, ResidualStepPlan* p) {
-    p->rounds = rounds_for(num_distances - 1);
-    if (p->rounds < 1 || p->rounds > 4) return false;
-    p->pair = false;
-    p->front_lds = static_cast<size_t>(backward_front_lds_floats(num_distances, N)) * sizeof(float) * kMaxWavesPerBlock;
-    if (p->front_lds > kLdsDefault) return false;
-    const size_t per_ray = static_cast<size_t>(N) * p->rounds * kSeedFloats * kWave * sizeof(float);
-    long long chunk = static_cast<long long>(kSeedBudgetBytes / per_ray);
-    if (chunk > num_rays) chunk = num_rays < 1 ? 1 : num_rays;
-    for (;; chunk = chunk * 3 / 4) {                                       // the largest chunk whose whole layout fits the budget
-        if (chunk < (num_rays < 64 ? num_rays : 64)) return false;
-        p->chunk = static_cast<int>(chunk);
-        const long long want = (chunk + kMaxWavesPerBlock - 1) / kMaxWavesPerBlock;
-        p->front_blocks = static_cast<int>(want > kFrontBlocks ? kFrontBlocks : want);
-        p->front_waves = p->front_blocks * kMaxWavesPerBlock;
-        p->slots_per_instance = chunk * p->rounds;
-        long long per_item = (p->slots_per_instance * N) / 16384;
-        per_item = per_item < 4 ? 4 : (per_item > 32 ? 32 : per_item);
-        p->slots_per_item = static_cast<int>(per_item);
-        p->items_per_instance = static_cast<int>((p->slots_per_instance + per_item - 1) / per_item);
-        size_t at = 0;
-        auto take = [&](size_t floats) { const size_t here = at; at += (floats + 3) & ~size_t(3); return here; };
-        p->box_partials = take(static_cast<size_t>(p->front_waves) * N * kGradStride);
-        p->loss_partials = take(4);
-        p->jets = take(static_cast<size_t>(p->front_waves) * jet_wave_float4s(p->rounds, N) * 4);
-        p->box_extra = take(static_cast<size_t>(N) * kGradStride);
-        p->segment_sums = take(static_cast<size_t>(N) * kItemSegments * kItemRowFloats);
-        p->seeds = take(static_cast<size_t>(N) * p->slots_per_instance * kSeedFloats * kWave);
-        p->item_rows = take(static_cast<size_t>(N) * p->items_per_instance * kItemRowFloats);
-        p->masks = take((static_cast<size_t>(N) * p->slots_per_instance + 3) / 4);
-        p->counter = take(4);
-        p->item_flags = take((static_cast<size_t>(N) * p->items_per_instance + 3) / 4);
-        p->total_bytes = at * sizeof(float);
-        if (p->total_bytes <= budget_bytes) return true;
-        if (chunk <= 1) return false;
-    }
-}
-
-int32_t render_backward_split(const vsrd_field* field, const vsrd_render_config* config, const float* origins, const float* directions,
-                              const float* distances, int32_t num_distances, const float* grad_labels, const float* grad_gradients,
-                              const float* grad_weights, void* workspace, size_t workspace_bytes, float* grad_instances, float* grad_mlp_weights,
-                              void* stream, bool* taken) {
-    const int N = field->num_instances;
-    ResidualStepPlan p;
-    *taken = plan_backward_split(N, num_distances, config->num_rays, workspace_bytes, &p);
-    if (!*taken) return VSRD_OK;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const int row = N * kGradStride;
-    const FieldArgs f = field_args(field);
-    RenderArgs c = render_args(config);
-    c.sh.inv_t = f.inv_t;
-    float* base = static_cast<float*>(workspace);
-    float* box_partials = base + p.box_partials;
-    float4* jets = reinterpret_cast<float4*>(base + p.jets);
-    float* box_extra = base + p.box_extra;
-    unsigned* counter = reinterpret_cast<unsigned*>(base + p.counter);
-    float* segment_sums = base + p.segment_sums;
-    float* seeds = base + p.seeds;
-    float* item_rows = base + p.item_rows;
-    unsigned char* masks = reinterpret_cast<unsigned char*>(base + p.masks);
-    unsigned char* item_flags = reinterpret_cast<unsigned char*>(base + p.item_flags);
-    const unsigned mlp_bits = (config->flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? kMlpCentredBit : 0u;
-    const size_t adjoint_lds = (static_cast<size_t>(kMlpWbarFloats) + static_cast<size_t>(kMlpStashTiles) * kTileFloats) * sizeof(float);
-    int chunk_index = 0;
-    for (int first = 0; first < config->num_rays; first += p.chunk, ++chunk_index) {
-        const int rays = std::min(p.chunk, config->num_rays - first);
-        const long long used_slots = static_cast<long long>(rays) * p.rounds;
-        if (hipMemsetAsync(masks, 0, (p.counter - p.masks + 4) * sizeof(float), s) != hipSuccess) return VSRD_E_LAUNCH;   // tile masks + the item counter's 16-byte slot (a multiple of 16 bytes: one fill kernel, not two)
-#define VSRD_LAUNCH(K)                                                                                                                   \
-        hipLaunchKernelGGL(render_backward_front_kernel<K>, dim3(p.front_blocks), dim3(kBlockThreads), p.front_lds, s, f, field->instances, \
-                           field->mlp_weights, c, origins, directions, distances, num_distances, grad_labels, grad_gradients, grad_weights,  \
-                           box_partials, jets, seeds, masks, p.slots_per_instance, first, rays, chunk_index > 0 ? 1 : 0)
-        switch (p.rounds) {
-            case 1: VSRD_LAUNCH(1); break;
-            case 2: VSRD_LAUNCH(2); break;
-            case 4: VSRD_LAUNCH(4); break;
-            default: return VSRD_E_UNSUPPORTED;
-        }
-#undef VSRD_LAUNCH
-        hipLaunchKernelGGL(residual_mlp_adjoint_kernel, dim3(kMlpAdjointBlocks), dim3(kWave), adjoint_lds, s, field->instances,
-                           field->mlp_weights, N, mlp_bits, seeds, masks, p.slots_per_instance, used_slots, p.items_per_instance, p.slots_per_item,
-                           counter, item_rows, item_flags, 0ll);
-        hipLaunchKernelGGL(reduce_item_rows_kernel, dim3(N, (kItemRowFloats + 255) / 256, kItemSegments), dim3(256), 0, s, item_rows, item_flags,
-                           p.items_per_instance, segment_sums, 0ll);
-        hipLaunchKernelGGL(reduce_item_segments_kernel, dim3(N, (kItemRowFloats + 255) / 256), dim3(256), 0, s, segment_sums, grad_mlp_weights, box_extra,
-                           chunk_index > 0 ? 1 : 0, 0ll);
-        if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, box_partials, p.front_waves, row, grad_instances, box_extra);
-    return launch_status();
-}
-
-}  // namespace
 
 size_t vsrd_render_backward_workspace_bytes(int32_t num_instances, int32_t residual, int32_t num_distances, int32_t num_rays) {
     if (num_instances < 1 || num_instances > VSRD_MAX_INSTANCES || num_distances < 2 || num_distances > 2 * VSRD_MAX_SAMPLES || num_rays < 0) return 0;
@@ -1058,103 +1007,37 @@ int32_t vsrd_render_residual_step_with_header(const vsrd_field* field, const vsr
     if (workspace_bytes < p.total_bytes) return VSRD_E_WORKSPACE;
     if (!origins || !directions || !targets) return VSRD_E_INVALID_ARGUMENT;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const int row = N * kGradStride, mlp_row = N * kMlpWeights;
+    const int row = N * kGradStride;
     const int num_points = 2 * S - 1;
     const FieldArgs f = field_args(field);
     RenderArgs c = render_args(config);
     c.sh.inv_t = f.inv_t;
-    float* base = static_cast<float*>(workspace);
-    float* box_partials = base + p.box_partials;
-    float* loss_partials = base + p.loss_partials;
-    float4* jets = reinterpret_cast<float4*>(base + p.jets);
-    float* box_extra = base + p.box_extra;
-    unsigned* counter = reinterpret_cast<unsigned*>(base + p.counter);
-    float* segment_sums = base + p.segment_sums;
-    float* seeds = base + p.seeds;
-    float* item_rows = base + p.item_rows;
-    unsigned char* masks = reinterpret_cast<unsigned char*>(base + p.masks);
-    unsigned char* item_flags = reinterpret_cast<unsigned char*>(base + p.item_flags);
+    const SplitWorkspace w = split_workspace(workspace, p);
     const float eikonal_norm = 1.0f / (static_cast<float>(config->num_rays) * static_cast<float>(num_points));
     const float eikonal_scale = eikonal_ratio * eikonal_norm;
-    const unsigned mlp_bits = (config->flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? kMlpCentredBit : 0u;
-    const size_t adjoint_lds = (static_cast<size_t>(kMlpWbarFloats) + static_cast<size_t>(kMlpStashTiles) * kTileFloats) * sizeof(float);
     // VSRD_FLAG_MLP_SPLIT_BF16: the front kernels of the OTHER translation unit (split_front.hip), which read the instances' split-bf16
     // operand images instead of their weights
     const bool split = (config->flags & VSRD_FLAG_MLP_SPLIT_BF16) != 0u;
-    const float* front_weights = field->mlp_weights;
-    if (split) {
-        unsigned* images = reinterpret_cast<unsigned*>(base + p.images);
-        if (vsrd_split_front::pack_images(field->mlp_weights, N, (config->flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? 1 : 0, images, frames.count, frames.stride, header, s) != vsrd_split_front::kOk)
-            return VSRD_E_LAUNCH;
-        front_weights = reinterpret_cast<const float*>(images);
-    }
+    if (split && vsrd_split_front::pack_images(field->mlp_weights, N, (config->flags & VSRD_FLAG_MLP_WEIGHTS_CENTRED) ? 1 : 0, w.images, frames.count, frames.stride,
+                                               header, s) != vsrd_split_front::kOk)
+        return VSRD_E_LAUNCH;
+    const float* front_weights = split ? reinterpret_cast<const float*>(w.images) : field->mlp_weights;
     int chunk_index = 0;
     for (int first = 0; first < config->num_rays; first += p.chunk, ++chunk_index) {
         const int rays = std::min(p.chunk, config->num_rays - first);
-        const long long used_slots = static_cast<long long>(rays) * p.rounds;
-        if (!clear_frames(masks, (p.counter - p.masks + 4) * sizeof(float), frames, s)) return VSRD_E_LAUNCH;   // tile masks + the item counter's 16-byte slot (a multiple of 16 bytes: one fill kernel, not two)
-#define VSRD_FRONT_ARGS                                                                                                                  \
-        f, field->instances, front_weights, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, eikonal_scale, \
-        eikonal_norm, labels, box_partials, jets, loss_partials, seeds, masks, p.slots_per_instance, first, rays, chunk_index > 0 ? 1 : 0
-#define VSRD_LAUNCH(K)                                                                                                                   \
-        if (opt_in_lds(residual_step_front_kernel<K>, p.front_lds) != VSRD_OK) return VSRD_E_LAUNCH;                                     \
-        if (frames.count > 1) return VSRD_E_UNSUPPORTED;      /* (a batch's frames are launches of <= 2048 rays: the pair kernel) */                    \
-        if (wants_samples(config)) return VSRD_E_UNSUPPORTED; /* (the samples are written by the two-round instantiation below) */                      \
-        hipLaunchKernelGGL(residual_step_front_kernel<K>, dim3(p.front_blocks), dim3(kBlockThreads), p.front_lds, s, VSRD_FRONT_ARGS)
-#define VSRD_LAUNCH_PAIR(K)                                                                                                              \
-        if (frames.count > 1 || header) {                                                                                                \
-            if (opt_in_lds(residual_step_pair_kernel<K, true>, p.front_lds) != VSRD_OK) return VSRD_E_LAUNCH;                            \
-            hipLaunchKernelGGL((residual_step_pair_kernel<K, true>), dim3(p.front_blocks, frames.count), dim3(kPairWaves * kWave), p.front_lds, s, VSRD_FRONT_ARGS, \
-                               header);                                                                                                  \
-        } else {                                                                                                                         \
-            if (opt_in_lds(residual_step_pair_kernel<K>, p.front_lds) != VSRD_OK) return VSRD_E_LAUNCH;                                  \
-            hipLaunchKernelGGL(residual_step_pair_kernel<K>, dim3(p.front_blocks), dim3(kPairWaves * kWave), p.front_lds, s, VSRD_FRONT_ARGS, nullptr); \
-        }
-        if (split) {
-            vsrd_split_front::FrontLaunch launch = {&f, sizeof f, &c, sizeof c, field->instances, front_weights, origins, directions, u_coarse, u_fine, targets, instance_weights,
-                                                    loss_scale, eikonal_scale, eikonal_norm, labels, box_partials, jets, loss_partials, seeds, masks, p.slots_per_instance,
-                                                    first, rays, chunk_index > 0 ? 1 : 0, p.pair, p.rounds, p.front_blocks, p.front_lds, wants_samples(config), frames.count,
-                                                    frame_header};
-            const int code = vsrd_split_front::launch_front(launch, s);
-            if (code != vsrd_split_front::kOk) return code == vsrd_split_front::kUnsupported ? VSRD_E_UNSUPPORTED : VSRD_E_LAUNCH;
-        } else if (p.pair) {
-            switch (p.rounds) {
-                case 2: VSRD_LAUNCH_PAIR(2); break;
-                case 4: VSRD_LAUNCH_PAIR(4); break;
-                default: return VSRD_E_UNSUPPORTED;
-            }
-        } else {
-            if (p.rounds == 2 && wants_samples(config) && frames.count == 1) {         // vsrd_render_config::out_*: num_samples in (32, 64]
-                if (opt_in_lds(residual_step_front_kernel<2, true>, p.front_lds) != VSRD_OK) return VSRD_E_LAUNCH;
-                hipLaunchKernelGGL((residual_step_front_kernel<2, true>), dim3(p.front_blocks), dim3(kBlockThreads), p.front_lds, s, VSRD_FRONT_ARGS);
-            } else switch (p.rounds) {
-                case 1: VSRD_LAUNCH(1); break;
-                case 2: VSRD_LAUNCH(2); break;
-                case 4: VSRD_LAUNCH(4); break;
-                default: return VSRD_E_UNSUPPORTED;
-            }
-        }
-#undef VSRD_LAUNCH
-#undef VSRD_LAUNCH_PAIR
-#undef VSRD_FRONT_ARGS
-        if (split) {
-            if (vsrd_split_front::launch_adjoint(kMlpAdjointBlocks, field->instances, front_weights, N, seeds, masks, p.slots_per_instance, used_slots,
-                                                 p.items_per_instance, p.slots_per_item, counter, item_rows, item_flags, frames.count, frames.stride, s) != vsrd_split_front::kOk)
-                return VSRD_E_LAUNCH;
-        } else {
-            hipLaunchKernelGGL(residual_mlp_adjoint_kernel, dim3(kMlpAdjointBlocks, frames.count), dim3(kWave), adjoint_lds, s, field->instances,
-                               field->mlp_weights, N, mlp_bits, seeds, masks, p.slots_per_instance, used_slots, p.items_per_instance, p.slots_per_item,
-                               counter, item_rows, item_flags, frames.stride);
-        }
-        hipLaunchKernelGGL(reduce_item_rows_kernel, dim3(N, (kItemRowFloats + 255) / 256, kItemSegments * frames.count), dim3(256), 0, s, item_rows, item_flags,
-                           p.items_per_instance, segment_sums, frames.stride, header);
-        hipLaunchKernelGGL(reduce_item_segments_kernel, dim3(N, (kItemRowFloats + 255) / 256, frames.count), dim3(256), 0, s, segment_sums, grad_mlp_weights, box_extra,
-                           chunk_index > 0 ? 1 : 0, frames.stride, header);
-        if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+        if (!clear_frames(w.masks, w.clear_bytes, frames, s)) return VSRD_E_LAUNCH;
+        // the front kernel: one dispatch (launch.h), this unit's copy for the fp32 products and split_front.hip's for the split-bf16 ones
+        const vsrd_split_front::FrontLaunch launch = {&f, sizeof f, &c, sizeof c, field->instances, front_weights, origins, directions, u_coarse, u_fine, targets,
+                                                      instance_weights, loss_scale, eikonal_scale, eikonal_norm, labels, w.box_partials, w.jets, w.loss_partials, w.seeds,
+                                                      w.masks, p.slots_per_instance, first, rays, chunk_index > 0 ? 1 : 0, p.pair, p.rounds, p.front_blocks, p.front_lds,
+                                                      wants_samples(config), frames.count, frame_header};
+        const int code = split ? vsrd_split_front::launch_front(launch, s, switches().debug) : vsrd::launch_front(launch, s, switches().debug);
+        if (code != vsrd_split_front::kOk) return code == vsrd_split_front::kUnsupported ? VSRD_E_UNSUPPORTED : VSRD_E_LAUNCH;
+        const int32_t status = launch_adjoint_tail(field, split ? w.images : nullptr, config->flags, p, w, rays, chunk_index > 0, grad_mlp_weights, frames, header, s);
+        if (status != VSRD_OK) return status;
     }
-    (void)mlp_row;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 2, frames.count), dim3(256), 0, s, box_partials, p.front_waves, row, grad_instances, box_extra, loss_partials, 2, losses,
-                       frames.stride, header);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 2, frames.count), dim3(256), 0, s, w.box_partials, p.front_waves, row, grad_instances, w.box_extra, w.loss_partials, 2,
+                       losses, frames.stride, header);
     return launch_status();
 }
 
@@ -1182,6 +1065,24 @@ static bool frame_args(const vsrd_frame_config* c, FrameStepArgs* a) {
     a->header = nullptr;
     return true;
 }
+// the buffers of a frame's prologue, none of which may be null (the scratch apart: its size is the caller's next check)
+bool frame_buffers(const float* raw_locations, const float* raw_dimensions, const float* raw_orientations, const float* extrinsics, const float* intrinsics,
+                   const float* gt_boxes, const uint8_t* visible, const int64_t* step, void* scratch, float* instances, int64_t* pd_indices, int64_t* gt_indices,
+                   int32_t* target_columns, float* instance_weights, float* schedule, float* projection_losses, float* grad_raw, FrameBuffers* b) {
+    if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible || !step || !instances ||
+        !pd_indices || !gt_indices || !target_columns || !instance_weights || !schedule || !projection_losses || !grad_raw)
+        return false;
+    b->raw_locations = raw_locations; b->raw_dimensions = raw_dimensions; b->raw_orientations = raw_orientations;
+    b->extrinsics = extrinsics; b->intrinsics = intrinsics; b->gt_boxes = gt_boxes; b->visible = visible;
+    b->step = reinterpret_cast<const long long*>(step);
+    b->scratch = static_cast<float*>(scratch);
+    b->instances = instances;
+    b->pd_indices = reinterpret_cast<long long*>(pd_indices); b->gt_indices = reinterpret_cast<long long*>(gt_indices);
+    b->target_map = target_columns; b->instance_weights = instance_weights; b->schedule = schedule; b->losses = projection_losses; b->grad_raw = grad_raw;
+    return true;
+}
+bool valid_adam(const vsrd_adam_tensors& t) { return t.parameter && t.exp_avg && t.exp_avg_sq && t.step && t.learning_rate; }
+AdamTensors adam_tensors(const vsrd_adam_tensors& t) { return AdamTensors{t.parameter, t.exp_avg, t.exp_avg_sq, t.step, t.learning_rate}; }
 }  // namespace
 
 int32_t vsrd_frame_prologue(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions,
@@ -1202,18 +1103,11 @@ int32_t vsrd_frame_prologue_with_header(const vsrd_frame_config* config, const f
     FrameStepArgs a;
     if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
     a.header = reinterpret_cast<const FrameHeader*>(frame_header);
-    if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible || !step || !instances ||
-        !pd_indices || !gt_indices || !target_columns || !instance_weights || !schedule || !projection_losses || !grad_raw)
+    FrameBuffers b;
+    if (!frame_buffers(raw_locations, raw_dimensions, raw_orientations, extrinsics, intrinsics, gt_boxes, visible, step, scratch, instances, pd_indices, gt_indices,
+                       target_columns, instance_weights, schedule, projection_losses, grad_raw, &b))
         return VSRD_E_INVALID_ARGUMENT;
     if (!scratch || scratch_bytes < vsrd_frame_scratch_bytes(a.num_views, a.num_boxes)) return VSRD_E_WORKSPACE;
-    FrameBuffers b;
-    b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
-    b.extrinsics = extrinsics; b.intrinsics = intrinsics; b.gt_boxes = gt_boxes; b.visible = visible;
-    b.step = reinterpret_cast<const long long*>(step);
-    b.scratch = static_cast<float*>(scratch);
-    b.instances = instances;
-    b.pd_indices = reinterpret_cast<long long*>(pd_indices); b.gt_indices = reinterpret_cast<long long*>(gt_indices);
-    b.target_map = target_columns; b.instance_weights = instance_weights; b.schedule = schedule; b.losses = projection_losses; b.grad_raw = grad_raw;
     hipLaunchKernelGGL(frame_prologue_kernel, dim3(1, config->num_frames > 1 ? config->num_frames : 1), dim3(kFrameThreads), 0, static_cast<hipStream_t>(stream), a, b);
     return launch_status();
 }
@@ -1239,19 +1133,12 @@ int32_t vsrd_frame_prologue_sample_with_header(const vsrd_frame_config* config, 
     FrameStepArgs a;
     if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
     a.header = reinterpret_cast<const FrameHeader*>(frame_header);
-    if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible || !step || !instances ||
-        !pd_indices || !gt_indices || !target_columns || !instance_weights || !schedule || !projection_losses || !grad_raw)
+    FrameBuffers b;
+    if (!frame_buffers(raw_locations, raw_dimensions, raw_orientations, extrinsics, intrinsics, gt_boxes, visible, step, scratch, instances, pd_indices, gt_indices,
+                       target_columns, instance_weights, schedule, projection_losses, grad_raw, &b))
         return VSRD_E_INVALID_ARGUMENT;
     if (!ray_table || !ray_indices || count < 1 || count >= 0xffffffffll || num_rays < 1 || num_rays > kSampleMax) return VSRD_E_INVALID_ARGUMENT;
     if (!scratch || scratch_bytes < vsrd_frame_scratch_bytes(a.num_views, a.num_boxes)) return VSRD_E_WORKSPACE;
-    FrameBuffers b;
-    b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
-    b.extrinsics = extrinsics; b.intrinsics = intrinsics; b.gt_boxes = gt_boxes; b.visible = visible;
-    b.step = reinterpret_cast<const long long*>(step);
-    b.scratch = static_cast<float*>(scratch);
-    b.instances = instances;
-    b.pd_indices = reinterpret_cast<long long*>(pd_indices); b.gt_indices = reinterpret_cast<long long*>(gt_indices);
-    b.target_map = target_columns; b.instance_weights = instance_weights; b.schedule = schedule; b.losses = projection_losses; b.grad_raw = grad_raw;
     // (a refused LDS opt-in is "this device / build cannot run the combined launch" -- VSRD_E_UNSUPPORTED, on which the caller falls back to
     //  vsrd_frame_prologue + vsrd_sample_rays_table -- and not a failed launch, which must not be mistaken for it)
     if (opt_in_lds(frame_prologue_sample_kernel, kTableLdsBytes) != VSRD_OK) return VSRD_E_UNSUPPORTED;
@@ -1280,16 +1167,11 @@ int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const f
     a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     if (!grad_instances || !grad_raw_projection || !projection_losses || !render_losses || !locations || !dimensions || !orientations || !step || !record)
         return VSRD_E_INVALID_ARGUMENT;
-    const vsrd_adam_tensors* groups[3] = {locations, dimensions, orientations};
-    AdamTensors tensors[3];
-    for (int k = 0; k < 3; ++k) {
-        if (!groups[k]->parameter || !groups[k]->exp_avg || !groups[k]->exp_avg_sq || !groups[k]->step || !groups[k]->learning_rate) return VSRD_E_INVALID_ARGUMENT;
-        tensors[k] = AdamTensors{groups[k]->parameter, groups[k]->exp_avg, groups[k]->exp_avg_sq, groups[k]->step, groups[k]->learning_rate};
-    }
+    if (!valid_adam(*locations) || !valid_adam(*dimensions) || !valid_adam(*orientations)) return VSRD_E_INVALID_ARGUMENT;
     EpilogueBuffers e;
     e.grad_instances = grad_instances; e.grad_raw_projection = grad_raw_projection; e.projection_losses = projection_losses;
     e.render_losses = render_losses; e.eikonal_ratio = eikonal_ratio;
-    e.locations = tensors[0]; e.dimensions = tensors[1]; e.orientations = tensors[2];
+    e.locations = adam_tensors(*locations); e.dimensions = adam_tensors(*dimensions); e.orientations = adam_tensors(*orientations);
     e.other_learning_rates[0] = other_learning_rate_0; e.other_learning_rates[1] = other_learning_rate_1;
     e.step = reinterpret_cast<long long*>(step); e.record = record; e.raw_gradients = raw_gradients;
     hipLaunchKernelGGL(frame_epilogue_kernel, dim3(1, config->num_frames > 1 ? config->num_frames : 1), dim3(kFrameMaxBoxes), 0, static_cast<hipStream_t>(stream), a, e);
@@ -1318,8 +1200,6 @@ static HyperPlan plan_hypernetwork(int num_instances) {
     p.total = p.norm_partials + (VSRD_HYPER_LAYERS - 1) * 2 * slab;
     return p;
 }
-static bool valid_adam(const vsrd_adam_tensors& t) { return t.parameter && t.exp_avg && t.exp_avg_sq && t.step && t.learning_rate; }
-static AdamTensors adam_tensors(const vsrd_adam_tensors& t) { return AdamTensors{t.parameter, t.exp_avg, t.exp_avg_sq, t.step, t.learning_rate}; }
 static bool valid_hypernetwork(const vsrd_hypernetwork* net) {
     if (!net || net->num_instances < 1 || net->num_instances > VSRD_MAX_INSTANCES || net->num_outputs != kMlpWeights) return false;
     if (!valid_adam(net->embeddings)) return false;
