@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define VSRD_ABI_VERSION 9
+#define VSRD_ABI_VERSION 10
 
 #define VSRD_OK 0
 #define VSRD_E_INVALID_ARGUMENT (-1) /* null pointer, non-positive size, unsupported N / S */
@@ -327,6 +327,33 @@ int32_t vsrd_sphere_trace(const vsrd_field* field, const float* origins, int32_t
 int32_t vsrd_polygon_soft_masks(const float* polygons, const int32_t* counts, int32_t num_polygons, int32_t max_vertices,
                                 int32_t height, int32_t width, const uint8_t* inside, float temperature,
                                 float* distance_maps, float* soft_masks, void* stream);
+
+/* Frame ingest (ABI 10): one frame's compact pack (vsrd_amd/frames.py: one polygon and one bit-packed binary mask per (view, instance)
+ * ENTRY, as the reference's dataset keeps them) straight into the buffers a frame's step reads -- SoftRasterizer
+ * (geometric_transforms.py:265-317), BoxGenerator (:151-159), the re-indexing of every view to the target's instance order
+ * (scripts/main.py:204-265) and the importance weights (main.py:620-624) in one call, with no [V,H,W,N] temporary.
+ *   polygon_vertices [num_vertices,2] int32 (x, y), all entries concatenated; polygon_offsets [num_entries + 1] int32 (every entry has
+ *   at least one vertex; one vertex is a single-pixel contour, two a line);
+ *   entry_table [V,N] int32, IN/OUT: the entry of (view, target slot), -1 where the instance is absent from the view.  An entry without a
+ *   set bit counts as invisible: the call REPLACES it by -1 (so do entries that do not address the pack);
+ *   inside [num_entries, H, ceil(W/8)] uint8: the binary masks, eight pixels per byte, most significant bit first (numpy.packbits);
+ *   target_stride >= N: the row's capacity, the stride of every output's instance axis.  V <= 32, N <= VSRD_MAX_INSTANCES.
+ * Outputs, each may be NULL; only instances 0..N-1 are written, columns N..target_stride-1 are left alone:
+ *   soft_masks [V*H*W, target_stride]: sigmoid((inside ? d : -d) / temperature), d the distance of the pixel centre to the closed polygon
+ *     with the reference's + 1e-6 in the projection's denominator; exactly 0.0 for an invisible pair (16-byte stores when target_stride
+ *     is a multiple of 4 and the buffer is 16-byte aligned);
+ *   sampling_weights [V*H*W]: the maximum over the N written columns, bit-equal to amax of them;
+ *   gt_boxes [V, target_stride, 4]: (xmin, ymin, xmax, ymax) of the set bits as inclusive pixel indices, zeros for an invisible pair.
+ *     These are the extremes of the ENTRY's bits -- the filled largest contour.  The reference's BoxGenerator takes the extremes of
+ *     `masks > threshold`, every component of the mask: the two agree for masks of one component; a mask with detached parts gets the box
+ *     of its largest part here;
+ *   visible [V, target_stride] uint8.
+ * vsrd_frame_ingest_chunk(): the polygon sides the pixel pass stages per round (longer polygons take several rounds). */
+int32_t vsrd_frame_ingest_chunk(void);
+int32_t vsrd_frame_ingest(const int32_t* polygon_vertices, int32_t num_vertices, const int32_t* polygon_offsets, int32_t num_entries,
+                          int32_t* entry_table, const uint8_t* inside, int32_t height, int32_t width, int32_t num_views, int32_t num_instances,
+                          int32_t target_stride, float temperature, float* soft_masks, float* sampling_weights, float* gt_boxes,
+                          uint8_t* visible, void* stream);
 
 /* samplers.quadrature_sampler over linspace bins (renderers.py:191-194, samplers.py:5-8).
  * u_coarse [R,S] in [0,1) -> distances [R,S]. */

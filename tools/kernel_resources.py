@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register / scratch footprint of every kernel of the library AS SHIPPED: the code-object metadata inside vsrd_amd/lib/libvsrd_hip.so
+"""Register / scratch / static LDS footprint of every kernel of the library AS SHIPPED: the code-object metadata inside vsrd_amd/lib/libvsrd_hip.so
 (what the loader sees -- a callee's registers and the AGPRs it parks callee-saved ones in count towards its callers here, which a
 one-kernel compile does not show: residual_step_pair_kernel<4> is 251 registers compiled alone and 256-260 in the library).
     python tools/kernel_resources.py [path/to/lib.so]          -> table on stdout (profiles/<round>/kernel_resources.txt)
@@ -43,11 +43,11 @@ def main():
         name = get("name").group(1)
         demangled = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0].replace("void ", "")
         rows.append((demangled, int(get("vgpr_count").group(1)), agpr, int(get("sgpr_count").group(1)), int(get("vgpr_spill_count").group(1)),
-                     int(get("sgpr_spill_count").group(1)), int(get("private_segment_fixed_size").group(1))))
+                     int(get("sgpr_spill_count").group(1)), int(get("private_segment_fixed_size").group(1)), int(get("group_segment_fixed_size").group(1))))
     print(f"# {os.path.relpath(library, ROOT)}: code-object metadata (llvm-readelf --notes)")
-    print(f"{'kernel':62s} {'vgpr+agpr':>9s} {'agpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'waves/SIMD':>10s}")
-    for name, vgpr, agpr, sgpr, vs, ss, scratch in sorted(rows):
-        print(f"{name[:62]:62s} {vgpr:9d} {agpr:5d} {sgpr:5d} {vs:6d} {ss:6d} {scratch:7d} {min(8, 512 // max(vgpr, 1)):10d}")
+    print(f"{'kernel':62s} {'vgpr+agpr':>9s} {'agpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'scratch':>7s} {'lds':>6s} {'waves/SIMD':>10s}")
+    for name, vgpr, agpr, sgpr, vs, ss, scratch, lds in sorted(rows):
+        print(f"{name[:62]:62s} {vgpr:9d} {agpr:5d} {sgpr:5d} {vs:6d} {ss:6d} {scratch:7d} {lds:6d} {min(8, 512 // max(vgpr, 1)):10d}")
 
 
 if __name__ == "__main__":

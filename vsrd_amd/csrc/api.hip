@@ -11,6 +11,7 @@
 #include "projection.h"
 #include "frame_step.h"
 #include "hypernetwork.h"
+#include "frame_ingest.h"
 #include "launch.h"
 
 namespace {
@@ -560,6 +561,34 @@ int32_t vsrd_polygon_soft_masks(const float* polygons, const int32_t* counts, in
     const dim3 grid(static_cast<unsigned>(std::min((pixels + 255) / 256, 4096)), static_cast<unsigned>(num_polygons));
     hipLaunchKernelGGL(polygon_soft_mask_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), polygons, counts, num_polygons,
                        max_vertices, height, width, inside, temperature, distance_maps, soft_masks);
+    return launch_status();
+}
+
+int32_t vsrd_frame_ingest_chunk(void) { return kIngestChunk; }
+
+int32_t vsrd_frame_ingest(const int32_t* polygon_vertices, int32_t num_vertices, const int32_t* polygon_offsets, int32_t num_entries,
+                          int32_t* entry_table, const uint8_t* inside, int32_t height, int32_t width, int32_t num_views, int32_t num_instances,
+                          int32_t target_stride, float temperature, float* soft_masks, float* sampling_weights, float* gt_boxes,
+                          uint8_t* visible, void* stream) {
+    if (!polygon_vertices || !polygon_offsets || !entry_table || !inside || num_vertices < 1 || num_entries < 1) return VSRD_E_INVALID_ARGUMENT;
+    if (height < 1 || width < 1 || num_views < 1 || num_views > kFrameMaxViews || num_instances < 1 || num_instances > VSRD_MAX_INSTANCES ||
+        target_stride < num_instances || !(temperature > 0.0f))
+        return VSRD_E_INVALID_ARGUMENT;
+    const int64_t pixels = static_cast<int64_t>(height) * width;
+    if (pixels * num_views * target_stride >= (int64_t{1} << 40) || pixels >= (int64_t{1} << 30)) return VSRD_E_UNSUPPORTED;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    // the boxes first: they take the entries without a set bit out of the table the pixel pass reads
+    hipLaunchKernelGGL(frame_ingest_boxes_kernel, dim3(num_instances, num_views), dim3(kIngestThreads), 0, s, entry_table, polygon_offsets, num_entries,
+                       num_vertices, inside, height, width, num_instances, target_stride, gt_boxes, visible);
+    if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+    if (!soft_masks && !sampling_weights) return VSRD_OK;
+    const int per_block = kIngestThreads * kIngestPixels;
+    const dim3 grid(static_cast<unsigned>((pixels + per_block - 1) / per_block), static_cast<unsigned>(num_views));
+    const bool vector = target_stride % 4 == 0 && reinterpret_cast<uintptr_t>(soft_masks) % 16 == 0;
+    for_bool(vector, [&](auto wide) {
+        hipLaunchKernelGGL(frame_ingest_pixels_kernel<decltype(wide)::value>, grid, dim3(kIngestThreads), 0, s, entry_table, polygon_offsets, polygon_vertices,
+                           inside, height, width, num_instances, target_stride, temperature, soft_masks, sampling_weights);
+    });
     return launch_status();
 }
 

@@ -223,6 +223,33 @@ def synthetic_frame_inputs(device, frame, views, instances, height=376, width=14
     return optimization.FrameInputs((height, width), K, E, soft, gt_boxes, torch.ones(views, instances, dtype=torch.bool, device=device))
 
 
+def scan_frames_dir(folder, limit=0):
+    """--frames-dir: the sorted *.npz files of `folder` (the first `limit` of them when limit > 0) and each one's
+    (V, H, W, N) (frames.pack_counts: no masks are loaded).  SystemExit when there is none, when a file is malformed, or when a file's
+    (V, H, W) differs from the first one's -- naming the odd file."""
+    import glob
+    from . import frames
+    files = sorted(glob.glob(os.path.join(folder, "*.npz")))
+    if not files:
+        raise SystemExit(f"--frames-dir {folder}: no *.npz frame packs there")
+    if limit > 0:
+        if limit > len(files):
+            raise SystemExit(f"--frames {limit}: --frames-dir {folder} holds {len(files)} frame packs")
+        files = files[:limit]
+    shapes = []
+    for path in files:
+        try:
+            shapes.append(frames.pack_counts(path))
+        except ValueError as error:
+            raise SystemExit(f"--frames-dir: {error}")
+        if shapes[-1][:3] != shapes[0][:3]:
+            raise SystemExit(f"--frames-dir: {path} has (views, height, width) = {shapes[-1][:3]}, {files[0]} has {shapes[0][:3]}: "
+                             "the frames of one job share their view count and image size")
+        if not 1 <= shapes[-1][3] <= 64:
+            raise SystemExit(f"--frames-dir: {path} has {shapes[-1][3]} target instances, 1..64")
+    return files, shapes
+
+
 def _newest_change(folder):
     """Modification time of the newest entry of the checkpoint directory: a frame's folder changes when its checkpoint is renamed into it."""
     try:
@@ -327,12 +354,26 @@ class _RenderWork:
         return (int(self.manifest["seed"]) * 1000003 + int(frame)) & 0x7FFFFFFF
 
     def inputs_of(self, frame):
-        """A static queue's inputs are resident before the clock (what main.py:106-316 prepares per frame is the dataset's work, not the
-        loop's); a dynamic queue's are built when the frame is taken -- inside the clock, like the reference's loader -- and dropped after."""
+        """A static queue's synthetic inputs are resident before the clock (what main.py:106-316 prepares per frame is the dataset's work, not the
+        loop's); a dynamic queue's are built when the frame is taken -- inside the clock, like the reference's loader -- and dropped after.
+        Frame packs (--frames-dir) are always read when the frame is taken and never kept."""
         if frame in self.inputs:
             return self.inputs[frame]
         args = self.args
+        if args.frames_dir:          # a frame pack (frames.py), host side: slots and batch rows reset from it, vsrd_frame_ingest fills the row
+            from . import frames
+            return frames.load_pack(self.manifest["packs"][int(frame)])
         return synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts), args.height, args.width)
+
+    def materialised(self, inputs):
+        """`inputs` as a FrameInputs on the device: what founds a slot or a batch, and what a loop of its own is built on."""
+        from . import frames
+        return frames.ingest(inputs, self.device) if isinstance(inputs, frames.FramePack) else inputs
+
+    @staticmethod
+    def count_of(inputs):
+        from . import frames
+        return inputs.num_instances if isinstance(inputs, frames.FramePack) else int(inputs.soft_masks.shape[-1])
 
     def optimization_config(self, **more):
         from . import optimization
@@ -347,8 +388,10 @@ class _RenderWork:
         from . import optimization
         args = self.args
         mine = [] if self.queue.dynamic else [frame for frame in self.queue.mine if not os.path.exists(self.path_of(frame))]
-        self.inputs = {frame: synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts), args.height, args.width)
-                       for frame in mine}
+        # (frame packs are NOT made resident: a directory holds any number of them, 9 MB each at the reference's size.  A pack is read when its
+        #  frame is taken -- inside the clock, under phase_seconds["inputs"] -- and dropped once its row is reset)
+        self.inputs = {} if args.frames_dir else {frame: synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts),
+                                                                                args.height, args.width) for frame in mine}
         self.slots, self.batch = queue.Queue(), None
         self.setup_seconds, self.graphs_per_slot, self.unsuitable_founders = 0.0, 0, []
         # the frames a slot or batch may be founded on: this rank's own (static), or the head of the job's queue (dynamic: built here, once)
@@ -356,7 +399,7 @@ class _RenderWork:
         if candidates and not args.fresh_loops:
             t_setup = time.perf_counter()
             if args.frame_batch > 1:
-                founders = [self.inputs_of(f) for f in candidates[:args.frame_batch]]
+                founders = [self.materialised(self.inputs_of(f)) for f in candidates[:args.frame_batch]]
                 founders += [founders[-1]] * (args.frame_batch - len(founders))           # (fewer frames than rows: the shape is what matters)
                 try:
                     mixed = len(set(args.instance_counts)) > 1           # (a mixed list: rows of capacity max(list), each frame its own count)
@@ -372,7 +415,7 @@ class _RenderWork:
                 for _ in range(min(args.frames_in_flight, len(candidates))):
                     for founder in candidates:      # (a slot is founded on a frame that suits the table sampler its graphs will draw from)
                         try:
-                            loop = optimization.FrameOptimizer(self.inputs_of(founder), self.optimization_config(), self.device, graph=True, persistent=True)
+                            loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(founder)), self.optimization_config(), self.device, graph=True, persistent=True)
                         except optimization.UnsuitableFrameError:
                             self.unsuitable_founders.append(int(founder))
                             continue
@@ -386,7 +429,7 @@ class _RenderWork:
     def _own_loop(self, frame):
         """A frame outside the slots / the batch (--fresh-loops, or importance weights that do not suit the table sampler): a loop of its own."""
         from . import formats, optimization
-        loop = optimization.FrameOptimizer(self.inputs_of(frame), self.optimization_config(init_seed=self.init_seed(frame)), self.device, graph=True)
+        loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(frame)), self.optimization_config(init_seed=self.init_seed(frame)), self.device, graph=True)
         record = loop.run(self.args.num_steps)
         with optimization.exclusive_device_access():
             torch.cuda.current_stream().synchronize()
@@ -412,7 +455,7 @@ class _RenderWork:
             try:
                 inputs = self.inputs_of(frame)
                 # (a slot serves frames of its founder's shape: a frame of another instance count runs in a loop of its own)
-                if slot is None or int(inputs.soft_masks.shape[-1]) != slot.num_instances or not slot.reset(inputs, init_seed=self.init_seed(frame)):
+                if slot is None or self.count_of(inputs) != slot.num_instances or not slot.reset(inputs, init_seed=self.init_seed(frame)):
                     fallbacks.append(int(frame))
                     losses[frame], payload = self._own_loop(frame)
                     return payload
@@ -433,7 +476,7 @@ class _RenderWork:
             done = run_frames(self.queue, optimise, self.path_of, frames_in_flight=args.frames_in_flight)
         torch.cuda.synchronize()
         taken = len(self.queue.taken)
-        return dict(frames=len(done), skipped=taken - len(done),
+        return dict(frames=len(done), skipped=taken - len(done), frames_done=sorted(int(f) for f in done),
                     gate_capture_seconds=optimization.exclusive_device_access().capture_seconds - self.captures_before,
                     slot_setup_seconds=self.setup_seconds, graphs_per_slot=self.graphs_per_slot, final_losses={int(f): losses[f] for f in sorted(losses)},
                     frames_outside_slots=sorted(fallbacks), unsuitable_founders=self.unsuitable_founders, frames_with_unhealthy_draws=sorted(unhealthy),
@@ -521,7 +564,7 @@ class _SleepWork:
             return dict(frame=int(frame), attempt=args.attempt, rank=self.rank)
 
         done = run_frames(self.queue, optimise, self.path_of, frames_in_flight=1)
-        return dict(frames=len(done), skipped=len(self.queue.taken) - len(done), gate_capture_seconds=0.0, slot_setup_seconds=0.0, graphs_per_slot=0, final_losses={},
+        return dict(frames=len(done), skipped=len(self.queue.taken) - len(done), frames_done=sorted(int(f) for f in done), gate_capture_seconds=0.0, slot_setup_seconds=0.0, graphs_per_slot=0, final_losses={},
                     frames_outside_slots=[], unsuitable_founders=[], frames_with_unhealthy_draws=[])
 
 
@@ -588,16 +631,20 @@ def main(argv=None):
                         help="OptimizationConfig.mlp_adjoint_item_slots (vsrd_render_config::adjoint_slots_per_item): 0 = planned (4 for one frame of 1000 rays; "
                              "a batch picks FrameBatch.item_slots).  A frame's trajectory is bit-identical alone and in a batch for equal numbers")
     parser.add_argument("--fp32-mlp", action="store_true", help="the residual MLP's products on the exact-fp32 matrix instruction instead of split bf16")
-    parser.add_argument("--views", type=int, default=17)
-    parser.add_argument("--instances", type=str, default="8",
+    parser.add_argument("--frames-dir", default="",
+                        help="optimise the frame packs of this directory (vsrd_amd/frames.py; tools/make_frame_packs.py writes synthetic ones) instead of "
+                             "synthetic frames: frame j is the j-th of its sorted *.npz files, --frames defaults to all of them, views / image size / "
+                             "instance counts are the packs' own (not to be combined with --views, --instances, --height, --width)")
+    parser.add_argument("--views", type=int, default=None, help="default 17")
+    parser.add_argument("--instances", type=str, default=None,
                         help="instances per frame: one count, or a comma list (frame j gets list[j %% len(list)]); with --frame-batch > 1 a mixed "
-                             "list runs in batches of capacity max(list) (optimization.FrameBatch(max_instances=...))")
+                             "list runs in batches of capacity max(list) (optimization.FrameBatch(max_instances=...)); default 8")
     parser.add_argument("--rays", type=int, default=1000)
     parser.add_argument("--samples", type=int, default=100)
     parser.add_argument("--num-steps", type=int, default=3000)
     parser.add_argument("--warmup-steps", type=int, default=1000)
-    parser.add_argument("--height", type=int, default=376)
-    parser.add_argument("--width", type=int, default=1408)
+    parser.add_argument("--height", type=int, default=None, help="default 376")
+    parser.add_argument("--width", type=int, default=None, help="default 1408")
     parser.add_argument("--out", default="", help="checkpoint directory (default: a temporary one)")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--ranks-share-gpu", action="store_true",
@@ -623,6 +670,18 @@ def main(argv=None):
     parser.add_argument("--selftest-hang", default="", help="RANK:FRAMES -- on attempt 0 that rank hangs (sleeps for ever) once it has finished FRAMES frames")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parser.parse_args(argv)
+    if args.frames_dir:
+        given = [flag for flag, value in (("--views", args.views), ("--instances", args.instances), ("--height", args.height), ("--width", args.width)) if value is not None]
+        if given:
+            raise SystemExit(f"--frames-dir: the packs carry their own views, image size and instance counts; drop {', '.join(given)}")
+        # (the supervisor starts its ranks in the repository root: they get the directory as an absolute path, in a flag of its own
+        #  behind the caller's -- the last one counts)
+        args.frames_dir = os.path.abspath(args.frames_dir)
+        argv = argv + ["--frames-dir", args.frames_dir]
+        if "RANK" not in os.environ:          # (a job nobody could run ends here, before any rank starts; rank 0 reads the counts again for the manifest)
+            scan_frames_dir(args.frames_dir, args.frames)
+    args.views, args.height, args.width = (default if value is None else value for value, default in ((args.views, 17), (args.height, 376), (args.width, 1408)))
+    args.instances = "8" if args.instances is None else args.instances
     args.instance_counts = parse_instances(args.instances)
     args.instances = args.instance_counts[0] if len(args.instance_counts) == 1 else args.instances
     if not 1 <= args.frames_in_flight <= (4 if args.fresh_loops else 8):
@@ -690,8 +749,11 @@ def _rank_main(args):
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", "29500")
             dist.init_process_group(backend="gloo", rank=rank, world_size=world)
+    packs = shapes = None
+    if args.frames_dir and rank == 0:        # rank 0 alone lists the directory and opens the files for their counts: the job is what ITS list says
+        packs, shapes = scan_frames_dir(args.frames_dir, args.frames)
+        args.frames = len(packs)
     total = args.frames or (2 * max(args.frames_in_flight, args.frame_batch) * world if use_gpu else 4 * world)
-    args.frame_batch = effective_frame_batch(args.frame_batch, total, world)
     out_dir = args.out or (tempfile.mkdtemp(prefix="vsrd_frames_") if rank == 0 else None)
     dynamic = args.queue == "dynamic" or (args.queue == "auto" and world > 1)
     store = None
@@ -701,7 +763,14 @@ def _rank_main(args):
         if rank == 0:
             store = dist.TCPStore(host, 0, world, is_master=True, wait_for_workers=False)
             store_port = store.port
-    manifest = broadcast_manifest(dict(frames=list(range(total)), seed=args.seed, out=out_dir, store_port=store_port, attempt=args.attempt) if rank == 0 else None)
+    manifest = broadcast_manifest(dict(frames=list(range(total)), seed=args.seed, out=out_dir, store_port=store_port, attempt=args.attempt,
+                                       packs=packs, pack_shapes=shapes) if rank == 0 else None)
+    total = len(manifest["frames"])          # (every rank sizes the job from the manifest)
+    args.frame_batch = effective_frame_batch(args.frame_batch, total, world)
+    if manifest.get("packs"):                # frame j's count is its pack's: instances_of(j, counts) with one entry per frame
+        args.views, args.height, args.width = manifest["pack_shapes"][0][:3]
+        args.instance_counts = [int(shape[3]) for shape in manifest["pack_shapes"]]
+        args.instances = ",".join(str(n) for n in sorted(set(args.instance_counts)))
     if not manifest["out"]:
         raise SystemExit("no checkpoint directory (--out; the supervisor supplies one)")
     if dynamic and rank != 0:
@@ -741,6 +810,9 @@ def _rank_main(args):
                     "procs_per_gpu": procs, "rank_devices": [r["device"] for r in gathered], "frames": frames_done,
                     "frames_skipped_as_done": sum(r["skipped"] for r in gathered), "per_rank_frames": [r["frames"] for r in gathered],
                     "restarts": args.attempt, "max_restarts": args.max_restarts, "queue": "dynamic" if dynamic else "static",
+                    "frames_dir": args.frames_dir or None,
+                    "frames_per_instances": {str(n): sum(1 for r in gathered for f in r["frames_done"] if instances_of(f, args.instance_counts) == n)
+                                             for n in sorted(set(args.instance_counts))},
                     "per_rank_seconds": [r["own_seconds"] for r in gathered],
                     "rank_finish_spread_seconds": max(r["own_seconds"] for r in gathered) - min(r["own_seconds"] for r in gathered),
                     "config": {"workload": f"sleep({args.selftest_seconds} s x (1 + {args.selftest_spread} u)) per frame on gloo / CPU", "checkpoints": manifest["out"]}}
@@ -754,19 +826,21 @@ def _rank_main(args):
                 "ranks": len(gathered), "procs_per_gpu": procs, "frames_in_flight_per_process": args.frames_in_flight, "rank_devices": [r["device"] for r in gathered],
                 "frame_batch": args.frame_batch,        # frames one process steps together, one launch of every kernel for all of them (optimization.FrameBatch)
                 # instances per frame (frame j: instance_list[j % len]); frames done per count; the rows' capacity of a mixed batch (None: one shape)
-                "instance_list": list(args.instance_counts),
+                "instance_list": sorted(set(args.instance_counts)) if args.frames_dir else list(args.instance_counts),
+                "frames_dir": args.frames_dir or None,
                 "frames_per_instances": {str(n): sum(1 for r in gathered for f in r["final_losses"] if instances_of(f, args.instance_counts) == n)
                                          for n in sorted(set(args.instance_counts))},
                 "batch_capacity": max(args.instance_counts) if args.frame_batch > 1 and len(set(args.instance_counts)) > 1 else None,
                 "control_plane": "gloo" if share else "RCCL",
                 "queue": "dynamic (TCPStore counter on rank 0; inputs built when a frame is taken, inside the clock)" if dynamic else
-                         "static (frame j of the seeded permutation to rank j mod world; inputs resident before the clock)",
+                         "static (frame j of the seeded permutation to rank j mod world; " +
+                         ("packs read when a frame is taken, inside the clock)" if args.frames_dir else "inputs resident before the clock)"),
                 # the spread of the ranks' own finishing times: what a static split of unequal frames costs the job, what the queue bounds by one group
                 "rank_finish_spread_seconds": max(r["own_seconds"] for r in gathered) - min(r["own_seconds"] for r in gathered),
                 "mlp_products": "exact fp32 (v_mfma_f32_16x16x4_f32)" if args.fp32_mlp else "split bf16 (v_mfma_f32_16x16x32_bf16 on hi/lo parts, fp32 accumulation)",
                 "per_rank_seconds": [r["own_seconds"] for r in gathered], "per_rank_frames": [r["frames"] for r in gathered],
                 "seconds_per_frame_per_rank": [r["own_seconds"] / r["frames"] if r["frames"] else None for r in gathered],
-                "mean_final_loss": [r["mean_final_loss"] for r in gathered], "data": "synthetic", "dtype": "f32",
+                "mean_final_loss": [r["mean_final_loss"] for r in gathered], "data": "frame packs" if args.frames_dir else "synthetic", "dtype": "f32",
                 "final_loss_per_frame": {str(f): v for r in gathered for f, v in r["final_losses"].items()},
                 # host time per frame spent capturing hipGraphs (optimization._CaptureGate): what the other frames in flight wait for
                 "capture_seconds_per_frame": [r["gate_capture_seconds"] / r["frames"] if r["frames"] else None for r in gathered],

@@ -21,7 +21,7 @@ import time
 
 import torch
 
-from . import _lib, fields, losses, models, operations, rendering
+from . import _lib, fields, frames, losses, models, operations, rendering
 
 
 class _CaptureGate:
@@ -989,6 +989,41 @@ class FrameOptimizer:
         self.reset(self.inputs)
         return len(self._graphs)
 
+    def _copy_inputs(self, inputs, V, N):
+        """reset() from a materialised FrameInputs: the strided copy into the row, the importance weights, the glue's tables."""
+        b = self._glue
+        if inputs.soft_masks.data_ptr() == self.flat_masks.data_ptr():
+            # `inputs` is what a reset from a frame pack left in self.inputs (_ingest_pack): its soft_masks and boxes_2d are VIEWS of this row's
+            # own buffers (capture_all ends with reset(self.inputs)).  The row holds the frame already; copying it onto itself would be an
+            # overlapping copy_, so only what is derived from it is refreshed.
+            if b["masks"].data_ptr() != self.flat_masks.data_ptr():
+                b["masks"].copy_(self.flat_masks)
+            torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)
+            b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
+            b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
+            return
+        self.flat_masks[:, :N].copy_(inputs.soft_masks.reshape(-1, N))
+        if b["masks"].data_ptr() != self.flat_masks.data_ptr():
+            b["masks"].copy_(self.flat_masks)
+        torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)
+        b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
+        b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
+        b["gt_boxes"][:, :N].copy_(inputs.boxes_2d.reshape(V, N, 4))
+        b["visible"][:, :N].copy_(inputs.visible_masks)
+
+    def _ingest_pack(self, pack, H, W, N):
+        """reset() from a frame pack: ONE vsrd_frame_ingest call writes columns 0..N-1 of the row's soft masks (stride: the row's capacity), its
+        importance weights, ground-truth boxes and visibility -- no [V,H,W,N] temporary, no strided copy, no amax.  Returns the FrameInputs
+        that `self.inputs` then holds: its camera matrices are the pack's, and its soft_masks, boxes_2d are VIEWS of the row's buffers (they
+        change with the row's next reset; visible_masks is a small copy)."""
+        b, V = self._glue, self.num_views
+        stride = int(self.flat_masks.shape[1])
+        frames.ingest_into(pack, self.device, stride, soft_masks=self.flat_masks, sampling_weights=self.sampling_weights, gt_boxes=b["gt_boxes"],
+                           visible=b["visible"])
+        intrinsics, extrinsics = frames.camera_matrices(pack, self.device)
+        return FrameInputs((H, W), intrinsics, extrinsics, self.flat_masks.view(V, H, W, stride)[..., :N],
+                           b["gt_boxes"][:, :N].unflatten(-1, (2, 2)), b["visible"][:, :N].bool())
+
     def reset(self, inputs: FrameInputs, init_seed=None):
         """Start ANOTHER frame of the same shape in this loop, in place: the new frame's matrices, boxes and soft masks are copied into
         the buffers the captured graphs read; parameters are re-initialised as a fresh ``BoxParameters3D`` / ``HyperDistanceField`` would
@@ -1000,7 +1035,15 @@ class FrameOptimizer:
             raise ValueError("reset() belongs to a persistent graph-mode loop (FrameOptimizer(..., graph=True, persistent=True))")
         cfg, dev, b = self.config, self.device, self._glue
         V, N = self.num_views, self.num_instances
-        if self._capacity is not None:       # a mixed batch's row: any frame of its views and image size with 1..capacity instances
+        pack = inputs if isinstance(inputs, frames.FramePack) else None
+        if pack is not None:
+            # a frame pack (frames.py): vsrd_frame_ingest writes the row's soft masks, importance weights, boxes and visibility in place
+            shape, limit = (pack.num_views, *[int(x) for x in pack.image_size]), self._capacity
+            if shape != (V, *[int(x) for x in self.inputs.image_size]) or not (1 <= pack.num_instances <= limit if limit is not None else pack.num_instances == N):
+                raise ValueError(f"this loop serves frames of shape {(V, *[int(x) for x in self.inputs.image_size])} with " +
+                                 (f"1..{limit}" if limit is not None else str(N)) + f" instances, got a pack of {shape} with {pack.num_instances}")
+            N = pack.num_instances
+        elif self._capacity is not None:       # a mixed batch's row: any frame of its views and image size with 1..capacity instances
             N = int(inputs.soft_masks.shape[-1])
             if (tuple(inputs.soft_masks.shape[:-1]) != (V, *[int(x) for x in self.inputs.image_size]) or tuple(inputs.image_size) != tuple(self.inputs.image_size)
                     or not 1 <= N <= self._capacity):
@@ -1013,17 +1056,18 @@ class FrameOptimizer:
             main.synchronize()                                      # (replays of the previous frame have finished: nothing reads the buffers)
             # ---- inputs ----
             H, W = (int(x) for x in inputs.image_size)
+            if pack is not None:
+                inputs = self._ingest_pack(pack, H, W, N)
             cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
             self.camera_positions.copy_(cam)
             self.ray_directions.copy_(dirs.reshape(-1, 3))
-            self.flat_masks[:, :N].copy_(inputs.soft_masks.reshape(-1, N))
-            if b["masks"].data_ptr() != self.flat_masks.data_ptr():
-                b["masks"].copy_(self.flat_masks)
-            torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)
-            b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
-            b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
-            b["gt_boxes"][:, :N].copy_(inputs.boxes_2d.reshape(V, N, 4))
-            b["visible"][:, :N].copy_(inputs.visible_masks)
+            if pack is not None:             # (masks, weights, boxes and visibility are in the row already)
+                if b["masks"].data_ptr() != self.flat_masks.data_ptr():
+                    b["masks"].copy_(self.flat_masks)
+                b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
+                b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
+            else:
+                self._copy_inputs(inputs, V, N)
             self.inputs = inputs
             if self._capacity is not None and N != self.num_instances:
                 # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
