@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define VSRD_ABI_VERSION 10
+#define VSRD_ABI_VERSION 11
 
 #define VSRD_OK 0
 #define VSRD_E_INVALID_ARGUMENT (-1) /* null pointer, non-positive size, unsupported N / S */
@@ -56,7 +56,7 @@ extern "C" {
  * frames: frame f's results are BIT-IDENTICAL to those of the same call on frame f alone (the launch is B copies of the one-frame grid,
  * tests/test_hip_step.py::test_frame_batch_walks_each_frames_own_trajectory).
  * The fields sit at the end of vsrd_render_config, vsrd_frame_config and vsrd_hypernetwork.  Entry points that accept B >= 2:
- * vsrd_frame_prologue, vsrd_frame_prologue_sample, vsrd_frame_epilogue, vsrd_hypernetwork_forward, vsrd_hypernetwork_backward_step,
+ * vsrd_frame_prologue, vsrd_frame_prologue_sample, vsrd_frame_epilogue, vsrd_frame_labels (ABI 11), vsrd_hypernetwork_forward, vsrd_hypernetwork_backward_step,
  * vsrd_render_silhouette_step (gathered launches in the split-ray form: at most 2048 rays per frame) and vsrd_render_residual_step
  * (two-kernel form, one chunk of rays per frame); every other entry point returns VSRD_E_UNSUPPORTED for B >= 2.
  *
@@ -528,6 +528,35 @@ int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const f
                                         const vsrd_adam_tensors* locations, const vsrd_adam_tensors* dimensions, const vsrd_adam_tensors* orientations,
                                         float* other_learning_rate_0, float* other_learning_rate_1, int64_t* step,
                                         float* record, float* raw_gradients, const vsrd_frame_header* frame_header, void* stream);
+
+/* Frame labels (ABI 11): a frame's pseudo-labels from the buffers its steps read, at the end of the optimisation -- the second pass of
+ * tools/kitti_360/make_predictions.py:61-192 in ONE single-workgroup launch per frame, no host synchronisation, no allocation, capturable:
+ * decode the boxes (box_parameters.py:124-146), camera corners = E_v corner / w and project_box_3d + clip_boxes_to_image in every view
+ * (main.py:339-362), torchvision.ops.box_iou against every view's ground-truth boxes (no epsilon; a NaN, 0/0, counts as 0: nan_to_num),
+ * the mean over the views in which the ground-truth instance exists (summed in ascending view order), then
+ * scipy.optimize.linear_sum_assignment(mean_iou, maximize=True) -- the solver of vsrd_linear_sum_assignment on -mean_iou, ties included --
+ * and confidence = the matched mean IoU.
+ * The inputs and their conventions are those of vsrd_frame_prologue_with_header: config->num_boxes is the capacity N and the stride of
+ * every instance axis, num_views V <= 32, N <= VSRD_MAX_INSTANCES, num_frames / frame_stride batch the call, frame_header (may be NULL:
+ * every frame has N boxes) carries the frame's own count n_f, clamped to [1, N].  Of config, the call reads the sizes, height / width /
+ * epsilon, the location and dimension ranges and the batch fields.  gt_boxes [V,N,4] and visible [V,N] are in the target's instance
+ * order (the table of make_predictions.py:142-162 is applied by vsrd_frame_ingest or by the caller), the extrinsics relative to the
+ * target view (make_predictions.py:74-109).
+ * Outputs, each may be NULL and is then skipped; entries of instances n_f .. N-1 are never read and never written (the rows and columns
+ * of mean_iou beyond n_f included):
+ *   camera_corners [V,N,8,3]  the boxes' corners in every view's camera frame, the reference's corner order;
+ *   boxes_2d [V,N,4]          (x1, y1, x2, y2), clipped to the image;
+ *   mean_iou [N,N]            [p,g]: prediction p against ground-truth slot g;
+ *   matched_gt [N]            the slot matched to prediction p;
+ *   confidences [N]           mean_iou[p, matched_gt[p]], bit for bit.
+ * A stated deviation: a ground-truth slot that NO view sees gets mean_iou exactly 0.0 in its column, where the reference divides 0 by 0
+ * and scipy raises on the NaN (vsrd_frame_ingest produces such slots: a target entry without a set bit). */
+int32_t vsrd_frame_labels(const vsrd_frame_config* config,
+                          const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                          const float* extrinsics, const float* intrinsics, const float* gt_boxes, const uint8_t* visible,
+                          float* camera_corners /* [V,N,8,3] */, float* boxes_2d /* [V,N,4] */, float* mean_iou /* [N,N] */,
+                          int64_t* matched_gt /* [N] */, float* confidences /* [N] */,
+                          const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
 
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]

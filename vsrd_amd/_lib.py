@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VSRD_HIP_LIBRARY: an experiment build of the same ABI (tools/phase_timers.py, A/B macros); the product path is the in-tree default
 LIBRARY_PATH = os.environ.get("VSRD_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libvsrd_hip.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_INSTANCES = 64
 MAX_SAMPLES = 256
 INSTANCE_STRIDE = 16
@@ -225,6 +225,10 @@ SIGNATURES = {
                                                                ctypes.c_void_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_backward_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p,
                                                                      ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
+    # ABI 11: a frame's pseudo-labels (camera corners, clipped 2-D boxes, mean IoU, assignment, confidences); header before the stream
+    "vsrd_frame_labels": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                           ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     "vsrd_hypernetwork_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
     "vsrd_hypernetwork_forward": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_backward_step": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_float,

@@ -12,6 +12,7 @@
 #include "frame_step.h"
 #include "hypernetwork.h"
 #include "frame_ingest.h"
+#include "frame_labels.h"
 #include "launch.h"
 
 namespace {
@@ -1204,6 +1205,33 @@ int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const f
     e.other_learning_rates[0] = other_learning_rate_0; e.other_learning_rates[1] = other_learning_rate_1;
     e.step = reinterpret_cast<long long*>(step); e.record = record; e.raw_gradients = raw_gradients;
     hipLaunchKernelGGL(frame_epilogue_kernel, dim3(1, config->num_frames > 1 ? config->num_frames : 1), dim3(kFrameMaxBoxes), 0, static_cast<hipStream_t>(stream), a, e);
+    return launch_status();
+}
+
+int32_t vsrd_frame_labels(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                          const float* extrinsics, const float* intrinsics, const float* gt_boxes, const uint8_t* visible,
+                          float* camera_corners, float* boxes_2d, float* mean_iou, int64_t* matched_gt, float* confidences,
+                          const vsrd_frame_header* frame_header, void* stream) {
+    if (!config || config->num_boxes < 1 || config->num_boxes > kFrameMaxBoxes || config->num_views < 1 || config->num_views > kFrameMaxViews)
+        return VSRD_E_INVALID_ARGUMENT;
+    Frames frames;
+    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible) return VSRD_E_INVALID_ARGUMENT;
+    FrameStepArgs a = {};                  // (the decode's ranges, the projection's guard and the image size: the schedules, loss weights and Adam's constants are not read)
+    a.num_boxes = config->num_boxes; a.num_views = config->num_views;
+    a.height = config->height; a.width = config->width; a.epsilon = config->epsilon;
+    for (int j = 0; j < 3; ++j) {
+        a.location_lo[j] = config->location_lo[j]; a.location_hi[j] = config->location_hi[j];
+        a.dimension_lo[j] = config->dimension_lo[j]; a.dimension_hi[j] = config->dimension_hi[j];
+    }
+    a.frame_stride = frames.stride;
+    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
+    LabelBuffers b;
+    b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
+    b.extrinsics = extrinsics; b.intrinsics = intrinsics; b.gt_boxes = gt_boxes; b.visible = visible;
+    b.camera_corners = camera_corners; b.boxes_2d = boxes_2d; b.mean_iou = mean_iou;
+    b.matched_gt = reinterpret_cast<long long*>(matched_gt); b.confidences = confidences;
+    hipLaunchKernelGGL(frame_labels_kernel, dim3(frames.count), dim3(kFrameThreads), 0, static_cast<hipStream_t>(stream), a, b);
     return launch_status();
 }
 

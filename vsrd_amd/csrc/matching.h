@@ -79,10 +79,10 @@ __device__ __forceinline__ float negative_distance_iou(const float* a, const flo
     return -(inter / uni - centres / diagonal);
 }
 
-// Solve the nr x nc (nr <= nc <= 64) assignment problem on `cost` (LDS, row-major with pitch nc, float64).
-// Returns col4row of row `lane` (valid for lane < nr).
-template <bool kSmall>
-__device__ __forceinline__ int lsap_rows_le_cols_impl(const double* cost, int nr, int nc) {
+// Solve the nr x nc (nr <= nc <= 64) assignment problem on `cost` (LDS, row-major with pitch nc; float64, or float32 widened as it is read:
+// the duals are float64 either way).  Returns col4row of row `lane` (valid for lane < nr).
+template <bool kSmall, typename Cost>
+__device__ __forceinline__ int lsap_rows_le_cols_impl(const Cost* cost, int nr, int nc) {
     const int lane = lane_id();
     // column state (lane = j)
     double v = 0.0, spc = kLsapInfinity;
@@ -104,7 +104,7 @@ __device__ __forceinline__ int lsap_rows_le_cols_impl(const double* cost, int nr
             if (lane == i) in_sr = true;
             const double ui = read_lane_double(u, i);
             if (!removed) {
-                const double r = min_val + cost[i * nc + lane] - ui - v;
+                const double r = min_val + static_cast<double>(cost[i * nc + lane]) - ui - v;
                 if (r < spc) { path = i; spc = r; }
             }
             // scipy's sequential scan over remaining[0..num_remaining): strictly lower wins; on a tie a FREE column wins (the last
@@ -148,7 +148,8 @@ __device__ __forceinline__ int lsap_rows_le_cols_impl(const double* cost, int nr
     return col4row;
 }
 
-__device__ __forceinline__ int lsap_rows_le_cols(const double* cost, int nr, int nc) {
+template <typename Cost>
+__device__ __forceinline__ int lsap_rows_le_cols(const Cost* cost, int nr, int nc) {
     return nc <= 16 ? lsap_rows_le_cols_impl<true>(cost, nr, nc) : lsap_rows_le_cols_impl<false>(cost, nr, nc);
 }
 

@@ -6,6 +6,7 @@ pseudo-label files derived from it.  Host-side I/O only.
   prediction JSON           tools/kitti_360/make_predictions.py:158-169   {boxes_3d, boxes_2d, confidences} per class
   multi-view confidences    tools/kitti_360/make_predictions.py:86-176    mean box IoU over source views + Hungarian (maximise)
   KITTI label line          tools/kitti_360/convert_predictions.py:16-78
+  per-frame label files     save_frame_labels: what optimization.FrameOptimizer.labels() returns (vsrd_frame_labels), as the two above
 """
 import json
 import math
@@ -120,3 +121,32 @@ def save_kitti_labels(path, class_names, boxes_3d, boxes_2d, scores):
     with open(path, "w") as file:
         for name, box_3d, box_2d, score in zip(class_names, boxes_3d, boxes_2d, scores):
             file.write(kitti_label_line(name, box_3d, box_2d, score))
+
+
+def _atomic_write(path, write):
+    """``write(temporary name)`` and os.replace onto ``path``, like atomic_torch_save; what a killed process left under this name goes first."""
+    folder, stem = os.path.dirname(path) or ".", os.path.basename(path) + ".tmp."
+    os.makedirs(folder, exist_ok=True)
+    for name in os.listdir(folder):
+        if name.startswith(stem):
+            os.remove(os.path.join(folder, name))
+    temporary = f"{path}.tmp.{os.getpid()}"
+    try:
+        write(temporary)
+        os.replace(temporary, path)
+    finally:
+        if os.path.exists(temporary):
+            os.remove(temporary)
+
+
+def save_frame_labels(folder, labels, class_name="car"):
+    """One frame's pseudo-labels as files.  ``labels``: the dictionary of ``FrameOptimizer.labels()`` (host or device tensors) -- boxes_3d
+    [V,n,8,3] camera-frame corners per view, boxes_2d [V,n,2,2], confidences [n].  Writes ``folder/predictions/view_VV.json`` for every view
+    (that view's corners and 2-D boxes, the same confidences in every file: make_predictions.py:164-192) and ``folder/labels/view_00.txt``,
+    the KITTI label lines of the target view (convert_predictions.py:16-78).  Every file is written under a temporary name and renamed."""
+    boxes_3d, boxes_2d, confidences = (labels[key].detach().cpu() for key in ("boxes_3d", "boxes_2d", "confidences"))
+    for view in range(boxes_3d.shape[0]):
+        _atomic_write(os.path.join(folder, "predictions", f"view_{view:02d}.json"),
+                      lambda name, view=view: save_prediction(name, boxes_3d[view], boxes_2d[view], confidences, class_name))
+    _atomic_write(os.path.join(folder, "labels", "view_00.txt"),
+                  lambda name: save_kitti_labels(name, [class_name] * len(confidences), boxes_3d[0], boxes_2d[0], confidences.tolist()))

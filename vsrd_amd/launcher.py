@@ -435,8 +435,33 @@ class _RenderWork:
             torch.cuda.current_stream().synchronize()
             loss = float(record["loss"])
             payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
+            labels = self._host_labels(loop.labels, [(frame, self.path_of(frame))]) if self.args.predictions else []
         loop.close()
+        self._write_labels(labels)
         return loss, payload
+
+    def _host_labels(self, device_call, frames):
+        """--predictions, inside the section that copies the checkpoint payloads: the ONE vsrd_frame_labels call of a group of frames
+        (`device_call` -> a dictionary or a list of them) and its copies to the host -> [(frame folder, labels)] for `_write_labels`."""
+        import time
+        from . import formats
+        t0 = time.perf_counter()
+        labels = device_call()
+        labels = labels if isinstance(labels, list) else [labels]
+        pending = [(os.path.dirname(path), formats.to_host(entry)) for (_, path), entry in zip(frames, labels)]
+        self.phase_seconds["labels"] += time.perf_counter() - t0
+        return pending
+
+    def _write_labels(self, pending):
+        """The label files of `_host_labels`' frames -- BEFORE their checkpoints: the final checkpoint is what marks a frame as done
+        (pending_frames), so a frame that has one has its labels."""
+        import time
+        from . import formats
+        t0 = time.perf_counter()
+        for folder, labels in pending:
+            formats.save_frame_labels(folder, labels)
+        if pending:
+            self.phase_seconds["labels_write"] += time.perf_counter() - t0
 
     def run(self):
         from . import formats, optimization
@@ -464,11 +489,16 @@ class _RenderWork:
                     torch.cuda.current_stream().synchronize()
                     losses[frame] = float(record["loss"])
                     health(frame, slot)
-                    return formats.checkpoint_payload(slot, step=args.num_steps - 1, metrics={}, host=True)
+                    payload = formats.checkpoint_payload(slot, step=args.num_steps - 1, metrics={}, host=True)
+                    labels = self._host_labels(slot.labels, [(frame, self.path_of(frame))]) if args.predictions else []
+                self._write_labels(labels)
+                return payload
             finally:
                 if slot is not None:
                     self.slots.put(slot)
 
+        if args.predictions:               # (the batch path keeps its own clock, with these two keys added)
+            self.phase_seconds = dict(labels=0.0, labels_write=0.0)
         self._have_slots = not args.fresh_loops and not self.slots.empty()
         if self.batch is not None:
             done = self._run_batches(losses, fallbacks, health)
@@ -489,6 +519,8 @@ class _RenderWork:
         from . import formats, optimization
         args, batch, done = self.args, self.batch, []
         clock = self.phase_seconds = dict(inputs=0.0, reset=0.0, steps=0.0, checkpoint_copy=0.0, checkpoint_write=0.0)
+        if args.predictions:
+            clock.update(labels=0.0, labels_write=0.0)
         while True:
             group = pending_frames(self.queue.take(args.frame_batch), self.path_of)
             if not group:
@@ -514,13 +546,17 @@ class _RenderWork:
                         losses[frame] = float(batch.outputs(row)["loss"])
                         health(frame, batch.frames[row])
                         payloads.append(formats.checkpoint_payload(batch.frames[row], step=args.num_steps - 1, metrics={}, host=True))
-                t2 = time.perf_counter()
+                    t2 = time.perf_counter()
+                    # --predictions: ONE vsrd_frame_labels call for the group, copied to the host with the payloads
+                    labels = self._host_labels(lambda: batch.labels(active=len(rows)), rows) if args.predictions else []
+                self._write_labels(labels)
+                t3 = time.perf_counter()
                 for (frame, path), payload in zip(rows, payloads):
                     formats.atomic_torch_save(payload, path)
                     done.append(frame)
                 clock["steps"] += t1 - t0
                 clock["checkpoint_copy"] += t2 - t1
-                clock["checkpoint_write"] += time.perf_counter() - t2
+                clock["checkpoint_write"] += time.perf_counter() - t3
             for frame, path in alone:
                 fallbacks.append(int(frame))
                 losses[frame], payload = self._own_loop(frame)
@@ -647,6 +683,11 @@ def main(argv=None):
     parser.add_argument("--width", type=int, default=None, help="default 1408")
     parser.add_argument("--out", default="", help="checkpoint directory (default: a temporary one)")
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--predictions", action="store_true",
+                        help="after a frame's steps, write its pseudo-labels next to its checkpoint: predictions/view_VV.json for every view "
+                             "(tools/kitti_360/make_predictions.py) and labels/view_00.txt, the target view's KITTI label lines "
+                             "(convert_predictions.py) -- vsrd_frame_labels, one launch per group of frames; with --frames-dir an end-to-end "
+                             "auto-labelling run.  Not with --selftest")
     parser.add_argument("--ranks-share-gpu", action="store_true",
                         help="TEST ONLY: every rank on cuda:0, gloo rendezvous (RCCL refuses two ranks on one device); the line says so")
     parser.add_argument("--fresh-loops", action="store_true",
@@ -670,6 +711,8 @@ def main(argv=None):
     parser.add_argument("--selftest-hang", default="", help="RANK:FRAMES -- on attempt 0 that rank hangs (sleeps for ever) once it has finished FRAMES frames")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parser.parse_args(argv)
+    if args.predictions and args.selftest:
+        raise SystemExit("--predictions writes the labels of optimised frames; --selftest optimises none: drop one of --selftest, --predictions")
     if args.frames_dir:
         given = [flag for flag, value in (("--views", args.views), ("--instances", args.instances), ("--height", args.height), ("--width", args.width)) if value is not None]
         if given:
@@ -850,6 +893,7 @@ def _rank_main(args):
                 # frames a slot could not take (their importance weights do not suit the sampling table its graphs draw from: a loop of their own, race sampler)
                 # where a batched rank's time went, in seconds over its frames: building inputs (dynamic queue only), resetting rows, the steps, checkpoints
                 "phase_seconds": [r.get("phase_seconds") for r in gathered],
+                **({"predictions": True} if args.predictions else {}),      # (--predictions: label files next to every checkpoint)
                 "frames_outside_slots": sorted(f for r in gathered for f in r["frames_outside_slots"]),
                 "unsuitable_founders": sorted(f for r in gathered for f in r["unsuitable_founders"]),
                 # frames in which some ray draw ran out of picks / overflowed (read at the end of each frame; RuntimeWarning on stderr)

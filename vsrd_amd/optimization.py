@@ -398,6 +398,7 @@ class FrameOptimizer:
             self.workspace.keep_outgrown = True          # a captured graph holds the buffer's address: an outgrown buffer must outlive it
             self.workspace.reserve(self.device, self.capacity, residual=True, step_shape=(config.num_samples, config.num_rays))
         self._graphs = {}
+        self._labels = None
         self._capture_stream = None
         self._eager_graph_steps = {}
         self._prepare_rays(inputs, config, H, W, N)
@@ -483,12 +484,10 @@ class FrameOptimizer:
         self.positive_weights = self.sampling_weights[self.positive_pixels].contiguous()
         return True
 
-    # ---- fused glue (csrc/frame_step.h) ---------------------------------------------------------------------------------
-    def _init_fused_glue(self):
-        cfg, inp, dev = self.config, self.inputs, self.device
-        V, N = self.num_views, self.capacity          # (a mixed batch's row: every per-instance buffer is laid out for the capacity)
-        lib = _lib.load()
-        det = self.detector
+    def _frame_config(self):
+        """include/vsrd_hip.h::vsrd_frame_config of this loop (one frame: the batch fields are set by whoever launches)."""
+        cfg, inp, det = self.config, self.inputs, self.detector
+        V, N = self.num_views, self.capacity
         w = cfg.loss_weights
         frame = _lib.FrameConfig()
         frame.num_boxes, frame.num_views = N, V
@@ -502,7 +501,14 @@ class FrameOptimizer:
         frame.weight_iou, frame.weight_l1, frame.weight_silhouette = w["iou_projection_loss"], w["l1_projection_loss"], w["silhouette_loss"]
         betas, eps = self.optimizer.param_groups[0]["betas"], self.optimizer.param_groups[0]["eps"]      # the box tensors' Adam constants
         frame.beta1, frame.beta2, frame.adam_epsilon, frame.lr_gamma = float(betas[0]), float(betas[1]), float(eps), cfg.lr_gamma
-        self._frame = frame
+        return frame
+
+    # ---- fused glue (csrc/frame_step.h) ---------------------------------------------------------------------------------
+    def _init_fused_glue(self):
+        cfg, inp, dev = self.config, self.inputs, self.device
+        V, N = self.num_views, self.capacity          # (a mixed batch's row: every per-instance buffer is laid out for the capacity)
+        lib = _lib.load()
+        self._frame = self._frame_config()
         f32 = dict(dtype=torch.float32, device=dev)
         b = self._glue = {}
         b["extrinsics"] = inp.extrinsic_matrices.to(**f32).reshape(V, 16).contiguous()
@@ -1110,6 +1116,57 @@ class FrameOptimizer:
         with torch.no_grad():
             return self.detector()
 
+    # ---- pseudo-labels (csrc/frame_labels.h) -------------------------------------------------------------------------------
+    def _label_state(self):
+        """What vsrd_frame_labels writes, created at first use -- in the frame's row when there is one (a FrameBatch creates them in every
+        row at once: equal offsets) -- and what it reads: the loop's own camera, ground-truth and header tensors (a loop without the fused
+        glue keeps float32 copies of its inputs' here)."""
+        if self._labels is not None:
+            return self._labels
+        V, N = self.num_views, self.capacity
+        with _capture_lock, torch.no_grad():
+            new = self._new
+            state = dict(camera_corners=new((V, N, 8, 3), fill=0.0), boxes_2d=new((V, N, 4), fill=0.0), mean_iou=new((N, N), fill=0.0),
+                         matched_gt=new(N, torch.int64, fill=0), confidences=new(N, fill=0.0))
+            if self.fused_glue:
+                state["inputs"] = self._glue
+                state["frame"] = _lib.FrameConfig.from_buffer_copy(self._frame)          # (its batch fields are this call's own)
+            else:
+                inp, f32 = self.inputs, dict(dtype=torch.float32, device=self.device)
+                state["inputs"] = dict(extrinsics=inp.extrinsic_matrices.to(**f32).reshape(V, 16).contiguous(),
+                                       intrinsics=inp.intrinsic_matrices.to(**f32).reshape(V, 9).contiguous(),
+                                       gt_boxes=inp.boxes_2d.to(**f32).reshape(V, N, 4).contiguous(),
+                                       visible=inp.visible_masks.to(device=self.device, dtype=torch.uint8).contiguous())
+                state["frame"] = self._frame_config()
+        self._labels = state
+        return state
+
+    def _launch_labels(self, frames=None):
+        """ONE vsrd_frame_labels call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
+        state, det = self._label_state(), self.detector
+        frame, t = state["frame"], state["inputs"]
+        frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
+        header = t.get("header")
+        with _capture_lock:
+            _lib.check(_lib.load().vsrd_frame_labels(
+                frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(t["extrinsics"]),
+                _lib.ptr(t["intrinsics"]), _lib.ptr(t["gt_boxes"]), t["visible"].data_ptr(), _lib.ptr(state["camera_corners"]), _lib.ptr(state["boxes_2d"]),
+                _lib.ptr(state["mean_iou"]), state["matched_gt"].data_ptr(), _lib.ptr(state["confidences"]),
+                None if header is None else header.data_ptr(), _lib.stream()))
+
+    def _label_views(self):
+        state, n = self._labels, self.num_instances
+        return dict(boxes_3d=state["camera_corners"][:, :n], boxes_2d=state["boxes_2d"][:, :n].unflatten(-1, (2, 2)), confidences=state["confidences"][:n],
+                    matched_gt=state["matched_gt"][:n], mean_iou=state["mean_iou"][:n, :n])
+
+    def labels(self):
+        """The frame's pseudo-labels from its CURRENT parameters (tools/kitti_360/make_predictions.py:61-192), by one vsrd_frame_labels
+        launch on the current stream, no host synchronisation: a dictionary of device tensors sliced to the frame's own n instances --
+        boxes_3d [V,n,8,3] (camera-frame corners in every view), boxes_2d [V,n,2,2] (clipped), confidences [n] (the matched mean IoU),
+        matched_gt [n], mean_iou [n,n].  They are views of buffers the next call overwrites (formats.save_frame_labels writes them out)."""
+        self._launch_labels()
+        return self._label_views()
+
     def close(self):
         """Drop the captured graphs and the scratch buffers (also happens when the optimizer is garbage-collected).  Once per frame
         this is also where the device ray sampler's sticky overflow flag is read back (a host synchronisation, so not per step): a
@@ -1307,6 +1364,17 @@ class FrameBatch:
         if m.step_index > self.config.warmup_steps:
             result["eikonal_loss"] = record[3]
         return result
+
+    def labels(self, active=None):
+        """The pseudo-labels of the first ``active`` frames (``FrameOptimizer.labels``) by ONE vsrd_frame_labels call for all of them: a
+        list of dictionaries of device tensors, each sliced to its frame's own instance count."""
+        active, members = self._members(active)
+        for m in self.frames:                      # (first use: the output buffers of EVERY row, so that the rows keep equal offsets)
+            m._label_state()
+        if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
+            raise RuntimeError("the frames of a batch laid their label buffers out differently: frame batches need equal offsets in every row")
+        members[0]._launch_labels(frames=(active, self.arena.stride))
+        return [m._label_views() for m in members]
 
     def _phase(self, active):
         _, members = self._members(active)
