@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define VSRD_ABI_VERSION 11
+#define VSRD_ABI_VERSION 12
 
 #define VSRD_OK 0
 #define VSRD_E_INVALID_ARGUMENT (-1) /* null pointer, non-positive size, unsupported N / S */
@@ -74,10 +74,37 @@ extern "C" {
  * not batch (the dense multi-ray kernels of vsrd_render_silhouette_step) is answered with VSRD_E_UNSUPPORTED, as B >= 2 is.
  * Twins: vsrd_frame_prologue, vsrd_frame_prologue_sample, vsrd_frame_epilogue, vsrd_render_silhouette_step (split-ray form),
  * vsrd_render_residual_step (two-kernel form with the ray split over a pair of waves, both MLP product forms), vsrd_hypernetwork_forward,
- * vsrd_hypernetwork_backward_step (N = vsrd_hypernetwork::num_instances is the capacity: the stride of the embeddings and the workspace). */
+ * vsrd_hypernetwork_backward_step (N = vsrd_hypernetwork::num_instances is the capacity: the stride of the embeddings and the workspace).
+ *
+ * Frames that differ in VIEW count (ABI 12).  A frame's view count is not a constant of a job (vsrd/datasets/kitti_360_dataset.py:192-197
+ * drops the empty parts of a target's source frames: 1 .. 1 + num_source_frames views), so the header carries it too, behind its two
+ * ABI-9 fields.  A caller of ABI 9-11 allocated 8 bytes per header, so the tail is read ONLY from a header that says it has one:
+ * num_instances = n_f | VSRD_FRAME_HEADER_HAS_VIEWS.  Without that bit a header means exactly what it meant in ABI 9 (and every kernel
+ * masks the bit off before it uses the count).  With it:
+ *   - the by-value vsrd_frame_config::num_views is the view capacity V_cap: the stride and extent of the row's per-view arrays
+ *     ([V,16] extrinsics, [V,9] intrinsics, [V,N,4] ground-truth boxes, [V,N] visibility, [V,N,8,3] / [V,N,4] label outputs), as
+ *     num_boxes is for N; every per-view array is view-major, so a frame with fewer views fills a prefix of each;
+ *   - num_views = v_f (0: the by-value V; else clamped to [1, V_cap]): vsrd_frame_prologue_with_header,
+ *     vsrd_frame_prologue_sample_with_header and vsrd_frame_labels read it once, as a wave-uniform scalar, and project, match, reduce
+ *     and normalise over v_f views only; views v_f .. V_cap - 1 of every per-view input and output are never read and never written.
+ *     The prologue's choice between LDS and the global scratch (V N <= 256) and its offsets into the scratch follow the frame's OWN
+ *     v_f n_f -- the path the frame takes alone; vsrd_frame_scratch_bytes stays sized by the capacities;
+ *   - num_pixels = v_f H W (0, or more than the by-value count: the by-value count): the count of the frame's sampling table, from
+ *     which the sampler half of vsrd_frame_prologue_sample_with_header derives the table's layout (chunk sums, guide) and guide bits.
+ *     The table inside the row is the one vsrd_ray_table_build(weights, v_f H W, ...) builds for the frame alone; only the row's
+ *     allocation is sized for V_cap H W (vsrd_ray_table_bytes is monotone in the count).
+ * Frame f then computes, bit for bit, what the same call computes on a frame of its own with V = v_f and N = n_f.  The epilogue, the
+ * hypernetwork twins and the two render-step twins read no view count: the render kernels gather rays by pixel index and never see V.
+ * vsrd_frame_ingest, vsrd_ray_directions and vsrd_ray_table_build are per-frame calls that take the frame's own V or count by value
+ * and write a prefix of a row laid out for V_cap, nothing behind it. */
+#define VSRD_FRAME_HEADER_HAS_VIEWS 0x10000 /* or-ed into vsrd_frame_header::num_instances: the header is the full ABI-12 struct */
 typedef struct vsrd_frame_header {
-    int32_t num_instances;      /* n_f, 1..N_cap (clamped)                                                      */
+    int32_t num_instances;      /* n_f, 1..N_cap (clamped) [| VSRD_FRAME_HEADER_HAS_VIEWS]                        */
     float loss_scale;           /* the silhouette loss normaliser of the frame: 1 / (R * n_f) as float32        */
+    /* ---- ABI 12: read only when num_instances carries VSRD_FRAME_HEADER_HAS_VIEWS ---- */
+    int32_t num_views;          /* v_f: 0 = the by-value V; else clamped to [1, V]                              */
+    int32_t reserved;           /* 0                                                                            */
+    int64_t num_pixels;         /* the sampler's count of this frame, v_f * H * W: 0 = the by-value count       */
 } vsrd_frame_header;
 
 /* Field = temperature soft-min union of N oriented boxes (+ optional residual MLP).

@@ -116,12 +116,14 @@ def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, ve
 
 
 def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), drop=(), shuffle=False, vertices=0):
-    """Packs frame_000000.npz .. of frames 0..count-1 in `out`; returns their paths."""
+    """Packs frame_000000.npz .. of frames 0..count-1 in `out`; returns their paths.  `views`: one count, or a list cycled over the frames
+    like `instances` (frame j gets views[j % len(views)], each list with its own length)."""
     from vsrd_amd import frames
     os.makedirs(out, exist_ok=True)
     paths = []
+    views = [int(views)] if isinstance(views, int) else [int(v) for v in views]
     for frame in range(int(count)):
-        pack = make_pack(frame, views, height, width, int(instances[frame % len(instances)]), drop, shuffle, vertices)
+        pack = make_pack(frame, views[frame % len(views)], height, width, int(instances[frame % len(instances)]), drop, shuffle, vertices)
         paths.append(os.path.join(out, f"frame_{frame:06d}.npz"))
         frames.save_pack(paths[-1], pack)
     return paths
@@ -131,7 +133,7 @@ def main(argv=None):
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--out", required=True)
     parser.add_argument("--count", type=int, default=16)
-    parser.add_argument("--views", type=int, default=17)
+    parser.add_argument("--views", default="17", help="one count or a comma list (frame j gets list[j %% len(list)])")
     parser.add_argument("--height", type=int, default=376)
     parser.add_argument("--width", type=int, default=1408)
     parser.add_argument("--instances", default="8", help="one count or a comma list (frame j gets list[j %% len(list)])")
@@ -140,7 +142,7 @@ def main(argv=None):
     parser.add_argument("--shuffle", action="store_true", help="source views list their entries in a seeded random order")
     args = parser.parse_args(argv)
     drop = [tuple(int(x) for x in item.split(":")) for item in args.drop.split(",") if item]
-    paths = write_packs(args.out, args.count, args.views, args.height, args.width, [int(x) for x in args.instances.split(",")], drop, args.shuffle, args.vertices)
+    paths = write_packs(args.out, args.count, [int(x) for x in args.views.split(",")], args.height, args.width, [int(x) for x in args.instances.split(",")], drop, args.shuffle, args.vertices)
     print(f"{len(paths)} packs in {args.out}")
     return 0
 

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VSRD_HIP_LIBRARY: an experiment build of the same ABI (tools/phase_timers.py, A/B macros); the product path is the in-tree default
 LIBRARY_PATH = os.environ.get("VSRD_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libvsrd_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_INSTANCES = 64
 MAX_SAMPLES = 256
 INSTANCE_STRIDE = 16
@@ -135,11 +135,19 @@ class Hypernetwork(ctypes.Structure):
 
 # symbol -> (restype, argtypes); mirrors include/vsrd_hip.h one to one
 class FrameHeader(ctypes.Structure):
-    """include/vsrd_hip.h::vsrd_frame_header (ABI 9, mixed batches): one frame's own instance count and silhouette normaliser."""
+    """include/vsrd_hip.h::vsrd_frame_header (ABI 9, mixed batches): one frame's own instance count and silhouette normaliser; ABI 12:
+    its own view count and the count of its sampling table, read when num_instances carries FRAME_HEADER_HAS_VIEWS."""
     _fields_ = [
         ("num_instances", ctypes.c_int32),
         ("loss_scale", ctypes.c_float),
+        ("num_views", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("num_pixels", ctypes.c_int64),
     ]
+
+
+FRAME_HEADER_HAS_VIEWS = 0x10000
+MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFrameMaxViews)
 
 
 SIGNATURES = {

@@ -459,6 +459,9 @@ int32_t render_backward_split(const vsrd_field* field, const vsrd_render_config*
 
 extern "C" {
 
+static_assert(sizeof(vsrd_frame_header) == sizeof(FrameHeader) && offsetof(vsrd_frame_header, num_views) == offsetof(FrameHeader, num_views) &&
+                  offsetof(vsrd_frame_header, num_pixels) == offsetof(FrameHeader, num_pixels) && VSRD_FRAME_HEADER_HAS_VIEWS == kFrameHeaderHasViews,
+              "wave.h: FrameHeader is vsrd_frame_header");
 int32_t vsrd_abi_version(void) { return VSRD_ABI_VERSION; }
 
 const char* vsrd_error_string(int32_t code) {

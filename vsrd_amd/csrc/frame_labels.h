@@ -21,7 +21,8 @@
 // set bit and takes it out of the table.
 //
 // Instances n_f .. N - 1 of a row laid out for a capacity N (a header, wave.h: mixed batches) are never read and never written, in any
-// output -- the rows and columns of mean_iou beyond n_f included.
+// output -- the rows and columns of mean_iou beyond n_f included.  Likewise the views v_f .. V - 1 of a row laid out for a view capacity V
+// (ABI 12): phases 2 and 3 cover the frame's own v_f views, the mean is over those among them that see the slot.
 #pragma once
 #include "frame_step.h"
 
@@ -105,7 +106,8 @@ __global__ __launch_bounds__(kFrameThreads) void frame_labels_kernel(FrameStepAr
     __shared__ float negative_mean[kFrameMaxBoxes * kFrameMaxBoxes];    // [n,n]: the assignment's cost
     const int tid = static_cast<int>(threadIdx.x);
     // n: the boxes this frame has; NS: the stride of every instance axis (the capacity of a mixed batch, else n)
-    const int NS = a.num_boxes, V = a.num_views;
+    // V: the views this frame has (wave.h: frame_views; rows v_f .. of camera_corners and boxes_2d are left alone)
+    const int NS = a.num_boxes, V = frame_views(a.header, a.num_views);
     const int n = a.header ? frame_count(a.header, NS) : NS;
     for (int idx = tid; idx < V * 25; idx += kFrameThreads) {
         const int v = idx / 25, r = idx - 25 * v;

@@ -36,7 +36,7 @@ struct FrameStepArgs {
     float weight_iou, weight_l1, weight_silhouette;
     float beta1, beta2, adam_epsilon, lr_gamma;
     long long frame_stride;            // vsrd_frame_config::frame_stride (bytes; wave.h: frame batches), 0 for one frame
-    const FrameHeader* header;         // the frame's own count (wave.h: mixed batches), or null: num_boxes is every frame's count
+    const FrameHeader* header;         // the frame's own counts (wave.h: mixed batches), or null: num_boxes / num_views are every frame's
 };
 
 // scratch (global, one per frame): boxes_2d [V,N,4], selection [V,N,4] (int), grad_boxes [V,N,4], grad_world [V,N,8,3]
@@ -139,7 +139,8 @@ __device__ __forceinline__ void frame_prologue_body(const FrameStepArgs& a, cons
     __shared__ float partial[kThreads / kWave][3];
     const int tid = static_cast<int>(threadIdx.x);
     // N: the boxes this frame has; NS: the stride of the [V, NS] ground-truth tables (the capacity of a mixed batch, else N)
-    const int NS = a.num_boxes, V = a.num_views;
+    // V: the views this frame has (the by-value count is the capacity of the [V, ...] arrays: a frame's views fill their first rows)
+    const int NS = a.num_boxes, V = frame_views(a.header, a.num_views);
     const int N = a.header ? frame_count(a.header, NS) : NS;
 #ifdef VSRD_PHASE_TIMERS
     const unsigned long long t_start = wall_clock64();                 // 100 MHz; mark k = time of the k-th barrier (tools/prologue_timers.py)
@@ -152,7 +153,8 @@ __device__ __forceinline__ void frame_prologue_body(const FrameStepArgs& a, cons
     // What the phases hand each other -- 2-D boxes, which edge end gave each extreme, their gradients, the corner gradients of every
     // (view, box) -- goes through LDS while V N <= 256 (the reference's 17 views x 8 boxes: 136), through the global scratch above
     // that: a global store -> barrier -> load is a ~2 us round trip for this lone workgroup, and there were four of them.  (The corner
-    // gradients reuse the cost matrix, which is dead once the matching is done.)
+    // gradients reuse the cost matrix, which is dead once the matching is done.)  V and N are the frame's OWN counts: a frame of a batch
+    // takes the path, and the offsets into the scratch, that it takes alone.
     __shared__ float small_boxes[kFrameThreads * 4];
     __shared__ int small_selection[kFrameThreads * 4];
     __shared__ float small_grad_boxes[kFrameThreads * 4];
@@ -445,7 +447,7 @@ __global__ __launch_bounds__(kTableThreads) void frame_prologue_sample_kernel(Fr
         VSRD_OF_FRAME(table, shift); VSRD_OF_FRAME(device_step, shift); VSRD_OF_FRAME(remap, shift); VSRD_OF_FRAME(ray_indices, shift);
     }
     if (blockIdx.x == 0) frame_prologue_body<kTableThreads>(a, b);
-    else sample_table_body(table, count, num_rays, seed, 0ull, device_step, remap, ray_indices);
+    else sample_table_body(table, frame_pixels(a.header, count), num_rays, seed, 0ull, device_step, remap, ray_indices);
 }
 
 struct AdamTensors {                   // torch.optim.Adam(capturable=True) state of one parameter tensor, all on the device

@@ -43,12 +43,35 @@ __device__ __forceinline__ T* of_frame_nonnull(T* p, long long shift) {
 // Read once per workgroup as a wave-uniform scalar and clamped to [1, capacity]; instances count .. capacity - 1 of a frame are
 // never read and never written.
 struct FrameHeader {
-    int num_instances;
+    int num_instances;                 // n_f, with kFrameHeaderHasViews or-ed in when the three fields behind loss_scale are there
     float loss_scale;
+    int num_views;                     // v_f (ABI 12): 0 = the by-value V
+    int reserved;
+    long long num_pixels;              // the sampler's count of the frame, v_f H W (ABI 12): 0 = the by-value count
 };
+// An ABI 9-11 caller's header ends behind loss_scale: the tail is read only from a header that says it has one.
+constexpr int kFrameHeaderHasViews = 0x10000, kFrameHeaderCountMask = 0xffff;
 __device__ __forceinline__ int frame_count(const FrameHeader* header, int capacity) {
-    const int n = __builtin_amdgcn_readfirstlane(header->num_instances);
+    const int n = __builtin_amdgcn_readfirstlane(header->num_instances) & kFrameHeaderCountMask;
     return n < 1 ? 1 : (n > capacity ? capacity : n);
+}
+// Frames that differ in view count (ABI 12): the by-value view count of a launch with headers is the view CAPACITY -- the stride and
+// extent of every per-view array ([V,16] extrinsics, [V,N,4] boxes, ...), as the by-value N is for the instances -- and the frame's own
+// v_f sits in its header.  Read once per workgroup as a wave-uniform scalar, clamped to [1, capacity]; views v_f .. capacity - 1 of a
+// frame are never read and never written.
+__device__ __forceinline__ bool frame_has_views(const FrameHeader* header) {
+    return (__builtin_amdgcn_readfirstlane(header->num_instances) & kFrameHeaderHasViews) != 0;
+}
+__device__ __forceinline__ int frame_views(const FrameHeader* header, int capacity) {
+    if (header == nullptr || !frame_has_views(header)) return capacity;
+    const int v = __builtin_amdgcn_readfirstlane(header->num_views);
+    return v == 0 ? capacity : (v < 1 ? 1 : (v > capacity ? capacity : v));
+}
+// ... and the count of the frame's sampling table, v_f H W (the table's layout and fixed-point scale follow from it: ray_sampling.h)
+__device__ __forceinline__ long long frame_pixels(const FrameHeader* header, long long count) {
+    if (header == nullptr || !frame_has_views(header)) return count;
+    const long long n = header->num_pixels;
+    return (n > 0 && n <= count) ? n : count;
 }
 // The count of frame `frame` of a launch whose header pointer addresses frame 0's (null: every frame has `capacity`).
 __device__ __forceinline__ int frame_count_of(const FrameHeader* header, long long frame_stride, unsigned frame, int capacity) {

@@ -225,8 +225,9 @@ def synthetic_frame_inputs(device, frame, views, instances, height=376, width=14
 
 def scan_frames_dir(folder, limit=0):
     """--frames-dir: the sorted *.npz files of `folder` (the first `limit` of them when limit > 0) and each one's
-    (V, H, W, N) (frames.pack_counts: no masks are loaded).  SystemExit when there is none, when a file is malformed, or when a file's
-    (V, H, W) differs from the first one's -- naming the odd file."""
+    (V, H, W, N) (frames.pack_counts: no masks are loaded).  The packs of one job share their image size; their view and instance
+    counts may differ (1..32 views, 1..64 instances: the batch rows' capacities are the maxima over the job).  SystemExit when there is no
+    pack, when a file is malformed, has a count outside those limits, or an (H, W) that differs from the first one's -- naming the odd file."""
     import glob
     from . import frames
     files = sorted(glob.glob(os.path.join(folder, "*.npz")))
@@ -242,9 +243,11 @@ def scan_frames_dir(folder, limit=0):
             shapes.append(frames.pack_counts(path))
         except ValueError as error:
             raise SystemExit(f"--frames-dir: {error}")
-        if shapes[-1][:3] != shapes[0][:3]:
-            raise SystemExit(f"--frames-dir: {path} has (views, height, width) = {shapes[-1][:3]}, {files[0]} has {shapes[0][:3]}: "
-                             "the frames of one job share their view count and image size")
+        if shapes[-1][1:3] != shapes[0][1:3]:
+            raise SystemExit(f"--frames-dir: {path} has (height, width) = {shapes[-1][1:3]}, {files[0]} has {shapes[0][1:3]}: "
+                             "the frames of one job share their image size")
+        if not 1 <= shapes[-1][0] <= 32:
+            raise SystemExit(f"--frames-dir: {path} has {shapes[-1][0]} views, 1..32")
         if not 1 <= shapes[-1][3] <= 64:
             raise SystemExit(f"--frames-dir: {path} has {shapes[-1][3]} target instances, 1..64")
     return files, shapes
@@ -363,7 +366,7 @@ class _RenderWork:
         if args.frames_dir:          # a frame pack (frames.py), host side: slots and batch rows reset from it, vsrd_frame_ingest fills the row
             from . import frames
             return frames.load_pack(self.manifest["packs"][int(frame)])
-        return synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts), args.height, args.width)
+        return synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts), instances_of(frame, args.instance_counts), args.height, args.width)
 
     def materialised(self, inputs):
         """`inputs` as a FrameInputs on the device: what founds a slot or a batch, and what a loop of its own is built on."""
@@ -374,6 +377,11 @@ class _RenderWork:
     def count_of(inputs):
         from . import frames
         return inputs.num_instances if isinstance(inputs, frames.FramePack) else int(inputs.soft_masks.shape[-1])
+
+    @staticmethod
+    def views_of(inputs):
+        from . import frames
+        return inputs.num_views if isinstance(inputs, frames.FramePack) else int(inputs.soft_masks.shape[0])
 
     def optimization_config(self, **more):
         from . import optimization
@@ -390,8 +398,8 @@ class _RenderWork:
         mine = [] if self.queue.dynamic else [frame for frame in self.queue.mine if not os.path.exists(self.path_of(frame))]
         # (frame packs are NOT made resident: a directory holds any number of them, 9 MB each at the reference's size.  A pack is read when its
         #  frame is taken -- inside the clock, under phase_seconds["inputs"] -- and dropped once its row is reset)
-        self.inputs = {} if args.frames_dir else {frame: synthetic_frame_inputs(self.device, frame, args.views, instances_of(frame, args.instance_counts),
-                                                                                args.height, args.width) for frame in mine}
+        self.inputs = {} if args.frames_dir else {frame: synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts),
+                                                                                instances_of(frame, args.instance_counts), args.height, args.width) for frame in mine}
         self.slots, self.batch = queue.Queue(), None
         self.setup_seconds, self.graphs_per_slot, self.unsuitable_founders = 0.0, 0, []
         # the frames a slot or batch may be founded on: this rank's own (static), or the head of the job's queue (dynamic: built here, once)
@@ -402,9 +410,11 @@ class _RenderWork:
                 founders = [self.materialised(self.inputs_of(f)) for f in candidates[:args.frame_batch]]
                 founders += [founders[-1]] * (args.frame_batch - len(founders))           # (fewer frames than rows: the shape is what matters)
                 try:
-                    mixed = len(set(args.instance_counts)) > 1           # (a mixed list: rows of capacity max(list), each frame its own count)
+                    # (a mixed list: rows of capacity max(list), each frame its own count -- the capacities, not the founders, fix the layout)
+                    mixed, mixed_views = len(set(args.instance_counts)) > 1, len(set(args.view_counts)) > 1
                     self.batch = optimization.FrameBatch(founders, self.optimization_config(), self.device,
-                                                         max_instances=max(args.instance_counts) if mixed else None)
+                                                         max_instances=max(args.instance_counts) if mixed else None,
+                                                         max_views=max(args.view_counts) if mixed_views else None)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
                     tail = len(mine) % args.frame_batch if mine else 0                   # a static queue's last group is known now: capture it too
                     self.graphs_per_slot = self.batch.capture_all(actives=sorted({args.frame_batch, tail} - {0}, reverse=True))
@@ -479,8 +489,9 @@ class _RenderWork:
             slot = self.slots.get() if self._have_slots else None      # (--fresh-loops, or no frame could found a slot)
             try:
                 inputs = self.inputs_of(frame)
-                # (a slot serves frames of its founder's shape: a frame of another instance count runs in a loop of its own)
-                if slot is None or self.count_of(inputs) != slot.num_instances or not slot.reset(inputs, init_seed=self.init_seed(frame)):
+                # (a slot serves frames of its founder's shape: a frame of another instance or view count runs in a loop of its own)
+                if (slot is None or self.count_of(inputs) != slot.num_instances or self.views_of(inputs) != slot.num_views
+                        or not slot.reset(inputs, init_seed=self.init_seed(frame))):
                     fallbacks.append(int(frame))
                     losses[frame], payload = self._own_loop(frame)
                     return payload
@@ -632,6 +643,23 @@ def instances_of(frame, counts):
     return int(counts[int(frame) % len(counts)])
 
 
+def parse_views(text):
+    """--views: one count (every frame) or a comma list -- frame j has list[j % len(list)] views (views_of)."""
+    try:
+        counts = [int(x) for x in str(text).split(",")]
+    except ValueError:
+        raise SystemExit(f"--views: an integer or a comma list of integers, got {text!r}")
+    if not counts or any(not 1 <= v <= 32 for v in counts):
+        raise SystemExit(f"--views: counts of 1..32, got {text!r}")
+    return counts
+
+
+def views_of(frame, counts):
+    """The view count of frame number `frame`: list[frame % len(list)], a pure function of the frame number like instances_of -- and
+    independent of the instance list's cycle (each list cycles with its own length)."""
+    return int(counts[int(frame) % len(counts)])
+
+
 def main(argv=None):
     """Optimise K synthetic frames, sharded over the ranks, each rank keeping `--frames-in-flight` frames on its GPU at a time with
     ``FrameOptimizer(graph=True)``; checkpoints through formats.checkpoint_payload (atomic, restartable: a frame whose final checkpoint
@@ -670,8 +698,12 @@ def main(argv=None):
     parser.add_argument("--frames-dir", default="",
                         help="optimise the frame packs of this directory (vsrd_amd/frames.py; tools/make_frame_packs.py writes synthetic ones) instead of "
                              "synthetic frames: frame j is the j-th of its sorted *.npz files, --frames defaults to all of them, views / image size / "
-                             "instance counts are the packs' own (not to be combined with --views, --instances, --height, --width)")
-    parser.add_argument("--views", type=int, default=None, help="default 17")
+                             "instance counts are the packs' own and may differ from pack to pack, the image size may not (not to be combined with --views, --instances, "
+                             "--height, --width)")
+    parser.add_argument("--views", type=str, default=None,
+                        help="views per frame: one count, or a comma list (frame j gets list[j %% len(list)], whatever the --instances list gives it: "
+                             "each list cycles with its own length); with --frame-batch > 1 a mixed list runs in batches of view capacity max(list) "
+                             "(optimization.FrameBatch(max_views=...)); 1..32, default 17")
     parser.add_argument("--instances", type=str, default=None,
                         help="instances per frame: one count, or a comma list (frame j gets list[j %% len(list)]); with --frame-batch > 1 a mixed "
                              "list runs in batches of capacity max(list) (optimization.FrameBatch(max_instances=...)); default 8")
@@ -723,7 +755,9 @@ def main(argv=None):
         argv = argv + ["--frames-dir", args.frames_dir]
         if "RANK" not in os.environ:          # (a job nobody could run ends here, before any rank starts; rank 0 reads the counts again for the manifest)
             scan_frames_dir(args.frames_dir, args.frames)
-    args.views, args.height, args.width = (default if value is None else value for value, default in ((args.views, 17), (args.height, 376), (args.width, 1408)))
+    args.height, args.width = (default if value is None else value for value, default in ((args.height, 376), (args.width, 1408)))
+    args.view_counts = parse_views("17" if args.views is None else args.views)
+    args.views = args.view_counts[0] if len(args.view_counts) == 1 else ",".join(str(v) for v in args.view_counts)
     args.instances = "8" if args.instances is None else args.instances
     args.instance_counts = parse_instances(args.instances)
     args.instances = args.instance_counts[0] if len(args.instance_counts) == 1 else args.instances
@@ -807,13 +841,15 @@ def _rank_main(args):
             store = dist.TCPStore(host, 0, world, is_master=True, wait_for_workers=False)
             store_port = store.port
     manifest = broadcast_manifest(dict(frames=list(range(total)), seed=args.seed, out=out_dir, store_port=store_port, attempt=args.attempt,
-                                       packs=packs, pack_shapes=shapes) if rank == 0 else None)
+                                       packs=packs, pack_shapes=shapes) if rank == 0 else None)      # (pack_shapes: every pack's (V, H, W, N))
     total = len(manifest["frames"])          # (every rank sizes the job from the manifest)
     args.frame_batch = effective_frame_batch(args.frame_batch, total, world)
     if manifest.get("packs"):                # frame j's count is its pack's: instances_of(j, counts) with one entry per frame
-        args.views, args.height, args.width = manifest["pack_shapes"][0][:3]
+        args.height, args.width = manifest["pack_shapes"][0][1:3]
         args.instance_counts = [int(shape[3]) for shape in manifest["pack_shapes"]]
         args.instances = ",".join(str(n) for n in sorted(set(args.instance_counts)))
+        args.view_counts = [int(shape[0]) for shape in manifest["pack_shapes"]]
+        args.views = ",".join(str(v) for v in sorted(set(args.view_counts)))
     if not manifest["out"]:
         raise SystemExit("no checkpoint directory (--out; the supervisor supplies one)")
     if dynamic and rank != 0:
@@ -856,6 +892,8 @@ def _rank_main(args):
                     "frames_dir": args.frames_dir or None,
                     "frames_per_instances": {str(n): sum(1 for r in gathered for f in r["frames_done"] if instances_of(f, args.instance_counts) == n)
                                              for n in sorted(set(args.instance_counts))},
+                    "frames_per_views": {str(v): sum(1 for r in gathered for f in r["frames_done"] if views_of(f, args.view_counts) == v)
+                                         for v in sorted(set(args.view_counts))},
                     "per_rank_seconds": [r["own_seconds"] for r in gathered],
                     "rank_finish_spread_seconds": max(r["own_seconds"] for r in gathered) - min(r["own_seconds"] for r in gathered),
                     "config": {"workload": f"sleep({args.selftest_seconds} s x (1 + {args.selftest_spread} u)) per frame on gloo / CPU", "checkpoints": manifest["out"]}}
@@ -874,6 +912,11 @@ def _rank_main(args):
                 "frames_per_instances": {str(n): sum(1 for r in gathered for f in r["final_losses"] if instances_of(f, args.instance_counts) == n)
                                          for n in sorted(set(args.instance_counts))},
                 "batch_capacity": max(args.instance_counts) if args.frame_batch > 1 and len(set(args.instance_counts)) > 1 else None,
+                # views per frame (frame j: view_list[j % len]); frames done per count; the rows' view capacity of a batch of mixed views
+                "view_list": sorted(set(args.view_counts)) if args.frames_dir else list(args.view_counts),
+                "frames_per_views": {str(v): sum(1 for r in gathered for f in r["final_losses"] if views_of(f, args.view_counts) == v)
+                                     for v in sorted(set(args.view_counts))},
+                "batch_view_capacity": max(args.view_counts) if args.frame_batch > 1 and len(set(args.view_counts)) > 1 else None,
                 "control_plane": "gloo" if share else "RCCL",
                 "queue": "dynamic (TCPStore counter on rank 0; inputs built when a frame is taken, inside the clock)" if dynamic else
                          "static (frame j of the seeded permutation to rank j mod world; " +
@@ -909,6 +952,8 @@ def _rank_main(args):
                                           + ("gloo (RCCL refuses two ranks on one device)" if share else "RCCL") + ": barriers, manifest broadcast, gather of the report",
                            "checkpoints": manifest["out"]},
             }
+            if len(set(args.view_counts)) > 1:
+                line["metric"] += f"; frames of {args.views} views"
             if args.ranks_share_gpu:
                 line["metric"] = "ranks share ONE GPU (--ranks-share-gpu): a test of the multi-rank path, NOT a scaling measurement; " + line["metric"]
         print(json.dumps(line), flush=True)

@@ -15,6 +15,7 @@ never exchange gradients.
 from dataclasses import dataclass, field as dataclass_field
 from typing import Optional, Sequence
 
+import ctypes
 import math
 import threading
 import time
@@ -334,18 +335,24 @@ class FrameOptimizer:
     (``fused_hypernetwork = False`` keeps them with torch: the A/B reference)."""
 
     def __init__(self, inputs: FrameInputs, config: OptimizationConfig, device, graph=False, fused_glue=None, persistent=False, row=None,
-                 capacity=None):
+                 capacity=None, view_capacity=None):
         """``persistent``: the loop will be given other frames of the same shape through ``reset()`` (a frame SLOT, launcher.py): it then
         owns every buffer a captured graph holds the address of -- in particular a copy of the soft masks instead of the caller's tensor.
         ``row`` (a ``FrameRow``): the loop is one frame of a ``FrameBatch`` and keeps EVERY device buffer its kernels touch -- parameters,
         Adam's state, rates, counters, rays, masks, sampling table, scratch -- in that row of the batch's arena.  ``capacity`` (with
         ``row``): the row of a MIXED batch (FrameBatch(max_instances=...)): every per-instance buffer is laid out for ``capacity``
-        instances, the frame's own N fill the first rows, and the row's header (include/vsrd_hip.h, vsrd_frame_header) carries N."""
+        instances, the frame's own N fill the first rows, and the row's header (include/vsrd_hip.h, vsrd_frame_header) carries N.
+        ``view_capacity`` (with ``row``; FrameBatch(max_views=...)): likewise every per-view buffer -- camera positions, ray directions,
+        inverse projections, extrinsics and intrinsics, ground-truth boxes and visibility, soft masks, sampling weights, the ray table, the
+        label outputs, the prologue's scratch -- is laid out for ``view_capacity`` views; they are view-major, so the frame's own V fill a
+        prefix of each, and the header carries V and V H W.  Either capacity gives the row a header; the other one is then the founder's
+        own count."""
         self._graphs = {}
         self.persistent = bool(persistent)
         self._row = row
         self._capacity = None if capacity is None else int(capacity)
-        if self._capacity is not None and row is None:
+        self._view_capacity = None if view_capacity is None else int(view_capacity)
+        if (self._capacity is not None or self._view_capacity is not None) and row is None:
             raise ValueError("a capacity belongs to a frame of a FrameBatch (row=...)")
         if row is not None and not (graph and persistent and fused_glue in (None, True)):
             raise ValueError("a frame of a batch is a persistent graph-mode loop with the fused glue")
@@ -365,9 +372,15 @@ class FrameOptimizer:
             raise ValueError("fused_glue keeps the learning rates and Adam's counters on the device: it needs graph=True")
         V, H, W, N = inputs.soft_masks.shape
         self.num_views, self.num_instances = V, N
+        if self._capacity is not None or self._view_capacity is not None:       # a row with a header: laid out for both capacities
+            self._capacity = N if self._capacity is None else self._capacity
+            self._view_capacity = V if self._view_capacity is None else self._view_capacity
         self.capacity = N if self._capacity is None else self._capacity
+        self.view_capacity = V if self._view_capacity is None else self._view_capacity
         if not 1 <= N <= self.capacity:
             raise ValueError(f"a row of capacity {self.capacity} serves frames of 1..{self.capacity} instances, got {N}")
+        if not 1 <= V <= self.view_capacity <= _lib.MAX_VIEWS:
+            raise ValueError(f"a row of view capacity {self.view_capacity} (at most {_lib.MAX_VIEWS}) serves frames of 1..{self.view_capacity} views, got {V}")
         with _initial_draw:
             if config.init_seed is not None:
                 torch.default_generator.manual_seed(int(config.init_seed))      # (the CPU generator: the modules are built on the host; the device generators, which captured graphs register, stay untouched)
@@ -401,8 +414,8 @@ class FrameOptimizer:
         self._labels = None
         self._capture_stream = None
         self._eager_graph_steps = {}
-        self._prepare_rays(inputs, config, H, W, N)
         self.pixels_per_view = H * W
+        self._prepare_rays(inputs, config, H, W, N)
         self.step_index = 0
         if self.fused_glue:
             self._init_fused_glue()
@@ -428,25 +441,57 @@ class FrameOptimizer:
         full.narrow(dim, 0, tensor.shape[dim]).copy_(tensor)
         return _instance_prefix(full, tensor.shape[dim]) if prefix else full
 
+    def _adopt_prefix(self, tensor, shape):
+        """A row laid out for capacities: `tensor` copied into the leading corner of a zero-filled buffer of `shape` in the row (views
+        along dimension 0, instances behind them).  Returns the FULL buffer: the kernels stride by the capacities."""
+        full = self._row.new(list(shape), tensor.dtype, fill=0)
+        corner = full
+        for dim, size in enumerate(tensor.shape):
+            corner = corner.narrow(dim, 0, size)
+        corner.copy_(tensor)
+        return full
+
+    def _set_views(self, V):
+        """A row laid out for a view capacity: the loop's per-view tensors are the first V views of the row's buffers (`self._full`) --
+        view-major, so contiguous prefixes at the buffers' own addresses, which is what the kernels and the captured graphs hold."""
+        full, pixels = self._full, V * self.pixels_per_view
+        self.num_views = V
+        self.camera_positions, self.ray_directions = full["camera_positions"][:V], full["ray_directions"][:pixels]
+        self.flat_masks, self.sampling_weights = full["flat_masks"][:pixels], full["sampling_weights"][:pixels]
+        if "extrinsics" in full:              # (the glue's tables, once _init_fused_glue has made them)
+            b = self._glue
+            for name in ("extrinsics", "intrinsics", "gt_boxes", "visible"):
+                b[name] = full[name][:V]
+            b["masks"] = self.flat_masks
+
     def _write_header(self):
-        """A mixed batch's row: the frame's own count and silhouette normaliser (the float32 the one-frame path passes by value)."""
-        header = self._glue["header"]
-        header.view(torch.int32)[0] = self.num_instances
-        header.view(torch.float32)[1] = 1.0 / (self.config.num_rays * self.num_instances)
+        """A mixed batch's row: the frame's own instance count and silhouette normaliser (the float32 the one-frame path passes by value),
+        its own view count and the count of its sampling table (include/vsrd_hip.h, vsrd_frame_header: ABI 12)."""
+        header = _lib.FrameHeader(self.num_instances | _lib.FRAME_HEADER_HAS_VIEWS, 1.0 / (self.config.num_rays * self.num_instances),
+                                  self.num_views, 0, self.num_views * self.pixels_per_view)
+        self._glue["header"].copy_(torch.frombuffer(bytearray(bytes(header)), dtype=torch.uint8))
 
     def _prepare_rays(self, inputs, config, H, W, N):
         # rays of every view, once per frame (main.py:267-296)
         cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
-        self.camera_positions = self._own(cam)                              # [V,3]
-        self.ray_directions = self._own(dirs.reshape(-1, 3).contiguous())   # [V*H*W,3]
-        self.flat_masks = inputs.soft_masks.reshape(-1, N)
-        if self._capacity is not None:               # [pixels, capacity]: the kernels read the targets with target_stride = capacity
-            self.flat_masks = self._adopt_instances(self.flat_masks.to(torch.float32), 1)
-        elif self._row is not None:
-            self.flat_masks = self._row.adopt(self.flat_masks.to(torch.float32))
-        elif self.persistent:                                               # (a slot's graphs read the masks through this address for every later frame)
-            self.flat_masks = self.flat_masks.to(torch.float32).clone(memory_format=torch.contiguous_format)
-        self.sampling_weights = self._own(self.flat_masks[:, :N].max(dim=-1).values.to(torch.float32).contiguous())          # main.py:620-624
+        if self._capacity is not None:
+            # a row with a header: [view capacity x H W, instance capacity] soft masks (the kernels read the targets with target_stride =
+            # capacity) and every other per-view buffer laid out for the view capacity; the frame fills their leading corners
+            views, pixels = self.view_capacity, self.view_capacity * H * W
+            self._full = dict(camera_positions=self._adopt_prefix(cam, (views, 3)), ray_directions=self._adopt_prefix(dirs.reshape(-1, 3), (pixels, 3)),
+                              flat_masks=self._adopt_prefix(inputs.soft_masks.reshape(-1, N).to(torch.float32), (pixels, self.capacity)),
+                              sampling_weights=self._row.new(pixels, torch.float32, fill=0))
+            self._set_views(self.num_views)
+            torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)                                             # main.py:620-624
+        else:
+            self.camera_positions = self._own(cam)                              # [V,3]
+            self.ray_directions = self._own(dirs.reshape(-1, 3).contiguous())   # [V*H*W,3]
+            self.flat_masks = inputs.soft_masks.reshape(-1, N)
+            if self._row is not None:
+                self.flat_masks = self._row.adopt(self.flat_masks.to(torch.float32))
+            elif self.persistent:                                               # (a slot's graphs read the masks through this address for every later frame)
+                self.flat_masks = self.flat_masks.to(torch.float32).clone(memory_format=torch.contiguous_format)
+            self.sampling_weights = self._own(self.flat_masks[:, :N].max(dim=-1).values.to(torch.float32).contiguous())      # main.py:620-624
         self.ray_table = self.ray_remap = None
         if not self._prepare_sampler(config):
             raise UnsuitableFrameError("this frame's importance weights do not suit the table sampler (too much of the weight in fewer pixels "
@@ -471,7 +516,9 @@ class FrameOptimizer:
         had_table = self.ray_table is not None
         if had_table:
             self.ray_table.rebuild(self.sampling_weights)
-        table = self.ray_table if had_table else rendering.RayTable(self.sampling_weights, allocate=None if self._row is None else self._row.bytes)
+        # (a row laid out for a view capacity: the table's allocation is sized for capacity x H W weights, the table in it is the frame's own)
+        table = self.ray_table if had_table else rendering.RayTable(self.sampling_weights, allocate=None if self._row is None else self._row.bytes,
+                                                                    capacity=self.view_capacity * self.pixels_per_view)
         if table.suits(config.num_rays):
             self.ray_table = table
             return True
@@ -487,7 +534,7 @@ class FrameOptimizer:
     def _frame_config(self):
         """include/vsrd_hip.h::vsrd_frame_config of this loop (one frame: the batch fields are set by whoever launches)."""
         cfg, inp, det = self.config, self.inputs, self.detector
-        V, N = self.num_views, self.capacity
+        V, N = self.view_capacity, self.capacity       # (a row with a header: the capacities; the frame's own counts are in the header)
         w = cfg.loss_weights
         frame = _lib.FrameConfig()
         frame.num_boxes, frame.num_views = N, V
@@ -516,14 +563,15 @@ class FrameOptimizer:
         b["gt_boxes"] = inp.boxes_2d.to(**f32).reshape(V, self.num_instances, 4).contiguous()
         b["visible"] = inp.visible_masks.to(device=dev, dtype=torch.uint8).contiguous()
         if self._capacity is not None:
-            b["gt_boxes"], b["visible"] = self._adopt_instances(b["gt_boxes"], 1), self._adopt_instances(b["visible"], 1)
-            for name in ("extrinsics", "intrinsics"):
-                b[name] = self._row.adopt(b[name])
+            views = self.view_capacity
+            for name, shape in (("extrinsics", (views, 16)), ("intrinsics", (views, 9)), ("gt_boxes", (views, N, 4)), ("visible", (views, N))):
+                self._full[name] = self._adopt_prefix(b[name], shape)
+            self._set_views(V)
         elif self.persistent:       # a slot OWNS what reset() overwrites: float32 contiguous inputs would otherwise be these very tensors -- the
             for name in ("extrinsics", "intrinsics", "gt_boxes", "visible"):      # caller's, and every other slot's built from the same frame
                 b[name] = b[name].clone() if self._row is None else self._row.adopt(b[name])
         new = self._new            # (a frame of a batch: everything below lives in the frame's row of the arena)
-        b["scratch"] = new(lib.vsrd_frame_scratch_bytes(V, N), torch.uint8)
+        b["scratch"] = new(lib.vsrd_frame_scratch_bytes(self.view_capacity, N), torch.uint8)
         b["instances"] = new((N, 16), fill=0.0)
         b["pd_indices"], b["gt_indices"] = new(N, torch.int64, fill=0), new(N, torch.int64, fill=0)
         b["target_columns"] = new(N, torch.int32, fill=0)
@@ -534,7 +582,7 @@ class FrameOptimizer:
         b["record"] = new(5, fill=0.0)
         b["masks"] = self.flat_masks.to(**f32).contiguous()        # (persistent: _prepare_rays made this the slot's own copy)
         if self._capacity is not None:
-            b["header"] = new(8, torch.uint8, fill=0)              # vsrd_frame_header: int32 num_instances, float32 loss_scale
+            b["header"] = new(ctypes.sizeof(_lib.FrameHeader), torch.uint8, fill=0)          # vsrd_frame_header
             self._write_header()
         self.fused_hypernetwork = True
         self.rebind()
@@ -663,7 +711,8 @@ class FrameOptimizer:
                          _lib.ptr(b["instance_weights"]), _lib.ptr(self.schedule), _lib.ptr(b["projection_losses"]), _lib.ptr(b["grad_raw"]))
         if with_prologue and header is not None:
             table = self.ray_table
-            code = lib.vsrd_frame_prologue_sample_with_header(*prologue_args, table.table.data_ptr(), table.count, cfg.num_rays,
+            # (by value: the count the table's allocation is sized for; each frame's own count is its header's num_pixels)
+            code = lib.vsrd_frame_prologue_sample_with_header(*prologue_args, table.table.data_ptr(), table.capacity, cfg.num_rays,
                                                               (cfg.seed + 1) & 0xFFFFFFFFFFFFFFFF, None, b["ray_indices"].data_ptr(), header.data_ptr(), stream)
             _lib.check(code)
         elif with_prologue:
@@ -1042,19 +1091,29 @@ class FrameOptimizer:
         cfg, dev, b = self.config, self.device, self._glue
         V, N = self.num_views, self.num_instances
         pack = inputs if isinstance(inputs, frames.FramePack) else None
-        if pack is not None:
-            # a frame pack (frames.py): vsrd_frame_ingest writes the row's soft masks, importance weights, boxes and visibility in place
-            shape, limit = (pack.num_views, *[int(x) for x in pack.image_size]), self._capacity
-            if shape != (V, *[int(x) for x in self.inputs.image_size]) or not (1 <= pack.num_instances <= limit if limit is not None else pack.num_instances == N):
-                raise ValueError(f"this loop serves frames of shape {(V, *[int(x) for x in self.inputs.image_size])} with " +
-                                 (f"1..{limit}" if limit is not None else str(N)) + f" instances, got a pack of {shape} with {pack.num_instances}")
-            N = pack.num_instances
-        elif self._capacity is not None:       # a mixed batch's row: any frame of its views and image size with 1..capacity instances
-            N = int(inputs.soft_masks.shape[-1])
-            if (tuple(inputs.soft_masks.shape[:-1]) != (V, *[int(x) for x in self.inputs.image_size]) or tuple(inputs.image_size) != tuple(self.inputs.image_size)
-                    or not 1 <= N <= self._capacity):
-                raise ValueError(f"a row of capacity {self._capacity} serves frames of shape {tuple(self.inputs.soft_masks.shape[:-1])} with 1..{self._capacity} "
-                                 f"instances, got {tuple(inputs.soft_masks.shape)}")
+        if self._capacity is not None:
+            # a row with a header: any frame -- a pack (frames.py) or a materialised FrameInputs -- of its image size with 1..view capacity
+            # views and 1..capacity instances
+            size = tuple(int(x) for x in self.inputs.image_size)
+            if pack is not None:
+                shape = (pack.num_views, *[int(x) for x in pack.image_size], pack.num_instances)
+            else:
+                shape = tuple(int(x) for x in inputs.soft_masks.shape)
+                if tuple(int(x) for x in inputs.image_size) != shape[1:3]:
+                    raise ValueError(f"image_size {tuple(inputs.image_size)} of soft masks of shape {shape}")
+            if shape[1:3] != size:
+                raise ValueError(f"this row serves frames of image size {size}, got {shape[1:3]}")
+            if not 1 <= shape[0] <= self.view_capacity:
+                raise ValueError(f"a row of view capacity {self.view_capacity} serves frames of 1..{self.view_capacity} views, got {shape[0]}")
+            if not 1 <= shape[3] <= self._capacity:
+                raise ValueError(f"a row of capacity {self._capacity} serves frames of 1..{self._capacity} instances, got {shape[3]}")
+            V, N = shape[0], shape[3]
+        elif pack is not None:
+            # a frame pack (frames.py): vsrd_frame_ingest writes the slot's soft masks, importance weights, boxes and visibility in place
+            shape = (pack.num_views, *[int(x) for x in pack.image_size])
+            if shape != (V, *[int(x) for x in self.inputs.image_size]) or pack.num_instances != N:
+                raise ValueError(f"this loop serves frames of shape {(V, *[int(x) for x in self.inputs.image_size])} with {N} instances, "
+                                 f"got a pack of {shape} with {pack.num_instances}")
         elif tuple(inputs.soft_masks.shape) != (V, *[int(x) for x in self.inputs.image_size], N) or tuple(inputs.image_size) != tuple(self.inputs.image_size):
             raise ValueError(f"a slot serves frames of ONE shape: {tuple(self.inputs.soft_masks.shape)}, got {tuple(inputs.soft_masks.shape)}")
         with _capture_lock, torch.no_grad():
@@ -1062,6 +1121,8 @@ class FrameOptimizer:
             main.synchronize()                                      # (replays of the previous frame have finished: nothing reads the buffers)
             # ---- inputs ----
             H, W = (int(x) for x in inputs.image_size)
+            if self._capacity is not None and V != self.num_views:
+                self._set_views(V)               # (the first V views of the row's buffers: the same addresses)
             if pack is not None:
                 inputs = self._ingest_pack(pack, H, W, N)
             cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
@@ -1123,7 +1184,7 @@ class FrameOptimizer:
         glue keeps float32 copies of its inputs' here)."""
         if self._labels is not None:
             return self._labels
-        V, N = self.num_views, self.capacity
+        V, N = self.view_capacity, self.capacity
         with _capture_lock, torch.no_grad():
             new = self._new
             state = dict(camera_corners=new((V, N, 8, 3), fill=0.0), boxes_2d=new((V, N, 4), fill=0.0), mean_iou=new((N, N), fill=0.0),
@@ -1155,13 +1216,13 @@ class FrameOptimizer:
                 None if header is None else header.data_ptr(), _lib.stream()))
 
     def _label_views(self):
-        state, n = self._labels, self.num_instances
-        return dict(boxes_3d=state["camera_corners"][:, :n], boxes_2d=state["boxes_2d"][:, :n].unflatten(-1, (2, 2)), confidences=state["confidences"][:n],
+        state, n, v = self._labels, self.num_instances, self.num_views
+        return dict(boxes_3d=state["camera_corners"][:v, :n], boxes_2d=state["boxes_2d"][:v, :n].unflatten(-1, (2, 2)), confidences=state["confidences"][:n],
                     matched_gt=state["matched_gt"][:n], mean_iou=state["mean_iou"][:n, :n])
 
     def labels(self):
         """The frame's pseudo-labels from its CURRENT parameters (tools/kitti_360/make_predictions.py:61-192), by one vsrd_frame_labels
-        launch on the current stream, no host synchronisation: a dictionary of device tensors sliced to the frame's own n instances --
+        launch on the current stream, no host synchronisation: a dictionary of device tensors sliced to the frame's own V views and n instances --
         boxes_3d [V,n,8,3] (camera-frame corners in every view), boxes_2d [V,n,2,2] (clipped), confidences [n] (the matched mean IoU),
         matched_gt [n], mean_iou [n,n].  They are views of buffers the next call overwrites (formats.save_frame_labels writes them out)."""
         self._launch_labels()
@@ -1228,7 +1289,7 @@ class FrameOptimizer:
 
 
 class FrameBatch:
-    """B frames of ONE shape optimised in lock-step: every launch of a step -- prologue + ray draw, hypernetwork forward, render +
+    """B frames of ONE shape (or, with capacities, of one image size) optimised in lock-step: every launch of a step -- prologue + ray draw, hypernetwork forward, render +
     losses + adjoint, MLP adjoint, reductions, hypernetwork backward + Adam, epilogue -- covers all B frames at once (include/vsrd_hip.h,
     "frame batches").  The reference's loop carries the same batch dimension (scripts/main.py:525-651: lists over the batch of distance
     fields, camera positions, ray directions, soft masks; BoxParameters3D(batch_size, num_instances), box_parameters.py:34-49); its
@@ -1243,27 +1304,41 @@ class FrameBatch:
     Like a frame slot, a batch is built and captured once (``capture_all``) and then serves group after group of frames through
     ``reset(f, inputs, init_seed)``; a last group of fewer than B frames runs with ``active < B`` (the first ``active`` rows)."""
 
-    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None):
-        """``max_instances`` None: every frame has ONE shape (views, height, width, instances).  An integer: a MIXED batch -- the frames
-        share (views, height, width) and have 1..max_instances instances each; every row is laid out for ``max_instances`` (the capacity)
+    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None):
+        """``max_instances`` and ``max_views`` None: every frame has ONE shape (views, height, width, instances).  ``max_instances`` an
+        integer: a MIXED batch -- the frames have 1..max_instances instances each; every row is laid out for ``max_instances`` (the capacity)
         and carries its frame's own count in a header (include/vsrd_hip.h, vsrd_frame_header), and frame f still walks, bit for bit, the
-        trajectory it walks in a slot of its own N, through both phases."""
+        trajectory it walks in a slot of its own N, through both phases.  ``max_views`` an integer (1..32): likewise the frames have
+        1..max_views views each and every row is laid out for ``max_views`` views (ABI 12).  The two combine; giving either one gives every
+        row a header, and the axis without a capacity stays uniform.  The frames always share (height, width)."""
         inputs = list(inputs)
         if not inputs:
             raise ValueError("FrameBatch needs at least one frame")
-        shape = tuple(inputs[0].soft_masks.shape)
+        shape = tuple(int(x) for x in inputs[0].soft_masks.shape)
         self.max_instances = None if max_instances is None else int(max_instances)
-        if self.max_instances is None:
+        self.max_views = None if max_views is None else int(max_views)
+        if self.max_instances is None and self.max_views is None:
             if any(tuple(i.soft_masks.shape) != shape or tuple(i.image_size) != tuple(inputs[0].image_size) for i in inputs):
-                raise ValueError("the frames of a batch share ONE shape (views, height, width, instances)")
+                raise ValueError("the frames of a batch share ONE shape (views, height, width, instances): frames that differ in instance or view "
+                                 "count need max_instances / max_views")
         else:
-            if not 1 <= self.max_instances <= _lib.MAX_INSTANCES:
+            if self.max_instances is not None and not 1 <= self.max_instances <= _lib.MAX_INSTANCES:
                 raise ValueError(f"max_instances: 1..{_lib.MAX_INSTANCES}, got {self.max_instances}")
-            if any(tuple(i.soft_masks.shape[:-1]) != shape[:-1] or tuple(i.image_size) != tuple(inputs[0].image_size) for i in inputs):
-                raise ValueError("the frames of a mixed batch share (views, height, width)")
-            if any(not 1 <= int(i.soft_masks.shape[-1]) <= self.max_instances for i in inputs):
+            if self.max_views is not None and not 1 <= self.max_views <= _lib.MAX_VIEWS:
+                raise ValueError(f"max_views: 1..{_lib.MAX_VIEWS}, got {self.max_views}")
+            if any(tuple(i.soft_masks.shape[1:3]) != shape[1:3] or tuple(i.image_size) != tuple(inputs[0].image_size) for i in inputs):
+                raise ValueError("the frames of a mixed batch share (height, width)")
+            if self.max_views is None and any(int(i.soft_masks.shape[0]) != shape[0] for i in inputs):
+                raise ValueError("the frames differ in view count: a batch of such frames needs max_views")
+            if self.max_instances is None and any(int(i.soft_masks.shape[-1]) != shape[-1] for i in inputs):
+                raise ValueError("the frames differ in instance count: a batch of such frames needs max_instances")
+            if self.max_views is not None and any(not 1 <= int(i.soft_masks.shape[0]) <= self.max_views for i in inputs):
+                raise ValueError(f"the frames of this batch have 1..max_views = {self.max_views} views")
+            if self.max_instances is not None and any(not 1 <= int(i.soft_masks.shape[-1]) <= self.max_instances for i in inputs):
                 raise ValueError(f"the frames of a mixed batch have 1..max_instances = {self.max_instances} instances")
-            shape = (*shape[:-1], self.max_instances)
+            # (the rows' layout: both capacities; the axis without one is uniform, and its count is the capacity)
+            shape = (shape[0] if self.max_views is None else self.max_views, *shape[1:3], shape[3] if self.max_instances is None else self.max_instances)
+        capacities = (None, None) if self.max_instances is None and self.max_views is None else (shape[3], shape[0])
         self.size = len(inputs)
         import dataclasses
         if config.mlp_adjoint_item_slots == 0:
@@ -1285,7 +1360,8 @@ class FrameBatch:
             for position, frame_inputs in enumerate(candidates):
                 row.cursor, row.layout = 0, []                           # (a founder that failed had begun to fill the row)
                 try:
-                    member = FrameOptimizer(frame_inputs, cfg, self.device, graph=True, persistent=True, row=row, capacity=self.max_instances)
+                    member = FrameOptimizer(frame_inputs, cfg, self.device, graph=True, persistent=True, row=row, capacity=capacities[0],
+                                            view_capacity=capacities[1])
                 except UnsuitableFrameError:
                     if position == 0:
                         self.unsuitable_founders.append(f)
@@ -1468,8 +1544,8 @@ class FrameBatch:
         return len(self._graphs)
 
     def reset(self, f, inputs, init_seed=None):
-        """Row f starts another frame (``FrameOptimizer.reset``; a mixed batch's row takes any frame of its views and image size with 1..max_instances
-        instances, ValueError otherwise).  False: the frame does not suit the table sampler -- optimise it in a loop of its own."""
+        """Row f starts another frame (``FrameOptimizer.reset``; a mixed batch's row takes any frame of its image size with 1..max_instances
+        instances and 1..max_views views -- the rows' capacities -- ValueError otherwise).  False: the frame does not suit the table sampler -- optimise it in a loop of its own."""
         return self.frames[f].reset(inputs, init_seed=init_seed)
 
     def close(self):

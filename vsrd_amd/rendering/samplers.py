@@ -95,25 +95,31 @@ class RayTable:
 
     MAX_PICKS = 32768          # csrc/ray_sampling.h: kTableRounds x 2048 candidates per draw
 
-    def __init__(self, weights, allocate=None):
+    def __init__(self, weights, allocate=None, capacity=None):
         """``allocate(nbytes) -> uint8 device tensor``: where the table lives instead of a ``torch.empty`` of its own (a frame of a batch:
-        its row of the batch's arena, optimization.FrameArena)."""
+        its row of the batch's arena, optimization.FrameArena).  ``capacity``: the largest count ``rebuild`` will be given (a row that
+        serves frames of 1..V_cap views: V_cap H W); the ALLOCATION is sized for it, the table in it is always the one of the current
+        weights alone (its layout follows from their count: csrc/ray_sampling.h)."""
         lib = _lib.load()
         self.weights = weights.detach().reshape(-1).to(torch.float32).contiguous()
         if not self.weights.is_cuda:
             raise _lib.VsrdHipError("RayTable needs device weights (there is no CPU path)")
         self.count = int(self.weights.numel())
-        nbytes = lib.vsrd_ray_table_bytes(self.count)
+        self.capacity = self.count if capacity is None else int(capacity)
+        if self.capacity < self.count:
+            raise ValueError(f"RayTable: {self.count} weights, capacity {self.capacity}")
+        nbytes = lib.vsrd_ray_table_bytes(self.capacity)
         self.table = torch.empty(nbytes, dtype=torch.uint8, device=self.weights.device) if allocate is None else allocate(nbytes)
         _lib.check(lib.vsrd_ray_table_build(_lib.ptr(self.weights), self.count, self.table.data_ptr(), self.table.numel(), _lib.stream()))
 
     def rebuild(self, weights):
-        """The table of OTHER weights of the same count, in place (same buffer, same address: a captured graph that draws from this table
-        draws from the new weights).  The build clears the header, the sticky `incomplete` flag included."""
+        """The table of OTHER weights, in place (same buffer, same address: a captured graph that draws from this table draws from the
+        new weights) -- of the same count, or of any count up to the table's ``capacity``.  The build clears the header, the sticky
+        `incomplete` flag included."""
         weights = weights.detach().reshape(-1).to(torch.float32).contiguous()
-        if int(weights.numel()) != self.count or weights.device != self.weights.device:
-            raise ValueError(f"RayTable.rebuild: {self.count} weights on {self.weights.device} expected")
-        self.weights = weights
+        if not 1 <= int(weights.numel()) <= self.capacity or weights.device != self.weights.device:
+            raise ValueError(f"RayTable.rebuild: 1..{self.capacity} weights on {self.weights.device} expected")
+        self.weights, self.count = weights, int(weights.numel())
         _lib.check(_lib.load().vsrd_ray_table_build(_lib.ptr(self.weights), self.count, self.table.data_ptr(), self.table.numel(), _lib.stream()))
 
     def suits(self, num_samples, margin=4.0):
