@@ -585,6 +585,48 @@ int32_t vsrd_frame_labels(const vsrd_frame_config* config,
                           int64_t* matched_gt /* [N] */, float* confidences /* [N] */,
                           const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
 
+/* Frame masks (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the dense
+ * predicted instance masks of ONE view of a frame, bit-packed -- what the reference renders every `image_intervals` steps
+ * (scripts/main.py:1011-1061): volume_masks (the two-pass hierarchical_volumetric_rendering of the soft union at every pixel) times
+ * surface_masks (sphere_tracing(..., initialization=False, differentiable=False)[1]) -- in ONE launch (plus a single-workgroup launch
+ * that zeroes `counts`), no host synchronisation, no allocation, capturable.  A wave traces a run of 64 pixels of an image row, one lane
+ * each, and then renders only the pixels whose trace converged; a run without one renders nothing.
+ * Conventions as for the *_with_header twins: field->num_instances is the capacity N and the stride of every instance axis;
+ * config->num_frames / frame_stride batch the call (every pointer addresses frame 0, frame f lies f * frame_stride bytes behind it);
+ * frame_header (may be NULL: every frame has N instances) carries the frame's own n_f, clamped to [1, N], VSRD_FRAME_HEADER_HAS_VIEWS
+ * masked off; instances n_f .. N-1 of every output are neither read nor written.  config->device_schedule / device_stream_offset are
+ * honoured as in the step kernels; config->num_rays is ignored (the ray count is H W); config->ray_indices, out_* and target_columns
+ * inside `config` are rejected, like `view` outside 0 .. num_views-1, N outside 1..VSRD_MAX_INSTANCES, num_samples outside what
+ * vsrd_render_hierarchical_forward's one-ray kernel serves (2..256 box-only, 2..128 residual), and `targets` without `counts` or the
+ * reverse: VSRD_E_INVALID_ARGUMENT.  The residual form evaluates the MLPs with the exact-fp32 products (VSRD_FLAG_MLP_SPLIT_BF16 is ignored).
+ * Pixel p = y W + x of view `view`: origin camera_positions[view], direction ray_directions[view H W + p];
+ *   converged = what vsrd_sphere_trace computes with the soft union, foreground = NULL, initialise = 0 (bounding_radius <= 0: none);
+ *   labels[N] = what vsrd_render_hierarchical_forward's one-ray kernel computes for that ray at the launch's schedule: ray p uses row p
+ *               of u_coarse / u_fine [H W, S], or with NULL the Philox stream keyed by (seed, stream_offset, ray = p);
+ *   soft[p, n] = converged ? labels[n] : 0.0f (exactly 0 where the trace did not converge);
+ *   bit (n, y, x) = soft[p, n] > threshold, laid out as numpy.packbits of [N, H, W] along W: most significant bit first, pad bits of a
+ *               row's last byte 0 -- the `inside` layout of vsrd_frame_ingest;
+ *   counts[n] = (#pred, #target, #pred and target) over the view's pixels, target bit = targets[view H W + p, col] > threshold with
+ *               col = target_columns ? target_columns[n] : n (a negative column: no target bit); int32, integer atomics, zeroed by the
+ *               call itself for n < n_f. */
+typedef struct vsrd_frame_masks_config {
+    int32_t view;               /* which view of the row, 0 = target                                              */
+    int32_t num_views;          /* V (the view capacity of the row): rows of camera_positions, views of ray_directions / targets */
+    int32_t height, width;
+    int32_t num_iterations;     /* sphere_tracing, initialization=False                                           */
+    float convergence_criteria;
+    float bounding_radius;
+    float threshold;            /* a bit is set where label * converged > threshold                               */
+    int32_t target_stride;      /* columns of a flat_masks row (the capacity)                                     */
+} vsrd_frame_masks_config;
+
+int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* config, const vsrd_frame_masks_config* masks,
+                         const float* camera_positions /* [V,3] */, const float* ray_directions /* [V*H*W,3] */,
+                         const float* u_coarse, const float* u_fine /* [H*W,S] recorded, or NULL: Philox keyed by pixel */,
+                         const float* targets /* flat_masks [V*H*W,stride] or NULL */, const int32_t* target_columns /* [N] or NULL */,
+                         uint8_t* mask_bits /* [N,H,ceil(W/8)] */, float* soft /* [H*W,N] or NULL */, int32_t* counts /* [N,3] or NULL */,
+                         const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
+
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]
  * -> weight_norm(Linear 256 -> 1617) = mlp_weights [N,1617].  weight_norm over dim 0: W[o,:] = g[o] v[o,:] / |v[o,:]|.

@@ -146,6 +146,22 @@ class FrameHeader(ctypes.Structure):
     ]
 
 
+class FrameMasksConfig(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_frame_masks_config (added within ABI 12): the view, the image size, the sphere-tracing constants and the
+    threshold of one vsrd_frame_masks call."""
+    _fields_ = [
+        ("view", ctypes.c_int32),
+        ("num_views", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("num_iterations", ctypes.c_int32),
+        ("convergence_criteria", ctypes.c_float),
+        ("bounding_radius", ctypes.c_float),
+        ("threshold", ctypes.c_float),
+        ("target_stride", ctypes.c_int32),
+    ]
+
+
 FRAME_HEADER_HAS_VIEWS = 0x10000
 MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFrameMaxViews)
 
@@ -237,6 +253,10 @@ SIGNATURES = {
     "vsrd_frame_labels": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                                            ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
                                            ctypes.c_void_p]),
+    # added within ABI 12: a view's dense predicted instance masks, bit-packed (+ soft values, pixel counts); header before the stream
+    "vsrd_frame_masks": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), ctypes.POINTER(FrameMasksConfig), c_float_p, c_float_p,
+                                          c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
     "vsrd_hypernetwork_forward": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_backward_step": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_float,

@@ -13,6 +13,7 @@
 #include "hypernetwork.h"
 #include "frame_ingest.h"
 #include "frame_labels.h"
+#include "frame_masks.h"
 #include "launch.h"
 
 namespace {
@@ -1235,6 +1236,54 @@ int32_t vsrd_frame_labels(const vsrd_frame_config* config, const float* raw_loca
     b.camera_corners = camera_corners; b.boxes_2d = boxes_2d; b.mean_iou = mean_iou;
     b.matched_gt = reinterpret_cast<long long*>(matched_gt); b.confidences = confidences;
     hipLaunchKernelGGL(frame_labels_kernel, dim3(frames.count), dim3(kFrameThreads), 0, static_cast<hipStream_t>(stream), a, b);
+    return launch_status();
+}
+
+int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* config, const vsrd_frame_masks_config* masks,
+                         const float* camera_positions, const float* ray_directions, const float* u_coarse, const float* u_fine,
+                         const float* targets, const int32_t* target_columns, uint8_t* mask_bits, float* soft, int32_t* counts,
+                         const vsrd_frame_header* frame_header, void* stream) {
+    if (!valid_field(field) || !config || !masks || !camera_positions || !ray_directions || !mask_bits) return VSRD_E_INVALID_ARGUMENT;
+    vsrd_render_config own = *config;
+    own.num_rays = 0;                                            // (ignored: the ray count is H W)
+    if (!valid_config(&own)) return VSRD_E_INVALID_ARGUMENT;     // (rejects ray_indices, target_columns and out_* inside the config)
+    if (masks->num_views < 1 || masks->num_views > kFrameMaxViews || masks->view < 0 || masks->view >= masks->num_views || masks->height < 1 ||
+        masks->width < 1 || masks->num_iterations < 0)
+        return VSRD_E_INVALID_ARGUMENT;
+    if ((targets != nullptr) != (counts != nullptr)) return VSRD_E_INVALID_ARGUMENT;
+    const int N = field->num_instances, S = config->num_samples;
+    if (targets != nullptr && masks->target_stride < (target_columns ? 1 : N)) return VSRD_E_INVALID_ARGUMENT;
+    const bool residual = field->mlp_weights != nullptr;
+    const int rounds = rounds_for(2 * S - 1);
+    if (rounds == 0 || (residual && rounds > 4)) return VSRD_E_INVALID_ARGUMENT;
+    const int64_t pixels = static_cast<int64_t>(masks->height) * masks->width;
+    if (pixels >= (int64_t{1} << 30)) return VSRD_E_UNSUPPORTED;
+    Frames frames;
+    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    const int num_runs = masks->height * ((masks->width + kWave - 1) / kWave);
+    Geometry g;
+    if (!plan(num_runs, static_cast<size_t>(hierarchical_lds_floats(S, N, residual)), &g)) return VSRD_E_UNSUPPORTED;
+    const FieldArgs f = field_args(field);
+    RenderArgs c = render_args(config);
+    c.sh.inv_t = f.inv_t;
+    c.frame_stride = frames.stride;
+    MaskArgs m;
+    m.view = masks->view; m.height = masks->height; m.width = masks->width; m.num_iterations = masks->num_iterations;
+    m.criteria = masks->convergence_criteria; m.bounding_radius = masks->bounding_radius; m.threshold = masks->threshold;
+    m.target_stride = masks->target_stride;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const FrameHeader* header = reinterpret_cast<const FrameHeader*>(frame_header);
+    int32_t status = VSRD_OK;
+    auto launch = [&](auto k, auto res) {
+        constexpr auto kernel = frame_masks_kernel<decltype(k)::value, decltype(res)::value>;
+        if ((status = opt_in_lds(kernel, g.lds_bytes)) != VSRD_OK) return;
+        if (counts != nullptr) hipLaunchKernelGGL(frame_masks_clear_kernel, dim3(frames.count), dim3(256), 0, s, counts, N, frames.stride, header);
+        hipLaunchKernelGGL(kernel, dim3(g.blocks, frames.count), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights, c, m, camera_positions,
+                           ray_directions, u_coarse, u_fine, targets, target_columns, mask_bits, soft, counts, header);
+    };
+    if (residual) for_rounds<1, 2, 4>(rounds, [&](auto k) { launch(k, std::true_type{}); });
+    else for_rounds<1, 2, 4, 8>(rounds, [&](auto k) { launch(k, std::false_type{}); });
+    if (status != VSRD_OK) return status;
     return launch_status();
 }
 

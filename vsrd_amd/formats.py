@@ -150,3 +150,34 @@ def save_frame_labels(folder, labels, class_name="car"):
                       lambda name, view=view: save_prediction(name, boxes_3d[view], boxes_2d[view], confidences, class_name))
     _atomic_write(os.path.join(folder, "labels", "view_00.txt"),
                   lambda name: save_kitti_labels(name, [class_name] * len(confidences), boxes_3d[0], boxes_2d[0], confidences.tolist()))
+
+
+def save_frame_masks(folder, masks, shape, view=0):
+    """One view's dense predicted instance masks as a file.  ``masks``: the dictionary of ``FrameOptimizer.masks()`` (host or device tensors)
+    -- inside [n,H,ceil(W/8)] uint8, counts [n,3], mask_iou [n], threshold; ``shape`` = (H, W).  Writes ``folder/masks/view_VV.npz`` with
+    `inside` (numpy.packbits along W, most significant bit first: the frame packs' mask format, frames.unpack_masks), `shape`, `threshold`,
+    `counts` and `mask_iou`, under a temporary name and renamed."""
+    import numpy as np
+    arrays = {key: torch.as_tensor(masks[key]).detach().cpu().numpy() for key in ("inside", "counts", "mask_iou")}
+    height, width = (int(x) for x in shape)
+    if arrays["inside"].ndim != 3 or arrays["inside"].shape[1:] != (height, (width + 7) // 8):
+        raise ValueError(f"inside of shape {arrays['inside'].shape} does not hold masks of {height} x {width} pixels")
+    path = os.path.join(folder, "masks", f"view_{int(view):02d}.npz")
+
+    def write(name):
+        with open(name, "wb") as file:         # (a file object: numpy appends no suffix to the temporary name)
+            np.savez(file, inside=arrays["inside"].astype(np.uint8), shape=np.asarray([height, width], dtype=np.int64),
+                     threshold=np.float32(masks.get("threshold", 0.5)), counts=arrays["counts"].astype(np.int32),
+                     mask_iou=arrays["mask_iou"].astype(np.float32))
+    _atomic_write(path, write)
+    return path
+
+
+def load_frame_masks(path):
+    """What save_frame_masks wrote (a folder: its masks/view_00.npz): a dictionary of numpy arrays, `shape` as a tuple (H, W) and `threshold` as a float."""
+    import numpy as np
+    if os.path.isdir(path):
+        path = os.path.join(path, "masks", "view_00.npz")
+    with np.load(path) as data:
+        return dict(inside=data["inside"], shape=tuple(int(x) for x in data["shape"]), threshold=float(data["threshold"]), counts=data["counts"],
+                    mask_iou=data["mask_iou"])

@@ -46,6 +46,14 @@ class FramePack:
         return int(self.view_offsets[1] - self.view_offsets[0])
 
 
+def unpack_masks(inside, width):
+    """Bit-packed masks [M,H,ceil(W/8)] (FramePack.inside; also what vsrd_frame_masks writes) as booleans [M,H,W]."""
+    inside = np.asarray(inside, dtype=np.uint8)
+    if inside.shape[-1] != (int(width) + 7) // 8:
+        raise ValueError(f"rows of {inside.shape[-1]} bytes do not hold {width} pixels")
+    return np.unpackbits(inside, axis=-1)[..., :int(width)].astype(bool)
+
+
 def _normalised(pack):
     height, width = (int(x) for x in np.asarray(pack.image_size).reshape(-1))
     return FramePack((height, width),

@@ -446,8 +446,10 @@ class _RenderWork:
             loss = float(record["loss"])
             payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
             labels = self._host_labels(loop.labels, [(frame, self.path_of(frame))]) if self.args.predictions else []
+            masks = self._host_masks(loop.masks, [(frame, self.path_of(frame))], [payload]) if self.args.masks else []
         loop.close()
         self._write_labels(labels)
+        self._write_masks(masks)
         return loss, payload
 
     def _host_labels(self, device_call, frames):
@@ -472,6 +474,33 @@ class _RenderWork:
             formats.save_frame_labels(folder, labels)
         if pending:
             self.phase_seconds["labels_write"] += time.perf_counter() - t0
+
+    def _host_masks(self, device_call, frames, payloads):
+        """--masks, inside the section that copies the checkpoint payloads: the ONE vsrd_frame_masks call of a group of frames (`device_call`
+        -> a dictionary or a list of them: the target view's predicted masks), its copies to the host -> [(frame folder, masks)] for
+        `_write_masks`, and every frame's checkpoint metric: mask_iou, the mean over its instances."""
+        import time
+        from . import formats
+        t0 = time.perf_counter()
+        masks = device_call()
+        masks = masks if isinstance(masks, list) else [masks]
+        pending = []
+        for (_, path), entry, payload in zip(frames, masks, payloads):
+            host = formats.to_host({key: value for key, value in entry.items() if key != "soft"})
+            payload["metrics"] = dict(payload.get("metrics") or {}, mask_iou=float(host["mask_iou"].mean()))
+            pending.append((os.path.dirname(path), host))
+        self.phase_seconds["masks"] += time.perf_counter() - t0
+        return pending
+
+    def _write_masks(self, pending):
+        """masks/view_00.npz of `_host_masks`' frames -- BEFORE their checkpoints, like the label files."""
+        import time
+        from . import formats
+        t0 = time.perf_counter()
+        for folder, masks in pending:
+            formats.save_frame_masks(folder, masks, masks["shape"])
+        if pending:
+            self.phase_seconds["masks_write"] += time.perf_counter() - t0
 
     def run(self):
         from . import formats, optimization
@@ -502,14 +531,20 @@ class _RenderWork:
                     health(frame, slot)
                     payload = formats.checkpoint_payload(slot, step=args.num_steps - 1, metrics={}, host=True)
                     labels = self._host_labels(slot.labels, [(frame, self.path_of(frame))]) if args.predictions else []
+                    masks = self._host_masks(slot.masks, [(frame, self.path_of(frame))], [payload]) if args.masks else []
                 self._write_labels(labels)
+                self._write_masks(masks)
                 return payload
             finally:
                 if slot is not None:
                     self.slots.put(slot)
 
-        if args.predictions:               # (the batch path keeps its own clock, with these two keys added)
-            self.phase_seconds = dict(labels=0.0, labels_write=0.0)
+        if args.predictions or args.masks:               # (the batch path keeps its own clock, with these keys added)
+            self.phase_seconds = {}
+            if args.predictions:
+                self.phase_seconds.update(labels=0.0, labels_write=0.0)
+            if args.masks:
+                self.phase_seconds.update(masks=0.0, masks_write=0.0)
         self._have_slots = not args.fresh_loops and not self.slots.empty()
         if self.batch is not None:
             done = self._run_batches(losses, fallbacks, health)
@@ -532,6 +567,8 @@ class _RenderWork:
         clock = self.phase_seconds = dict(inputs=0.0, reset=0.0, steps=0.0, checkpoint_copy=0.0, checkpoint_write=0.0)
         if args.predictions:
             clock.update(labels=0.0, labels_write=0.0)
+        if args.masks:
+            clock.update(masks=0.0, masks_write=0.0)
         while True:
             group = pending_frames(self.queue.take(args.frame_batch), self.path_of)
             if not group:
@@ -560,7 +597,10 @@ class _RenderWork:
                     t2 = time.perf_counter()
                     # --predictions: ONE vsrd_frame_labels call for the group, copied to the host with the payloads
                     labels = self._host_labels(lambda: batch.labels(active=len(rows)), rows) if args.predictions else []
+                    # --masks: ONE vsrd_frame_masks call for the group; every payload gets its frame's mask_iou
+                    masks = self._host_masks(lambda: batch.masks(active=len(rows)), rows, payloads) if args.masks else []
                 self._write_labels(labels)
+                self._write_masks(masks)
                 t3 = time.perf_counter()
                 for (frame, path), payload in zip(rows, payloads):
                     formats.atomic_torch_save(payload, path)
@@ -720,6 +760,11 @@ def main(argv=None):
                              "(tools/kitti_360/make_predictions.py) and labels/view_00.txt, the target view's KITTI label lines "
                              "(convert_predictions.py) -- vsrd_frame_labels, one launch per group of frames; with --frames-dir an end-to-end "
                              "auto-labelling run.  Not with --selftest")
+    parser.add_argument("--masks", action="store_true",
+                        help="after a frame's steps, render the target view's dense predicted instance masks (scripts/main.py:1011-1061: volume_masks "
+                             "x surface_masks) -- vsrd_frame_masks, one launch per group of frames -- write them bit-packed to masks/view_00.npz next "
+                             "to the frame's checkpoint and store their mean IoU against the masks the frame was fitted to as the checkpoint's "
+                             "metric `mask_iou` (tools/select_model.py --metrics mask_iou --maximum).  Needs --out; not with --selftest")
     parser.add_argument("--ranks-share-gpu", action="store_true",
                         help="TEST ONLY: every rank on cuda:0, gloo rendezvous (RCCL refuses two ranks on one device); the line says so")
     parser.add_argument("--fresh-loops", action="store_true",
@@ -745,6 +790,10 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.predictions and args.selftest:
         raise SystemExit("--predictions writes the labels of optimised frames; --selftest optimises none: drop one of --selftest, --predictions")
+    if args.masks and args.selftest:
+        raise SystemExit("--masks renders the masks of optimised frames; --selftest optimises none: drop one of --selftest, --masks")
+    if args.masks and not args.out:
+        raise SystemExit("--masks writes masks/view_00.npz and a mask_iou metric next to every frame's checkpoint: it needs --out")
     if args.frames_dir:
         given = [flag for flag, value in (("--views", args.views), ("--instances", args.instances), ("--height", args.height), ("--width", args.width)) if value is not None]
         if given:
@@ -936,7 +985,8 @@ def _rank_main(args):
                 # frames a slot could not take (their importance weights do not suit the sampling table its graphs draw from: a loop of their own, race sampler)
                 # where a batched rank's time went, in seconds over its frames: building inputs (dynamic queue only), resetting rows, the steps, checkpoints
                 "phase_seconds": [r.get("phase_seconds") for r in gathered],
-                **({"predictions": True} if args.predictions else {}),      # (--predictions: label files next to every checkpoint)
+                **({"predictions": True} if args.predictions else {}),
+                **({"masks": True} if args.masks else {}),      # (--predictions: label files next to every checkpoint)
                 "frames_outside_slots": sorted(f for r in gathered for f in r["frames_outside_slots"]),
                 "unsuitable_founders": sorted(f for r in gathered for f in r["unsuitable_founders"]),
                 # frames in which some ray draw ran out of picks / overflowed (read at the end of each frame; RuntimeWarning on stderr)

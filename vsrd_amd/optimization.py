@@ -227,6 +227,10 @@ class OptimizationConfig:
     # frames its rank optimised before).  An integer: the generator is seeded with it right before the draw -- a frame's result then depends on
     # the frame alone, not on the rank, process or slot that runs it (vsrd_amd.launcher passes seed and frame number).
     init_seed: Optional[int] = None
+    # sphere tracing of the dense predicted masks (FrameOptimizer.masks; scripts/main.py:1029-1041 calls sphere_tracing with these)
+    surface_num_iterations: int = 1000
+    surface_convergence_criteria: float = 0.01
+    surface_bounding_radius: float = 100.0
 
 
 class FrameArena:
@@ -326,6 +330,14 @@ def hypernetwork_tensors(hyper_distance_field, embeddings, optimizer, lr_gamma, 
     return net
 
 
+def mask_iou(counts):
+    """inter / (pred + target - inter) of counts [...,3] = (#pred, #target, #pred and target), 0 where the union is empty."""
+    counts = torch.as_tensor(counts)
+    inter = counts[..., 2].to(torch.float32)
+    union = (counts[..., 0] + counts[..., 1] - counts[..., 2]).to(torch.float32)
+    return torch.where(union > 0, inter / union.clamp(min=1.0), torch.zeros_like(union))
+
+
 class FrameOptimizer:
     """``graph=True``: the step is captured in a hipGraph and replayed.  ``fused_glue`` (default: on in graph mode): everything around
     the render launch that concerns the boxes -- decode, projection, matching, projection losses and their gradients, schedules,
@@ -412,6 +424,7 @@ class FrameOptimizer:
             self.workspace.reserve(self.device, self.capacity, residual=True, step_shape=(config.num_samples, config.num_rays))
         self._graphs = {}
         self._labels = None
+        self._masks = None
         self._capture_stream = None
         self._eager_graph_steps = {}
         self.pixels_per_view = H * W
@@ -1228,6 +1241,74 @@ class FrameOptimizer:
         self._launch_labels()
         return self._label_views()
 
+    # ---- dense predicted masks (csrc/frame_masks.h) --------------------------------------------------------------------------
+    def _mask_state(self):
+        """What vsrd_frame_masks writes, created at first use -- in the frame's row when there is one (a FrameBatch creates them in every
+        row at once: equal offsets): the bit-packed masks, the soft values and the pixel counts, laid out for the capacity."""
+        if self._masks is not None:
+            return self._masks
+        if not self.fused_glue:
+            raise RuntimeError("masks() renders the field block the fused glue keeps on the device (graph=True)")
+        H, W = (int(x) for x in self.inputs.image_size)
+        N = self.capacity
+        with _capture_lock, torch.no_grad():
+            new = self._new
+            self._masks = dict(inside=new((N, H, (W + 7) // 8), torch.uint8, fill=0), soft=new((H * W, N), fill=0.0),
+                               counts=new((N, 3), torch.int32, fill=0))
+        return self._masks
+
+    def _launch_masks(self, frames=None, view=0, threshold=0.5, soft=False):
+        """ONE vsrd_frame_masks call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
+        if self.step_index < 1:
+            raise RuntimeError("masks() renders the field of the last step: no step has run since the loop was built or reset()")
+        cfg, b, state = self.config, self._glue, self._mask_state()
+        H, W = (int(x) for x in self.inputs.image_size)
+        from .rendering import renderers
+        # the field the last step rendered: its instance block, and in the residual phase its (centred) MLP weights, exact-fp32 products
+        residual = self.step_index - 1 >= cfg.warmup_steps
+        flags = renderers._base_flags() & ~_lib.FLAG_MLP_SPLIT_BF16
+        if residual:
+            if not self.fused_hypernetwork:
+                raise RuntimeError("masks() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
+            flags |= _lib.FLAG_MLP_WEIGHTS_CENTRED
+        elif cfg.skip_exact_misses:
+            flags |= _lib.FLAG_SKIP_EXACT_MISSES
+        field = _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
+        config = _lib.make_config(0, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, seed=cfg.seed, stream_offset=self.step_tensor, flags=flags,
+                                  schedule=self.schedule, frames=frames)
+        masks = _lib.FrameMasksConfig(int(view), self.view_capacity, H, W, int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria),
+                                      float(cfg.surface_bounding_radius), float(threshold), self.capacity)
+        header = b.get("header")
+        with _capture_lock:
+            _lib.check(_lib.load().vsrd_frame_masks(
+                field, config, masks, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None, _lib.ptr(b["masks"]),
+                b["target_columns"].data_ptr(), state["inside"].data_ptr(), _lib.ptr(state["soft"]) if soft else None, state["counts"].data_ptr(),
+                None if header is None else header.data_ptr(), _lib.stream()))
+
+    def _mask_views(self, threshold, soft):
+        state, n = self._masks, self.num_instances
+        H, W = (int(x) for x in self.inputs.image_size)
+        counts = state["counts"][:n]
+        result = dict(inside=state["inside"][:n], counts=counts, mask_iou=mask_iou(counts), threshold=float(threshold), shape=(H, W))
+        if soft:
+            result["soft"] = state["soft"].view(H, W, self.capacity)[:, :, :n]
+        return result
+
+    def masks(self, view=0, threshold=0.5, soft=False):
+        """The frame's dense predicted instance masks of view ``view`` (0: the target view) -- what the reference renders every
+        ``image_intervals`` steps (scripts/main.py:1011-1061: volume_masks * surface_masks) -- by one vsrd_frame_masks launch on the current
+        stream, no host synchronisation.  They render the field of the loop's `instances` (and, in the residual phase, MLP weight) buffers at
+        the loop's `schedule`: the field the LAST STEP rendered, built from the parameters that step started from -- which is what the
+        reference logs (main.py:1013 uses the fields built at the top of the step), not the parameters after that step's Adam update.
+        RuntimeError when no step has run since construction or ``reset()``.  A dictionary of device tensors sliced to the frame's own n
+        instances: inside [n,H,ceil(W/8)] uint8 (numpy.packbits along W, the frame packs' mask format), counts [n,3] int32 (#pred,
+        #target, #both against the soft masks the frame was fitted to, through the last step's assignment), mask_iou [n], and with
+        ``soft`` the values themselves, soft [H,W,n].  They are views of buffers the next call overwrites (formats.save_frame_masks)."""
+        if not 0 <= int(view) < self.num_views:
+            raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
+        self._launch_masks(view=view, threshold=threshold, soft=soft)
+        return self._mask_views(threshold, soft)
+
     def close(self):
         """Drop the captured graphs and the scratch buffers (also happens when the optimizer is garbage-collected).  Once per frame
         this is also where the device ray sampler's sticky overflow flag is read back (a host synchronisation, so not per step): a
@@ -1408,6 +1489,7 @@ class FrameBatch:
         total += lib.vsrd_ray_table_bytes(pixels)
         total += workspace + lib.vsrd_hypernetwork_workspace_bytes(N) + lib.vsrd_frame_scratch_bytes(V, N)
         total += 4 * (3 * N * _lib.MLP_WEIGHTS + 64 * N + 128 * V) + 16 * int(config.num_rays)          # the glue's tables
+        total += N * H * ((W + 7) // 8) + 4 * H * W * N + 12 * N     # masks(): bit-packed masks, soft values, counts
         return total + (4 << 20)                                     # 256-byte alignment of ~400 buffers, step counters, rates, slack
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
@@ -1451,6 +1533,23 @@ class FrameBatch:
             raise RuntimeError("the frames of a batch laid their label buffers out differently: frame batches need equal offsets in every row")
         members[0]._launch_labels(frames=(active, self.arena.stride))
         return [m._label_views() for m in members]
+
+    def masks(self, active=None, view=0, threshold=0.5, soft=False):
+        """The dense predicted masks of the first ``active`` frames (``FrameOptimizer.masks``) by ONE vsrd_frame_masks call for all of
+        them: a list of dictionaries of device tensors, each sliced to its frame's own instance count.  ``view`` must exist in every
+        active frame."""
+        active, members = self._members(active)
+        if any(not 0 <= int(view) < m.num_views for m in members):
+            raise ValueError(f"view {view} does not exist in every active frame")
+        if any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
+            raise RuntimeError("masks() renders the field of the frames' last step: no step has run since a frame's reset(), or the frames "
+                               "are not in step")
+        for m in self.frames:                      # (first use: the output buffers of EVERY row, so that the rows keep equal offsets)
+            m._mask_state()
+        if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
+            raise RuntimeError("the frames of a batch laid their mask buffers out differently: frame batches need equal offsets in every row")
+        members[0]._launch_masks(frames=(active, self.arena.stride), view=view, threshold=threshold, soft=soft)
+        return [m._mask_views(threshold, soft) for m in members]
 
     def _phase(self, active):
         _, members = self._members(active)
