@@ -523,3 +523,90 @@ def test_initial_draw_runs_on_one_thread_and_draws_the_same_values():
     assert torch.get_num_threads() == before
     for a, b in zip(single, draw()):
         assert torch.equal(a, b)
+
+
+def test_buffer_placement_in_a_row_in_a_slot_and_alone():
+    """optimization._place, the one rule for where a loop's buffer lives.  In a row of an arena: a zero-filled buffer of the full shape in the
+    row, the tensor in its leading corner, at the same offset of every row.  No row, private (a frame slot): a buffer of its own.  Neither:
+    the tensor itself when it already has the shape, dtype and contiguity (a loop of one frame aliases the caller's soft masks), a converted
+    copy otherwise."""
+    from vsrd_amd import optimization
+    tensor = torch.arange(1.0, 13.0, dtype=torch.float64).reshape(2, 6)[:, ::2]            # [2, 3], float64, not contiguous, no zeros
+    flags = torch.tensor([[1, 0, 1], [1, 1, 1]], dtype=torch.bool)
+    arena = optimization.FrameArena(3, 10_000, "cpu")
+    arena.buffer.fill_(0xFF)                 # (fresh host memory is usually zero already: the zeros below must be _place's own)
+    low, high = arena.buffer.data_ptr(), arena.buffer.data_ptr() + arena.buffer.numel()
+    placed = []
+    for row in arena.rows:
+        full = optimization._place(tensor, (4, 5), torch.float32, row)
+        bits = optimization._place(flags, (4, 5), torch.uint8, row)
+        same = optimization._place(tensor, (2, 3), torch.float32, row, private=True)      # (a row's loop is persistent: the row decides)
+        placed.append((full, bits, same))
+        assert full.shape == (4, 5) and full.dtype == torch.float32 and full.is_contiguous() and bits.dtype == torch.uint8
+        assert torch.equal(full[:2, :3], tensor.to(torch.float32)) and torch.equal(bits[:2, :3], flags.to(torch.uint8)) and torch.equal(same, tensor.to(torch.float32))
+        outside = torch.ones(4, 5, dtype=torch.bool)
+        outside[:2, :3] = False
+        assert bool((full[outside] == 0).all()) and bool((bits[outside] == 0).all())
+        assert all(low <= t.data_ptr() and t.data_ptr() + t.numel() * t.element_size() <= high for t in (full, bits, same))
+    assert arena.rows[0].layout == arena.rows[1].layout == arena.rows[2].layout and len(arena.rows[0].layout) == 3
+    for k in range(3):
+        assert placed[1][k].data_ptr() - placed[0][k].data_ptr() == arena.stride and placed[2][k].data_ptr() - placed[0][k].data_ptr() == 2 * arena.stride
+    placed[1][0].fill_(9.0)      # rows do not overlap
+    assert float(placed[0][0].max()) == float(tensor.max()) == float(placed[2][0].max())
+    with pytest.raises(RuntimeError, match="exhausted"):
+        optimization._place(tensor, (100, 100), torch.float32, arena.rows[0])
+
+    # a frame slot: a buffer of its own, also for a tensor that would do as it is
+    plain = torch.arange(6, dtype=torch.float32).reshape(2, 3)
+    own = optimization._place(plain, (2, 3), torch.float32, private=True)
+    assert own.data_ptr() != plain.data_ptr() and torch.equal(own, plain)
+    own.fill_(-1.0)
+    assert torch.equal(plain, torch.arange(6, dtype=torch.float32).reshape(2, 3))
+    larger = optimization._place(plain, (3, 4), torch.float32, private=True)
+    assert larger.shape == (3, 4) and torch.equal(larger[:2, :3], plain) and float(larger[2:].abs().sum() + larger[:, 3:].abs().sum()) == 0.0
+
+    # a loop of one frame: the caller's tensor itself, or a converted copy
+    assert optimization._place(plain, (2, 3), torch.float32).data_ptr() == plain.data_ptr()
+    for other in (plain.double(), torch.arange(12, dtype=torch.float32).reshape(2, 6)[:, ::2]):
+        converted = optimization._place(other, (2, 3), torch.float32)
+        assert converted.data_ptr() != other.data_ptr() and converted.dtype == torch.float32 and converted.is_contiguous()
+        assert torch.equal(converted, other.to(torch.float32))
+    with pytest.raises(ValueError):
+        optimization._place(plain, (3, 4), torch.float32)          # (nothing to lay out for: the capacities are the frame's own counts)
+
+
+def test_reset_admits_the_loops_shape_or_up_to_its_capacities():
+    """optimization._incoming_shape, reset()'s admission check: a frame pack or a FrameInputs of the loop's image size; under a header 1..capacity
+    views and instances, without one exactly the loop's own counts; each refusal a ValueError that names the axis and the limit."""
+    from vsrd_amd import frames, optimization
+
+    def inputs(v, h, w, n):
+        return optimization.FrameInputs((h, w), torch.zeros(v, 3, 3), torch.zeros(v, 4, 4), torch.zeros(v, h, w, n), torch.zeros(v, n, 2, 2),
+                                        torch.zeros(v, n, dtype=torch.bool))
+
+    def pack(v, h, w, n):
+        import numpy as np
+        entries = v * n
+        return frames.FramePack((h, w), np.zeros((v, 3, 3), np.float32), np.zeros((v, 4, 4), np.float32), np.arange(v + 1, dtype=np.int64) * n,
+                                np.tile(np.arange(n, dtype=np.int64), v), np.zeros(entries + 1, np.int64), np.zeros((0, 2), np.int32),
+                                np.zeros((entries, h, (w + 7) // 8), np.uint8))
+
+    loop, capacities = (2, 4, 6, 3), (3, 5)
+    for make in (inputs, pack):
+        for v in (1, 2, 3):
+            for n in (1, 3, 5):
+                assert optimization._incoming_shape(make(v, 4, 6, n), loop, capacities) == (v, 4, 6, n)
+        for refused, word in (((0, 4, 6, 3), r"1\.\.3 views, got 0"), ((4, 4, 6, 3), r"1\.\.3 views, got 4"), ((2, 4, 6, 0), r"1\.\.5 instances, got 0"),
+                              ((2, 4, 6, 6), r"1\.\.5 instances, got 6"), ((2, 4, 8, 3), "image size"), ((2, 5, 6, 3), "image size")):
+            with pytest.raises(ValueError, match=word):
+                optimization._incoming_shape(make(*refused), loop, capacities)
+        # without a header: the loop's own shape and nothing else
+        assert optimization._incoming_shape(make(*loop), loop) == loop
+        for refused, word in (((1, 4, 6, 3), r"2\.\.2 views, got 1"), ((3, 4, 6, 3), r"2\.\.2 views, got 3"), ((2, 4, 6, 2), r"3\.\.3 instances, got 2"),
+                              ((2, 4, 6, 4), r"3\.\.3 instances, got 4"), ((2, 4, 8, 3), "image size")):
+            with pytest.raises(ValueError, match=word):
+                optimization._incoming_shape(make(*refused), loop)
+    wrong = inputs(2, 4, 6, 3)
+    wrong.image_size = (4, 8)            # a FrameInputs whose image_size is not its soft masks'
+    with pytest.raises(ValueError, match="image_size"):
+        optimization._incoming_shape(wrong, loop, capacities)

@@ -277,9 +277,7 @@ class FrameRow:
 
     def adopt(self, tensor):
         """A row-resident copy of `tensor` (same shape, dtype and values)."""
-        view = self.new(tensor.shape, tensor.dtype)
-        view.copy_(tensor)
-        return view
+        return _place(tensor, tensor.shape, tensor.dtype, self)
 
 
 def _instance_prefix(tensor, count):
@@ -287,11 +285,72 @@ def _instance_prefix(tensor, count):
     return tensor.as_strided((tensor.shape[0], int(count), *tensor.shape[2:]), tensor.stride(), tensor.storage_offset())
 
 
+def _place(tensor, shape, dtype, row=None, private=False):
+    """The ONE rule for where a loop's buffer lives: `tensor` as a `dtype` buffer of the FULL `shape` (views along dimension 0, instances
+    behind them: the kernels stride by the capacities), the tensor in its leading corner and zeros around it.  `row` (a FrameRow): the
+    buffer lies in the row.  No row, `private` (a frame slot): a buffer of its own -- a slot OWNS what reset() overwrites; float32
+    contiguous inputs would otherwise be these very tensors: the caller's, and every other slot's built from the same frame.  Neither:
+    the tensor ITSELF where it already has the shape, dtype and contiguity (a loop of one frame aliases the caller's soft masks --
+    V x 376 x 1408 x N floats at the reference's size), a converted copy otherwise."""
+    shape = tuple(int(x) for x in shape)
+    if row is None and not private:
+        if tuple(tensor.shape) != shape:
+            raise ValueError(f"a buffer of shape {shape} cannot alias a tensor of shape {tuple(tensor.shape)}")
+        return tensor.to(dtype).contiguous()
+    full = row.new(shape, dtype, fill=0) if row is not None else torch.zeros(shape, dtype=dtype, device=tensor.device)
+    corner = full
+    for dim, size in enumerate(tensor.shape):
+        corner = corner.narrow(dim, 0, size)
+    corner.copy_(tensor)
+    return full
+
+
+def _incoming_shape(inputs, shape, capacities=None):
+    """(V, H, W, N) of the frame -- a frames.FramePack or a FrameInputs -- that a loop of `shape` = (V, H, W, N) is asked to take over
+    (FrameOptimizer.reset), or ValueError: the image size is the loop's; the counts are the loop's own, or with `capacities` =
+    (view capacity, instance capacity) -- a row with a header -- anything from 1 up to them."""
+    if isinstance(inputs, frames.FramePack):
+        # (a pack counts its instances in its target view: without views it has none)
+        incoming = (int(inputs.num_views), *[int(x) for x in inputs.image_size], int(inputs.num_instances) if inputs.num_views else 0)
+    else:
+        incoming = tuple(int(x) for x in inputs.soft_masks.shape)
+        if tuple(int(x) for x in inputs.image_size) != incoming[1:3]:
+            raise ValueError(f"image_size {tuple(inputs.image_size)} of soft masks of shape {incoming}")
+    shape = tuple(int(x) for x in shape)
+    if incoming[1:3] != shape[1:3]:
+        raise ValueError(f"this loop serves frames of image size {shape[1:3]}, got {incoming[1:3]}")
+    for k, (axis, name) in enumerate(((0, "views"), (3, "instances"))):
+        low, high = (shape[axis], shape[axis]) if capacities is None else (1, int(capacities[k]))
+        if not low <= incoming[axis] <= high:
+            raise ValueError(f"this loop serves frames of {low}..{high} {name}, got {incoming[axis]}")
+    return incoming
+
+
+def _initial_rates(config):
+    """The initial learning rates of the optimiser's five groups (locations, dimensions, orientations, embeddings, hypernetwork)."""
+    return [config.learning_rate] * 3 + [config.embedding_learning_rate, config.hypernetwork_learning_rate]
+
+
+def _fresh_modules(num_instances):
+    """A frame's modules as scripts/main.py:106-199 builds them per frame: the detector and (config.json:143-156) the per-instance residual
+    MLP 48->16->16->16->16->1 generated from 256-d embeddings.  Draws from torch's host generator (unless built on the meta device)."""
+    return models.BoxParameters3D(1, num_instances), models.HyperDistanceField(48, [16, 16, 16, 16], 256, [256, 256, 256, 256])
+
+
+def _indexed(device):
+    """`device` with its index spelled out (the scratch buffers are keyed by device: one spelling of it)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 def adam_state_tensors(optimizer, parameter, group, row=None, capacity=None):
     """`parameter`'s torch.optim.Adam(capturable=True) state as the C ABI's pointer block, created now if the optimiser has not
     stepped yet (torch creates it lazily): the kernels update the moments, the counter and the parameter in place.  `row`: the frame's
     row of a batch's arena (FrameRow) -- the state is created there.  `capacity`: the parameter is [1, N, ...] and its moments are the
-    first N instances of [1, capacity, ...] buffers (a mixed batch's row, FrameBatch(max_instances=...))."""
+    first N instances of [1, capacity, ...] buffers (every row of a FrameBatch: FrameOptimizer.rebind passes the loop's capacity, which is N
+    itself unless the batch has max_instances -- the same bytes at the same addresses as buffers of the parameter's own shape)."""
     state = optimizer.state[parameter]
     if not state:
         if row is not None:
@@ -362,9 +421,8 @@ class FrameOptimizer:
         self._graphs = {}
         self.persistent = bool(persistent)
         self._row = row
-        self._capacity = None if capacity is None else int(capacity)
-        self._view_capacity = None if view_capacity is None else int(view_capacity)
-        if (self._capacity is not None or self._view_capacity is not None) and row is None:
+        self._headed = capacity is not None or view_capacity is not None        # (a row with a header)
+        if self._headed and row is None:
             raise ValueError("a capacity belongs to a frame of a FrameBatch (row=...)")
         if row is not None and not (graph and persistent and fused_glue in (None, True)):
             raise ValueError("a frame of a batch is a persistent graph-mode loop with the fused glue")
@@ -372,23 +430,19 @@ class FrameOptimizer:
         # nonzero -- host synchronisations that, next to ANOTHER frame's capture, fail now and then or break that capture ("capturing
         # stream has unjoined work" in the other thread: one 36-frame run in fourteen)
         with _capture_lock:
-            self._construct(inputs, config, device, graph, fused_glue)
+            self._construct(inputs, config, device, graph, fused_glue, capacity, view_capacity)
 
-    def _construct(self, inputs, config, device, graph, fused_glue):
-        self.inputs, self.config, self.device = inputs, config, torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:      # the scratch buffers are keyed by device: one spelling of it
-            self.device = torch.device("cuda", torch.cuda.current_device())
+    def _construct(self, inputs, config, device, graph, fused_glue, capacity, view_capacity):
+        self.inputs, self.config, self.device = inputs, config, _indexed(device)
         self.graph = bool(graph)
         self.fused_glue = self.graph if fused_glue is None else bool(fused_glue)
         if self.fused_glue and not self.graph:
             raise ValueError("fused_glue keeps the learning rates and Adam's counters on the device: it needs graph=True")
         V, H, W, N = inputs.soft_masks.shape
         self.num_views, self.num_instances = V, N
-        if self._capacity is not None or self._view_capacity is not None:       # a row with a header: laid out for both capacities
-            self._capacity = N if self._capacity is None else self._capacity
-            self._view_capacity = V if self._view_capacity is None else self._view_capacity
-        self.capacity = N if self._capacity is None else self._capacity
-        self.view_capacity = V if self._view_capacity is None else self._view_capacity
+        # every loop lays its per-view and per-instance buffers out for (view_capacity, capacity): the frame's own counts unless the row has a header
+        self.capacity = N if capacity is None else int(capacity)
+        self.view_capacity = V if view_capacity is None else int(view_capacity)
         if not 1 <= N <= self.capacity:
             raise ValueError(f"a row of capacity {self.capacity} serves frames of 1..{self.capacity} instances, got {N}")
         if not 1 <= V <= self.view_capacity <= _lib.MAX_VIEWS:
@@ -396,21 +450,16 @@ class FrameOptimizer:
         with _initial_draw:
             if config.init_seed is not None:
                 torch.default_generator.manual_seed(int(config.init_seed))      # (the CPU generator: the modules are built on the host; the device generators, which captured graphs register, stay untouched)
-            detector = models.BoxParameters3D(1, N)
-            # config.json:143-156: per-instance residual MLP 48->16->16->16->16->1 generated from 256-d embeddings
-            field = models.HyperDistanceField(48, [16, 16, 16, 16], 256, [256, 256, 256, 256])
+            detector, field = _fresh_modules(N)
         self.detector, self.hyper_distance_field = detector.to(self.device), field.to(self.device)
         if self._row is not None:          # the parameters move into the frame's row (module order: the same in every frame of the batch)
-            per_instance = set(self.detector.parameters()) if self._capacity is not None else set()     # ([1, N, ...]: laid out for the capacity)
-            for p in [*self.detector.parameters(), *self.hyper_distance_field.parameters()]:
-                p.data = self._adopt_instances(p.data, 1, prefix=True) if p in per_instance else self._row.adopt(p.data)
+            for p in self.detector.parameters():           # ([1, N, ...]: the first N instances of a buffer laid out for the capacity)
+                p.data = _instance_prefix(self._place(p.data, (1, self.capacity, *p.shape[2:]), p.dtype), N)
+            for p in self.hyper_distance_field.parameters():
+                p.data = self._place(p.data, p.shape, p.dtype)
         def rate(value):   # graph mode: learning rates are device tensors decayed in place inside the captured step
-            if self._row is not None:
-                return self._row.new((), torch.float32, fill=value)
-            return torch.tensor(value, dtype=torch.float32, device=self.device) if self.graph else value
-        groups = [dict(params=[p], lr=rate(config.learning_rate)) for p in (self.detector.locations, self.detector.dimensions, self.detector.orientations)]
-        groups.append(dict(params=[self.detector.embeddings], lr=rate(config.embedding_learning_rate)))
-        groups.append(dict(params=list(self.hyper_distance_field.parameters()), lr=rate(config.hypernetwork_learning_rate)))
+            return self._new((), fill=value) if self.graph else value
+        groups = [dict(params=params, lr=rate(value)) for params, value in zip(self._module_parameters(), _initial_rates(config))]
         self.optimizer = torch.optim.Adam(groups, lr=rate(config.learning_rate), capturable=self.graph)
         self.scheduler = None if self.graph else torch.optim.lr_scheduler.ExponentialLR(self.optimizer, gamma=config.lr_gamma)
         # per-step scalars on the device (graph mode): step index = Philox counter, (temperature, std, cosine_ratio)
@@ -441,32 +490,21 @@ class FrameOptimizer:
             return torch.empty(shape, dtype=dtype, device=self.device)
         return torch.full(shape if isinstance(shape, (tuple, list)) else (shape,), fill, dtype=dtype, device=self.device)
 
-    def _own(self, tensor):
-        """`tensor` as a buffer of this loop: a copy in the frame's row of the batch's arena, or the tensor itself."""
-        return tensor if self._row is None else self._row.adopt(tensor)
+    def _place(self, tensor, shape, dtype=torch.float32):
+        """`tensor` as this loop's buffer of the full `shape` (module-level `_place`): in the frame's row, a slot's own, or the tensor itself."""
+        return _place(tensor.to(self.device), shape, dtype, self._row, self.persistent)
 
-    def _adopt_instances(self, tensor, dim, prefix=False):
-        """A mixed batch's row: `tensor` (N instances along `dim`) copied into the first N of a buffer of `capacity` instances.  Returns
-        the FULL buffer (the kernels stride by the capacity), or with `prefix` the [1, N, ...] view of a [1, capacity, ...] parameter."""
-        shape = list(tensor.shape)
-        shape[dim] = self.capacity
-        full = self._row.new(shape, tensor.dtype, fill=0)
-        full.narrow(dim, 0, tensor.shape[dim]).copy_(tensor)
-        return _instance_prefix(full, tensor.shape[dim]) if prefix else full
-
-    def _adopt_prefix(self, tensor, shape):
-        """A row laid out for capacities: `tensor` copied into the leading corner of a zero-filled buffer of `shape` in the row (views
-        along dimension 0, instances behind them).  Returns the FULL buffer: the kernels stride by the capacities."""
-        full = self._row.new(list(shape), tensor.dtype, fill=0)
-        corner = full
-        for dim, size in enumerate(tensor.shape):
-            corner = corner.narrow(dim, 0, size)
-        corner.copy_(tensor)
-        return full
+    def _input_tables(self):
+        """The frame's cameras, ground-truth boxes and visibility as the kernels read them, laid out for the capacities."""
+        inp, V, N, views = self.inputs, self.num_views, self.num_instances, self.view_capacity
+        return dict(extrinsics=self._place(inp.extrinsic_matrices.reshape(V, 16), (views, 16)),
+                    intrinsics=self._place(inp.intrinsic_matrices.reshape(V, 9), (views, 9)),
+                    gt_boxes=self._place(inp.boxes_2d.reshape(V, N, 4), (views, self.capacity, 4)),
+                    visible=self._place(inp.visible_masks, (views, self.capacity), torch.uint8))
 
     def _set_views(self, V):
-        """A row laid out for a view capacity: the loop's per-view tensors are the first V views of the row's buffers (`self._full`) --
-        view-major, so contiguous prefixes at the buffers' own addresses, which is what the kernels and the captured graphs hold."""
+        """The loop's per-view tensors are the first V views of its buffers (`self._full`: laid out for the view capacity) -- view-major,
+        so contiguous prefixes at the buffers' own addresses, which is what the kernels and the captured graphs hold."""
         full, pixels = self._full, V * self.pixels_per_view
         self.num_views = V
         self.camera_positions, self.ray_directions = full["camera_positions"][:V], full["ray_directions"][:pixels]
@@ -487,24 +525,15 @@ class FrameOptimizer:
     def _prepare_rays(self, inputs, config, H, W, N):
         # rays of every view, once per frame (main.py:267-296)
         cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
-        if self._capacity is not None:
-            # a row with a header: [view capacity x H W, instance capacity] soft masks (the kernels read the targets with target_stride =
-            # capacity) and every other per-view buffer laid out for the view capacity; the frame fills their leading corners
-            views, pixels = self.view_capacity, self.view_capacity * H * W
-            self._full = dict(camera_positions=self._adopt_prefix(cam, (views, 3)), ray_directions=self._adopt_prefix(dirs.reshape(-1, 3), (pixels, 3)),
-                              flat_masks=self._adopt_prefix(inputs.soft_masks.reshape(-1, N).to(torch.float32), (pixels, self.capacity)),
-                              sampling_weights=self._row.new(pixels, torch.float32, fill=0))
-            self._set_views(self.num_views)
-            torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)                                             # main.py:620-624
-        else:
-            self.camera_positions = self._own(cam)                              # [V,3]
-            self.ray_directions = self._own(dirs.reshape(-1, 3).contiguous())   # [V*H*W,3]
-            self.flat_masks = inputs.soft_masks.reshape(-1, N)
-            if self._row is not None:
-                self.flat_masks = self._row.adopt(self.flat_masks.to(torch.float32))
-            elif self.persistent:                                               # (a slot's graphs read the masks through this address for every later frame)
-                self.flat_masks = self.flat_masks.to(torch.float32).clone(memory_format=torch.contiguous_format)
-            self.sampling_weights = self._own(self.flat_masks[:, :N].max(dim=-1).values.to(torch.float32).contiguous())      # main.py:620-624
+        # [view capacity x H W, instance capacity] soft masks (the kernels read the targets with target_stride = capacity) and every other
+        # per-view buffer laid out for the view capacity; the frame fills their leading corners.  (A slot's graphs read the masks through
+        # this address for every later frame; a loop of one frame reads the caller's own tensor.)
+        views, pixels = self.view_capacity, self.view_capacity * H * W
+        self._full = dict(camera_positions=self._place(cam, (views, 3)), ray_directions=self._place(dirs.reshape(-1, 3), (pixels, 3)),
+                          flat_masks=self._place(inputs.soft_masks.reshape(-1, N), (pixels, self.capacity)),
+                          sampling_weights=self._new(pixels, fill=0.0))
+        self._set_views(self.num_views)
+        torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)                                             # main.py:620-624
         self.ray_table = self.ray_remap = None
         if not self._prepare_sampler(config):
             raise UnsuitableFrameError("this frame's importance weights do not suit the table sampler (too much of the weight in fewer pixels "
@@ -565,24 +594,13 @@ class FrameOptimizer:
 
     # ---- fused glue (csrc/frame_step.h) ---------------------------------------------------------------------------------
     def _init_fused_glue(self):
-        cfg, inp, dev = self.config, self.inputs, self.device
-        V, N = self.num_views, self.capacity          # (a mixed batch's row: every per-instance buffer is laid out for the capacity)
+        cfg, dev = self.config, self.device
+        N = self.capacity          # (every per-instance buffer is laid out for the capacity)
         lib = _lib.load()
         self._frame = self._frame_config()
-        f32 = dict(dtype=torch.float32, device=dev)
         b = self._glue = {}
-        b["extrinsics"] = inp.extrinsic_matrices.to(**f32).reshape(V, 16).contiguous()
-        b["intrinsics"] = inp.intrinsic_matrices.to(**f32).reshape(V, 9).contiguous()
-        b["gt_boxes"] = inp.boxes_2d.to(**f32).reshape(V, self.num_instances, 4).contiguous()
-        b["visible"] = inp.visible_masks.to(device=dev, dtype=torch.uint8).contiguous()
-        if self._capacity is not None:
-            views = self.view_capacity
-            for name, shape in (("extrinsics", (views, 16)), ("intrinsics", (views, 9)), ("gt_boxes", (views, N, 4)), ("visible", (views, N))):
-                self._full[name] = self._adopt_prefix(b[name], shape)
-            self._set_views(V)
-        elif self.persistent:       # a slot OWNS what reset() overwrites: float32 contiguous inputs would otherwise be these very tensors -- the
-            for name in ("extrinsics", "intrinsics", "gt_boxes", "visible"):      # caller's, and every other slot's built from the same frame
-                b[name] = b[name].clone() if self._row is None else self._row.adopt(b[name])
+        self._full.update(self._input_tables())
+        self._set_views(self.num_views)         # (the glue's tables and b["masks"]: the first V views of the full buffers)
         new = self._new            # (a frame of a batch: everything below lives in the frame's row of the arena)
         b["scratch"] = new(lib.vsrd_frame_scratch_bytes(self.view_capacity, N), torch.uint8)
         b["instances"] = new((N, 16), fill=0.0)
@@ -593,8 +611,7 @@ class FrameOptimizer:
         b["grad_raw"], b["raw_gradients"] = new((N, 8), fill=0.0), new((N, 8), fill=0.0)
         b["grad_instances"], b["grad_mlp"] = new((N, 16), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
         b["record"] = new(5, fill=0.0)
-        b["masks"] = self.flat_masks.to(**f32).contiguous()        # (persistent: _prepare_rays made this the slot's own copy)
-        if self._capacity is not None:
+        if self._headed:
             b["header"] = new(ctypes.sizeof(_lib.FrameHeader), torch.uint8, fill=0)          # vsrd_frame_header
             self._write_header()
         self.fused_hypernetwork = True
@@ -649,11 +666,11 @@ class FrameOptimizer:
                 state = self.optimizer.state.get(p)
                 if state and not (isinstance(state.get("step"), torch.Tensor) and state["step"].device == self.device and state["step"].dtype == torch.float32):
                     state["step"] = torch.as_tensor(float(state["step"]), dtype=torch.float32, device=self.device).clone()
-        self._adam = [adam_state_tensors(self.optimizer, p, group, self._row, self._capacity)
+        self._adam = [adam_state_tensors(self.optimizer, p, group, self._row, self.capacity)
                       for group, p in zip(self.optimizer.param_groups[:3], (det.locations, det.dimensions, det.orientations))]
         # the hypernetwork and the embeddings (residual phase) run through csrc/hypernetwork.h on the same footing: torch's module
         # owns the parameters, torch.optim.Adam owns the moments and counters, the kernels update both in place
-        self._hypernetwork = hypernetwork_tensors(self.hyper_distance_field, det.embeddings, self.optimizer, cfg.lr_gamma, self._row, self._capacity)
+        self._hypernetwork = hypernetwork_tensors(self.hyper_distance_field, det.embeddings, self.optimizer, cfg.lr_gamma, self._row, self.capacity)
         _destroy_graphs(self._graphs)
         # references keep every bound tensor alive until the next rebind: a replaced tensor's memory is not handed to somebody else
         # while a graph that writes through its address may still be replayed
@@ -689,7 +706,8 @@ class FrameOptimizer:
         det = self.detector
         N = self.capacity               # (the stride of every per-instance buffer; a mixed batch's row carries its own count in its header)
         residual = self.step_index >= cfg.warmup_steps
-        header = b.get("header")            # a mixed batch's row (FrameBatch(max_instances=...)): every launch takes the *_with_header twin
+        # every launch goes through the *_with_header entry point: the plain one is its forward with a null header (csrc/api.hip)
+        header = b["header"].data_ptr() if "header" in b else None          # (a row with a header: FrameBatch(max_instances=..., max_views=...))
         main = torch.cuda.current_stream(self.device)
         stream = _lib.stream()
         rays_branch, net_branch = self._branches
@@ -711,28 +729,21 @@ class FrameOptimizer:
             if joins[0]:                # (inside a several-step graph the branch simply continues behind the hypernetwork backward of the step
                 net_branch.wait_stream(main)     # before: nothing on the main stream concerns it until this step's render adjoint)
             with torch.cuda.stream(net_branch):
-                if header is not None:
-                    _lib.check(lib.vsrd_hypernetwork_forward_with_header(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["mlp_weights"]),
-                                                                         _lib.ptr(b["mlp_centred"]), header.data_ptr(), _lib.stream()))
-                else:
-                    _lib.check(lib.vsrd_hypernetwork_forward(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["mlp_weights"]),
-                                                             _lib.ptr(b["mlp_centred"]), _lib.stream()))
+                _lib.check(lib.vsrd_hypernetwork_forward_with_header(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["mlp_weights"]),
+                                                                     _lib.ptr(b["mlp_centred"]), header, _lib.stream()))
         prologue_args = (frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data),
                          _lib.ptr(b["extrinsics"]), _lib.ptr(b["intrinsics"]), _lib.ptr(b["gt_boxes"]), b["visible"].data_ptr(),
                          self.step_tensor.data_ptr(), b["scratch"].data_ptr(), b["scratch"].numel(), _lib.ptr(b["instances"]),
                          b["pd_indices"].data_ptr(), b["gt_indices"].data_ptr(), b["target_columns"].data_ptr(),
                          _lib.ptr(b["instance_weights"]), _lib.ptr(self.schedule), _lib.ptr(b["projection_losses"]), _lib.ptr(b["grad_raw"]))
-        if with_prologue and header is not None:
+        if with_prologue:
             table = self.ray_table
-            # (by value: the count the table's allocation is sized for; each frame's own count is its header's num_pixels)
+            # (by value: the count the table's allocation is sized for -- under a header each frame's own count is its header's num_pixels;
+            #  without one the two are equal, RayTable.__init__: a loop without a header never rebuilds with another count.  The table
+            #  covers every pixel: no remap)
             code = lib.vsrd_frame_prologue_sample_with_header(*prologue_args, table.table.data_ptr(), table.capacity, cfg.num_rays,
-                                                              (cfg.seed + 1) & 0xFFFFFFFFFFFFFFFF, None, b["ray_indices"].data_ptr(), header.data_ptr(), stream)
-            _lib.check(code)
-        elif with_prologue:
-            table = self.ray_table
-            code = lib.vsrd_frame_prologue_sample(*prologue_args, table.table.data_ptr(), table.count, cfg.num_rays, (cfg.seed + 1) & 0xFFFFFFFFFFFFFFFF,
-                                                  None, b["ray_indices"].data_ptr(), stream)          # (the table covers every pixel: no remap)
-            if code == _lib.E_UNSUPPORTED and batch[0] == 1 and not torch.cuda.is_current_stream_capturing():
+                                                              (cfg.seed + 1) & 0xFFFFFFFFFFFFFFFF, None, b["ray_indices"].data_ptr(), header, stream)
+            if code == _lib.E_UNSUPPORTED and header is None and batch[0] == 1 and not torch.cuda.is_current_stream_capturing():
                 # the combined launch needs ~125 KB of LDS in one workgroup (cost matrix + the sampler's hash table): where that opt-in is
                 # refused (and only then: a failed launch is an error), the frame keeps the bit-identical two-launch form
                 # (tests: test_frame_prologue_matches_the_torch_path)
@@ -740,14 +751,12 @@ class FrameOptimizer:
                 warnings.warn("vsrd_frame_prologue_sample: the LDS opt-in of the combined launch was refused; this frame draws its rays "
                               "in a launch of their own (vsrd_frame_prologue + vsrd_sample_rays_table)", RuntimeWarning)
                 self._prologue_draws = False
-                _lib.check(lib.vsrd_frame_prologue(*prologue_args, stream))
+                _lib.check(lib.vsrd_frame_prologue_with_header(*prologue_args, None, stream))
                 self._draw_rays(b["ray_indices"], b["picks"])
             else:
                 _lib.check(code)
-        elif header is not None:
-            _lib.check(lib.vsrd_frame_prologue_with_header(*prologue_args, header.data_ptr(), stream))
         else:
-            _lib.check(lib.vsrd_frame_prologue(*prologue_args, stream))
+            _lib.check(lib.vsrd_frame_prologue_with_header(*prologue_args, header, stream))
         if sampled and not with_prologue:
             main.wait_stream(rays_branch)
         if fused_net:
@@ -777,35 +786,21 @@ class FrameOptimizer:
                                   schedule=self.schedule, gather=(ray_indices, self.pixels_per_view, b["target_columns"], N), frames=frames,
                                   adjoint_slots_per_item=cfg.mlp_adjoint_item_slots if residual else 0)
         loss_scale = 1.0 / (R * self.num_instances)
-        if residual and header is not None:
+        if residual:
             _lib.check(lib.vsrd_render_residual_step_with_header(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
                                                                  _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale, float(eikonal_ratio),
                                                                  workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]),
-                                                                 _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_mlp"]), None, header.data_ptr(), stream))
-        elif residual:
-            _lib.check(lib.vsrd_render_residual_step(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
-                                                     _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale, float(eikonal_ratio),
-                                                     workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]), _lib.ptr(b["grad_instances"]),
-                                                     _lib.ptr(b["grad_mlp"]), None, stream))
-        elif header is not None:
+                                                                 _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_mlp"]), None, header, stream))
+        else:
             _lib.check(lib.vsrd_render_silhouette_step_with_header(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
                                                                    _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale,
                                                                    workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]),
-                                                                   _lib.ptr(b["grad_instances"]), None, header.data_ptr(), stream))
-        else:
-            _lib.check(lib.vsrd_render_silhouette_step(field, config, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None,
-                                                       _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale,
-                                                       workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]), _lib.ptr(b["grad_instances"]),
-                                                       None, stream))
+                                                                   _lib.ptr(b["grad_instances"]), None, header, stream))
         if fused_net:     # branch: backward through the hypernetwork, Adam on it and on the embeddings, both rates decayed (next to the epilogue)
             net_branch.wait_stream(main)
             with torch.cuda.stream(net_branch):
-                if header is not None:
-                    _lib.check(lib.vsrd_hypernetwork_backward_step_with_header(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["grad_mlp"]),
-                                                                               float(weights["silhouette_loss"]), header.data_ptr(), _lib.stream()))
-                else:
-                    _lib.check(lib.vsrd_hypernetwork_backward_step(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["grad_mlp"]),
-                                                                   float(weights["silhouette_loss"]), _lib.stream()))
+                _lib.check(lib.vsrd_hypernetwork_backward_step_with_header(self._hypernetwork, hyper_ws.data_ptr(), hyper_ws.numel(), _lib.ptr(b["grad_mlp"]),
+                                                                           float(weights["silhouette_loss"]), header, _lib.stream()))
         groups = self.optimizer.param_groups
         # ExponentialLR decays every group's rate AFTER the optimiser step: the epilogue does it for the groups it steps itself (and, in
         # the box-only phase, for the two that have nothing to step); in the residual phase those two are decayed after torch's step
@@ -813,10 +808,7 @@ class FrameOptimizer:
         epilogue_args = (frame, _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_raw"]), _lib.ptr(b["projection_losses"]), _lib.ptr(b["render_losses"]),
                          float(eikonal_ratio), self._adam[0], self._adam[1], self._adam[2], others[0], others[1], self.step_tensor.data_ptr(),
                          _lib.ptr(b["record"]), _lib.ptr(b["raw_gradients"]))
-        if header is not None:
-            _lib.check(lib.vsrd_frame_epilogue_with_header(*epilogue_args, header.data_ptr(), stream))
-        else:
-            _lib.check(lib.vsrd_frame_epilogue(*epilogue_args, stream))
+        _lib.check(lib.vsrd_frame_epilogue_with_header(*epilogue_args, header, stream))
         if residual and not fused_net:    # autograd + torch.optim.Adam (the box tensors have no .grad: skipped)
             mlp_weights.backward(b["grad_mlp"] * weights["silhouette_loss"])
             self.optimizer.step()
@@ -826,7 +818,12 @@ class FrameOptimizer:
             main.wait_stream(net_branch)
         if count:
             self.step_index += 1
-        record, raw = b["record"], b["raw_gradients"][:self.num_instances]
+        return self._step_record(residual)
+
+    def _step_record(self, residual):
+        """The dictionary a fused step returns: views of the record the epilogue writes (device tensors, rewritten by every step);
+        `residual`: the step ran in the residual phase and has an eikonal term."""
+        record, raw = self._glue["record"], self._glue["raw_gradients"][:self.num_instances]
         result = dict(iou_projection_loss=record[0], l1_projection_loss=record[1], silhouette_loss=record[2], loss=record[4],
                       raw_gradients=[raw[:, 0:3].unsqueeze(0), raw[:, 3:6].unsqueeze(0), raw[:, 6:8].unsqueeze(0)])
         if residual:
@@ -1058,26 +1055,16 @@ class FrameOptimizer:
         return len(self._graphs)
 
     def _copy_inputs(self, inputs, V, N):
-        """reset() from a materialised FrameInputs: the strided copy into the row, the importance weights, the glue's tables."""
+        """reset() from a materialised FrameInputs: the strided copy into the loop's buffers and the importance weights."""
         b = self._glue
-        if inputs.soft_masks.data_ptr() == self.flat_masks.data_ptr():
-            # `inputs` is what a reset from a frame pack left in self.inputs (_ingest_pack): its soft_masks and boxes_2d are VIEWS of this row's
-            # own buffers (capture_all ends with reset(self.inputs)).  The row holds the frame already; copying it onto itself would be an
-            # overlapping copy_, so only what is derived from it is refreshed.
-            if b["masks"].data_ptr() != self.flat_masks.data_ptr():
-                b["masks"].copy_(self.flat_masks)
-            torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)
-            b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
-            b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
-            return
-        self.flat_masks[:, :N].copy_(inputs.soft_masks.reshape(-1, N))
-        if b["masks"].data_ptr() != self.flat_masks.data_ptr():
-            b["masks"].copy_(self.flat_masks)
+        # `inputs` may be what a reset from a frame pack left in self.inputs (_ingest_pack): its soft_masks and boxes_2d are VIEWS of this
+        # loop's own buffers (capture_all ends with reset(self.inputs)).  The loop holds the frame already; copying it onto itself would be an
+        # overlapping copy_, so only what is derived from it is refreshed.
+        if inputs.soft_masks.data_ptr() != self.flat_masks.data_ptr():
+            self.flat_masks[:, :N].copy_(inputs.soft_masks.reshape(-1, N))
+            b["gt_boxes"][:, :N].copy_(inputs.boxes_2d.reshape(V, N, 4))
+            b["visible"][:, :N].copy_(inputs.visible_masks)
         torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)
-        b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
-        b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
-        b["gt_boxes"][:, :N].copy_(inputs.boxes_2d.reshape(V, N, 4))
-        b["visible"][:, :N].copy_(inputs.visible_masks)
 
     def _ingest_pack(self, pack, H, W, N):
         """reset() from a frame pack: ONE vsrd_frame_ingest call writes columns 0..N-1 of the row's soft masks (stride: the row's capacity), its
@@ -1102,54 +1089,28 @@ class FrameOptimizer:
         if not (self.graph and self.fused_glue and self.persistent):
             raise ValueError("reset() belongs to a persistent graph-mode loop (FrameOptimizer(..., graph=True, persistent=True))")
         cfg, dev, b = self.config, self.device, self._glue
-        V, N = self.num_views, self.num_instances
-        pack = inputs if isinstance(inputs, frames.FramePack) else None
-        if self._capacity is not None:
-            # a row with a header: any frame -- a pack (frames.py) or a materialised FrameInputs -- of its image size with 1..view capacity
-            # views and 1..capacity instances
-            size = tuple(int(x) for x in self.inputs.image_size)
-            if pack is not None:
-                shape = (pack.num_views, *[int(x) for x in pack.image_size], pack.num_instances)
-            else:
-                shape = tuple(int(x) for x in inputs.soft_masks.shape)
-                if tuple(int(x) for x in inputs.image_size) != shape[1:3]:
-                    raise ValueError(f"image_size {tuple(inputs.image_size)} of soft masks of shape {shape}")
-            if shape[1:3] != size:
-                raise ValueError(f"this row serves frames of image size {size}, got {shape[1:3]}")
-            if not 1 <= shape[0] <= self.view_capacity:
-                raise ValueError(f"a row of view capacity {self.view_capacity} serves frames of 1..{self.view_capacity} views, got {shape[0]}")
-            if not 1 <= shape[3] <= self._capacity:
-                raise ValueError(f"a row of capacity {self._capacity} serves frames of 1..{self._capacity} instances, got {shape[3]}")
-            V, N = shape[0], shape[3]
-        elif pack is not None:
-            # a frame pack (frames.py): vsrd_frame_ingest writes the slot's soft masks, importance weights, boxes and visibility in place
-            shape = (pack.num_views, *[int(x) for x in pack.image_size])
-            if shape != (V, *[int(x) for x in self.inputs.image_size]) or pack.num_instances != N:
-                raise ValueError(f"this loop serves frames of shape {(V, *[int(x) for x in self.inputs.image_size])} with {N} instances, "
-                                 f"got a pack of {shape} with {pack.num_instances}")
-        elif tuple(inputs.soft_masks.shape) != (V, *[int(x) for x in self.inputs.image_size], N) or tuple(inputs.image_size) != tuple(self.inputs.image_size):
-            raise ValueError(f"a slot serves frames of ONE shape: {tuple(self.inputs.soft_masks.shape)}, got {tuple(inputs.soft_masks.shape)}")
+        # any frame -- a pack (frames.py) or a materialised FrameInputs -- of the loop's image size; a row with a header: with 1..view capacity
+        # views and 1..capacity instances, any other loop: with its own counts
+        V, H, W, N = _incoming_shape(inputs, (self.num_views, *self.inputs.image_size, self.num_instances),
+                                     (self.view_capacity, self.capacity) if self._headed else None)
         with _capture_lock, torch.no_grad():
             main = torch.cuda.current_stream(dev)
             main.synchronize()                                      # (replays of the previous frame have finished: nothing reads the buffers)
             # ---- inputs ----
-            H, W = (int(x) for x in inputs.image_size)
-            if self._capacity is not None and V != self.num_views:
+            if V != self.num_views:
                 self._set_views(V)               # (the first V views of the row's buffers: the same addresses)
-            if pack is not None:
-                inputs = self._ingest_pack(pack, H, W, N)
+            if isinstance(inputs, frames.FramePack):
+                # vsrd_frame_ingest writes the soft masks, importance weights, boxes and visibility in place
+                inputs = self._ingest_pack(inputs, H, W, N)
+            else:
+                self._copy_inputs(inputs, V, N)
+            b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
+            b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
             cam, dirs = rendering.ray_casting((H, W), inputs.intrinsic_matrices, inputs.extrinsic_matrices)
             self.camera_positions.copy_(cam)
             self.ray_directions.copy_(dirs.reshape(-1, 3))
-            if pack is not None:             # (masks, weights, boxes and visibility are in the row already)
-                if b["masks"].data_ptr() != self.flat_masks.data_ptr():
-                    b["masks"].copy_(self.flat_masks)
-                b["extrinsics"].copy_(inputs.extrinsic_matrices.reshape(V, 16))
-                b["intrinsics"].copy_(inputs.intrinsic_matrices.reshape(V, 9))
-            else:
-                self._copy_inputs(inputs, V, N)
             self.inputs = inputs
-            if self._capacity is not None and N != self.num_instances:
+            if N != self.num_instances:
                 # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
                 # addresses: the pointer blocks and the captured graphs stay valid)
                 for param in (self.detector.locations, self.detector.dimensions, self.detector.orientations, self.detector.embeddings):
@@ -1163,13 +1124,11 @@ class FrameOptimizer:
             with _initial_draw:                                   # (OptimizationConfig.init_seed, for THIS frame: seed and draw as one step -- the generator is the process's,
                 if init_seed is not None:                         #  and the capture gate lets several frames' threads in here at once)
                     torch.default_generator.manual_seed(int(init_seed))
-                fresh_detector = models.BoxParameters3D(1, N)
-                fresh_field = models.HyperDistanceField(48, [16, 16, 16, 16], 256, [256, 256, 256, 256])
-            for module, fresh in ((self.detector, fresh_detector), (self.hyper_distance_field, fresh_field)):
+                fresh_modules = _fresh_modules(N)
+            for module, fresh in zip((self.detector, self.hyper_distance_field), fresh_modules):
                 for p, q in zip(module.parameters(), fresh.parameters()):
                     p.copy_(q)
-            initial = [cfg.learning_rate] * 3 + [cfg.embedding_learning_rate, cfg.hypernetwork_learning_rate]
-            for group, rate in zip(self.optimizer.param_groups, initial):
+            for group, rate in zip(self.optimizer.param_groups, _initial_rates(cfg)):
                 group["lr"].fill_(rate)
                 for p in group["params"]:
                     state = self.optimizer.state.get(p)
@@ -1180,7 +1139,7 @@ class FrameOptimizer:
             self.step_index = 0
             for name in ("record", "raw_gradients", "grad_raw", "grad_instances", "grad_mlp", "projection_losses", "render_losses"):
                 b[name].zero_()
-            if self._capacity is not None:
+            if self._headed:
                 self._write_header()
             suits = self._prepare_sampler(cfg)
             main.synchronize()
@@ -1202,16 +1161,9 @@ class FrameOptimizer:
             new = self._new
             state = dict(camera_corners=new((V, N, 8, 3), fill=0.0), boxes_2d=new((V, N, 4), fill=0.0), mean_iou=new((N, N), fill=0.0),
                          matched_gt=new(N, torch.int64, fill=0), confidences=new(N, fill=0.0))
-            if self.fused_glue:
-                state["inputs"] = self._glue
-                state["frame"] = _lib.FrameConfig.from_buffer_copy(self._frame)          # (its batch fields are this call's own)
-            else:
-                inp, f32 = self.inputs, dict(dtype=torch.float32, device=self.device)
-                state["inputs"] = dict(extrinsics=inp.extrinsic_matrices.to(**f32).reshape(V, 16).contiguous(),
-                                       intrinsics=inp.intrinsic_matrices.to(**f32).reshape(V, 9).contiguous(),
-                                       gt_boxes=inp.boxes_2d.to(**f32).reshape(V, N, 4).contiguous(),
-                                       visible=inp.visible_masks.to(device=self.device, dtype=torch.uint8).contiguous())
-                state["frame"] = self._frame_config()
+            # (the frame config's batch fields are this call's own: a copy of the glue's)
+            state["inputs"], state["frame"] = (self._glue, _lib.FrameConfig.from_buffer_copy(self._frame)) if self.fused_glue else \
+                (self._input_tables(), self._frame_config())
         self._labels = state
         return state
 
@@ -1339,11 +1291,9 @@ class FrameOptimizer:
         """``optimizer.state_dict()`` in the layout the reference's ``torch.optim.Adam`` loads: float learning rates (graph mode
         keeps them as device tensors decayed in place), ``initial_lr`` per group as ExponentialLR records it, step counters as
         host float tensors (capturable Adam keeps them on the device)."""
-        cfg = self.config
         state = self.optimizer.state_dict()
-        initial = [cfg.learning_rate] * 3 + [cfg.embedding_learning_rate, cfg.hypernetwork_learning_rate]
         groups = []
-        for group, base in zip(state["param_groups"], initial):
+        for group, base in zip(state["param_groups"], _initial_rates(self.config)):
             group = dict(group)
             group["lr"] = float(group["lr"])
             group.setdefault("initial_lr", base)
@@ -1364,7 +1314,7 @@ class FrameOptimizer:
             return self.scheduler.state_dict()
         cfg = self.config
         return {"gamma": cfg.lr_gamma,
-                "base_lrs": [cfg.learning_rate] * 3 + [cfg.embedding_learning_rate, cfg.hypernetwork_learning_rate],
+                "base_lrs": _initial_rates(cfg),
                 "last_epoch": self.step_index, "_step_count": self.step_index + 1, "_is_initial": False,
                 "_get_lr_called_within_step": False, "_last_lr": [float(group["lr"]) for group in self.optimizer.param_groups]}
 
@@ -1424,9 +1374,7 @@ class FrameBatch:
         import dataclasses
         if config.mlp_adjoint_item_slots == 0:
             config = dataclasses.replace(config, mlp_adjoint_item_slots=self.item_slots(self.size, config, shape[-1]))
-        self.config, self.device = config, torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.config, self.device = config, _indexed(device)
         with _capture_lock:
             self.arena = FrameArena(self.size, self._row_bytes(shape, config), self.device)
         # A row is FOUNDED on a frame that suits the table sampler its graphs will draw from (the frames a row later serves come through reset(),
@@ -1481,8 +1429,7 @@ class FrameBatch:
         lib = _lib.load()
         pixels = V * H * W
         with torch.device("meta"):               # (no memory, no random numbers drawn)
-            parameters = sum(p.numel() for p in models.BoxParameters3D(1, N).parameters()) + \
-                sum(p.numel() for p in models.HyperDistanceField(48, [16, 16, 16, 16], 256, [256, 256, 256, 256]).parameters())
+            parameters = sum(p.numel() for module in _fresh_modules(N) for p in module.parameters())
         workspace = max(lib.vsrd_workspace_bytes(N, 1), lib.vsrd_residual_step_workspace_bytes(N, int(config.num_samples), int(config.num_rays)))
         total = 4 * 3 * parameters                                   # parameters, exp_avg, exp_avg_sq
         total += pixels * (12 + 4 * N + 4) + 12 * V                  # ray directions, soft masks, importance weights, camera positions
@@ -1516,22 +1463,23 @@ class FrameBatch:
     def outputs(self, f):
         """Frame f's record of its last step: the dictionary ``FrameOptimizer.step`` returns (device tensors, rewritten by every step)."""
         m = self.frames[f]
-        record, raw = m._glue["record"], m._glue["raw_gradients"][:m.num_instances]
-        result = dict(iou_projection_loss=record[0], l1_projection_loss=record[1], silhouette_loss=record[2], loss=record[4],
-                      raw_gradients=[raw[:, 0:3].unsqueeze(0), raw[:, 3:6].unsqueeze(0), raw[:, 6:8].unsqueeze(0)])
-        if m.step_index > self.config.warmup_steps:
-            result["eikonal_loss"] = record[3]
-        return result
+        # (step_index counts the steps done: the last one had index step_index - 1, and `step_index - 1 >= warmup_steps` is its `residual`)
+        return m._step_record(m.step_index > self.config.warmup_steps)
+
+    def _launch_on_rows(self, active, what, state, launch, **arguments):
+        """First use creates the `what` buffers that `state` (a FrameOptimizer method) makes in EVERY row, so that the rows keep equal
+        offsets; then ONE call of `launch` on row 0 covers the first `active` rows."""
+        for m in self.frames:
+            state(m)
+        if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
+            raise RuntimeError(f"the frames of a batch laid their {what} buffers out differently: frame batches need equal offsets in every row")
+        launch(self.frames[0], frames=(active, self.arena.stride), **arguments)
 
     def labels(self, active=None):
         """The pseudo-labels of the first ``active`` frames (``FrameOptimizer.labels``) by ONE vsrd_frame_labels call for all of them: a
         list of dictionaries of device tensors, each sliced to its frame's own instance count."""
         active, members = self._members(active)
-        for m in self.frames:                      # (first use: the output buffers of EVERY row, so that the rows keep equal offsets)
-            m._label_state()
-        if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
-            raise RuntimeError("the frames of a batch laid their label buffers out differently: frame batches need equal offsets in every row")
-        members[0]._launch_labels(frames=(active, self.arena.stride))
+        self._launch_on_rows(active, "label", FrameOptimizer._label_state, FrameOptimizer._launch_labels)
         return [m._label_views() for m in members]
 
     def masks(self, active=None, view=0, threshold=0.5, soft=False):
@@ -1544,11 +1492,7 @@ class FrameBatch:
         if any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
             raise RuntimeError("masks() renders the field of the frames' last step: no step has run since a frame's reset(), or the frames "
                                "are not in step")
-        for m in self.frames:                      # (first use: the output buffers of EVERY row, so that the rows keep equal offsets)
-            m._mask_state()
-        if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
-            raise RuntimeError("the frames of a batch laid their mask buffers out differently: frame batches need equal offsets in every row")
-        members[0]._launch_masks(frames=(active, self.arena.stride), view=view, threshold=threshold, soft=soft)
+        self._launch_on_rows(active, "mask", FrameOptimizer._mask_state, FrameOptimizer._launch_masks, view=view, threshold=threshold, soft=soft)
         return [m._mask_views(threshold, soft) for m in members]
 
     def _phase(self, active):
