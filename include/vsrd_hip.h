@@ -627,6 +627,40 @@ int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* conf
                          uint8_t* mask_bits /* [N,H,ceil(W/8)] */, float* soft /* [H*W,N] or NULL */, int32_t* counts /* [N,3] or NULL */,
                          const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
 
+/* Frame metrics (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): a frame's
+ * evaluation against its 3-D ground truth -- what the reference logs every `scalar_intervals` steps (scripts/main.py:870-924) -- in ONE
+ * launch, one wave per frame, no host synchronisation, no allocation, capturable.  Lane k handles the matched pair
+ * k = (p = pd_indices[k], g = gt_indices[k]) (both NULL: pair k = (k, k); exactly one NULL: VSRD_E_INVALID_ARGUMENT):
+ *   decode box p in float32 (box_parameters.py:124-146, the decode of vsrd_frame_labels) -> `corners`;
+ *   rectify both boxes in float32, c' = Rect c as (R0 c0 + R1 c1) + R2 c2, every product and sum rounded on its own, then turn them z-up
+ *     by the exact map (x, y, z) -> (x, z, -y);
+ *   vsrd.operations.box_3d_iou (kitti360_operations.py:82-108) in double on those float32 numbers, with its quirks: the footprint is
+ *     corners 3, 2, 1, 0; Sutherland-Hodgman with the strict inside test; crossings divide by determinant + 0.01; the intersection area is
+ *     the area of the clipped polygon's convex hull, capped by the smaller footprint; volumes from three edge lengths, heights from
+ *     corners 0 and 4.
+ * Stated deviations: the reference turns the boxes with the float32 matrix rotation_matrix_x(-pi/2), whose cosine is -4.37e-8 and not 0
+ * (the effect on the IoUs stays within a few 1e-6: tests/test_hip_frame_metrics.py); a clipped polygon with fewer than three distinct
+ * points or a hull of zero area has area 0, where the reference's qhull raises.
+ * Conventions as for vsrd_frame_labels: config->num_boxes is the capacity N (1..VSRD_MAX_INSTANCES) and the stride of every instance
+ * axis, num_frames / frame_stride batch the call, frame_header (may be NULL: every frame has N boxes) carries the frame's own count n_f,
+ * clamped to [1, N]; instances n_f .. N-1 are never read and never written.  Of config, the call reads num_boxes, the location and
+ * dimension ranges and the batch fields.  A pair whose index lies outside 0 .. n_f-1 is skipped.
+ *   gt_boxes_3d [N,8,3]  ground-truth corners in the frame of the decoded boxes, the reference's corner order, by ground-truth slot; a slot
+ *                        with any non-finite entry has no annotation;
+ *   rectification [3,3]  row-major, or NULL: the identity;
+ *   corners [N,8,3]      out or NULL: the decoded corners of every box, unrectified;
+ *   ious [N,2]           out: (iou_3d, iou_bev) of pair k at the PREDICTION's slot p; NaN where its ground truth has no annotation;
+ *   summary [8]          out: (count, iou_3d, iou_bev, accuracy_3d_25, accuracy_bev_25, accuracy_3d_50, accuracy_bev_50, 0) over the pairs
+ *                        with an annotation, summed in ascending k in double: the means, and the shares of pairs with IoU > 0.25 / > 0.5
+ *                        (main.py:908-915); count == 0: eight zeros (the reference logs no metrics then).
+ * NULL gt_boxes_3d, ious or summary: VSRD_E_INVALID_ARGUMENT. */
+int32_t vsrd_frame_metrics(const vsrd_frame_config* config,
+                           const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                           const float* gt_boxes_3d /* [N,8,3] */, const float* rectification /* [3,3] or NULL */,
+                           const int64_t* pd_indices, const int64_t* gt_indices /* [N], or both NULL */,
+                           float* corners /* [N,8,3] or NULL */, float* ious /* [N,2] */, float* summary /* [8] */,
+                           const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
+
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]
  * -> weight_norm(Linear 256 -> 1617) = mlp_weights [N,1617].  weight_norm over dim 0: W[o,:] = g[o] v[o,:] / |v[o,:]|.

@@ -1,0 +1,703 @@
+"""vsrd_frame_metrics (csrc/frame_metrics.h): a frame's 3-D / BEV IoU metrics against its ground truth in one launch, one wave per frame.
+
+The yardstick is oracle/geometry.py::box_3d_iou (pinned to the reference by tests/golden/g14_box_3d_iou.npz), fed in two ways:
+
+(a) LINK: the kernel exports the corners it decoded; the test rectifies and permutes them (and the ground truth) in float32 exactly as
+    the kernel does -- (R0 c0 + R1 c1) + R2 c2, every operation rounded, then (x, y, z) -> (x, z, -y) -- so the kernel and the oracle
+    compute in double from IDENTICAL numbers and differ only by the float32 rounding of the stored IoUs (2^-24 = 6.0e-8 for a value
+    below 1) and the summation order of the hull.  Measured on an MI355X over all the cases below: max |device - oracle| = 3.7e-8
+    (MEASURED_LINK; N = 64, seed 2); asserted: ten times that.
+
+(b) END TO END: the oracle fed the way the reference feeds it (scripts/main.py:877-905): models.BoxParameters3D decode on the CPU,
+    @ rectification.T, @ rotation_matrix_x(-pi/2).T in float32 torch.  The corners then differ from the kernel's in their last float32
+    bits (and by the rotation matrix's cosine of -4.37e-8), so pairs the oracle itself calls ill-conditioned are re-drawn on the CPU
+    before anything runs: a crossing used with |determinant + 0.01| < 0.05, an IoU within 1e-4 of 0.25 or 0.5; the self and shared-edge
+    kinds are not drawn here at all.  Recorded: the oracle's own sensitivity to the float32 rounding of its inputs on these scenes
+    (float32-fed against float64-decoded) 1.06e-5 over 170 draws, 8 of them re-drawn (SENSITIVITY_END_TO_END), the device's distance
+    1.9e-6 on an MI355X (DEVICE_END_TO_END); asserted: three times the larger of the two.  Counts and accuracies must be equal exactly."""
+import json
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import margin
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+MEASURED_LINK = 3.7e-8                      # max |device - oracle| of (a) on an MI355X, all cases
+BOUND_LINK = 10.0 * MEASURED_LINK
+SENSITIVITY_END_TO_END = 1.06e-5            # the oracle against itself, float32-fed vs float64-decoded, on the scenes of (b)
+DEVICE_END_TO_END = 1.9e-6                  # the device against the float32-fed oracle on the same scenes, on an MI355X
+BOUND_END_TO_END = 3.0 * max(SENSITIVITY_END_TO_END, DEVICE_END_TO_END)
+
+SENTINEL = -777.0
+SENTINEL_BITS = int(np.array(SENTINEL, dtype=np.float32).view(np.int32))
+GAP = 256
+UNIT = np.array([[-1, -1, 1], [1, -1, 1], [1, -1, -1], [-1, -1, -1], [-1, 1, 1], [1, 1, 1], [1, 1, -1], [-1, 1, -1]], dtype=np.float64)
+KINDS_LINK = ("self", "random", "small_yaw", "disjoint", "height_apart", "inside", "turn45", "nan", "shared_edge", "random", "small_yaw", "random")
+KINDS_END_TO_END = tuple(kind for kind in KINDS_LINK if kind not in ("self", "shared_edge"))
+INPUTS = ("loc", "dim", "ori", "gt", "rect", "pd", "gi", "header")
+OUTPUTS = ("corners", "ious", "summary")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    import __graft_entry__
+    __graft_entry__.build()
+    return torch.device("cuda:0")
+
+
+# ---- scenes (host) --------------------------------------------------------------------------------------------------------------------
+def tilt():
+    """A rectification matrix: a tilt of a few degrees about x and z, float32."""
+    a, b = math.radians(3.0), math.radians(-2.0)
+    about_x = np.array([[1, 0, 0], [0, math.cos(a), -math.sin(a)], [0, math.sin(a), math.cos(a)]])
+    about_z = np.array([[math.cos(b), -math.sin(b), 0], [math.sin(b), math.cos(b), 0], [0, 0, 1]])
+    return (about_x @ about_z).astype(np.float32)
+
+
+def raw_boxes(rng, n, kinds):
+    """Raw parameters [n,8] (locations, dimensions, orientations); the slots of the shared-edge kind are axis-aligned."""
+    raw = np.concatenate([rng.normal(size=(n, 3)) * 0.6, rng.normal(size=(n, 3)) * 0.8, rng.normal(size=(n, 2))], axis=1)
+    raw[:, 2] = rng.uniform(-2.0, 0.5, n)                                  # (depth 12 .. 62 m)
+    for slot in range(n):
+        if kinds[slot % len(kinds)] == "shared_edge":
+            raw[slot, 6:8] = (1.0, 0.0) if slot % 2 else (0.0, -2.0)
+    return raw.astype(np.float32)
+
+
+def ground_truth(corners, kind, rng):
+    """A ground-truth box [8,3] float32 for the prediction `corners` [8,3] (float32, the camera frame: y down, yaw about y)."""
+    c = corners.astype(np.float64)
+    centre = c.mean(0)
+
+    def moved(yaw=0.0, scale=1.0, height_scale=1.0, shift=(0.0, 0.0, 0.0)):
+        rotation = np.array([[math.cos(yaw), 0, math.sin(yaw)], [0, 1, 0], [-math.sin(yaw), 0, math.cos(yaw)]])
+        return (((c - centre) * (scale, height_scale, scale)) @ rotation.T + centre + np.asarray(shift)).astype(np.float32)
+
+    def planar(length):
+        angle = rng.uniform(-math.pi, math.pi)
+        return (length * math.cos(angle), rng.uniform(-0.3, 0.3), length * math.sin(angle))
+    if kind == "self":
+        return corners.copy()
+    if kind == "random":
+        return moved(rng.uniform(-math.pi, math.pi), rng.uniform(0.8, 1.25), rng.uniform(0.8, 1.25), planar(rng.uniform(0.0, 3.0)))
+    if kind == "small_yaw":
+        return moved(rng.uniform(-0.05, 0.05), rng.uniform(0.8, 1.25), rng.uniform(0.8, 1.25), planar(rng.uniform(0.0, 0.6)))
+    if kind == "disjoint":
+        return moved(rng.uniform(-math.pi, math.pi), 1.0, 1.0, (30.0, 0.0, 0.0))
+    if kind == "height_apart":
+        return moved(rng.uniform(-0.3, 0.3), 1.0, 1.0, (0.1, 5.0, -0.1))
+    if kind == "inside":
+        return moved(rng.uniform(-0.2, 0.2), 0.5, 0.9)
+    if kind == "turn45":
+        return moved(math.pi / 4.0)
+    if kind == "nan":
+        box = moved(0.1)
+        box[int(rng.integers(8)), int(rng.integers(3))] = (np.nan, np.inf, -np.inf)[int(rng.integers(3))]
+        return box
+    if kind == "shared_edge":
+        axis = 0 if len(np.unique(corners[:, 0])) == 2 else 2
+        values = np.unique(corners[:, axis])
+        assert len(values) == 2, "the prediction of a shared-edge pair must decode bit-exactly axis-aligned (raw_boxes)"
+        box = corners.copy()                                               # the neighbour along `axis`: the two boxes share an edge LINE, bit for bit
+        box[:, axis] = np.where(corners[:, axis] == values[0], values[1], values[1] + np.float32(1.5))
+        return box
+    raise ValueError(kind)
+
+
+def rectified_z_up(corners, rect):
+    """[...,8,3] float32 -> the numbers the kernel computes in double from: c' = Rect c as (R0 c0 + R1 c1) + R2 c2, every operation
+    rounded to float32, then (x, y, z) -> (x, z, -y)."""
+    c = np.asarray(corners, dtype=np.float32)
+    if rect is not None:
+        R = np.asarray(rect, dtype=np.float32)
+        c = np.stack([(R[j, 0] * c[..., 0] + R[j, 1] * c[..., 1]) + R[j, 2] * c[..., 2] for j in range(3)], axis=-1)
+        assert c.dtype == np.float32
+    return np.stack([c[..., 0], c[..., 2], -c[..., 1]], axis=-1)
+
+
+def oracle_iou(c1, c2):
+    """oracle/geometry.py::box_3d_iou; where the reference's qhull refuses a degenerate clipped polygon the area is 0 (the kernel's stated rule)."""
+    from scipy.spatial import QhullError
+    from oracle import geometry
+    try:
+        iou_3d, iou_bev = geometry.box_3d_iou(c1, c2)
+    except QhullError:
+        return 0.0, 0.0
+    return float(iou_3d), float(iou_bev)
+
+
+def conditioning(c1, c2):
+    """The smallest |determinant + 0.01| over the crossings the oracle's clip of this pair uses (inf: none) -- a replica of the clip's
+    control flow (oracle/geometry.py::clip_polygon) that only records the denominators."""
+    c1, c2 = np.asarray(c1, dtype=np.float64), np.asarray(c2, dtype=np.float64)
+    subject = [np.array([c1[i, 0], c1[i, 1]]) for i in (3, 2, 1, 0)]
+    clip = [np.array([c2[i, 0], c2[i, 1]]) for i in (3, 2, 1, 0)]
+    smallest, previous = math.inf, clip[-1]
+    for current in clip:
+        edge = current - previous
+        inside = lambda p: edge[0] * (p[1] - previous[1]) > edge[1] * (p[0] - previous[0])
+        source, subject = subject, []
+        s = source[-1]
+        for e in source:
+            if inside(e) != inside(s):
+                dc, dp = previous - current, s - e
+                determinant = dc[0] * dp[1] - dc[1] * dp[0] + 0.01
+                smallest = min(smallest, abs(determinant))
+                n1, n2 = previous[0] * current[1] - previous[1] * current[0], s[0] * e[1] - s[1] * e[0]
+                subject.append(np.array([(n1 * dp[0] - n2 * dc[0]) / determinant, (n1 * dp[1] - n2 * dc[1]) / determinant]))
+            if inside(e):
+                subject.append(e)
+            s = e
+        previous = current
+        if not subject:
+            break
+    return smallest
+
+
+# ---- the C ABI by hand ----------------------------------------------------------------------------------------------------------------
+class Arena:
+    """B rows laid out for a capacity of N boxes; every byte starts as the sentinel."""
+
+    def __init__(self, N, B=1):
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        fields = [("loc", (N, 3), f32), ("dim", (N, 3), f32), ("ori", (N, 2), f32), ("gt", (N, 8, 3), f32), ("rect", (3, 3), f32), ("pd", (N,), i64),
+                  ("gi", (N,), i64), ("header", (6,), i32), ("corners", (N, 8, 3), f32), ("ious", (N, 2), f32), ("summary", (8,), f32)]
+        self.N, self.B, self.layout, cursor = N, B, {}, 0
+        for name, shape, dtype in fields:
+            nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+            self.layout[name] = (cursor, nbytes, shape, dtype)
+            cursor = (cursor + nbytes + 255) // 256 * 256
+        self.stride = cursor + GAP
+        self.host = torch.empty(B * self.stride, dtype=torch.uint8)
+        self.host.view(torch.int32).fill_(SENTINEL_BITS)
+
+    def view(self, name, f=0, host=None):
+        offset, nbytes, shape, dtype = self.layout[name]
+        start = f * self.stride + offset
+        return (self.host if host is None else host)[start:start + nbytes].view(dtype).view(shape)
+
+    def put(self, f, raw, gt=None, rect=None, pairs=None, header=True):
+        n = len(raw)
+        raw = torch.from_numpy(np.asarray(raw, dtype=np.float32))
+        self.view("loc", f)[:n], self.view("dim", f)[:n], self.view("ori", f)[:n] = raw[:, 0:3], raw[:, 3:6], raw[:, 6:8]
+        self.view("gt", f)[:n] = float("nan") if gt is None else torch.from_numpy(np.asarray(gt, dtype=np.float32))
+        if rect is not None:
+            self.view("rect", f).copy_(torch.from_numpy(np.asarray(rect, dtype=np.float32)))
+        if pairs is not None:
+            self.view("pd", f)[:n], self.view("gi", f)[:n] = torch.as_tensor(pairs[0]), torch.as_tensor(pairs[1])
+        if header:
+            self.view("header", f).zero_()
+            self.view("header", f)[0] = n
+            self.view("header", f).view(torch.float32)[1] = 1.0
+
+
+def frame_config(N, B=1, stride=0):
+    from oracle import geometry
+    from vsrd_amd import _lib
+    frame = _lib.FrameConfig()
+    frame.num_boxes, frame.num_views = N, 1
+    frame.height, frame.width, frame.epsilon = 32.0, 64.0, 1.0e-6
+    for j in range(3):
+        frame.location_lo[j], frame.location_hi[j] = geometry.LOCATION_RANGE[0][j], geometry.LOCATION_RANGE[1][j]
+        frame.dimension_lo[j], frame.dimension_hi[j] = geometry.DIMENSION_RANGE[0][j], geometry.DIMENSION_RANGE[1][j]
+    frame.num_steps = 3000
+    frame.num_frames, frame.frame_stride = B, stride
+    return frame
+
+
+def launch(dev, arena, header=True, rect=True, pairs=True, null=(), frame=None, expect_ok=True):
+    """One vsrd_frame_metrics call on the arena -> (return code, the arena's bytes afterwards, on the host)."""
+    from vsrd_amd import _lib
+    lib = _lib.load()
+    device = arena.host.to(dev)
+    base = device.data_ptr()
+    skipped = set(null) | (set() if rect else {"rect"}) | (set() if pairs else {"pd", "gi"}) | (set() if header else {"header"})
+    pointer = lambda name: None if name in skipped else base + arena.layout[name][0]
+    if frame is None:
+        frame = frame_config(arena.N, arena.B, arena.stride if arena.B > 1 else 0)
+    code = lib.vsrd_frame_metrics(frame, *[pointer(name) for name in INPUTS[:-1]], *[pointer(name) for name in OUTPUTS], pointer("header"), _lib.stream())
+    torch.cuda.synchronize()
+    if expect_ok:
+        _lib.check(code)
+    return code, device.cpu()
+
+
+def untouched(arena, after, f, n, written=OUTPUTS):
+    """Nothing but instances 0..n-1 of the outputs (and the whole summary) of row f changed."""
+    for name in INPUTS + OUTPUTS:
+        before_view, after_view = arena.view(name, f), arena.view(name, f, after)
+        if name in written and name != "summary":
+            before_view, after_view = before_view[n:], after_view[n:]
+        elif name in written:
+            continue
+        assert torch.equal(before_view.contiguous().view(torch.uint8), after_view.contiguous().view(torch.uint8)), (f, name)      # (bytes: NaN inputs compare equal)
+    end = (f + 1) * arena.stride
+    assert torch.equal(after[end - GAP:end], arena.host[end - GAP:end])
+
+
+def exported_corners(dev, raw):
+    """The kernel's own decode of `raw` [n,8]: a launch with no annotation at all (which must report count 0 and NaN IoUs)."""
+    arena = Arena(len(raw))
+    arena.put(0, raw, header=False)
+    _, after = launch(dev, arena, header=False, rect=False, pairs=False)
+    assert torch.equal(arena.view("summary", 0, after), torch.zeros(8)) and bool(torch.isnan(arena.view("ious", 0, after)).all())
+    return arena.view("corners", 0, after).numpy().copy()
+
+
+def expected_link(corners, gt, rect, pairs):
+    """The oracle on the kernel's own numbers -> (ious [n,2] float64 by PREDICTION slot, NaN without annotation; the pairs' values in order)."""
+    n = len(corners)
+    pd, gi = (np.arange(n), np.arange(n)) if pairs is None else (np.asarray(pairs[0]), np.asarray(pairs[1]))
+    first, second = rectified_z_up(corners, rect), rectified_z_up(np.nan_to_num(gt, nan=0.0, posinf=0.0, neginf=0.0), rect)
+    ious, ordered = np.full((n, 2), np.nan), []
+    for p, g in zip(pd, gi):
+        if np.isfinite(gt[g]).all():
+            ious[p] = oracle_iou(first[p], second[g])
+            ordered.append(ious[p])
+    return ious, ordered
+
+
+def summary_of(ordered):
+    """main.py:908-915 in float64 from the oracle's values."""
+    if not ordered:
+        return np.zeros(8)
+    values = np.asarray(ordered, dtype=np.float64)
+    return np.array([len(values), values[:, 0].mean(), values[:, 1].mean(), (values[:, 0] > 0.25).mean(), (values[:, 1] > 0.25).mean(),
+                     (values[:, 0] > 0.5).mean(), (values[:, 1] > 0.5).mean(), 0.0])
+
+
+def compare(label, got_ious, got_summary, want_ious, ordered, bound):
+    """NaN exactly where there is no annotation; IoUs and means within `bound`; count and accuracies exactly -> the largest IoU difference."""
+    got_ious = got_ious.numpy().astype(np.float64)
+    assert np.array_equal(np.isnan(got_ious), np.isnan(want_ious)), label
+    finite = ~np.isnan(want_ious)
+    error = float(np.abs(got_ious[finite] - want_ious[finite]).max()) if finite.any() else 0.0
+    want = summary_of(ordered)
+    got = got_summary.numpy().astype(np.float64)
+    print(f"{label}: pairs {int(want[0])}, max |iou - oracle| = {error:.3e}, max |mean - oracle| = {np.abs(got[1:3] - want[1:3]).max():.3e}")
+    assert got[0] == want[0] and got[7] == 0.0, label
+    assert np.array_equal(got[3:7], want[3:7].astype(np.float32).astype(np.float64)), (label, got, want)
+    assert error <= bound, (label, error)
+    assert np.abs(got[1:3] - want[1:3]).max() <= bound, (label, got, want)
+    return error
+
+
+def link_scene(dev, n, seed, rect, permute):
+    rng = np.random.default_rng(seed)
+    kinds = [KINDS_LINK[(slot + seed) % len(KINDS_LINK)] for slot in range(n)]
+    raw = raw_boxes(rng, n, kinds)
+    corners = exported_corners(dev, raw)
+    pd, gi = (rng.permutation(n), rng.permutation(n)) if permute else (np.arange(n), np.arange(n))
+    gt = np.empty((n, 8, 3), dtype=np.float32)
+    for p, g in zip(pd, gi):
+        gt[g] = ground_truth(corners[p], kinds[p], rng)
+    return dict(raw=raw, corners=corners, gt=gt, rect=rect, pairs=(pd.astype(np.int64), gi.astype(np.int64)) if permute else None, kinds=kinds)
+
+
+LINK_CASES = [(1, 0, False, False), (1, 8, True, False), (5, 1, True, True), (64, 2, False, True), (64, 3, True, False), (13, 4, True, True)]
+
+
+@pytest.mark.parametrize("n,seed,with_rect,permute", LINK_CASES, ids=[f"n{n}-s{s}" + ("-rect" if r else "") + ("-perm" if p else "") for n, s, r, p in LINK_CASES])
+def test_link_one_frame(dev, n, seed, with_rect, permute):
+    """(a): by-value N = n, no header."""
+    scene = link_scene(dev, n, seed, tilt() if with_rect else None, permute)
+    arena = Arena(n)
+    arena.put(0, scene["raw"], scene["gt"], scene["rect"], scene["pairs"], header=False)
+    _, after = launch(dev, arena, header=False, rect=with_rect, pairs=permute)
+    untouched(arena, after, 0, n)
+    assert np.array_equal(arena.view("corners", 0, after).numpy(), scene["corners"])
+    want, ordered = expected_link(scene["corners"], scene["gt"], scene["rect"], scene["pairs"])
+    error = compare(f"link n={n} seed={seed}", arena.view("ious", 0, after), arena.view("summary", 0, after), want, ordered, BOUND_LINK)
+    margin(f"test_link_one_frame[{n}-{seed}]", "max |iou - oracle|", error, BOUND_LINK)
+    if n >= len(KINDS_LINK):                                                # every kind was really built, the shared edge line bit for bit
+        assert set(scene["kinds"]) == set(KINDS_LINK)
+        pd, gi = scene["pairs"] if scene["pairs"] is not None else (np.arange(n), np.arange(n))
+        shared = [(p, g) for p, g in zip(pd, gi) if scene["kinds"][p] == "shared_edge"]
+        assert len(shared) >= 1 and all(np.unique(scene["corners"][p][:, 0]).max() == np.unique(scene["gt"][g][:, 0]).min() for p, g in shared)
+    if "self" in scene["kinds"]:                                            # the box itself: the case FMA contraction of the predicates breaks (IoU 0)
+        p = scene["kinds"].index("self")
+        # (the oracle's own value: BEV 1.0; 3-D about 1.0000000146 untilted, about 0.992 under the tilt, whose heights are not edge lengths)
+        assert float(arena.view("ious", 0, after)[p, 0]) > 0.99 and float(arena.view("ious", 0, after)[p, 1]) > 0.999999
+
+
+def test_link_identity_matching_is_the_default(dev):
+    """Both index arrays NULL = pair k is (k, k): bit-identical to the explicit identity; a permuted matching moves the values with it."""
+    scene = link_scene(dev, 9, 5, tilt(), False)
+    results = []
+    for pairs in (None, (np.arange(9), np.arange(9))):
+        arena = Arena(9)
+        arena.put(0, scene["raw"], scene["gt"], scene["rect"], pairs, header=False)
+        _, after = launch(dev, arena, header=False, pairs=pairs is not None)
+        results.append([arena.view(name, 0, after).clone() for name in OUTPUTS])
+    for a, b in zip(*results):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    # the same boxes matched the other way round: ground-truth slot g now belongs to prediction pd[k]
+    order = np.random.default_rng(1).permutation(9).astype(np.int64)
+    shuffled = np.empty_like(scene["gt"])
+    shuffled[order] = scene["gt"]                                          # (prediction k's ground truth now sits in slot order[k])
+    arena = Arena(9)
+    arena.put(0, scene["raw"], shuffled, scene["rect"], (np.arange(9), order), header=False)
+    _, after = launch(dev, arena, header=False)
+    assert torch.equal(arena.view("ious", 0, after).view(torch.int32), results[0][1].view(torch.int32))
+    assert torch.equal(arena.view("summary", 0, after).view(torch.int32), results[0][2].view(torch.int32))
+
+
+def test_link_header_leaves_the_pad_slots_alone(dev):
+    """n = 5 in a row of capacity 8 with a header: slots 5..7 of every output keep the sentinel, and the values are those of N = 5."""
+    scene = link_scene(dev, 5, 6, tilt(), True)
+    arena = Arena(8)
+    arena.put(0, scene["raw"], scene["gt"], scene["rect"], scene["pairs"], header=True)
+    _, after = launch(dev, arena)
+    untouched(arena, after, 0, 5)
+    for name in ("corners", "ious"):
+        assert bool((arena.view(name, 0, after)[5:] == SENTINEL).all()), name
+    want, ordered = expected_link(scene["corners"], scene["gt"], scene["rect"], scene["pairs"])
+    assert np.array_equal(arena.view("corners", 0, after)[:5].numpy(), scene["corners"])
+    error = compare("link header 5 of 8", arena.view("ious", 0, after)[:5], arena.view("summary", 0, after), want, ordered, BOUND_LINK)
+    margin("test_link_header_leaves_the_pad_slots_alone", "max |iou - oracle|", error, BOUND_LINK)
+    alone = Arena(5)
+    alone.put(0, scene["raw"], scene["gt"], scene["rect"], scene["pairs"], header=False)
+    _, single = launch(dev, alone, header=False)
+    for name in OUTPUTS:
+        assert torch.equal(arena.view(name, 0, after)[:5 if name != "summary" else 8].view(torch.int32), alone.view(name, 0, single).view(torch.int32)), name
+
+
+def test_link_batch_of_three_frames(dev):
+    """B = 3 frames with n = 3, 8, 5 in one launch (capacity 8, headers): each bit-identical to its own single-frame launch, and right."""
+    counts = (3, 8, 5)
+    scenes = [link_scene(dev, n, 10 + k, tilt() if k != 1 else np.eye(3, dtype=np.float32), k != 0) for k, n in enumerate(counts)]
+    arena = Arena(8, B=3)
+    for f, scene in enumerate(scenes):
+        pairs = scene["pairs"] if scene["pairs"] is not None else (np.arange(counts[f]), np.arange(counts[f]))
+        arena.put(f, scene["raw"], scene["gt"], scene["rect"], pairs, header=True)
+    _, after = launch(dev, arena)
+    worst = 0.0
+    for f, (n, scene) in enumerate(zip(counts, scenes)):
+        untouched(arena, after, f, n)
+        pairs = scene["pairs"] if scene["pairs"] is not None else (np.arange(n), np.arange(n))
+        alone = Arena(n)
+        alone.put(0, scene["raw"], scene["gt"], scene["rect"], pairs, header=False)
+        _, single = launch(dev, alone, header=False)
+        for name in OUTPUTS:
+            assert torch.equal(arena.view(name, f, after)[:n if name != "summary" else 8].view(torch.int32), alone.view(name, 0, single).view(torch.int32)), (f, name)
+        want, ordered = expected_link(scene["corners"], scene["gt"], scene["rect"], pairs)
+        worst = max(worst, compare(f"link batch frame {f}", arena.view("ious", f, after)[:n], arena.view("summary", f, after), want, ordered, BOUND_LINK))
+    margin("test_link_batch_of_three_frames", "max |iou - oracle|", worst, BOUND_LINK)
+
+
+def test_summary_without_annotation_and_with_a_mix(dev):
+    rng = np.random.default_rng(21)
+    raw = raw_boxes(rng, 6, ("random",))
+    corners = exported_corners(dev, raw)                                    # (asserts eight zeros and NaN IoUs for a frame without annotation)
+    gt = np.stack([ground_truth(corners[p], ("small_yaw", "nan", "random", "inside", "nan", "disjoint")[p], rng) for p in range(6)])
+    arena = Arena(6)
+    arena.put(0, raw, gt, None, None, header=False)
+    _, after = launch(dev, arena, header=False, rect=False, pairs=False)
+    want, ordered = expected_link(corners, gt, None, None)
+    assert len(ordered) == 4
+    compare("summary mix", arena.view("ious", 0, after), arena.view("summary", 0, after), want, ordered, BOUND_LINK)
+
+
+def test_invalid_arguments_are_refused(dev):
+    from vsrd_amd import _lib
+    arena = Arena(4)
+    arena.put(0, raw_boxes(np.random.default_rng(0), 4, ("random",)), header=False)
+    refused = [launch(dev, arena, header=False, null=(name,), expect_ok=False) for name in ("gt", "ious", "summary", "pd", "gi", "loc")]
+    refused.append(launch(dev, arena, header=False, frame=frame_config(0), expect_ok=False))
+    refused.append(launch(dev, arena, header=False, frame=frame_config(_lib.MAX_INSTANCES + 1), expect_ok=False))
+    refused.append(launch(dev, arena, header=False, frame=frame_config(4, B=2, stride=100), expect_ok=False))
+    for code, after in refused:
+        assert code == _lib.E_INVALID_ARGUMENT and torch.equal(after, arena.host)
+    code, after = launch(dev, arena, header=False, null=("corners",))      # (corners may be NULL)
+    assert code == 0 and bool((arena.view("corners", 0, after) == SENTINEL).all()) and float(arena.view("summary", 0, after)[0]) == 0.0
+
+
+# ---- (b) end to end ----------------------------------------------------------------------------------------------------------------------
+def reference_fed(raw, gt, rect):
+    """The reference's inputs to box_3d_iou (main.py:877-905): BoxParameters3D decode on the CPU, @ rectification.T, @ rotation_matrix_x(-pi/2).T,
+    float32 torch -> (prediction corners [n,8,3], ground-truth corners [n,8,3]) as numpy float32."""
+    from vsrd_amd import models, operations
+    n = len(raw)
+    detector = models.BoxParameters3D(1, n)
+    with torch.no_grad():
+        t = torch.from_numpy(raw)
+        detector.locations.copy_(t[None, :, 0:3]); detector.dimensions.copy_(t[None, :, 3:6]); detector.orientations.copy_(t[None, :, 6:8])
+        boxes = detector()["boxes_3d"][0]
+    assert boxes.dtype == torch.float32
+    return boxes.numpy(), reference_turn(boxes.numpy(), rect), (None if gt is None else reference_turn(gt, rect))
+
+
+def reference_turn(corners, rect):
+    """[n,8,3] float32 -> @ rectification.T for all boxes (main.py:877-886), then @ rotation_matrix_x(-pi/2).T box by box (:896-899)."""
+    from vsrd_amd import operations
+    rectification = torch.from_numpy(np.asarray(rect, dtype=np.float32))
+    rotation = operations.rotation_matrix_x(torch.tensor(-np.pi / 2.0))
+    assert rotation.dtype == torch.float32
+    rectified = torch.from_numpy(np.nan_to_num(np.asarray(corners, dtype=np.float32), nan=0.0, posinf=0.0, neginf=0.0)) @ rectification.T
+    return torch.stack([box @ rotation.T for box in rectified]).numpy()
+
+
+def float64_fed(raw, gt, rect):
+    """The same inputs without float32 rounding: decoded, rectified and turned in float64 (the exact turn)."""
+    from oracle import geometry
+    t = torch.from_numpy(raw).double()
+    corners = geometry.decode_box_parameters(t[:, 0:3], t[:, 3:6], t[:, 6:8])[3].numpy()
+    def turn(c):
+        r = c @ np.asarray(rect, dtype=np.float64).T
+        return np.stack([r[..., 0], r[..., 2], -r[..., 1]], axis=-1)
+    return turn(corners), turn(np.nan_to_num(gt.astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0))
+
+
+def ill_conditioned(c1, c2):
+    if conditioning(c1, c2) < 0.05:
+        return True
+    return any(abs(value - bound) < 1.0e-4 for value in oracle_iou(c1, c2) for bound in (0.25, 0.5))
+
+
+def end_to_end_scene(n, seed, rect):
+    """Raw boxes and ground truth drawn on the CPU alone; pairs the oracle calls ill-conditioned are re-drawn (as `random`) -> scene, draws, re-draws."""
+    rng = np.random.default_rng(seed)
+    kinds = [KINDS_END_TO_END[(slot + seed) % len(KINDS_END_TO_END)] for slot in range(n)]
+    raw = raw_boxes(rng, n, kinds)
+    boxes, first, _ = reference_fed(raw, None, rect)
+    gt, redraws = np.empty((n, 8, 3), dtype=np.float32), 0
+    rotation_and_rect = lambda box: reference_turn(box[None], rect)[0]
+    for p in range(n):
+        gt[p] = ground_truth(boxes[p], kinds[p], rng)
+        while np.isfinite(gt[p]).all() and ill_conditioned(first[p], rotation_and_rect(gt[p])):
+            redraws += 1
+            assert redraws <= n
+            gt[p] = ground_truth(boxes[p], "random", rng)
+    return dict(raw=raw, gt=gt, rect=rect), n, redraws
+
+
+END_TO_END_CASES = [(64, 31), (64, 32), (37, 33), (5, 34)]
+
+
+def test_end_to_end_against_the_reference_fed_oracle(dev):
+    """(b), all scenes in one test: the re-draw share, the oracle's own sensitivity and the device's distance are properties of the whole set."""
+    rect = tilt()
+    scenes, draws, redraws = [], 0, 0
+    for n, seed in END_TO_END_CASES:                                       # (everything is drawn before anything runs on the GPU)
+        scene, d, r = end_to_end_scene(n, seed, rect)
+        scenes.append(scene); draws += d; redraws += r
+    print(f"end to end: {draws} draws, {redraws} re-drawn")
+    assert redraws <= 0.05 * draws
+    sensitivity = distance = 0.0
+    for scene in scenes:
+        n = len(scene["raw"])
+        _, first, second = reference_fed(scene["raw"], scene["gt"], rect)
+        exact_first, exact_second = float64_fed(scene["raw"], scene["gt"], rect)
+        want, ordered = np.full((n, 2), np.nan), []
+        for p in range(n):
+            if np.isfinite(scene["gt"][p]).all():
+                want[p] = oracle_iou(first[p], second[p])
+                ordered.append(want[p])
+                sensitivity = max(sensitivity, float(np.abs(np.asarray(oracle_iou(exact_first[p], exact_second[p])) - want[p]).max()))
+        arena = Arena(n)
+        arena.put(0, scene["raw"], scene["gt"], rect, None, header=False)
+        _, after = launch(dev, arena, header=False, pairs=False)
+        distance = max(distance, compare(f"end to end n={n}", arena.view("ious", 0, after), arena.view("summary", 0, after), want, ordered, BOUND_END_TO_END))
+    print(f"end to end: oracle sensitivity to float32 inputs = {sensitivity:.3e}, device distance = {distance:.3e}")
+    margin("test_end_to_end", "oracle sensitivity", sensitivity, BOUND_END_TO_END)
+    margin("test_end_to_end", "device distance", distance, BOUND_END_TO_END)
+
+
+# ---- through the classes ---------------------------------------------------------------------------------------------------------------
+SIZE = (32, 64)
+
+
+def make_frame_packs():
+    """tools/make_frame_packs.py as a module (synthetic packs, which carry their true boxes)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_frame_packs", os.path.join(ROOT, "tools", "make_frame_packs.py"))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
+def loop_config(**changes):
+    from vsrd_amd import optimization
+    values = dict(num_samples=40, num_rays=64, warmup_steps=3, num_steps=12, seed=3, mlp_adjoint_item_slots=8)
+    values.update(changes)
+    return optimization.OptimizationConfig(**values)
+
+
+def by_hand(dev, loop):
+    """vsrd_frame_metrics called by hand on a one-frame loop's own tensors (N = the loop's count, no header)."""
+    from vsrd_amd import _lib
+    n, det, glue = loop.num_instances, loop.detector, loop._glue
+    frame = loop._frame_config()
+    frame.num_frames, frame.frame_stride = 1, 0
+    corners, ious, summary = torch.full((n, 8, 3), SENTINEL, device=dev), torch.full((n, 2), SENTINEL, device=dev), torch.full((8,), SENTINEL, device=dev)
+    gt = loop.inputs.boxes_3d.float().contiguous()
+    _lib.check(_lib.load().vsrd_frame_metrics(frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(gt),
+                                              None, glue["pd_indices"].data_ptr(), glue["gt_indices"].data_ptr(), _lib.ptr(corners), _lib.ptr(ious),
+                                              _lib.ptr(summary), None, _lib.stream()))
+    return dict(iou_3d=ious[:, 0], iou_bev=ious[:, 1], summary=summary, corners=corners)
+
+
+def snapshot(result):
+    return {key: value.clone() for key, value in result.items()}
+
+
+def parameters(loop):
+    return [t.detach().clone() for t in (loop.detector.locations, loop.detector.dimensions, loop.detector.orientations, loop.detector.embeddings)]
+
+
+def test_frame_optimizer_metrics_and_reset(dev):
+    import dataclasses
+    from vsrd_amd import formats, launcher, optimization
+    first, second = launcher.synthetic_frame_inputs(dev, 3, 2, 3, *SIZE), launcher.synthetic_frame_inputs(dev, 4, 2, 3, *SIZE)
+    assert first.boxes_3d.shape == (3, 8, 3) and first.rectification_matrix is None
+    loop = optimization.FrameOptimizer(first, loop_config(init_seed=70), dev, graph=True, persistent=True)
+    with pytest.raises(RuntimeError, match="no step has run"):
+        loop.metrics()
+    loop.run(4, steps_per_graph=1)
+    got = snapshot(loop.metrics())
+    want = by_hand(dev, loop)
+    torch.cuda.synchronize()
+    assert got["iou_3d"].shape == (3,) and got["iou_bev"].shape == (3,) and got["summary"].shape == (8,) and got["corners"].shape == (3, 8, 3)
+    for key in want:
+        assert torch.equal(got[key], want[key]), key
+    assert float(got["summary"][0]) == 3.0 and set(formats.frame_metrics(got["summary"])) == set(formats.FRAME_METRIC_NAMES)
+    assert torch.equal(got["corners"], loop.boxes()["boxes_3d"][0]) or float((got["corners"] - loop.boxes()["boxes_3d"][0]).abs().max()) < 1e-4
+    # the slot serves a second frame: the metrics are that frame's (its ground truth replaced the first one's)
+    assert loop.reset(second, init_seed=71)
+    with pytest.raises(RuntimeError, match="no step has run"):
+        loop.metrics()
+    loop.run(4, steps_per_graph=1)
+    again = snapshot(loop.metrics())
+    fresh = optimization.FrameOptimizer(second, loop_config(init_seed=71), dev, graph=True, persistent=True)
+    fresh.run(4, steps_per_graph=1)
+    own = snapshot(fresh.metrics())
+    torch.cuda.synchronize()
+    for key in own:
+        assert torch.equal(again[key], own[key]), key
+    assert not torch.equal(again["corners"], got["corners"])
+    # ... and a frame without ground truth clears it
+    bare = dataclasses.replace(first, boxes_3d=None)
+    assert loop.reset(bare, init_seed=70)
+    loop.run(1, steps_per_graph=1)
+    with pytest.raises(ValueError, match="boxes_3d"):
+        loop.metrics()
+    assert bool(torch.isnan(loop._metrics["gt_boxes_3d"]).all())
+    # the same through frame packs: a pack with boxes_3d replaces the row's ground truth, a pack without clears it
+    pack = make_frame_packs().make_pack(4, 2, *SIZE, 3)
+    assert pack.boxes_3d.shape == (3, 8, 3)
+    assert loop.reset(pack, init_seed=72)
+    assert torch.equal(loop._metrics["gt_boxes_3d"].cpu(), torch.from_numpy(pack.boxes_3d)) and torch.equal(loop.inputs.boxes_3d.cpu(), torch.from_numpy(pack.boxes_3d))
+    loop.run(2, steps_per_graph=1)
+    packed = snapshot(loop.metrics())
+    want = by_hand(dev, loop)
+    torch.cuda.synchronize()
+    assert float(packed["summary"][0]) == 3.0 and all(torch.equal(packed[key], want[key]) for key in want)
+    assert loop.reset(dataclasses.replace(pack, boxes_3d=None), init_seed=72)
+    loop.run(1, steps_per_graph=1)
+    with pytest.raises(ValueError, match="boxes_3d"):
+        loop.metrics()
+    assert bool(torch.isnan(loop._metrics["gt_boxes_3d"]).all())
+    # a ground truth of the wrong shape is refused before the row is touched
+    before = loop.flat_masks.clone()
+    with pytest.raises(ValueError, match="boxes_3d"):
+        loop.reset(dataclasses.replace(second, boxes_3d=second.boxes_3d[:2]), init_seed=71)
+    assert torch.equal(loop.flat_masks, before) and loop.step_index == 1
+    loop.close(); fresh.close()
+
+
+def test_frame_batch_metrics_equal_each_frame_alone_and_leave_the_trajectory(dev):
+    import dataclasses
+    from vsrd_amd import launcher, optimization
+    inputs = [launcher.synthetic_frame_inputs(dev, 3, 2, 3, *SIZE), launcher.synthetic_frame_inputs(dev, 4, 2, 5, *SIZE)]
+    config = loop_config()
+    alone = []
+    for k, frame in enumerate(inputs):
+        loop = optimization.FrameOptimizer(frame, dataclasses.replace(config, init_seed=70 + k), dev, graph=True, persistent=True)
+        loop.run(3, steps_per_graph=1)
+        alone.append(snapshot(loop.metrics()))
+        torch.cuda.synchronize()
+        loop.close()
+
+    def walk(with_metrics):
+        batch = optimization.FrameBatch(inputs, config, dev, init_seeds=[70, 71], max_instances=8)
+        if with_metrics:
+            with pytest.raises(RuntimeError, match="no step has run"):
+                batch.metrics()
+        batch.run(3, steps_per_graph=1)
+        got = [snapshot(entry) for entry in batch.metrics()] if with_metrics else None
+        batch.run(3, steps_per_graph=1)
+        torch.cuda.synchronize()
+        record = [dict(record=member._glue["record"].clone(), raw_gradients=member._glue["raw_gradients"].clone(), loss=batch.outputs(f)["loss"].clone())
+                  for f, member in enumerate(batch.frames)]
+        state = [parameters(member) for member in batch.frames]
+        laid_out = batch.frames[0]._metrics is not None
+        if with_metrics:
+            # a row whose frame has no ground truth is no error in a batch: count 0, NaN IoUs, no metrics; its neighbour is evaluated as ever
+            from vsrd_amd import formats
+            assert batch.reset(0, inputs[0], init_seed=70) and batch.reset(1, dataclasses.replace(inputs[1], boxes_3d=None), init_seed=71)
+            batch.run(1, steps_per_graph=1)
+            with_truth, without = batch.metrics()
+            torch.cuda.synchronize()
+            assert float(with_truth["summary"][0]) == 3.0 and len(formats.frame_metrics(with_truth["summary"])) == 6
+            assert torch.equal(without["summary"], torch.zeros(8, device=dev)) and bool(torch.isnan(without["iou_3d"]).all() and torch.isnan(without["iou_bev"]).all())
+            assert formats.frame_metrics(without["summary"]) == {}
+        batch.close()
+        return got, record, state, laid_out
+    got, record, state, laid_out = walk(True)
+    _, plain_record, plain_state, plain_laid_out = walk(False)
+    assert laid_out and not plain_laid_out                               # (rows that never ask keep today's layout)
+    for k, (mine, want) in enumerate(zip(got, alone)):
+        n = inputs[k].soft_masks.shape[-1]
+        assert mine["iou_3d"].shape == (n,) and mine["corners"].shape == (n, 8, 3) and float(mine["summary"][0]) == n
+        for key in want:
+            assert torch.equal(mine[key], want[key]), (k, key)
+    for f in range(2):                                                   # the call only reads: the trajectory is bit-identical
+        assert record[f].keys() == plain_record[f].keys() and all(torch.equal(record[f][key], plain_record[f][key]) for key in record[f])
+        assert all(torch.equal(a, b) for a, b in zip(state[f], plain_state[f]))
+
+
+def test_launcher_metrics(tmp_path):
+    names = ("iou_3d", "iou_bev", "accuracy_3d_25", "accuracy_bev_25", "accuracy_3d_50", "accuracy_bev_50")
+
+    def run(name, extra, shape=("--height", "32", "--width", "64", "--views", "2", "--instances", "3")):
+        out = str(tmp_path / name)
+        cmd = [sys.executable, "-m", "vsrd_amd.launcher", "--gpus", "1", "--frames", "2", "--frame-batch", "2", "--num-steps", "6", "--warmup-steps", "3",
+               *shape, "--out", out,
+               # (an image of 32 x 64 has fewer than the default 1000 pixels with a positive soft mask: the job needs a ray count it can draw)
+               "--rays", "32", "--samples", "40", "--adjoint-item-slots", "8", *extra]
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        done = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+        assert done.returncode == 0, done.stderr[-4000:]
+        line = json.loads([l for l in done.stdout.splitlines() if l.startswith("{")][-1])
+        payloads = [torch.load(os.path.join(out, f"frame_{f:06d}", "step_5.pt"), weights_only=False) for f in range(2)]
+        return line, payloads
+    line, payloads = run("with", ["--metrics"])
+    assert line["frame_metrics_frames"] == 2 and set(line["frame_metrics"]) == set(names)
+    for payload in payloads:
+        assert set(payload["metrics"]) == set(names)
+        assert all(type(payload["metrics"][name]) is float and 0.0 <= payload["metrics"][name] <= 1.000001 for name in names)
+    for name in names:
+        assert line["frame_metrics"][name] == pytest.approx(sum(p["metrics"][name] for p in payloads) / 2.0, abs=1e-12)
+    line, payloads = run("without", [])
+    assert "frame_metrics" not in line and "frame_metrics_frames" not in line
+    assert all(not payload["metrics"] for payload in payloads)
+    # frames from disk: a pack without ground truth is skipped, not an error
+    from vsrd_amd import frames
+    import dataclasses
+    folder = str(tmp_path / "packs")
+    paths = make_frame_packs().write_packs(folder, 2, views=2, height=32, width=64, instances=(3,))
+    frames.save_pack(paths[1], dataclasses.replace(frames.load_pack(paths[1]), boxes_3d=None))
+    line, payloads = run("packs", ["--metrics", "--frames-dir", folder], shape=())
+    assert line["frame_metrics_frames"] == 1 and set(line["frame_metrics"]) == set(names)
+    assert set(payloads[0]["metrics"]) == set(names) and not payloads[1]["metrics"]
+    assert all(line["frame_metrics"][name] == payloads[0]["metrics"][name] for name in names)

@@ -112,7 +112,8 @@ def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, ve
         view_offsets.append(len(ids))
     polygon_offsets = np.concatenate([[0], np.cumsum([len(p) for p in polygons])])
     return frames.FramePack((height, width), K.numpy().astype(np.float32), E.numpy().astype(np.float32), np.asarray(view_offsets, dtype=np.int64),
-                            np.asarray(ids, dtype=np.int64), polygon_offsets.astype(np.int64), np.concatenate(polygons).astype(np.int32), np.stack(masks))
+                            np.asarray(ids, dtype=np.int64), polygon_offsets.astype(np.int64), np.concatenate(polygons).astype(np.int32), np.stack(masks),
+                            boxes_3d=corners.numpy().astype(np.float32))      # (the true boxes in the target's instance order: ground truth for --metrics)
 
 
 def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), drop=(), shuffle=False, vertices=0):

@@ -257,6 +257,9 @@ SIGNATURES = {
     "vsrd_frame_masks": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), ctypes.POINTER(FrameMasksConfig), c_float_p, c_float_p,
                                           c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p]),
+    # added within ABI 12: a frame's 3-D / BEV IoU metrics against its ground truth (corners, IoUs per pair, summary); header before the stream
+    "vsrd_frame_metrics": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
     "vsrd_hypernetwork_forward": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p, ctypes.c_void_p]),
     "vsrd_hypernetwork_backward_step": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_float,

@@ -14,6 +14,7 @@
 #include "frame_ingest.h"
 #include "frame_labels.h"
 #include "frame_masks.h"
+#include "frame_metrics.h"
 #include "launch.h"
 
 namespace {
@@ -1284,6 +1285,31 @@ int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* conf
     if (residual) for_rounds<1, 2, 4>(rounds, [&](auto k) { launch(k, std::true_type{}); });
     else for_rounds<1, 2, 4, 8>(rounds, [&](auto k) { launch(k, std::false_type{}); });
     if (status != VSRD_OK) return status;
+    return launch_status();
+}
+
+int32_t vsrd_frame_metrics(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                           const float* gt_boxes_3d, const float* rectification, const int64_t* pd_indices, const int64_t* gt_indices,
+                           float* corners, float* ious, float* summary, const vsrd_frame_header* frame_header, void* stream) {
+    if (!config || config->num_boxes < 1 || config->num_boxes > kFrameMaxBoxes) return VSRD_E_INVALID_ARGUMENT;
+    Frames frames;
+    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (!raw_locations || !raw_dimensions || !raw_orientations || !gt_boxes_3d || !ious || !summary) return VSRD_E_INVALID_ARGUMENT;
+    if ((pd_indices != nullptr) != (gt_indices != nullptr)) return VSRD_E_INVALID_ARGUMENT;
+    FrameStepArgs a = {};                  // (the decode's ranges and the batch fields: nothing else is read)
+    a.num_boxes = config->num_boxes;
+    for (int j = 0; j < 3; ++j) {
+        a.location_lo[j] = config->location_lo[j]; a.location_hi[j] = config->location_hi[j];
+        a.dimension_lo[j] = config->dimension_lo[j]; a.dimension_hi[j] = config->dimension_hi[j];
+    }
+    a.frame_stride = frames.stride;
+    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
+    MetricBuffers b;
+    b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
+    b.gt_boxes_3d = gt_boxes_3d; b.rectification = rectification;
+    b.pd_indices = reinterpret_cast<const long long*>(pd_indices); b.gt_indices = reinterpret_cast<const long long*>(gt_indices);
+    b.corners = corners; b.ious = ious; b.summary = summary;
+    hipLaunchKernelGGL(frame_metrics_kernel, dim3(frames.count), dim3(kWave), 0, static_cast<hipStream_t>(stream), a, b);
     return launch_status();
 }
 

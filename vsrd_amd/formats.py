@@ -7,6 +7,8 @@ pseudo-label files derived from it.  Host-side I/O only.
   multi-view confidences    tools/kitti_360/make_predictions.py:86-176    mean box IoU over source views + Hungarian (maximise)
   KITTI label line          tools/kitti_360/convert_predictions.py:16-78
   per-frame label files     save_frame_labels: what optimization.FrameOptimizer.labels() returns (vsrd_frame_labels), as the two above
+  per-frame metrics         frame_metrics: the summary of optimization.FrameOptimizer.metrics() (vsrd_frame_metrics) under the reference's
+                            six names (scripts/main.py:908-924)
 """
 import json
 import math
@@ -150,6 +152,34 @@ def save_frame_labels(folder, labels, class_name="car"):
                       lambda name, view=view: save_prediction(name, boxes_3d[view], boxes_2d[view], confidences, class_name))
     _atomic_write(os.path.join(folder, "labels", "view_00.txt"),
                   lambda name: save_kitti_labels(name, [class_name] * len(confidences), boxes_3d[0], boxes_2d[0], confidences.tolist()))
+
+
+FRAME_METRIC_NAMES = ("iou_3d", "iou_bev", "accuracy_3d_25", "accuracy_bev_25", "accuracy_3d_50", "accuracy_bev_50")     # main.py:917-924
+
+
+def frame_metrics_summary(ious_3d, ious_bev):
+    """The summary vsrd_frame_metrics writes, computed on the host from per-pair IoUs (any sequence; a NaN pair has no annotation and is
+    left out): [count, mean iou_3d, mean iou_bev, the shares of pairs with IoU > 0.25 (3-D, BEV) and > 0.5 (3-D, BEV), 0] as Python
+    floats, summed in the given order in double; eight zeros without a pair (scripts/main.py:908-915)."""
+    pairs = [(float(a), float(b)) for a, b in zip(ious_3d, ious_bev) if not (math.isnan(float(a)) or math.isnan(float(b)))]
+    if not pairs:
+        return [0.0] * 8
+    count = float(len(pairs))
+    columns = [[a for a, _ in pairs], [b for _, b in pairs]]
+    sums = [sum(columns[0]), sum(columns[1])] + [float(sum(1 for v in columns[j] if v > bound)) for bound in (0.25, 0.5) for j in (0, 1)]
+    return [count] + [value / count for value in sums] + [0.0]
+
+
+def frame_metrics(summary):
+    """``metrics()["summary"]`` (vsrd_frame_metrics: count, then the six values) as the dictionary the reference logs
+    (scripts/main.py:917-924: iou_3d, iou_bev, accuracy_3d_25, accuracy_bev_25, accuracy_3d_50, accuracy_bev_50), Python floats; {} when
+    the count is 0 -- no pair had ground truth, and the reference logs no metrics then."""
+    values = [float(v) for v in (summary.detach().cpu().tolist() if isinstance(summary, torch.Tensor) else summary)]
+    if len(values) != 8:
+        raise ValueError(f"a metrics summary has 8 entries, got {len(values)}")
+    if values[0] == 0.0:
+        return {}
+    return dict(zip(FRAME_METRIC_NAMES, values[1:7]))
 
 
 def save_frame_masks(folder, masks, shape, view=0):

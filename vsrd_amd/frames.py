@@ -9,7 +9,7 @@ a pack into soft masks, importance weights, boxes and visibility in one call: ``
 ``FrameOptimizer.reset`` / ``FrameBatch.reset`` let it write straight into a persistent row (``ingest_into``)."""
 import os
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -21,6 +21,8 @@ TEMPERATURE = 10.0             # SoftRasterizer's default (geometric_transforms.
 
 _FIELDS = ("image_size", "intrinsic_matrices", "extrinsic_matrices", "view_offsets", "instance_ids", "polygon_offsets", "polygon_vertices",
            "inside")
+# optional members (3-D ground truth for FrameOptimizer.metrics): written only when present; a pack without them loads with None
+_OPTIONAL = ("boxes_3d", "rectification_matrix")
 
 
 @dataclass
@@ -36,6 +38,8 @@ class FramePack:
     polygon_offsets: np.ndarray             # [M+1] int64: entry m's vertices are polygon_offsets[m] .. polygon_offsets[m+1] - 1
     polygon_vertices: np.ndarray            # [sum P,2] int32 (x, y): cv.findContours' output (SoftRasterizer.make_polygon)
     inside: np.ndarray                      # [M,H,ceil(W/8)] uint8: np.packbits(binary mask, axis=-1), most significant bit first
+    boxes_3d: Optional[np.ndarray] = None               # [N,8,3] float32 or None: 3-D ground truth in the target's instance order, NaN rows = no annotation
+    rectification_matrix: Optional[np.ndarray] = None   # [3,3] float32 or None (identity)
 
     @property
     def num_views(self):
@@ -60,7 +64,8 @@ def _normalised(pack):
                      np.ascontiguousarray(pack.intrinsic_matrices, dtype=np.float32), np.ascontiguousarray(pack.extrinsic_matrices, dtype=np.float32),
                      np.ascontiguousarray(pack.view_offsets, dtype=np.int64), np.ascontiguousarray(pack.instance_ids, dtype=np.int64),
                      np.ascontiguousarray(pack.polygon_offsets, dtype=np.int64), np.ascontiguousarray(pack.polygon_vertices, dtype=np.int32),
-                     np.ascontiguousarray(pack.inside, dtype=np.uint8))
+                     np.ascontiguousarray(pack.inside, dtype=np.uint8),
+                     *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=np.float32) for field in _OPTIONAL])
 
 
 def validate(pack, name="frame pack"):
@@ -104,6 +109,14 @@ def validate(pack, name="frame pack"):
         own = ids[offsets[view]:offsets[view + 1]]
         if len(np.unique(own)) != len(own):
             bad(f"view {view} lists an instance id twice")
+    for field, shape in zip(_OPTIONAL, ((int(offsets[1]), 8, 3), (3, 3))):
+        array = getattr(pack, field)
+        if array is None:
+            continue
+        if not isinstance(array, np.ndarray) or array.dtype.kind not in "iuf":
+            bad(f"{field} is not a numeric array")
+        if array.shape != shape:
+            bad(f"{field} of shape {array.shape}, expected {shape}")
     return pack
 
 
@@ -113,7 +126,7 @@ def save_pack(path, pack):
     staged = f"{path}.tmp.{os.getpid()}"
     try:
         with open(staged, "wb") as handle:
-            np.savez(handle, **{field: np.asarray(getattr(pack, field)) for field in _FIELDS})
+            np.savez(handle, **{field: np.asarray(getattr(pack, field)) for field in _FIELDS + _OPTIONAL if getattr(pack, field) is not None})
         os.replace(staged, path)
     finally:
         if os.path.exists(staged):
@@ -140,9 +153,10 @@ def load_pack(path):
     """Read and validate a pack; ValueError naming the file when it is malformed."""
     with _open(path) as data:
         arrays = {field: _member(data, path, field) for field in _FIELDS}
+        arrays.update({field: _member(data, path, field) for field in _OPTIONAL if field in data.files})
     if arrays["image_size"].size != 2:
         raise ValueError(f"{path}: malformed frame pack: image_size of shape {arrays['image_size'].shape}")
-    for field in _FIELDS:
+    for field in arrays:
         if arrays[field].dtype.kind not in "iuf":
             raise ValueError(f"{path}: malformed frame pack: {field} has dtype {arrays[field].dtype}")
     return validate(_normalised(FramePack(**arrays)), str(path))
@@ -203,6 +217,12 @@ def ingest_into(pack, device, target_stride, soft_masks=None, sampling_weights=N
         staged.record_stream(torch.cuda.current_stream(device))
 
 
+def ground_truth_3d(pack, device):
+    """(boxes_3d [N,8,3], rectification_matrix [3,3]) of the pack on `device`, None where the pack has none."""
+    return tuple(None if array is None else torch.from_numpy(np.ascontiguousarray(array, dtype=np.float32)).to(device)
+                 for array in (pack.boxes_3d, pack.rectification_matrix))
+
+
 def camera_matrices(pack, device):
     return (torch.from_numpy(pack.intrinsic_matrices).to(device=device, dtype=torch.float32),
             torch.from_numpy(pack.extrinsic_matrices).to(device=device, dtype=torch.float32))
@@ -220,4 +240,5 @@ def ingest(pack, device, temperature=TEMPERATURE):
     visible = torch.empty(views, instances, dtype=torch.uint8, device=device)
     ingest_into(pack, device, instances, soft_masks=soft, gt_boxes=boxes, visible=visible, temperature=temperature)
     intrinsics, extrinsics = camera_matrices(pack, device)
-    return FrameInputs((height, width), intrinsics, extrinsics, soft, boxes.reshape(views, instances, 2, 2), visible.bool())
+    return FrameInputs((height, width), intrinsics, extrinsics, soft, boxes.reshape(views, instances, 2, 2), visible.bool(),
+                       *ground_truth_3d(pack, device))

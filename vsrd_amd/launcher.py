@@ -206,7 +206,7 @@ def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], s
 def synthetic_frame_inputs(device, frame, views, instances, height=376, width=1408):
     """FrameInputs of synthetic frame number `frame` (synthetic.synthetic_frame(seed = frame): KITTI-360 intrinsics, boxes in the
     reference's ranges): soft masks rendered from the true boxes at the sharp end of the schedule, ground-truth 2-D boxes projected
-    from them, every instance visible in every view."""
+    from them, every instance visible in every view; the true boxes' corners are the frame's 3-D ground truth (boxes_3d)."""
     from . import fields, models, operations, optimization, rendering, synthetic
     K, E, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(int(frame), views, height, width, instances)
     K, E = K.to(device), E.to(device)
@@ -220,7 +220,8 @@ def synthetic_frame_inputs(device, frame, views, instances, height=376, width=14
         soft = rendering.render_hierarchical(block, origins, dirs.reshape(-1, 3), (0.0, 100.0), 64, 0.1, 1.0, seed=1,
                                              skip_exact_misses=True)["labels"].clamp(0, 1).reshape(views, height, width, instances).contiguous()
         gt_boxes, _ = operations.project_boxes_multi_view(out["boxes_3d"][0], E, K, (height, width))
-    return optimization.FrameInputs((height, width), K, E, soft, gt_boxes, torch.ones(views, instances, dtype=torch.bool, device=device))
+    return optimization.FrameInputs((height, width), K, E, soft, gt_boxes, torch.ones(views, instances, dtype=torch.bool, device=device),
+                                    boxes_3d=out["boxes_3d"][0].contiguous())
 
 
 def scan_frames_dir(folder, limit=0):
@@ -447,6 +448,8 @@ class _RenderWork:
             payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
             labels = self._host_labels(loop.labels, [(frame, self.path_of(frame))]) if self.args.predictions else []
             masks = self._host_masks(loop.masks, [(frame, self.path_of(frame))], [payload]) if self.args.masks else []
+            if self.args.metrics and loop.inputs.boxes_3d is not None:
+                self._host_metrics(loop.metrics, [(frame, self.path_of(frame))], [payload])
         loop.close()
         self._write_labels(labels)
         self._write_masks(masks)
@@ -492,6 +495,22 @@ class _RenderWork:
         self.phase_seconds["masks"] += time.perf_counter() - t0
         return pending
 
+    def _host_metrics(self, device_call, frames, payloads):
+        """--metrics, inside the section that copies the checkpoint payloads: the ONE vsrd_frame_metrics call of a group of frames
+        (`device_call` -> a dictionary or a list of them); every frame that had ground truth gets the reference's six metrics into its
+        checkpoint's `metrics` (next to mask_iou, when --masks put it there) and into the rank's report."""
+        import time
+        from . import formats
+        t0 = time.perf_counter()
+        metrics = device_call()
+        metrics = metrics if isinstance(metrics, list) else [metrics]
+        for (frame, _), entry, payload in zip(frames, metrics, payloads):
+            named = formats.frame_metrics(entry["summary"])
+            if named:
+                payload["metrics"] = dict(payload.get("metrics") or {}, **named)
+                self.frame_metrics[int(frame)] = named
+        self.phase_seconds["metrics"] += time.perf_counter() - t0
+
     def _write_masks(self, pending):
         """masks/view_00.npz of `_host_masks`' frames -- BEFORE their checkpoints, like the label files."""
         import time
@@ -532,6 +551,8 @@ class _RenderWork:
                     payload = formats.checkpoint_payload(slot, step=args.num_steps - 1, metrics={}, host=True)
                     labels = self._host_labels(slot.labels, [(frame, self.path_of(frame))]) if args.predictions else []
                     masks = self._host_masks(slot.masks, [(frame, self.path_of(frame))], [payload]) if args.masks else []
+                    if args.metrics and slot.inputs.boxes_3d is not None:
+                        self._host_metrics(slot.metrics, [(frame, self.path_of(frame))], [payload])
                 self._write_labels(labels)
                 self._write_masks(masks)
                 return payload
@@ -539,8 +560,11 @@ class _RenderWork:
                 if slot is not None:
                     self.slots.put(slot)
 
-        if args.predictions or args.masks:               # (the batch path keeps its own clock, with these keys added)
+        self.frame_metrics = {}
+        if args.predictions or args.masks or args.metrics:               # (the batch path keeps its own clock, with these keys added)
             self.phase_seconds = {}
+            if args.metrics:
+                self.phase_seconds.update(metrics=0.0)
             if args.predictions:
                 self.phase_seconds.update(labels=0.0, labels_write=0.0)
             if args.masks:
@@ -556,7 +580,7 @@ class _RenderWork:
                     gate_capture_seconds=optimization.exclusive_device_access().capture_seconds - self.captures_before,
                     slot_setup_seconds=self.setup_seconds, graphs_per_slot=self.graphs_per_slot, final_losses={int(f): losses[f] for f in sorted(losses)},
                     frames_outside_slots=sorted(fallbacks), unsuitable_founders=self.unsuitable_founders, frames_with_unhealthy_draws=sorted(unhealthy),
-                    phase_seconds=getattr(self, "phase_seconds", None))
+                    phase_seconds=getattr(self, "phase_seconds", None), **({"frame_metrics": self.frame_metrics} if args.metrics else {}))
 
     def _run_batches(self, losses, fallbacks, health):
         """Groups of --frame-batch frames through the FrameBatch: reset row by row, ONE graph replay per (four) step(s) for the whole group,
@@ -569,6 +593,8 @@ class _RenderWork:
             clock.update(labels=0.0, labels_write=0.0)
         if args.masks:
             clock.update(masks=0.0, masks_write=0.0)
+        if args.metrics:
+            clock.update(metrics=0.0)
         while True:
             group = pending_frames(self.queue.take(args.frame_batch), self.path_of)
             if not group:
@@ -599,6 +625,9 @@ class _RenderWork:
                     labels = self._host_labels(lambda: batch.labels(active=len(rows)), rows) if args.predictions else []
                     # --masks: ONE vsrd_frame_masks call for the group; every payload gets its frame's mask_iou
                     masks = self._host_masks(lambda: batch.masks(active=len(rows)), rows, payloads) if args.masks else []
+                    # --metrics: ONE vsrd_frame_metrics call for the group; frames without 3-D ground truth come back with count 0 and are skipped
+                    if args.metrics:
+                        self._host_metrics(lambda: batch.metrics(active=len(rows)), rows, payloads)
                 self._write_labels(labels)
                 self._write_masks(masks)
                 t3 = time.perf_counter()
@@ -665,6 +694,14 @@ def effective_frame_batch(requested: int, total_frames: int, world_size: int) ->
         return 1
     share = -(-max(int(total_frames), 1) // max(int(world_size), 1))
     return max(1, min(int(requested), share))
+
+
+def mean_frame_metrics(reports):
+    """--metrics, the job's line: the mean of each metric over the frames (of every rank's report) that had ground truth, and their number."""
+    from . import formats
+    frames = [named for report in reports for named in (report.get("frame_metrics") or {}).values()]
+    means = {name: sum(named[name] for named in frames) / len(frames) for name in formats.FRAME_METRIC_NAMES} if frames else {}
+    return {"frame_metrics": means, "frame_metrics_frames": len(frames)}
 
 
 def parse_instances(text):
@@ -765,6 +802,12 @@ def main(argv=None):
                              "x surface_masks) -- vsrd_frame_masks, one launch per group of frames -- write them bit-packed to masks/view_00.npz next "
                              "to the frame's checkpoint and store their mean IoU against the masks the frame was fitted to as the checkpoint's "
                              "metric `mask_iou` (tools/select_model.py --metrics mask_iou --maximum).  Needs --out; not with --selftest")
+    parser.add_argument("--metrics", action="store_true",
+                        help="after a frame's steps, evaluate its boxes against the frame's 3-D ground truth (FrameInputs.boxes_3d / a frame pack's "
+                             "boxes_3d; synthetic frames carry their true boxes) -- vsrd_frame_metrics, one launch per group of frames -- and store the "
+                             "reference's iou_3d, iou_bev, accuracy_3d_25, accuracy_bev_25, accuracy_3d_50, accuracy_bev_50 (scripts/main.py:870-924) in "
+                             "the checkpoint's `metrics` (tools/select_model.py); the job's line gets their means over the frames that had ground "
+                             "truth (`frame_metrics`, `frame_metrics_frames`); frames without it are skipped.  Not with --selftest")
     parser.add_argument("--ranks-share-gpu", action="store_true",
                         help="TEST ONLY: every rank on cuda:0, gloo rendezvous (RCCL refuses two ranks on one device); the line says so")
     parser.add_argument("--fresh-loops", action="store_true",
@@ -792,6 +835,8 @@ def main(argv=None):
         raise SystemExit("--predictions writes the labels of optimised frames; --selftest optimises none: drop one of --selftest, --predictions")
     if args.masks and args.selftest:
         raise SystemExit("--masks renders the masks of optimised frames; --selftest optimises none: drop one of --selftest, --masks")
+    if args.metrics and args.selftest:
+        raise SystemExit("--metrics evaluates the boxes of optimised frames; --selftest optimises none: drop one of --selftest, --metrics")
     if args.masks and not args.out:
         raise SystemExit("--masks writes masks/view_00.npz and a mask_iou metric next to every frame's checkpoint: it needs --out")
     if args.frames_dir:
@@ -987,6 +1032,7 @@ def _rank_main(args):
                 "phase_seconds": [r.get("phase_seconds") for r in gathered],
                 **({"predictions": True} if args.predictions else {}),
                 **({"masks": True} if args.masks else {}),      # (--predictions: label files next to every checkpoint)
+                **(mean_frame_metrics(gathered) if args.metrics else {}),
                 "frames_outside_slots": sorted(f for r in gathered for f in r["frames_outside_slots"]),
                 "unsuitable_founders": sorted(f for r in gathered for f in r["unsuitable_founders"]),
                 # frames in which some ray draw ran out of picks / overflowed (read at the end of each frame; RuntimeWarning on stderr)

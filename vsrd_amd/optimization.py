@@ -193,6 +193,9 @@ class FrameInputs:
     soft_masks: torch.Tensor                # [V,H,W,N] re-indexed to the target's instance order (main.py:204-265)
     boxes_2d: torch.Tensor                  # [V,N,2,2] ground-truth 2-D boxes, zeros where invisible
     visible_masks: torch.Tensor             # [V,N] bool
+    # 3-D ground truth for metrics() (main.py:877-886: target_inputs.boxes_3d and the dataset's rectification matrix), optional
+    boxes_3d: Optional[torch.Tensor] = None              # [N,8,3] corners in the target's instance order, in the frame of the decoded boxes; NaN rows = no annotation
+    rectification_matrix: Optional[torch.Tensor] = None  # [3,3] (None: identity)
 
 
 @dataclass
@@ -324,6 +327,15 @@ def _incoming_shape(inputs, shape, capacities=None):
         if not low <= incoming[axis] <= high:
             raise ValueError(f"this loop serves frames of {low}..{high} {name}, got {incoming[axis]}")
     return incoming
+
+
+def _check_ground_truth(inputs, num_instances):
+    """ValueError unless the optional 3-D ground truth of `inputs` -- a frames.FramePack or a FrameInputs -- has the shapes [N,8,3] and [3,3]:
+    checked before a loop writes anything of the frame (construction of the metric buffers, FrameOptimizer.reset)."""
+    for name, shape in (("boxes_3d", (int(num_instances), 8, 3)), ("rectification_matrix", (3, 3))):
+        value = getattr(inputs, name, None)
+        if value is not None and tuple(int(x) for x in value.shape) != shape:
+            raise ValueError(f"{name} of shape {tuple(value.shape)} for a frame of {int(num_instances)} instances: expected {shape}")
 
 
 def _initial_rates(config):
@@ -474,6 +486,7 @@ class FrameOptimizer:
         self._graphs = {}
         self._labels = None
         self._masks = None
+        self._metrics = None
         self._capture_stream = None
         self._eager_graph_steps = {}
         self.pixels_per_view = H * W
@@ -1077,7 +1090,7 @@ class FrameOptimizer:
                            visible=b["visible"])
         intrinsics, extrinsics = frames.camera_matrices(pack, self.device)
         return FrameInputs((H, W), intrinsics, extrinsics, self.flat_masks.view(V, H, W, stride)[..., :N],
-                           b["gt_boxes"][:, :N].unflatten(-1, (2, 2)), b["visible"][:, :N].bool())
+                           b["gt_boxes"][:, :N].unflatten(-1, (2, 2)), b["visible"][:, :N].bool(), *frames.ground_truth_3d(pack, self.device))
 
     def reset(self, inputs: FrameInputs, init_seed=None):
         """Start ANOTHER frame of the same shape in this loop, in place: the new frame's matrices, boxes and soft masks are copied into
@@ -1093,6 +1106,7 @@ class FrameOptimizer:
         # views and 1..capacity instances, any other loop: with its own counts
         V, H, W, N = _incoming_shape(inputs, (self.num_views, *self.inputs.image_size, self.num_instances),
                                      (self.view_capacity, self.capacity) if self._headed else None)
+        _check_ground_truth(inputs, N)           # (before anything of the row is overwritten)
         with _capture_lock, torch.no_grad():
             main = torch.cuda.current_stream(dev)
             main.synchronize()                                      # (replays of the previous frame have finished: nothing reads the buffers)
@@ -1110,6 +1124,8 @@ class FrameOptimizer:
             self.camera_positions.copy_(cam)
             self.ray_directions.copy_(dirs.reshape(-1, 3))
             self.inputs = inputs
+            if self._metrics is not None:
+                self._write_ground_truth(N)      # (the row's 3-D ground truth becomes the new frame's, or none)
             if N != self.num_instances:
                 # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
                 # addresses: the pointer blocks and the captured graphs stay valid)
@@ -1260,6 +1276,68 @@ class FrameOptimizer:
             raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
         self._launch_masks(view=view, threshold=threshold, soft=soft)
         return self._mask_views(threshold, soft)
+
+    # ---- 3-D / BEV IoU metrics against the ground truth (csrc/frame_metrics.h) --------------------------------------------------
+    def _write_ground_truth(self, n):
+        """The row's ground-truth corners and rectification matrix from `self.inputs`: NaN (no annotation) in every slot the frame does not
+        fill -- all of them when the frame has no boxes_3d -- and the identity without a rectification matrix."""
+        state, inp = self._metrics, self.inputs
+        state["gt_boxes_3d"].fill_(float("nan"))
+        if inp.boxes_3d is not None:
+            state["gt_boxes_3d"][:int(n)].copy_(inp.boxes_3d)
+        state["rectification"].copy_(torch.eye(3) if inp.rectification_matrix is None else inp.rectification_matrix)
+
+    def _metric_state(self):
+        """What vsrd_frame_metrics reads and writes beyond the glue's tensors, created at first use -- in the frame's row when there is one (a
+        FrameBatch creates them in every row at once: equal offsets): the ground-truth corners and the rectification matrix, the decoded
+        corners, the IoUs and the summary, laid out for the capacity.  A few KB."""
+        if self._metrics is not None:
+            return self._metrics
+        if not self.fused_glue:
+            raise RuntimeError("metrics() pairs the boxes by the matching the fused glue keeps on the device (graph=True)")
+        N = self.capacity
+        _check_ground_truth(self.inputs, self.num_instances)
+        with _capture_lock, torch.no_grad():
+            new = self._new
+            self._metrics = dict(gt_boxes_3d=new((N, 8, 3), fill=float("nan")), rectification=new((3, 3), fill=0.0), corners=new((N, 8, 3), fill=0.0),
+                                 ious=new((N, 2), fill=float("nan")), summary=new(8, fill=0.0), frame=_lib.FrameConfig.from_buffer_copy(self._frame))
+            self._write_ground_truth(self.num_instances)
+        return self._metrics
+
+    def _launch_metrics(self, frames=None):
+        """ONE vsrd_frame_metrics call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
+        state, det, b = self._metric_state(), self.detector, self._glue
+        frame = state["frame"]
+        frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
+        header = b.get("header")
+        with _capture_lock:
+            _lib.check(_lib.load().vsrd_frame_metrics(
+                frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(state["gt_boxes_3d"]),
+                _lib.ptr(state["rectification"]), b["pd_indices"].data_ptr(), b["gt_indices"].data_ptr(), _lib.ptr(state["corners"]),
+                _lib.ptr(state["ious"]), _lib.ptr(state["summary"]), None if header is None else header.data_ptr(), _lib.stream()))
+
+    def _metric_views(self):
+        state, n = self._metrics, self.num_instances
+        return dict(iou_3d=state["ious"][:n, 0], iou_bev=state["ious"][:n, 1], summary=state["summary"], corners=state["corners"][:n])
+
+    def metrics(self):
+        """The frame's evaluation against its 3-D ground truth (``FrameInputs.boxes_3d``) -- the reference's iou_3d, iou_bev and accuracies
+        (scripts/main.py:870-924) -- by one vsrd_frame_metrics launch on the current stream, no host synchronisation.  The boxes are decoded
+        from the loop's CURRENT parameters, as ``labels()`` decodes them and as a checkpoint stores them, and paired with the ground truth by
+        the LAST STEP's matching (the glue's pd_indices / gt_indices); the reference logs the boxes that step started from, one Adam update
+        earlier.  RuntimeError when no step has run since construction or ``reset()`` (there is no matching yet), ValueError when the
+        frame has no ``boxes_3d``.  A dictionary of device tensors sliced to the frame's own n instances: iou_3d [n], iou_bev [n] (by
+        prediction; NaN where the matched ground-truth slot has no annotation), summary [8] (count, iou_3d, iou_bev, accuracy_3d_25,
+        accuracy_bev_25, accuracy_3d_50, accuracy_bev_50, 0: ``formats.frame_metrics`` names them), corners [n,8,3] (the decoded boxes).
+        They are views of buffers the next call overwrites."""
+        if not self.fused_glue:
+            raise RuntimeError("metrics() pairs the boxes by the matching the fused glue keeps on the device (graph=True)")
+        if self.step_index < 1:
+            raise RuntimeError("metrics() pairs the boxes by the last step's matching: no step has run since the loop was built or reset()")
+        if self.inputs.boxes_3d is None:
+            raise ValueError("metrics() needs the frame's 3-D ground truth: FrameInputs.boxes_3d is None")
+        self._launch_metrics()
+        return self._metric_views()
 
     def close(self):
         """Drop the captured graphs and the scratch buffers (also happens when the optimizer is garbage-collected).  Once per frame
@@ -1437,6 +1515,7 @@ class FrameBatch:
         total += workspace + lib.vsrd_hypernetwork_workspace_bytes(N) + lib.vsrd_frame_scratch_bytes(V, N)
         total += 4 * (3 * N * _lib.MLP_WEIGHTS + 64 * N + 128 * V) + 16 * int(config.num_rays)          # the glue's tables
         total += N * H * ((W + 7) // 8) + 4 * H * W * N + 12 * N     # masks(): bit-packed masks, soft values, counts
+        # (metrics(): 200 N + 68 bytes in five buffers, at most 14 KB: within the slack below)
         return total + (4 << 20)                                     # 256-byte alignment of ~400 buffers, step counters, rates, slack
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
@@ -1494,6 +1573,17 @@ class FrameBatch:
                                "are not in step")
         self._launch_on_rows(active, "mask", FrameOptimizer._mask_state, FrameOptimizer._launch_masks, view=view, threshold=threshold, soft=soft)
         return [m._mask_views(threshold, soft) for m in members]
+
+    def metrics(self, active=None):
+        """The 3-D / BEV IoU metrics of the first ``active`` frames (``FrameOptimizer.metrics``) by ONE vsrd_frame_metrics call for all of
+        them: a list of dictionaries of device tensors, each sliced to its frame's own instance count.  A frame without ``boxes_3d`` is not
+        an error here: its IoUs are NaN and its summary is eight zeros (count 0), for which ``formats.frame_metrics`` gives {}."""
+        active, members = self._members(active)
+        if any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
+            raise RuntimeError("metrics() pairs the boxes by the frames' last step's matching: no step has run since a frame's reset(), or the "
+                               "frames are not in step")
+        self._launch_on_rows(active, "metric", FrameOptimizer._metric_state, FrameOptimizer._launch_metrics)
+        return [m._metric_views() for m in members]
 
     def _phase(self, active):
         _, members = self._members(active)
