@@ -244,3 +244,54 @@ def test_frame_prologue_and_epilogue_header_twins(dev):
     for a, c in zip(*results):
         assert torch.equal(a, c)
     loop.close()
+
+
+def test_outputs_asked_in_any_order_equal_each_frame_alone(dev):
+    """labels() / masks() / metrics() create their buffers at first use, in the order they are first asked for: a batch asked in the order
+    metrics, masks, labels and one asked in the order labels, masks, metrics lay their rows out differently behind what a batch that never
+    asks has, give -- bit for bit -- what each frame gives alone in a slot of its own, and leave the trajectory alone."""
+    import dataclasses
+    from vsrd_amd import launcher, optimization
+    inputs = [launcher.synthetic_frame_inputs(dev, 3, 2, 3, height=32, width=64), launcher.synthetic_frame_inputs(dev, 4, 2, 5, height=32, width=64)]
+    config = optimization.OptimizationConfig(num_samples=40, num_rays=64, warmup_steps=3, num_steps=12, seed=3, mlp_adjoint_item_slots=8)
+
+    def snapshot(result):
+        return {key: value.clone() if isinstance(value, torch.Tensor) else value for key, value in result.items()}
+
+    def same(got, want):
+        return got.keys() == want.keys() and all(torch.equal(got[key], want[key]) if isinstance(want[key], torch.Tensor) else got[key] == want[key] for key in want)
+
+    alone = []
+    for k, frame in enumerate(inputs):
+        loop = optimization.FrameOptimizer(frame, dataclasses.replace(config, init_seed=70 + k), dev, graph=True, persistent=True)
+        loop.run(4, steps_per_graph=1)                  # (one step into the residual phase)
+        alone.append(dict(labels=snapshot(loop.labels()), masks=snapshot(loop.masks(soft=True)), metrics=snapshot(loop.metrics())))
+        torch.cuda.synchronize()
+        loop.close()
+
+    def walk(order):
+        batch = optimization.FrameBatch(inputs, config, dev, init_seeds=[70, 71], max_instances=8)
+        prefix = list(batch.arena.rows[0].layout)
+        batch.run(4, steps_per_graph=1)
+        ask = dict(labels=batch.labels, masks=lambda: batch.masks(soft=True), metrics=batch.metrics)
+        got = {name: [snapshot(entry) for entry in ask[name]()] for name in order}
+        layout = list(batch.arena.rows[0].layout)
+        assert all(row.layout == layout for row in batch.arena.rows) and layout[:len(prefix)] == prefix and list(batch.frames[0]._outputs) == list(order)
+        batch.run(3, steps_per_graph=1)
+        torch.cuda.synchronize()
+        record = [[m._glue["record"].clone(), m._glue["raw_gradients"].clone(), batch.outputs(f)["loss"].clone()] for f, m in enumerate(batch.frames)]
+        record += [[p.detach().clone() for p in m.detector.parameters()] for m in batch.frames]
+        batch.close()
+        return got, layout[len(prefix):], record
+
+    got_a, tail_a, record_a = walk(("metrics", "masks", "labels"))
+    got_b, tail_b, record_b = walk(("labels", "masks", "metrics"))
+    got_c, tail_c, record_c = walk(())
+    for name in ("labels", "masks", "metrics"):
+        for f in range(2):
+            assert same(got_a[name][f], alone[f][name]), (name, f)
+            assert same(got_b[name][f], got_a[name][f]), (name, f)
+    assert tail_c == [] and len(tail_a) == len(tail_b) == 13 and tail_a != tail_b
+    assert sorted(nbytes for _, nbytes in tail_a) == sorted(nbytes for _, nbytes in tail_b)
+    for other in (record_b, record_c):
+        assert all(torch.equal(x, y) for mine, theirs in zip(record_a, other) for x, y in zip(mine, theirs))

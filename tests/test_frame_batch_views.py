@@ -63,7 +63,7 @@ def _pads(member):
     from vsrd_amd import optimization
     v, n, cap = member.num_views, member.num_instances, member.capacity
     pixels = v * member.pixels_per_view
-    det, full, labels = member.detector, member._full, member._labels
+    det, full, labels = member.detector, member._full, member._outputs["labels"]
     assert full["extrinsics"].shape[0] == member.view_capacity == VIEW_CAPACITY and full["flat_masks"].shape == (VIEW_CAPACITY * member.pixels_per_view, cap)
     pads = [(full[name][v:], "nan") for name in ("camera_positions", "extrinsics", "intrinsics", "gt_boxes")]
     pads += [(full[name][pixels:], "nan") for name in ("ray_directions", "flat_masks", "sampling_weights")]
@@ -135,7 +135,7 @@ def test_frames_of_different_view_counts_walk_their_own_trajectories(dev, split_
     assert all(m.capacity == CAPACITY and m.view_capacity == VIEW_CAPACITY for m in batch.frames)
     batch.capture_all(actives=[4, 2])
     for m in batch.frames:
-        m._label_state()                 # (the label outputs exist in every row before the pads are filled)
+        m._output_state("labels")                 # (the label outputs exist in every row before the pads are filled)
     for group, active in (([0, 1, 2, 3], 4), ([4, 5], 2)):
         for row, k in enumerate(group):
             assert batch.reset(row, frames[k], init_seed=70 + k)

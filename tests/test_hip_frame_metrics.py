@@ -591,12 +591,12 @@ def test_frame_optimizer_metrics_and_reset(dev):
     loop.run(1, steps_per_graph=1)
     with pytest.raises(ValueError, match="boxes_3d"):
         loop.metrics()
-    assert bool(torch.isnan(loop._metrics["gt_boxes_3d"]).all())
+    assert bool(torch.isnan(loop._outputs["metrics"]["gt_boxes_3d"]).all())
     # the same through frame packs: a pack with boxes_3d replaces the row's ground truth, a pack without clears it
     pack = make_frame_packs().make_pack(4, 2, *SIZE, 3)
     assert pack.boxes_3d.shape == (3, 8, 3)
     assert loop.reset(pack, init_seed=72)
-    assert torch.equal(loop._metrics["gt_boxes_3d"].cpu(), torch.from_numpy(pack.boxes_3d)) and torch.equal(loop.inputs.boxes_3d.cpu(), torch.from_numpy(pack.boxes_3d))
+    assert torch.equal(loop._outputs["metrics"]["gt_boxes_3d"].cpu(), torch.from_numpy(pack.boxes_3d)) and torch.equal(loop.inputs.boxes_3d.cpu(), torch.from_numpy(pack.boxes_3d))
     loop.run(2, steps_per_graph=1)
     packed = snapshot(loop.metrics())
     want = by_hand(dev, loop)
@@ -606,7 +606,7 @@ def test_frame_optimizer_metrics_and_reset(dev):
     loop.run(1, steps_per_graph=1)
     with pytest.raises(ValueError, match="boxes_3d"):
         loop.metrics()
-    assert bool(torch.isnan(loop._metrics["gt_boxes_3d"]).all())
+    assert bool(torch.isnan(loop._outputs["metrics"]["gt_boxes_3d"]).all())
     # a ground truth of the wrong shape is refused before the row is touched
     before = loop.flat_masks.clone()
     with pytest.raises(ValueError, match="boxes_3d"):
@@ -640,7 +640,7 @@ def test_frame_batch_metrics_equal_each_frame_alone_and_leave_the_trajectory(dev
         record = [dict(record=member._glue["record"].clone(), raw_gradients=member._glue["raw_gradients"].clone(), loss=batch.outputs(f)["loss"].clone())
                   for f, member in enumerate(batch.frames)]
         state = [parameters(member) for member in batch.frames]
-        laid_out = batch.frames[0]._metrics is not None
+        laid_out = batch.frames[0]._outputs.get("metrics") is not None
         if with_metrics:
             # a row whose frame has no ground truth is no error in a batch: count 0, NaN IoUs, no metrics; its neighbour is evaluated as ever
             from vsrd_amd import formats

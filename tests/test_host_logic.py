@@ -610,3 +610,129 @@ def test_reset_admits_the_loops_shape_or_up_to_its_capacities():
     wrong.image_size = (4, 8)            # a FrameInputs whose image_size is not its soft masks'
     with pytest.raises(ValueError, match="image_size"):
         optimization._incoming_shape(wrong, loop, capacities)
+
+
+def test_frame_output_buffer_lists_and_their_rows():
+    """The buffers labels() / masks() / metrics() create at first use (optimization._OUTPUTS[...].buffers: plain functions of the capacities
+    and the image size), against literals: names, shapes, dtypes, fills and order; and the rows they give in an arena, in two orders of
+    first use -- equal in both rows, at the offsets 256-byte alignment gives."""
+    from vsrd_amd import optimization
+    V, N, H, W = 3, 5, 6, 9
+    f32, nan = torch.float32, float("nan")
+    want = dict(labels=[("camera_corners", (V, N, 8, 3), f32, 0.0), ("boxes_2d", (V, N, 4), f32, 0.0), ("mean_iou", (N, N), f32, 0.0),
+                        ("matched_gt", (N,), torch.int64, 0), ("confidences", (N,), f32, 0.0)],
+                masks=[("inside", (N, H, 2), torch.uint8, 0), ("soft", (H * W, N), f32, 0.0), ("counts", (N, 3), torch.int32, 0)],
+                metrics=[("gt_boxes_3d", (N, 8, 3), f32, nan), ("rectification", (3, 3), f32, 0.0), ("corners", (N, 8, 3), f32, 0.0),
+                         ("ious", (N, 2), f32, nan), ("summary", (8,), f32, 0.0)])
+    assert list(optimization._OUTPUTS) == ["labels", "masks", "metrics"]
+    for name, buffers in want.items():
+        got = optimization._OUTPUTS[name].buffers(V, N, H, W)
+        assert [(key, tuple(shape), dtype) for key, shape, dtype, _ in got] == [(key, shape, dtype) for key, shape, dtype, _ in buffers], name
+        assert all(fill == expected or fill != fill and expected != expected for (*_, fill), (*_, expected) in zip(got, buffers)), name
+    item = {f32: 4, torch.int64: 8, torch.int32: 4, torch.uint8: 1}
+    for order in (("labels", "masks", "metrics"), ("metrics", "masks", "labels")):
+        arena = optimization.FrameArena(2, 20_000, "cpu")
+        layout, cursor = [], 0
+        for name in order:
+            for _, shape, dtype, _ in want[name]:
+                nbytes = item[dtype] * functools.reduce(lambda a, b: a * b, shape)
+                layout.append((cursor, nbytes))
+                cursor = (cursor + nbytes + 255) // 256 * 256
+        for row in arena.rows:
+            for name in order:
+                for key, shape, dtype, fill in optimization._OUTPUTS[name].buffers(V, N, H, W):
+                    tensor = row.new(shape, dtype, fill)
+                    assert tensor.shape == tuple(shape) and tensor.dtype == dtype
+                    assert bool(torch.isnan(tensor).all() if fill != fill else (tensor == fill).all()), (name, key)
+        assert arena.rows[0].layout == arena.rows[1].layout == layout, order
+
+
+class _StandInSource:
+    """What the launcher's `_collect` asks of a loop (`active` None) or a batch: labels / masks / metrics of the documented shapes, on the host."""
+
+    def __init__(self, counts, summaries, boxes_3d="given"):
+        self.counts, self.summaries, self.asked = counts, summaries, []
+        self.inputs = type("Inputs", (), dict(boxes_3d=None if boxes_3d is None else torch.zeros(counts[0], 8, 3)))()
+
+    def _answer(self, name, active, make):
+        self.asked.append(name)
+        return make(0) if active is None else [make(f) for f in range(active)]
+
+    def labels(self, active=None):
+        def make(f):
+            n = self.counts[f]
+            corners = torch.tensor([[0., 0, 0], [1, 0, 0], [1, 0, 2], [0, 0, 2], [0, 1, 0], [1, 1, 0], [1, 1, 2], [0, 1, 2]]) + torch.tensor([0.0, 0.0, 10.0 + f])
+            return dict(boxes_3d=corners.expand(1, n, 8, 3).clone(), boxes_2d=torch.tensor([[10.0, 20.0], [30.0, 40.0]]).expand(1, n, 2, 2).clone(),
+                        confidences=torch.full((n,), 0.5), matched_gt=torch.arange(n), mean_iou=torch.eye(n))
+        return self._answer("labels", active, make)
+
+    def masks(self, active=None):
+        def make(f):
+            n = self.counts[f]
+            return dict(inside=torch.zeros(n, 4, 2, dtype=torch.uint8), counts=torch.ones(n, 3, dtype=torch.int32), mask_iou=torch.full((n,), 0.25 * (f + 1)),
+                        threshold=0.5, shape=(4, 9), soft=torch.zeros(4, 9, n))
+        return self._answer("masks", active, make)
+
+    def metrics(self, active=None):
+        return self._answer("metrics", active, lambda f: dict(summary=torch.tensor(self.summaries[f]), iou_3d=torch.zeros(self.counts[f])))
+
+
+def _render_work(out, **flags):
+    import argparse
+    from vsrd_amd import launcher
+    args = argparse.Namespace(num_steps=3, warmup_steps=1, rays=8, samples=8, fp32_mlp=False, adjoint_item_slots=0,
+                              **dict(dict(predictions=False, masks=False, metrics=False), **flags))
+    work = launcher._RenderWork(args, dict(out=str(out), seed=0), "cpu", None)
+    work._begin_outputs()
+    return work
+
+
+def test_launcher_collects_and_writes_a_frames_outputs_in_one_place(tmp_path):
+    """launcher._RenderWork._collect / _write_outputs on stand-in sources: one loop, and a batch of two."""
+    from vsrd_amd import formats
+    summary, empty = [2.0, 0.5, 0.75, 1.0, 1.0, 0.5, 1.0, 0.0], [0.0] * 8
+    files = ("predictions/view_00.json", "labels/view_00.txt", "masks/view_00.npz")
+
+    def folder(work, frame):
+        return os.path.dirname(work.path_of(frame))
+    # ---- one loop, every flag ----
+    work = _render_work(tmp_path / "loop", predictions=True, masks=True, metrics=True)
+    assert set(work.phase_seconds) == {"labels", "labels_write", "masks", "masks_write", "metrics"}
+    loop, payloads = _StandInSource([3], [summary]), [dict(metrics={})]
+    pending = work._collect(loop, [(7, work.path_of(7))], payloads)
+    assert loop.asked == ["labels", "masks", "metrics"] and len(pending) == 2 and not os.path.exists(folder(work, 7))
+    assert work.phase_seconds["labels_write"] == 0.0 and work.phase_seconds["masks_write"] == 0.0
+    work._write_outputs(pending)
+    assert all(os.path.exists(os.path.join(folder(work, 7), name)) for name in files) and not os.path.exists(work.path_of(7))    # (before any checkpoint)
+    assert set(payloads[0]["metrics"]) == {"mask_iou", *formats.FRAME_METRIC_NAMES} and payloads[0]["metrics"]["mask_iou"] == 0.25
+    assert work.frame_metrics == {7: formats.frame_metrics(summary)} and work.frame_metrics[7]["iou_bev"] == 0.75
+    assert all(work.phase_seconds[key] > 0.0 for key in ("labels", "labels_write", "masks", "masks_write", "metrics"))
+    assert "soft" not in formats.load_frame_masks(folder(work, 7)) and formats.load_frame_masks(folder(work, 7))["shape"] == (4, 9)
+    # ---- a loop whose frame has no 3-D ground truth is never asked for metrics ----
+    work = _render_work(tmp_path / "bare", masks=True, metrics=True)
+    assert set(work.phase_seconds) == {"masks", "masks_write", "metrics"}
+    bare, payloads = _StandInSource([3], [summary], boxes_3d=None), [dict(metrics={})]
+    work._write_outputs(work._collect(bare, [(1, work.path_of(1))], payloads))
+    assert bare.asked == ["masks"] and payloads[0]["metrics"] == dict(mask_iou=0.25) and work.frame_metrics == {} and work.phase_seconds["metrics"] == 0.0
+    assert os.listdir(folder(work, 1)) == ["masks"]
+    # ---- a batch of two: always asked; the member with an all-zero summary is skipped ----
+    work = _render_work(tmp_path / "batch", predictions=True, masks=True, metrics=True)
+    batch, payloads = _StandInSource([3, 5], [empty, summary], boxes_3d=None), [dict(metrics={}), dict(metrics={})]
+    rows = [(4, work.path_of(4)), (9, work.path_of(9))]
+    pending = work._collect(batch, rows, payloads, active=2)
+    assert batch.asked == ["labels", "masks", "metrics"] and [key for key, *_ in pending] == ["labels_write"] * 2 + ["masks_write"] * 2
+    work._write_outputs(pending)
+    for frame in (4, 9):
+        assert all(os.path.exists(os.path.join(folder(work, frame), name)) for name in files) and not os.path.exists(work.path_of(frame))
+    assert payloads[0]["metrics"] == dict(mask_iou=0.25) and set(payloads[1]["metrics"]) == {"mask_iou", *formats.FRAME_METRIC_NAMES}
+    assert payloads[1]["metrics"]["mask_iou"] == 0.5 and work.frame_metrics == {9: formats.frame_metrics(summary)}
+    # ---- one flag: its keys only; no flag: no clock, nothing asked, nothing written ----
+    work = _render_work(tmp_path / "labels", predictions=True)
+    only = _StandInSource([2], [summary])
+    work._write_outputs(work._collect(only, [(0, work.path_of(0))], [dict(metrics={})]))
+    assert set(work.phase_seconds) == {"labels", "labels_write"} and only.asked == ["labels"] and sorted(os.listdir(folder(work, 0))) == ["labels", "predictions"]
+    work = _render_work(tmp_path / "none")
+    nothing, payloads = _StandInSource([2], [summary]), [dict(metrics={})]
+    pending = work._collect(nothing, [(0, work.path_of(0))], payloads)
+    work._write_outputs(pending)
+    assert work.phase_seconds is None and nothing.asked == [] and pending == [] and payloads == [dict(metrics={})] and not os.path.exists(tmp_path / "none")

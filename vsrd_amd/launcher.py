@@ -439,90 +439,79 @@ class _RenderWork:
 
     def _own_loop(self, frame):
         """A frame outside the slots / the batch (--fresh-loops, or importance weights that do not suit the table sampler): a loop of its own."""
-        from . import formats, optimization
+        from . import optimization
         loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(frame)), self.optimization_config(init_seed=self.init_seed(frame)), self.device, graph=True)
-        record = loop.run(self.args.num_steps)
-        with optimization.exclusive_device_access():
-            torch.cuda.current_stream().synchronize()
-            loss = float(record["loss"])
-            payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
-            labels = self._host_labels(loop.labels, [(frame, self.path_of(frame))]) if self.args.predictions else []
-            masks = self._host_masks(loop.masks, [(frame, self.path_of(frame))], [payload]) if self.args.masks else []
-            if self.args.metrics and loop.inputs.boxes_3d is not None:
-                self._host_metrics(loop.metrics, [(frame, self.path_of(frame))], [payload])
+        loss, payload, pending = self._finish_alone(frame, loop, loop.run(self.args.num_steps))
         loop.close()
-        self._write_labels(labels)
-        self._write_masks(masks)
+        self._write_outputs(pending)
         return loss, payload
 
-    def _host_labels(self, device_call, frames):
-        """--predictions, inside the section that copies the checkpoint payloads: the ONE vsrd_frame_labels call of a group of frames
-        (`device_call` -> a dictionary or a list of them) and its copies to the host -> [(frame folder, labels)] for `_write_labels`."""
-        import time
-        from . import formats
-        t0 = time.perf_counter()
-        labels = device_call()
-        labels = labels if isinstance(labels, list) else [labels]
-        pending = [(os.path.dirname(path), formats.to_host(entry)) for (_, path), entry in zip(frames, labels)]
-        self.phase_seconds["labels"] += time.perf_counter() - t0
-        return pending
+    def _finish_alone(self, frame, loop, record, health=None):
+        """The end of a frame that ran alone, in a slot or in a loop of its own, `record` its last step's: its loss, the sampler's `health`
+        where the caller reads it, its checkpoint payload and its outputs -> (loss, payload, pending file writes)."""
+        from . import formats, optimization
+        with optimization.exclusive_device_access():       # (host synchronisations and copies: refused now and then while another frame's thread captures)
+            torch.cuda.current_stream().synchronize()
+            loss = float(record["loss"])
+            if health is not None:
+                health(frame, loop)
+            payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
+            return loss, payload, self._collect(loop, [(frame, self.path_of(frame))], [payload])
 
-    def _write_labels(self, pending):
-        """The label files of `_host_labels`' frames -- BEFORE their checkpoints: the final checkpoint is what marks a frame as done
-        (pending_frames), so a frame that has one has its labels."""
-        import time
-        from . import formats
-        t0 = time.perf_counter()
-        for folder, labels in pending:
-            formats.save_frame_labels(folder, labels)
-        if pending:
-            self.phase_seconds["labels_write"] += time.perf_counter() - t0
+    def _begin_outputs(self):
+        """The clock's keys of --predictions / --masks / --metrics (None without any of them: outside the batch path such a job has no
+        clock) and the rank's report of per-frame metrics."""
+        args = self.args
+        keys = [key for wanted, keys in ((args.predictions, ("labels", "labels_write")), (args.masks, ("masks", "masks_write")), (args.metrics, ("metrics",)))
+                if wanted for key in keys]
+        self.phase_seconds, self.frame_metrics = dict.fromkeys(keys, 0.0) or None, {}
 
-    def _host_masks(self, device_call, frames, payloads):
-        """--masks, inside the section that copies the checkpoint payloads: the ONE vsrd_frame_masks call of a group of frames (`device_call`
-        -> a dictionary or a list of them: the target view's predicted masks), its copies to the host -> [(frame folder, masks)] for
-        `_write_masks`, and every frame's checkpoint metric: mask_iou, the mean over its instances."""
+    def _collect(self, source, frames, payloads, active=None):
+        """What the flags ask of a group of finished frames, inside the section that copies their checkpoint `payloads`: `source` is the
+        loop of ONE frame, or the batch whose first `active` rows hold the `frames` = [(frame, checkpoint path)].  In this order, each ONE
+        vsrd_frame_* call for the group and its copies to the host: --predictions, the labels; --masks, the target view's predicted masks,
+        and every payload's metric mask_iou (the mean over its instances); --metrics, the reference's six metrics into the payload's
+        `metrics` and the rank's report, for every frame that had 3-D ground truth (a loop without it is not asked; a batch is, and its
+        frames without come back with count 0 and are skipped).  Returns the pending file writes for `_write_outputs`."""
         import time
         from . import formats
-        t0 = time.perf_counter()
-        masks = device_call()
-        masks = masks if isinstance(masks, list) else [masks]
-        pending = []
-        for (_, path), entry, payload in zip(frames, masks, payloads):
+        args, pending = self.args, []
+
+        def labels(frame, folder, entry, payload):
+            pending.append(("labels_write", formats.save_frame_labels, (folder, formats.to_host(entry))))
+
+        def masks(frame, folder, entry, payload):
             host = formats.to_host({key: value for key, value in entry.items() if key != "soft"})
             payload["metrics"] = dict(payload.get("metrics") or {}, mask_iou=float(host["mask_iou"].mean()))
-            pending.append((os.path.dirname(path), host))
-        self.phase_seconds["masks"] += time.perf_counter() - t0
-        return pending
+            pending.append(("masks_write", formats.save_frame_masks, (folder, host, host["shape"])))
 
-    def _host_metrics(self, device_call, frames, payloads):
-        """--metrics, inside the section that copies the checkpoint payloads: the ONE vsrd_frame_metrics call of a group of frames
-        (`device_call` -> a dictionary or a list of them); every frame that had ground truth gets the reference's six metrics into its
-        checkpoint's `metrics` (next to mask_iou, when --masks put it there) and into the rank's report."""
-        import time
-        from . import formats
-        t0 = time.perf_counter()
-        metrics = device_call()
-        metrics = metrics if isinstance(metrics, list) else [metrics]
-        for (frame, _), entry, payload in zip(frames, metrics, payloads):
+        def metrics(frame, folder, entry, payload):
             named = formats.frame_metrics(entry["summary"])
             if named:
                 payload["metrics"] = dict(payload.get("metrics") or {}, **named)
                 self.frame_metrics[int(frame)] = named
-        self.phase_seconds["metrics"] += time.perf_counter() - t0
 
-    def _write_masks(self, pending):
-        """masks/view_00.npz of `_host_masks`' frames -- BEFORE their checkpoints, like the label files."""
+        for key, wanted, each in (("labels", args.predictions, labels), ("masks", args.masks, masks),
+                                  ("metrics", args.metrics and (active is not None or source.inputs.boxes_3d is not None), metrics)):
+            if wanted:
+                t0 = time.perf_counter()
+                entries = getattr(source, key)() if active is None else getattr(source, key)(active=active)
+                for (frame, path), entry, payload in zip(frames, entries if isinstance(entries, list) else [entries], payloads):
+                    each(frame, os.path.dirname(path), entry, payload)
+                self.phase_seconds[key] += time.perf_counter() - t0
+        return pending
+
+    def _write_outputs(self, pending):
+        """The label and mask files `_collect` left pending -- BEFORE the frames' checkpoints: the final checkpoint is what marks a frame as
+        done (pending_frames), so a frame that has one has its files."""
         import time
-        from . import formats
-        t0 = time.perf_counter()
-        for folder, masks in pending:
-            formats.save_frame_masks(folder, masks, masks["shape"])
-        if pending:
-            self.phase_seconds["masks_write"] += time.perf_counter() - t0
+        for key, save, arguments in pending:
+            t0 = time.perf_counter()
+            save(*arguments)
+            self.phase_seconds[key] += time.perf_counter() - t0
 
     def run(self):
-        from . import formats, optimization
+        from . import optimization
         args, losses, fallbacks, unhealthy = self.args, {}, [], []
 
         def health(frame, loop):
@@ -543,32 +532,14 @@ class _RenderWork:
                     fallbacks.append(int(frame))
                     losses[frame], payload = self._own_loop(frame)
                     return payload
-                record = slot.run(args.num_steps)
-                with optimization.exclusive_device_access():       # (host synchronisations and copies: refused now and then while another frame's thread captures)
-                    torch.cuda.current_stream().synchronize()
-                    losses[frame] = float(record["loss"])
-                    health(frame, slot)
-                    payload = formats.checkpoint_payload(slot, step=args.num_steps - 1, metrics={}, host=True)
-                    labels = self._host_labels(slot.labels, [(frame, self.path_of(frame))]) if args.predictions else []
-                    masks = self._host_masks(slot.masks, [(frame, self.path_of(frame))], [payload]) if args.masks else []
-                    if args.metrics and slot.inputs.boxes_3d is not None:
-                        self._host_metrics(slot.metrics, [(frame, self.path_of(frame))], [payload])
-                self._write_labels(labels)
-                self._write_masks(masks)
+                losses[frame], payload, pending = self._finish_alone(frame, slot, slot.run(args.num_steps), health)
+                self._write_outputs(pending)
                 return payload
             finally:
                 if slot is not None:
                     self.slots.put(slot)
 
-        self.frame_metrics = {}
-        if args.predictions or args.masks or args.metrics:               # (the batch path keeps its own clock, with these keys added)
-            self.phase_seconds = {}
-            if args.metrics:
-                self.phase_seconds.update(metrics=0.0)
-            if args.predictions:
-                self.phase_seconds.update(labels=0.0, labels_write=0.0)
-            if args.masks:
-                self.phase_seconds.update(masks=0.0, masks_write=0.0)
+        self._begin_outputs()                   # (the batch path keeps a clock of its own, with these keys added)
         self._have_slots = not args.fresh_loops and not self.slots.empty()
         if self.batch is not None:
             done = self._run_batches(losses, fallbacks, health)
@@ -580,7 +551,7 @@ class _RenderWork:
                     gate_capture_seconds=optimization.exclusive_device_access().capture_seconds - self.captures_before,
                     slot_setup_seconds=self.setup_seconds, graphs_per_slot=self.graphs_per_slot, final_losses={int(f): losses[f] for f in sorted(losses)},
                     frames_outside_slots=sorted(fallbacks), unsuitable_founders=self.unsuitable_founders, frames_with_unhealthy_draws=sorted(unhealthy),
-                    phase_seconds=getattr(self, "phase_seconds", None), **({"frame_metrics": self.frame_metrics} if args.metrics else {}))
+                    phase_seconds=self.phase_seconds, **({"frame_metrics": self.frame_metrics} if args.metrics else {}))
 
     def _run_batches(self, losses, fallbacks, health):
         """Groups of --frame-batch frames through the FrameBatch: reset row by row, ONE graph replay per (four) step(s) for the whole group,
@@ -588,13 +559,7 @@ class _RenderWork:
         import time
         from . import formats, optimization
         args, batch, done = self.args, self.batch, []
-        clock = self.phase_seconds = dict(inputs=0.0, reset=0.0, steps=0.0, checkpoint_copy=0.0, checkpoint_write=0.0)
-        if args.predictions:
-            clock.update(labels=0.0, labels_write=0.0)
-        if args.masks:
-            clock.update(masks=0.0, masks_write=0.0)
-        if args.metrics:
-            clock.update(metrics=0.0)
+        clock = self.phase_seconds = dict(inputs=0.0, reset=0.0, steps=0.0, checkpoint_copy=0.0, checkpoint_write=0.0, **(self.phase_seconds or {}))
         while True:
             group = pending_frames(self.queue.take(args.frame_batch), self.path_of)
             if not group:
@@ -621,15 +586,8 @@ class _RenderWork:
                         health(frame, batch.frames[row])
                         payloads.append(formats.checkpoint_payload(batch.frames[row], step=args.num_steps - 1, metrics={}, host=True))
                     t2 = time.perf_counter()
-                    # --predictions: ONE vsrd_frame_labels call for the group, copied to the host with the payloads
-                    labels = self._host_labels(lambda: batch.labels(active=len(rows)), rows) if args.predictions else []
-                    # --masks: ONE vsrd_frame_masks call for the group; every payload gets its frame's mask_iou
-                    masks = self._host_masks(lambda: batch.masks(active=len(rows)), rows, payloads) if args.masks else []
-                    # --metrics: ONE vsrd_frame_metrics call for the group; frames without 3-D ground truth come back with count 0 and are skipped
-                    if args.metrics:
-                        self._host_metrics(lambda: batch.metrics(active=len(rows)), rows, payloads)
-                self._write_labels(labels)
-                self._write_masks(masks)
+                    pending = self._collect(batch, rows, payloads, active=len(rows))
+                self._write_outputs(pending)
                 t3 = time.perf_counter()
                 for (frame, path), payload in zip(rows, payloads):
                     formats.atomic_torch_save(payload, path)

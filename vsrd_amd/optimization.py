@@ -409,6 +409,111 @@ def mask_iou(counts):
     return torch.where(union > 0, inter / union.clamp(min=1.0), torch.zeros_like(union))
 
 
+# ---- what a frame can be asked for after its steps: labels(), masks(), metrics() --------------------------------------------------------
+@dataclass(frozen=True)
+class _FrameOutput:
+    """What differs between the outputs; `FrameOptimizer._output_state` / `_launch_output` / `_ask` and `FrameBatch._ask` are the ONE path all take."""
+    buffers: object                  # (V, N, H, W), the capacities -> [(name, shape, dtype, fill)] of what vsrd writes, in order: a plain function, no device
+    launch: object                   # (loop, state, frame, header, **arguments) -> the status of the ONE vsrd_frame_* call; `frame`: the call's own frame config
+    views: object                    # (loop, state, **arguments) -> the caller's dictionary: the buffers sliced to the frame's own V views / n instances
+    last_step: Optional[str] = None  # what the output reads of the LAST STEP in the fused glue's tensors (it needs the glue AND a step to have run: the two needs coincide in today's outputs, one that had only one of them would split this field)
+
+
+def _check_asked(name, members):
+    """RuntimeError unless the loops `members` -- one loop, or the active frames of a batch -- can be asked for output `name` now."""
+    reads = _OUTPUTS[name].last_step
+    if reads and not members[0].fused_glue:
+        raise RuntimeError(f"{name}() reads the {reads} the fused glue keeps on the device (graph=True)")
+    if reads and any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
+        raise RuntimeError(f"{name}() reads the {reads} of the last step: no step has run since the loop was built or reset() (or, in a "
+                           "batch, the frames are not in step)")
+
+
+def _label_buffers(V, N, H, W):
+    f32 = torch.float32
+    return [("camera_corners", (V, N, 8, 3), f32, 0.0), ("boxes_2d", (V, N, 4), f32, 0.0), ("mean_iou", (N, N), f32, 0.0),
+            ("matched_gt", (N,), torch.int64, 0), ("confidences", (N,), f32, 0.0)]
+
+
+def _launch_labels(loop, state, frame, header):
+    # (a loop without the fused glue keeps float32 copies of its inputs' tables in the state: FrameOptimizer.labels)
+    det, t = loop.detector, loop._glue if loop.fused_glue else state["tables"]
+    return _lib.load().vsrd_frame_labels(
+        frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(t["extrinsics"]),
+        _lib.ptr(t["intrinsics"]), _lib.ptr(t["gt_boxes"]), t["visible"].data_ptr(), _lib.ptr(state["camera_corners"]), _lib.ptr(state["boxes_2d"]),
+        _lib.ptr(state["mean_iou"]), state["matched_gt"].data_ptr(), _lib.ptr(state["confidences"]), header, _lib.stream())
+
+
+def _label_views(loop, state):
+    n, v = loop.num_instances, loop.num_views
+    return dict(boxes_3d=state["camera_corners"][:v, :n], boxes_2d=state["boxes_2d"][:v, :n].unflatten(-1, (2, 2)), confidences=state["confidences"][:n],
+                matched_gt=state["matched_gt"][:n], mean_iou=state["mean_iou"][:n, :n])
+
+
+def _mask_buffers(V, N, H, W):           # (the bit-packed masks, the soft values and the pixel counts)
+    return [("inside", (N, H, (W + 7) // 8), torch.uint8, 0), ("soft", (H * W, N), torch.float32, 0.0), ("counts", (N, 3), torch.int32, 0)]
+
+
+def _launch_masks(loop, state, frame, header, view=0, threshold=0.5, soft=False):
+    cfg, b = loop.config, loop._glue
+    H, W = (int(x) for x in loop.inputs.image_size)
+    from .rendering import renderers
+    # the field the last step rendered: its instance block, and in the residual phase its (centred) MLP weights, exact-fp32 products
+    residual = loop.step_index - 1 >= cfg.warmup_steps
+    flags = renderers._base_flags() & ~_lib.FLAG_MLP_SPLIT_BF16
+    if residual:
+        if not loop.fused_hypernetwork:
+            raise RuntimeError("masks() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
+        flags |= _lib.FLAG_MLP_WEIGHTS_CENTRED
+    elif cfg.skip_exact_misses:
+        flags |= _lib.FLAG_SKIP_EXACT_MISSES
+    field = _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
+    config = _lib.make_config(0, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, seed=cfg.seed, stream_offset=loop.step_tensor, flags=flags,
+                              schedule=loop.schedule, frames=(frame.num_frames, frame.frame_stride))
+    masks = _lib.FrameMasksConfig(int(view), loop.view_capacity, H, W, int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria),
+                                  float(cfg.surface_bounding_radius), float(threshold), loop.capacity)
+    return _lib.load().vsrd_frame_masks(
+        field, config, masks, _lib.ptr(loop.camera_positions), _lib.ptr(loop.ray_directions), None, None, _lib.ptr(b["masks"]),
+        b["target_columns"].data_ptr(), state["inside"].data_ptr(), _lib.ptr(state["soft"]) if soft else None, state["counts"].data_ptr(),
+        header, _lib.stream())
+
+
+def _mask_views(loop, state, view=0, threshold=0.5, soft=False):
+    n = loop.num_instances
+    H, W = (int(x) for x in loop.inputs.image_size)
+    counts = state["counts"][:n]
+    result = dict(inside=state["inside"][:n], counts=counts, mask_iou=mask_iou(counts), threshold=float(threshold), shape=(H, W))
+    if soft:
+        result["soft"] = state["soft"].view(H, W, loop.capacity)[:, :, :n]
+    return result
+
+
+def _metric_buffers(V, N, H, W):
+    """Beyond the glue's tensors: the ground-truth corners and the rectification matrix (read); the decoded corners, the IoUs, the summary."""
+    f32, nan = torch.float32, float("nan")
+    return [("gt_boxes_3d", (N, 8, 3), f32, nan), ("rectification", (3, 3), f32, 0.0), ("corners", (N, 8, 3), f32, 0.0), ("ious", (N, 2), f32, nan),
+            ("summary", (8,), f32, 0.0)]
+
+
+def _launch_metrics(loop, state, frame, header):
+    det, b = loop.detector, loop._glue
+    return _lib.load().vsrd_frame_metrics(
+        frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(state["gt_boxes_3d"]),
+        _lib.ptr(state["rectification"]), b["pd_indices"].data_ptr(), b["gt_indices"].data_ptr(), _lib.ptr(state["corners"]),
+        _lib.ptr(state["ious"]), _lib.ptr(state["summary"]), header, _lib.stream())
+
+
+def _metric_views(loop, state):
+    n = loop.num_instances
+    return dict(iou_3d=state["ious"][:n, 0], iou_bev=state["ious"][:n, 1], summary=state["summary"], corners=state["corners"][:n])
+
+
+_OUTPUTS = dict(
+    labels=_FrameOutput(_label_buffers, _launch_labels, _label_views),                                        # csrc/frame_labels.h
+    masks=_FrameOutput(_mask_buffers, _launch_masks, _mask_views, last_step="field block"),                   # csrc/frame_masks.h
+    metrics=_FrameOutput(_metric_buffers, _launch_metrics, _metric_views, last_step="matching"))              # csrc/frame_metrics.h
+
+
 class FrameOptimizer:
     """``graph=True``: the step is captured in a hipGraph and replayed.  ``fused_glue`` (default: on in graph mode): everything around
     the render launch that concerns the boxes -- decode, projection, matching, projection losses and their gradients, schedules,
@@ -484,9 +589,7 @@ class FrameOptimizer:
             self.workspace.keep_outgrown = True          # a captured graph holds the buffer's address: an outgrown buffer must outlive it
             self.workspace.reserve(self.device, self.capacity, residual=True, step_shape=(config.num_samples, config.num_rays))
         self._graphs = {}
-        self._labels = None
-        self._masks = None
-        self._metrics = None
+        self._outputs = {}                  # labels() / masks() / metrics(): the buffers of each, by name, created at its first use
         self._capture_stream = None
         self._eager_graph_steps = {}
         self.pixels_per_view = H * W
@@ -1124,7 +1227,7 @@ class FrameOptimizer:
             self.camera_positions.copy_(cam)
             self.ray_directions.copy_(dirs.reshape(-1, 3))
             self.inputs = inputs
-            if self._metrics is not None:
+            if "metrics" in self._outputs:
                 self._write_ground_truth(N)      # (the row's 3-D ground truth becomes the new frame's, or none)
             if N != self.num_instances:
                 # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
@@ -1165,102 +1268,46 @@ class FrameOptimizer:
         with torch.no_grad():
             return self.detector()
 
-    # ---- pseudo-labels (csrc/frame_labels.h) -------------------------------------------------------------------------------
-    def _label_state(self):
-        """What vsrd_frame_labels writes, created at first use -- in the frame's row when there is one (a FrameBatch creates them in every
-        row at once: equal offsets) -- and what it reads: the loop's own camera, ground-truth and header tensors (a loop without the fused
-        glue keeps float32 copies of its inputs' here)."""
-        if self._labels is not None:
-            return self._labels
-        V, N = self.view_capacity, self.capacity
-        with _capture_lock, torch.no_grad():
-            new = self._new
-            state = dict(camera_corners=new((V, N, 8, 3), fill=0.0), boxes_2d=new((V, N, 4), fill=0.0), mean_iou=new((N, N), fill=0.0),
-                         matched_gt=new(N, torch.int64, fill=0), confidences=new(N, fill=0.0))
-            # (the frame config's batch fields are this call's own: a copy of the glue's)
-            state["inputs"], state["frame"] = (self._glue, _lib.FrameConfig.from_buffer_copy(self._frame)) if self.fused_glue else \
-                (self._input_tables(), self._frame_config())
-        self._labels = state
+    # ---- what a frame can be asked for after its steps (_OUTPUTS) ------------------------------------------------------------------
+    def _output_state(self, name):
+        """The buffers of output `name` (_OUTPUTS[name].buffers), created at first use -- in the frame's row when there is one (a
+        FrameBatch creates them in every row at once: equal offsets) -- and laid out for the capacities.  metrics() keeps the frame's 3-D
+        ground truth among them: checked before anything is created, written here and by every reset()."""
+        if name not in self._outputs:
+            H, W = (int(x) for x in self.inputs.image_size)
+            if name == "metrics":      # (by name, like reset(): the one output with inputs in its state; a hook for it alone would be an extension point)
+                _check_ground_truth(self.inputs, self.num_instances)
+            with _capture_lock, torch.no_grad():
+                self._outputs[name] = {key: self._new(*buffer) for key, *buffer in _OUTPUTS[name].buffers(self.view_capacity, self.capacity, H, W)}
+                if name == "metrics":
+                    self._write_ground_truth(self.num_instances)
+        return self._outputs[name]
+
+    def _launch_output(self, name, frames=None, **arguments):
+        """ONE vsrd_frame_* call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
+        state = self._output_state(name)       # (the frame config's batch fields are this call's own: a copy of the glue's)
+        frame = _lib.FrameConfig.from_buffer_copy(self._frame if self.fused_glue else state["frame"])
+        frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
+        header = self._glue.get("header") if self.fused_glue else None
+        with _capture_lock:
+            _lib.check(_OUTPUTS[name].launch(self, state, frame, None if header is None else header.data_ptr(), **arguments))
         return state
 
-    def _launch_labels(self, frames=None):
-        """ONE vsrd_frame_labels call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
-        state, det = self._label_state(), self.detector
-        frame, t = state["frame"], state["inputs"]
-        frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
-        header = t.get("header")
-        with _capture_lock:
-            _lib.check(_lib.load().vsrd_frame_labels(
-                frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(t["extrinsics"]),
-                _lib.ptr(t["intrinsics"]), _lib.ptr(t["gt_boxes"]), t["visible"].data_ptr(), _lib.ptr(state["camera_corners"]), _lib.ptr(state["boxes_2d"]),
-                _lib.ptr(state["mean_iou"]), state["matched_gt"].data_ptr(), _lib.ptr(state["confidences"]),
-                None if header is None else header.data_ptr(), _lib.stream()))
-
-    def _label_views(self):
-        state, n, v = self._labels, self.num_instances, self.num_views
-        return dict(boxes_3d=state["camera_corners"][:v, :n], boxes_2d=state["boxes_2d"][:v, :n].unflatten(-1, (2, 2)), confidences=state["confidences"][:n],
-                    matched_gt=state["matched_gt"][:n], mean_iou=state["mean_iou"][:n, :n])
+    def _ask(self, name, **arguments):
+        """Output `name` (_OUTPUTS) of this loop: the preconditions, ONE launch on the current stream, the frame's own views."""
+        _check_asked(name, [self])
+        state = self._launch_output(name, **arguments)
+        return _OUTPUTS[name].views(self, state, **arguments)
 
     def labels(self):
         """The frame's pseudo-labels from its CURRENT parameters (tools/kitti_360/make_predictions.py:61-192), by one vsrd_frame_labels
         launch on the current stream, no host synchronisation: a dictionary of device tensors sliced to the frame's own V views and n instances --
         boxes_3d [V,n,8,3] (camera-frame corners in every view), boxes_2d [V,n,2,2] (clipped), confidences [n] (the matched mean IoU),
         matched_gt [n], mean_iou [n,n].  They are views of buffers the next call overwrites (formats.save_frame_labels writes them out)."""
-        self._launch_labels()
-        return self._label_views()
-
-    # ---- dense predicted masks (csrc/frame_masks.h) --------------------------------------------------------------------------
-    def _mask_state(self):
-        """What vsrd_frame_masks writes, created at first use -- in the frame's row when there is one (a FrameBatch creates them in every
-        row at once: equal offsets): the bit-packed masks, the soft values and the pixel counts, laid out for the capacity."""
-        if self._masks is not None:
-            return self._masks
-        if not self.fused_glue:
-            raise RuntimeError("masks() renders the field block the fused glue keeps on the device (graph=True)")
-        H, W = (int(x) for x in self.inputs.image_size)
-        N = self.capacity
-        with _capture_lock, torch.no_grad():
-            new = self._new
-            self._masks = dict(inside=new((N, H, (W + 7) // 8), torch.uint8, fill=0), soft=new((H * W, N), fill=0.0),
-                               counts=new((N, 3), torch.int32, fill=0))
-        return self._masks
-
-    def _launch_masks(self, frames=None, view=0, threshold=0.5, soft=False):
-        """ONE vsrd_frame_masks call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
-        if self.step_index < 1:
-            raise RuntimeError("masks() renders the field of the last step: no step has run since the loop was built or reset()")
-        cfg, b, state = self.config, self._glue, self._mask_state()
-        H, W = (int(x) for x in self.inputs.image_size)
-        from .rendering import renderers
-        # the field the last step rendered: its instance block, and in the residual phase its (centred) MLP weights, exact-fp32 products
-        residual = self.step_index - 1 >= cfg.warmup_steps
-        flags = renderers._base_flags() & ~_lib.FLAG_MLP_SPLIT_BF16
-        if residual:
-            if not self.fused_hypernetwork:
-                raise RuntimeError("masks() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
-            flags |= _lib.FLAG_MLP_WEIGHTS_CENTRED
-        elif cfg.skip_exact_misses:
-            flags |= _lib.FLAG_SKIP_EXACT_MISSES
-        field = _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
-        config = _lib.make_config(0, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, seed=cfg.seed, stream_offset=self.step_tensor, flags=flags,
-                                  schedule=self.schedule, frames=frames)
-        masks = _lib.FrameMasksConfig(int(view), self.view_capacity, H, W, int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria),
-                                      float(cfg.surface_bounding_radius), float(threshold), self.capacity)
-        header = b.get("header")
-        with _capture_lock:
-            _lib.check(_lib.load().vsrd_frame_masks(
-                field, config, masks, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), None, None, _lib.ptr(b["masks"]),
-                b["target_columns"].data_ptr(), state["inside"].data_ptr(), _lib.ptr(state["soft"]) if soft else None, state["counts"].data_ptr(),
-                None if header is None else header.data_ptr(), _lib.stream()))
-
-    def _mask_views(self, threshold, soft):
-        state, n = self._masks, self.num_instances
-        H, W = (int(x) for x in self.inputs.image_size)
-        counts = state["counts"][:n]
-        result = dict(inside=state["inside"][:n], counts=counts, mask_iou=mask_iou(counts), threshold=float(threshold), shape=(H, W))
-        if soft:
-            result["soft"] = state["soft"].view(H, W, self.capacity)[:, :, :n]
-        return result
+        if not self.fused_glue and "labels" not in self._outputs:
+            with _capture_lock, torch.no_grad():       # (a loop without the fused glue: float32 copies of its inputs' tables and a frame config)
+                self._output_state("labels").update(tables=self._input_tables(), frame=self._frame_config())
+        return self._ask("labels")
 
     def masks(self, view=0, threshold=0.5, soft=False):
         """The frame's dense predicted instance masks of view ``view`` (0: the target view) -- what the reference renders every
@@ -1274,51 +1321,16 @@ class FrameOptimizer:
         ``soft`` the values themselves, soft [H,W,n].  They are views of buffers the next call overwrites (formats.save_frame_masks)."""
         if not 0 <= int(view) < self.num_views:
             raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
-        self._launch_masks(view=view, threshold=threshold, soft=soft)
-        return self._mask_views(threshold, soft)
+        return self._ask("masks", view=view, threshold=threshold, soft=soft)
 
-    # ---- 3-D / BEV IoU metrics against the ground truth (csrc/frame_metrics.h) --------------------------------------------------
     def _write_ground_truth(self, n):
         """The row's ground-truth corners and rectification matrix from `self.inputs`: NaN (no annotation) in every slot the frame does not
         fill -- all of them when the frame has no boxes_3d -- and the identity without a rectification matrix."""
-        state, inp = self._metrics, self.inputs
+        state, inp = self._outputs["metrics"], self.inputs
         state["gt_boxes_3d"].fill_(float("nan"))
         if inp.boxes_3d is not None:
             state["gt_boxes_3d"][:int(n)].copy_(inp.boxes_3d)
         state["rectification"].copy_(torch.eye(3) if inp.rectification_matrix is None else inp.rectification_matrix)
-
-    def _metric_state(self):
-        """What vsrd_frame_metrics reads and writes beyond the glue's tensors, created at first use -- in the frame's row when there is one (a
-        FrameBatch creates them in every row at once: equal offsets): the ground-truth corners and the rectification matrix, the decoded
-        corners, the IoUs and the summary, laid out for the capacity.  A few KB."""
-        if self._metrics is not None:
-            return self._metrics
-        if not self.fused_glue:
-            raise RuntimeError("metrics() pairs the boxes by the matching the fused glue keeps on the device (graph=True)")
-        N = self.capacity
-        _check_ground_truth(self.inputs, self.num_instances)
-        with _capture_lock, torch.no_grad():
-            new = self._new
-            self._metrics = dict(gt_boxes_3d=new((N, 8, 3), fill=float("nan")), rectification=new((3, 3), fill=0.0), corners=new((N, 8, 3), fill=0.0),
-                                 ious=new((N, 2), fill=float("nan")), summary=new(8, fill=0.0), frame=_lib.FrameConfig.from_buffer_copy(self._frame))
-            self._write_ground_truth(self.num_instances)
-        return self._metrics
-
-    def _launch_metrics(self, frames=None):
-        """ONE vsrd_frame_metrics call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
-        state, det, b = self._metric_state(), self.detector, self._glue
-        frame = state["frame"]
-        frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
-        header = b.get("header")
-        with _capture_lock:
-            _lib.check(_lib.load().vsrd_frame_metrics(
-                frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(state["gt_boxes_3d"]),
-                _lib.ptr(state["rectification"]), b["pd_indices"].data_ptr(), b["gt_indices"].data_ptr(), _lib.ptr(state["corners"]),
-                _lib.ptr(state["ious"]), _lib.ptr(state["summary"]), None if header is None else header.data_ptr(), _lib.stream()))
-
-    def _metric_views(self):
-        state, n = self._metrics, self.num_instances
-        return dict(iou_3d=state["ious"][:n, 0], iou_bev=state["ious"][:n, 1], summary=state["summary"], corners=state["corners"][:n])
 
     def metrics(self):
         """The frame's evaluation against its 3-D ground truth (``FrameInputs.boxes_3d``) -- the reference's iou_3d, iou_bev and accuracies
@@ -1330,14 +1342,10 @@ class FrameOptimizer:
         prediction; NaN where the matched ground-truth slot has no annotation), summary [8] (count, iou_3d, iou_bev, accuracy_3d_25,
         accuracy_bev_25, accuracy_3d_50, accuracy_bev_50, 0: ``formats.frame_metrics`` names them), corners [n,8,3] (the decoded boxes).
         They are views of buffers the next call overwrites."""
-        if not self.fused_glue:
-            raise RuntimeError("metrics() pairs the boxes by the matching the fused glue keeps on the device (graph=True)")
-        if self.step_index < 1:
-            raise RuntimeError("metrics() pairs the boxes by the last step's matching: no step has run since the loop was built or reset()")
+        _check_asked("metrics", [self])          # (first, as ever: a loop that cannot be asked says so whatever its ground truth)
         if self.inputs.boxes_3d is None:
             raise ValueError("metrics() needs the frame's 3-D ground truth: FrameInputs.boxes_3d is None")
-        self._launch_metrics()
-        return self._metric_views()
+        return self._ask("metrics")
 
     def close(self):
         """Drop the captured graphs and the scratch buffers (also happens when the optimizer is garbage-collected).  Once per frame
@@ -1545,45 +1553,36 @@ class FrameBatch:
         # (step_index counts the steps done: the last one had index step_index - 1, and `step_index - 1 >= warmup_steps` is its `residual`)
         return m._step_record(m.step_index > self.config.warmup_steps)
 
-    def _launch_on_rows(self, active, what, state, launch, **arguments):
-        """First use creates the `what` buffers that `state` (a FrameOptimizer method) makes in EVERY row, so that the rows keep equal
-        offsets; then ONE call of `launch` on row 0 covers the first `active` rows."""
+    def _ask(self, name, active, **arguments):
+        """Output `name` (_OUTPUTS) of the first ``active`` frames: first use creates its buffers in EVERY row, so that the rows keep equal
+        offsets; then ONE launch on row 0 covers the first ``active`` rows, and every frame gets its own views."""
+        active, members = self._members(active)
+        _check_asked(name, members)
         for m in self.frames:
-            state(m)
+            m._output_state(name)
         if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
-            raise RuntimeError(f"the frames of a batch laid their {what} buffers out differently: frame batches need equal offsets in every row")
-        launch(self.frames[0], frames=(active, self.arena.stride), **arguments)
+            raise RuntimeError(f"the frames of a batch laid their {name} buffers out differently: frame batches need equal offsets in every row")
+        self.frames[0]._launch_output(name, frames=(active, self.arena.stride), **arguments)
+        return [_OUTPUTS[name].views(m, m._outputs[name], **arguments) for m in members]
 
     def labels(self, active=None):
         """The pseudo-labels of the first ``active`` frames (``FrameOptimizer.labels``) by ONE vsrd_frame_labels call for all of them: a
         list of dictionaries of device tensors, each sliced to its frame's own instance count."""
-        active, members = self._members(active)
-        self._launch_on_rows(active, "label", FrameOptimizer._label_state, FrameOptimizer._launch_labels)
-        return [m._label_views() for m in members]
+        return self._ask("labels", active)
 
     def masks(self, active=None, view=0, threshold=0.5, soft=False):
         """The dense predicted masks of the first ``active`` frames (``FrameOptimizer.masks``) by ONE vsrd_frame_masks call for all of
         them: a list of dictionaries of device tensors, each sliced to its frame's own instance count.  ``view`` must exist in every
         active frame."""
-        active, members = self._members(active)
-        if any(not 0 <= int(view) < m.num_views for m in members):
+        if any(not 0 <= int(view) < m.num_views for m in self._members(active)[1]):
             raise ValueError(f"view {view} does not exist in every active frame")
-        if any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
-            raise RuntimeError("masks() renders the field of the frames' last step: no step has run since a frame's reset(), or the frames "
-                               "are not in step")
-        self._launch_on_rows(active, "mask", FrameOptimizer._mask_state, FrameOptimizer._launch_masks, view=view, threshold=threshold, soft=soft)
-        return [m._mask_views(threshold, soft) for m in members]
+        return self._ask("masks", active, view=view, threshold=threshold, soft=soft)
 
     def metrics(self, active=None):
         """The 3-D / BEV IoU metrics of the first ``active`` frames (``FrameOptimizer.metrics``) by ONE vsrd_frame_metrics call for all of
         them: a list of dictionaries of device tensors, each sliced to its frame's own instance count.  A frame without ``boxes_3d`` is not
         an error here: its IoUs are NaN and its summary is eight zeros (count 0), for which ``formats.frame_metrics`` gives {}."""
-        active, members = self._members(active)
-        if any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
-            raise RuntimeError("metrics() pairs the boxes by the frames' last step's matching: no step has run since a frame's reset(), or the "
-                               "frames are not in step")
-        self._launch_on_rows(active, "metric", FrameOptimizer._metric_state, FrameOptimizer._launch_metrics)
-        return [m._metric_views() for m in members]
+        return self._ask("metrics", active)
 
     def _phase(self, active):
         _, members = self._members(active)
