@@ -70,6 +70,9 @@ def test_wave_primitives(dev):
     assert torch.equal(out[320:384], torch.cat([torch.tensor([-7.0]), v[:-1]]))
     u = out[384:448]
     assert torch.all((u >= 0) & (u < 1)) and u.unique().numel() > 60
+    import philox_reference                                        # lane l: uniform(x) of philox(l, 1, 2, 3; deadbeef, 12345678), exactly
+    words = philox_reference.philox4x32_10_array(np.arange(64), 1, 2, 3, 0xdeadbeef, 0x12345678)
+    assert torch.equal(u, torch.from_numpy(philox_reference.uniform(words[0]).astype(np.float32)))
     assert torch.equal(out[448:512], torch.linspace(0.0, 100.0, 65)[:64])
     j = torch.arange(64) % 16
     torch.testing.assert_close(out[512:576], (v64.sum() * (j + 1) + 64.0 * j).float(), rtol=1e-5, atol=1e-4)
