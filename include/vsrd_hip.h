@@ -585,6 +585,42 @@ int32_t vsrd_frame_labels(const vsrd_frame_config* config,
                           int64_t* matched_gt /* [N] */, float* confidences /* [N] */,
                           const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
 
+/* Frame group labels (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field):
+ * vsrd_frame_labels in label views of the call's own, any number up to VSRD_MAX_LABEL_VIEWS -- the frame's GROUP, what
+ * tools/kitti_360/make_predictions.py:50-192 labels: every frame of grouped_image_filenames.txt whose filtered instance-id set equals the
+ * target's (sample_annotations.py:133,164-170).  The views a frame is optimised on are another set (the target and the medians of at most 16
+ * chunks of its sources, of which a source needs only half the target's instances): a group can hold far more frames, and need not hold
+ * the sources.  Up to three launches inside the call, ordered by the stream, no host synchronisation, no allocation, capturable:
+ *   project    (blocks of four label views, frame): a wave per view, a lane per box -> camera_corners, boxes_2d;
+ *   mean IoU   (blocks of four predictions, frame): a wave per prediction, a lane per ground-truth slot, every lane sums its own pair
+ *              over the views in ascending order -> mean_iou;
+ *   assign     one wave per frame -> matched_gt, confidences (skipped when both are NULL).
+ * Semantics are vsrd_frame_labels' step by step with the label views in place of the row's views -- the same device functions: handed a
+ * row's own E, K, gt_boxes and visible, the call writes the bits vsrd_frame_labels writes.  The stated deviation is the same (a slot NO
+ * label view sees: mean_iou exactly 0.0 in its column).
+ * Conventions as for vsrd_frame_labels: config->num_boxes is the capacity N (1..VSRD_MAX_INSTANCES) and the stride of every instance axis,
+ * num_frames / frame_stride batch the call, frame_header (may be NULL) carries n_f, clamped to [1, N], VSRD_FRAME_HEADER_HAS_VIEWS masked
+ * off.  config->num_views and the header's num_views are NOT read: of config the call reads num_boxes, height / width / epsilon, the
+ * location and dimension ranges and the batch fields.
+ *   num_label_views L         capacity and stride of every label-view axis, 1..VSRD_MAX_LABEL_VIEWS;
+ *   label_view_count [1]      device, per frame (it follows frame_stride like every other pointer): the frame's own l_f, clamped to [1, L]
+ *                             (a group always holds its target); NULL: every frame has L;
+ *   label_extrinsics [L,16], label_intrinsics [L,9]   relative to the rectified target view, like a row's own;
+ *   label_gt_boxes [L,N,4], label_visible [L,N]        in the target's instance order.
+ * Views l_f .. L-1 of every label-view input and output are never read and never written; instances n_f .. N-1 are never read and never
+ * written, rows and columns of mean_iou included.  camera_corners, matched_gt and confidences may each be NULL and are then skipped;
+ * boxes_2d and mean_iou are REQUIRED (the next kernel reads them back).  A NULL required pointer, L outside 1..VSRD_MAX_LABEL_VIEWS or N
+ * outside 1..VSRD_MAX_INSTANCES: VSRD_E_INVALID_ARGUMENT before any launch, nothing written. */
+#define VSRD_MAX_LABEL_VIEWS 4096
+int32_t vsrd_frame_group_labels(const vsrd_frame_config* config,
+                                const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                                int32_t num_label_views, const int32_t* label_view_count /* [1] or NULL */,
+                                const float* label_extrinsics /* [L,16] */, const float* label_intrinsics /* [L,9] */,
+                                const float* label_gt_boxes /* [L,N,4] */, const uint8_t* label_visible /* [L,N] */,
+                                float* camera_corners /* [L,N,8,3] or NULL */, float* boxes_2d /* [L,N,4] */, float* mean_iou /* [N,N] */,
+                                int64_t* matched_gt /* [N] */, float* confidences /* [N] */,
+                                const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
+
 /* Frame masks (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the dense
  * predicted instance masks of ONE view of a frame, bit-packed -- what the reference renders every `image_intervals` steps
  * (scripts/main.py:1011-1061): volume_masks (the two-pass hierarchical_volumetric_rendering of the soft union at every pixel) times

@@ -2,7 +2,7 @@
 """Write K synthetic frame packs (vsrd_amd/frames.py) for `python -m vsrd_amd.launcher --frames-dir DIR`.  Host only, no GPU.
 
     python tools/make_frame_packs.py --out DIR --count 16 [--views 17 --height 376 --width 1408 --instances 8 | --instances 2,3,4]
-                                     [--drop 1:0,2:1] [--shuffle] [--vertices 200]
+                                     [--drop 1:0,2:1] [--shuffle] [--vertices 200] [--label-views 40]
 
 Frame j is synthetic.synthetic_frame(seed = j) with instances[j % len(instances)] boxes.  Per view, an instance's polygon is the
 integer-rounded convex hull of its true box's eight projected corners (clamped to the image), and its inside bits come from an
@@ -14,7 +14,11 @@ exporter that runs the reference's own OpenCV steps (SoftRasterizer.make_polygon
 recipe), which is out of scope of this repository.
 
 --drop VIEW:SLOT[,...] removes the target's instance SLOT from source view VIEW (invisible there); --shuffle lists the entries of
-every source view in a seeded random order: both exercise the visibility and the re-indexing of frames.collate_tables."""
+every source view in a seeded random order: both exercise the visibility and the re-indexing of frames.collate_tables.
+
+--label-views L gives every pack a GROUP (the label_* members of a pack: the frames that get the target's labels, `launcher
+--group-predictions`): synthetic.synthetic_group, L cameras on the frame's trajectory between the sources' positions, the target among
+them, with the true boxes' clipped 2-D boxes.  Without the flag the packs have no group."""
 import argparse
 import os
 import sys
@@ -77,7 +81,7 @@ def even_odd_mask(polygon, height, width):
     return mask
 
 
-def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, vertices=0):
+def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, vertices=0, label_views=0):
     """The FramePack of synthetic frame number `frame`."""
     from vsrd_amd import frames, models, synthetic
     K, E, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(int(frame), views, height, width, instances)
@@ -111,12 +115,14 @@ def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, ve
             masks.append(np.packbits(even_odd_mask(hull, height, width), axis=-1))
         view_offsets.append(len(ids))
     polygon_offsets = np.concatenate([[0], np.cumsum([len(p) for p in polygons])])
+    group = {key: value.numpy() for key, value in synthetic.synthetic_group(frame, height, width, label_views, corners).items()} if label_views else {}
     return frames.FramePack((height, width), K.numpy().astype(np.float32), E.numpy().astype(np.float32), np.asarray(view_offsets, dtype=np.int64),
                             np.asarray(ids, dtype=np.int64), polygon_offsets.astype(np.int64), np.concatenate(polygons).astype(np.int32), np.stack(masks),
-                            boxes_3d=corners.numpy().astype(np.float32))      # (the true boxes in the target's instance order: ground truth for --metrics)
+                            boxes_3d=corners.numpy().astype(np.float32),      # (the true boxes in the target's instance order: ground truth for --metrics)
+                            **group)
 
 
-def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), drop=(), shuffle=False, vertices=0):
+def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), drop=(), shuffle=False, vertices=0, label_views=0):
     """Packs frame_000000.npz .. of frames 0..count-1 in `out`; returns their paths.  `views`: one count, or a list cycled over the frames
     like `instances` (frame j gets views[j % len(views)], each list with its own length)."""
     from vsrd_amd import frames
@@ -124,7 +130,7 @@ def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), dr
     paths = []
     views = [int(views)] if isinstance(views, int) else [int(v) for v in views]
     for frame in range(int(count)):
-        pack = make_pack(frame, views[frame % len(views)], height, width, int(instances[frame % len(instances)]), drop, shuffle, vertices)
+        pack = make_pack(frame, views[frame % len(views)], height, width, int(instances[frame % len(instances)]), drop, shuffle, vertices, label_views)
         paths.append(os.path.join(out, f"frame_{frame:06d}.npz"))
         frames.save_pack(paths[-1], pack)
     return paths
@@ -141,9 +147,10 @@ def main(argv=None):
     parser.add_argument("--drop", default="", help="VIEW:SLOT[,VIEW:SLOT...]: the target's instance SLOT is missing from source view VIEW")
     parser.add_argument("--vertices", type=int, default=0, help="subdivide every polygon to about this many vertices (real contours have hundreds)")
     parser.add_argument("--shuffle", action="store_true", help="source views list their entries in a seeded random order")
+    parser.add_argument("--label-views", type=int, default=0, help="give every pack a group of this many label views (default: none)")
     args = parser.parse_args(argv)
     drop = [tuple(int(x) for x in item.split(":")) for item in args.drop.split(",") if item]
-    paths = write_packs(args.out, args.count, [int(x) for x in args.views.split(",")], args.height, args.width, [int(x) for x in args.instances.split(",")], drop, args.shuffle, args.vertices)
+    paths = write_packs(args.out, args.count, [int(x) for x in args.views.split(",")], args.height, args.width, [int(x) for x in args.instances.split(",")], drop, args.shuffle, args.vertices, args.label_views)
     print(f"{len(paths)} packs in {args.out}")
     return 0
 

@@ -164,6 +164,7 @@ class FrameMasksConfig(ctypes.Structure):
 
 FRAME_HEADER_HAS_VIEWS = 0x10000
 MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFrameMaxViews)
+MAX_LABEL_VIEWS = 4096         # VSRD_MAX_LABEL_VIEWS: the label views (a frame's group) of vsrd_frame_group_labels
 
 
 SIGNATURES = {
@@ -253,6 +254,10 @@ SIGNATURES = {
     "vsrd_frame_labels": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                                            ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
                                            ctypes.c_void_p]),
+    # added within ABI 12: vsrd_frame_labels in label views of the call's own, the frame's group (L <= MAX_LABEL_VIEWS, per-frame count on the device)
+    "vsrd_frame_group_labels": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_void_p,
+                                                 c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p,
+                                                 c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
     # added within ABI 12: a view's dense predicted instance masks, bit-packed (+ soft values, pixel counts); header before the stream
     "vsrd_frame_masks": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), ctypes.POINTER(FrameMasksConfig), c_float_p, c_float_p,
                                           c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,

@@ -13,6 +13,7 @@
 #include "hypernetwork.h"
 #include "frame_ingest.h"
 #include "frame_labels.h"
+#include "frame_group_labels.h"
 #include "frame_masks.h"
 #include "frame_metrics.h"
 #include "launch.h"
@@ -1237,6 +1238,40 @@ int32_t vsrd_frame_labels(const vsrd_frame_config* config, const float* raw_loca
     b.camera_corners = camera_corners; b.boxes_2d = boxes_2d; b.mean_iou = mean_iou;
     b.matched_gt = reinterpret_cast<long long*>(matched_gt); b.confidences = confidences;
     hipLaunchKernelGGL(frame_labels_kernel, dim3(frames.count), dim3(kFrameThreads), 0, static_cast<hipStream_t>(stream), a, b);
+    return launch_status();
+}
+
+int32_t vsrd_frame_group_labels(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                                int32_t num_label_views, const int32_t* label_view_count, const float* label_extrinsics, const float* label_intrinsics,
+                                const float* label_gt_boxes, const uint8_t* label_visible, float* camera_corners, float* boxes_2d, float* mean_iou,
+                                int64_t* matched_gt, float* confidences, const vsrd_frame_header* frame_header, void* stream) {
+    static_assert(kGroupMaxViews == VSRD_MAX_LABEL_VIEWS, "frame_group_labels.h and the ABI agree on the label-view capacity");
+    if (!config || config->num_boxes < 1 || config->num_boxes > kFrameMaxBoxes || num_label_views < 1 || num_label_views > kGroupMaxViews)
+        return VSRD_E_INVALID_ARGUMENT;
+    Frames frames;
+    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (!raw_locations || !raw_dimensions || !raw_orientations || !label_extrinsics || !label_intrinsics || !label_gt_boxes || !label_visible ||
+        !boxes_2d || !mean_iou)
+        return VSRD_E_INVALID_ARGUMENT;
+    FrameStepArgs a = {};                  // (the decode's ranges, the projection's guard and the image size; num_views is not read)
+    a.num_boxes = config->num_boxes;
+    a.height = config->height; a.width = config->width; a.epsilon = config->epsilon;
+    for (int j = 0; j < 3; ++j) {
+        a.location_lo[j] = config->location_lo[j]; a.location_hi[j] = config->location_hi[j];
+        a.dimension_lo[j] = config->dimension_lo[j]; a.dimension_hi[j] = config->dimension_hi[j];
+    }
+    a.frame_stride = frames.stride;
+    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
+    GroupLabelBuffers b;
+    b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
+    b.view_count = label_view_count; b.extrinsics = label_extrinsics; b.intrinsics = label_intrinsics; b.gt_boxes = label_gt_boxes; b.visible = label_visible;
+    b.camera_corners = camera_corners; b.boxes_2d = boxes_2d; b.mean_iou = mean_iou;
+    b.matched_gt = reinterpret_cast<long long*>(matched_gt); b.confidences = confidences;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const int L = num_label_views, N = config->num_boxes;
+    hipLaunchKernelGGL(frame_group_project_kernel, dim3((L + kGroupWaves - 1) / kGroupWaves, frames.count), dim3(kGroupThreads), 0, s, a, b, L);
+    hipLaunchKernelGGL(frame_group_mean_iou_kernel, dim3((N + kGroupWaves - 1) / kGroupWaves, frames.count), dim3(kGroupThreads), 0, s, a, b, L);
+    if (matched_gt || confidences) hipLaunchKernelGGL(frame_group_assign_kernel, dim3(frames.count), dim3(kWave), 0, s, a, b);
     return launch_status();
 }
 

@@ -1,6 +1,7 @@
 // vsrd_frame_labels: a frame's pseudo-labels from its arena row at the end of the optimisation -- what the reference produces in a second
-// pass over the checkpoints (tools/kitti_360/make_predictions.py:61-192): decode the boxes, transform and project them into every view of
-// the group, torchvision.ops.box_iou against each view's ground-truth boxes, the mean over the views in which an instance exists,
+// pass over the checkpoints (tools/kitti_360/make_predictions.py:61-192): decode the boxes, transform and project them into every view the
+// row was optimised on (NOT the target's group of make_predictions.py:50-60: frame_group_labels.h labels that), torchvision.ops.box_iou
+// against each view's ground-truth boxes, the mean over the views in which an instance exists,
 // scipy.optimize.linear_sum_assignment(maximize=True), confidence = the matched mean IoU.  One workgroup of kFrameThreads per frame:
 //
 //   1. decode          decode_box + unit_corner (frame_step.h) on the frame's n boxes -> world corners (LDS)
@@ -83,6 +84,42 @@ __device__ __forceinline__ void clipped_box_2d(const float (&cam)[8][3], const f
     }
 }
 
+// A decoded box's eight world corners (box_parameters.py:78-90) -> out [8,3]; shared with frame_group_labels.h like project_pair.
+__device__ __forceinline__ void world_corners(const DecodedBox& d, float* out) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float u[3];
+        unit_corner(k, u);
+        const float lx = u[0] * d.dim[0], ly = u[1] * d.dim[1], lz = u[2] * d.dim[2];
+        // (c lx + s lz and -s lx + c lz with the fused multiply-add SPELLED OUT: under -ffp-contract=fast the compiler picks which product of
+        //  such a sum it fuses by the code around it, and the two kernels that share this function must round alike -- this is the form
+        //  frame_labels_kernel has always been compiled to: the product with s rounded, the one with c fused)
+        out[3 * k + 0] = __builtin_fmaf(d.c, lx, d.s * lz) + d.loc[0];
+        out[3 * k + 1] = ly + d.loc[1];
+        out[3 * k + 2] = __builtin_fmaf(d.c, lz, -d.s * lx) + d.loc[2];
+    }
+}
+
+// One (view, box) pair, the body both vsrd_frame_labels and vsrd_frame_group_labels (frame_group_labels.h) run: camera corners = E corner / w
+// (main.py:343-344) from the view's 25 floats `view` = (E [16], K [9]) and the box's eight world corners, written to `camera_out` ([8,3]) unless
+// it is null, then the clipped 2-D box.
+__device__ __forceinline__ void project_pair(const float* view, const float* corners, float eps, float height, float width, float* camera_out, float (&box)[4]) {
+    const float* E = view;
+    float cam[8][3];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float* c = corners + 3 * k;
+        const float w = E[12] * c[0] + E[13] * c[1] + E[14] * c[2] + E[15];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cam[k][j] = (E[4 * j] * c[0] + E[4 * j + 1] * c[1] + E[4 * j + 2] * c[2] + E[4 * j + 3]) / w;
+        if (camera_out) {
+            float* o = camera_out + 3 * k;
+            o[0] = cam[k][0]; o[1] = cam[k][1]; o[2] = cam[k][2];
+        }
+    }
+    clipped_box_2d(cam, E + 16, eps, height, width, box);
+}
+
 // torchvision.ops.box_iou of one pair (vsrd_amd/formats.py::box_iou), NaN -> 0 (make_predictions.py: nan_to_num).  An infinite value
 // (only a malformed ground-truth box, xmax < xmin, can produce one; the reference's scipy call raises on it) counts as 0 as well, so that
 // the assignment's costs are always finite.
@@ -115,37 +152,15 @@ __global__ __launch_bounds__(kFrameThreads) void frame_labels_kernel(FrameStepAr
     }
     // ---- 1. decode -> world corners (box_parameters.py:78-90) ------------------------------------------------------------------
     if (tid < n) {
-        const DecodedBox d = decode_box(a, b.raw_locations + 3 * tid, b.raw_dimensions + 3 * tid, b.raw_orientations + 2 * tid);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float u[3];
-            unit_corner(k, u);
-            const float lx = u[0] * d.dim[0], ly = u[1] * d.dim[1], lz = u[2] * d.dim[2];
-            corners[tid * 24 + 3 * k + 0] = d.c * lx + d.s * lz + d.loc[0];
-            corners[tid * 24 + 3 * k + 1] = ly + d.loc[1];
-            corners[tid * 24 + 3 * k + 2] = -d.s * lx + d.c * lz + d.loc[2];
-        }
+        world_corners(decode_box(a, b.raw_locations + 3 * tid, b.raw_dimensions + 3 * tid, b.raw_orientations + 2 * tid), corners + tid * 24);
     }
     __syncthreads();
     // ---- 2. every (view, box) pair: camera corners, clipped 2-D box ------------------------------------------------------------------
     for (int idx = tid; idx < V * n; idx += kFrameThreads) {
         const int v = idx / n, p = idx - v * n;
-        const float* E = view_matrices + v * 25;
         const size_t pair = static_cast<size_t>(v) * NS + p;
-        float cam[8][3];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float* c = corners + p * 24 + 3 * k;
-            const float w = E[12] * c[0] + E[13] * c[1] + E[14] * c[2] + E[15];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) cam[k][j] = (E[4 * j] * c[0] + E[4 * j + 1] * c[1] + E[4 * j + 2] * c[2] + E[4 * j + 3]) / w;
-            if (b.camera_corners) {
-                float* o = b.camera_corners + (pair * 8 + k) * 3;
-                o[0] = cam[k][0]; o[1] = cam[k][1]; o[2] = cam[k][2];
-            }
-        }
         float box[4];
-        clipped_box_2d(cam, E + 16, a.epsilon, a.height, a.width, box);
+        project_pair(view_matrices + v * 25, corners + p * 24, a.epsilon, a.height, a.width, b.camera_corners ? b.camera_corners + pair * 24 : nullptr, box);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             boxes[idx * 4 + k] = box[k];

@@ -154,6 +154,23 @@ def save_frame_labels(folder, labels, class_name="car"):
                   lambda name: save_kitti_labels(name, [class_name] * len(confidences), boxes_3d[0], boxes_2d[0], confidences.tolist()))
 
 
+def save_frame_group_labels(folder, labels, class_name="car"):
+    """One frame's pseudo-labels in the frames of its GROUP as files -- what the reference's second pass leaves for a detector to be trained
+    on.  ``labels``: the dictionary of ``FrameOptimizer.group_labels()`` (host or device tensors) -- boxes_3d [L,n,8,3] camera-frame corners
+    per group frame, boxes_2d [L,n,2,2], confidences [n], frame_ids [L].  Writes, for every group frame, ``folder/group/predictions/<id:010d>.json``
+    (that frame's corners and 2-D boxes, the same confidences in every file: make_predictions.py:164-192) and
+    ``folder/group/labels/<id:010d>.txt``, its KITTI label lines (convert_predictions.py:16-78).  Every file is written under a temporary
+    name and renamed."""
+    boxes_3d, boxes_2d, confidences, frame_ids = (labels[key].detach().cpu() for key in ("boxes_3d", "boxes_2d", "confidences", "frame_ids"))
+    if len(set(frame_ids.tolist())) != len(frame_ids) or boxes_3d.shape[0] != len(frame_ids):
+        raise ValueError(f"frame_ids {frame_ids.tolist()} for {boxes_3d.shape[0]} group frames: one id per frame, none twice")
+    for view, frame_id in enumerate(frame_ids.tolist()):
+        _atomic_write(os.path.join(folder, "group", "predictions", f"{int(frame_id):010d}.json"),
+                      lambda name, view=view: save_prediction(name, boxes_3d[view], boxes_2d[view], confidences, class_name))
+        _atomic_write(os.path.join(folder, "group", "labels", f"{int(frame_id):010d}.txt"),
+                      lambda name, view=view: save_kitti_labels(name, [class_name] * len(confidences), boxes_3d[view], boxes_2d[view], confidences.tolist()))
+
+
 FRAME_METRIC_NAMES = ("iou_3d", "iou_bev", "accuracy_3d_25", "accuracy_bev_25", "accuracy_3d_50", "accuracy_bev_50")     # main.py:917-924
 
 

@@ -23,6 +23,11 @@ _FIELDS = ("image_size", "intrinsic_matrices", "extrinsic_matrices", "view_offse
            "inside")
 # optional members (3-D ground truth for FrameOptimizer.metrics): written only when present; a pack without them loads with None
 _OPTIONAL = ("boxes_3d", "rectification_matrix")
+# optional members, all or none: the frame's GROUP (tools/kitti_360/make_predictions.py:50-60: the frames whose filtered instance-id set equals
+# the target's -- the frames that get labels, FrameOptimizer.group_labels), L label views with their cameras and 2-D boxes; (field, dtype)
+_GROUP = (("label_frame_ids", np.int64), ("label_intrinsic_matrices", np.float32), ("label_extrinsic_matrices", np.float32),
+          ("label_boxes_2d", np.float32), ("label_visible", np.uint8))
+MAX_LABEL_VIEWS = _lib.MAX_LABEL_VIEWS         # VSRD_MAX_LABEL_VIEWS
 
 
 @dataclass
@@ -40,6 +45,17 @@ class FramePack:
     inside: np.ndarray                      # [M,H,ceil(W/8)] uint8: np.packbits(binary mask, axis=-1), most significant bit first
     boxes_3d: Optional[np.ndarray] = None               # [N,8,3] float32 or None: 3-D ground truth in the target's instance order, NaN rows = no annotation
     rectification_matrix: Optional[np.ndarray] = None   # [3,3] float32 or None (identity)
+    # the frame's group (all five, or none): the frames make_predictions.py labels, the target among them
+    label_frame_ids: Optional[np.ndarray] = None            # [L] int64, unique: the files' names (<id:010d>)
+    label_intrinsic_matrices: Optional[np.ndarray] = None   # [L,3,3] float32
+    label_extrinsic_matrices: Optional[np.ndarray] = None   # [L,4,4] float32, relative to the rectified target like extrinsic_matrices
+    label_boxes_2d: Optional[np.ndarray] = None             # [L,N,4] float32 (xmin, ymin, xmax, ymax) in the target's instance order, zeros where invisible
+    label_visible: Optional[np.ndarray] = None              # [L,N] uint8
+
+    @property
+    def num_label_views(self):
+        """L, or 0 for a pack without a group."""
+        return 0 if self.label_frame_ids is None else len(self.label_frame_ids)
 
     @property
     def num_views(self):
@@ -65,7 +81,8 @@ def _normalised(pack):
                      np.ascontiguousarray(pack.view_offsets, dtype=np.int64), np.ascontiguousarray(pack.instance_ids, dtype=np.int64),
                      np.ascontiguousarray(pack.polygon_offsets, dtype=np.int64), np.ascontiguousarray(pack.polygon_vertices, dtype=np.int32),
                      np.ascontiguousarray(pack.inside, dtype=np.uint8),
-                     *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=np.float32) for field in _OPTIONAL])
+                     *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=np.float32) for field in _OPTIONAL],
+                     *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=dtype) for field, dtype in _GROUP])
 
 
 def validate(pack, name="frame pack"):
@@ -117,6 +134,27 @@ def validate(pack, name="frame pack"):
             bad(f"{field} is not a numeric array")
         if array.shape != shape:
             bad(f"{field} of shape {array.shape}, expected {shape}")
+    group = {field: getattr(pack, field) for field, _ in _GROUP}
+    present = [field for field, array in group.items() if array is not None]
+    if present and len(present) != len(_GROUP):
+        bad(f"a group needs all of {', '.join(field for field, _ in _GROUP)}: only {', '.join(present)} given")
+    if present:
+        for field, array in group.items():
+            if not isinstance(array, np.ndarray) or array.dtype.kind not in "iuf":
+                bad(f"{field} is not a numeric array")
+        label_ids = group["label_frame_ids"]
+        if label_ids.ndim != 1 or label_ids.dtype.kind not in "iu":
+            bad(f"label_frame_ids of shape {label_ids.shape}, dtype {label_ids.dtype}: expected [L] integers")
+        count, instances = len(label_ids), int(offsets[1])
+        if not 1 <= count <= MAX_LABEL_VIEWS:
+            bad(f"{count} label views, 1..{MAX_LABEL_VIEWS}")
+        if len(np.unique(label_ids)) != count:
+            bad("label_frame_ids lists a frame id twice")
+        shapes = dict(label_intrinsic_matrices=(count, 3, 3), label_extrinsic_matrices=(count, 4, 4), label_boxes_2d=(count, instances, 4),
+                      label_visible=(count, instances))
+        for field, shape in shapes.items():
+            if group[field].shape != shape:
+                bad(f"{field} of shape {group[field].shape}, expected {shape}")
     return pack
 
 
@@ -126,7 +164,8 @@ def save_pack(path, pack):
     staged = f"{path}.tmp.{os.getpid()}"
     try:
         with open(staged, "wb") as handle:
-            np.savez(handle, **{field: np.asarray(getattr(pack, field)) for field in _FIELDS + _OPTIONAL if getattr(pack, field) is not None})
+            members = _FIELDS + _OPTIONAL + tuple(field for field, _ in _GROUP)
+            np.savez(handle, **{field: np.asarray(getattr(pack, field)) for field in members if getattr(pack, field) is not None})
         os.replace(staged, path)
     finally:
         if os.path.exists(staged):
@@ -153,7 +192,7 @@ def load_pack(path):
     """Read and validate a pack; ValueError naming the file when it is malformed."""
     with _open(path) as data:
         arrays = {field: _member(data, path, field) for field in _FIELDS}
-        arrays.update({field: _member(data, path, field) for field in _OPTIONAL if field in data.files})
+        arrays.update({field: _member(data, path, field) for field in _OPTIONAL + tuple(f for f, _ in _GROUP) if field in data.files})
     if arrays["image_size"].size != 2:
         raise ValueError(f"{path}: malformed frame pack: image_size of shape {arrays['image_size'].shape}")
     for field in arrays:
@@ -170,6 +209,17 @@ def pack_counts(path):
         raise ValueError(f"{path}: malformed frame pack: image_size {size.shape}, view_offsets {offsets.shape}")
     height, width = (int(x) for x in size.reshape(-1))
     return len(offsets) - 1, height, width, int(offsets[1] - offsets[0])
+
+
+def pack_label_views(path):
+    """L of the pack at `path` -- the label views of its group -- without loading anything else; 0 for a pack without a group."""
+    with _open(path) as data:
+        if "label_frame_ids" not in data.files:
+            return 0
+        label_ids = _member(data, path, "label_frame_ids")
+    if label_ids.ndim != 1:
+        raise ValueError(f"{path}: malformed frame pack: label_frame_ids of shape {label_ids.shape}")
+    return len(label_ids)
 
 
 def collate_tables(pack):
@@ -223,6 +273,13 @@ def ground_truth_3d(pack, device):
                  for array in (pack.boxes_3d, pack.rectification_matrix))
 
 
+def group_tables(pack, device):
+    """The pack's group on `device` as FrameInputs' keyword arguments (label_frame_ids, ... label_visible); {} for a pack without one."""
+    if pack.label_frame_ids is None:
+        return {}
+    return {field: torch.from_numpy(np.ascontiguousarray(getattr(pack, field), dtype=dtype)).to(device) for field, dtype in _GROUP}
+
+
 def camera_matrices(pack, device):
     return (torch.from_numpy(pack.intrinsic_matrices).to(device=device, dtype=torch.float32),
             torch.from_numpy(pack.extrinsic_matrices).to(device=device, dtype=torch.float32))
@@ -241,4 +298,4 @@ def ingest(pack, device, temperature=TEMPERATURE):
     ingest_into(pack, device, instances, soft_masks=soft, gt_boxes=boxes, visible=visible, temperature=temperature)
     intrinsics, extrinsics = camera_matrices(pack, device)
     return FrameInputs((height, width), intrinsics, extrinsics, soft, boxes.reshape(views, instances, 2, 2), visible.bool(),
-                       *ground_truth_3d(pack, device))
+                       *ground_truth_3d(pack, device), **group_tables(pack, device))

@@ -203,10 +203,11 @@ def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], s
 #   python -m vsrd_amd.launcher --gpus N --frames K      (or under torchrun; `python bench.py --native --gpus N ...` forwards here)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
-def synthetic_frame_inputs(device, frame, views, instances, height=376, width=1408):
+def synthetic_frame_inputs(device, frame, views, instances, height=376, width=1408, label_views=0):
     """FrameInputs of synthetic frame number `frame` (synthetic.synthetic_frame(seed = frame): KITTI-360 intrinsics, boxes in the
     reference's ranges): soft masks rendered from the true boxes at the sharp end of the schedule, ground-truth 2-D boxes projected
-    from them, every instance visible in every view; the true boxes' corners are the frame's 3-D ground truth (boxes_3d)."""
+    from them, every instance visible in every view; the true boxes' corners are the frame's 3-D ground truth (boxes_3d).
+    ``label_views`` L > 0: the frame also carries a group of L label views (synthetic.synthetic_group)."""
     from . import fields, models, operations, optimization, rendering, synthetic
     K, E, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(int(frame), views, height, width, instances)
     K, E = K.to(device), E.to(device)
@@ -220,8 +221,10 @@ def synthetic_frame_inputs(device, frame, views, instances, height=376, width=14
         soft = rendering.render_hierarchical(block, origins, dirs.reshape(-1, 3), (0.0, 100.0), 64, 0.1, 1.0, seed=1,
                                              skip_exact_misses=True)["labels"].clamp(0, 1).reshape(views, height, width, instances).contiguous()
         gt_boxes, _ = operations.project_boxes_multi_view(out["boxes_3d"][0], E, K, (height, width))
+    group = {key: value.to(device) for key, value in synthetic.synthetic_group(frame, height, width, label_views, out["boxes_3d"][0].cpu()).items()} \
+        if label_views else {}
     return optimization.FrameInputs((height, width), K, E, soft, gt_boxes, torch.ones(views, instances, dtype=torch.bool, device=device),
-                                    boxes_3d=out["boxes_3d"][0].contiguous())
+                                    boxes_3d=out["boxes_3d"][0].contiguous(), **group)
 
 
 def scan_frames_dir(folder, limit=0):
@@ -252,6 +255,24 @@ def scan_frames_dir(folder, limit=0):
         if not 1 <= shapes[-1][3] <= 64:
             raise SystemExit(f"--frames-dir: {path} has {shapes[-1][3]} target instances, 1..64")
     return files, shapes
+
+
+def scan_label_views(files):
+    """--group-predictions with --frames-dir: every pack's L (frames.pack_label_views: nothing else is read); the rows' label-view capacity
+    is the job's largest.  SystemExit naming the first pack that carries no group."""
+    from . import frames
+    counts = []
+    for path in files:
+        try:
+            counts.append(frames.pack_label_views(path))
+        except ValueError as error:
+            raise SystemExit(f"--frames-dir: {error}")
+        if counts[-1] < 1:
+            raise SystemExit(f"--group-predictions: {path} carries no group (label_frame_ids, label_intrinsic_matrices, label_extrinsic_matrices, "
+                             "label_boxes_2d, label_visible): the exporter writes them from the dataset's grouped frames")
+        if counts[-1] > frames.MAX_LABEL_VIEWS:
+            raise SystemExit(f"--frames-dir: {path} has {counts[-1]} label views, 1..{frames.MAX_LABEL_VIEWS}")
+    return counts
 
 
 def _newest_change(folder):
@@ -367,7 +388,8 @@ class _RenderWork:
         if args.frames_dir:          # a frame pack (frames.py), host side: slots and batch rows reset from it, vsrd_frame_ingest fills the row
             from . import frames
             return frames.load_pack(self.manifest["packs"][int(frame)])
-        return synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts), instances_of(frame, args.instance_counts), args.height, args.width)
+        return synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts), instances_of(frame, args.instance_counts), args.height, args.width,
+                                      args.label_views)
 
     def materialised(self, inputs):
         """`inputs` as a FrameInputs on the device: what founds a slot or a batch, and what a loop of its own is built on."""
@@ -400,7 +422,7 @@ class _RenderWork:
         # (frame packs are NOT made resident: a directory holds any number of them, 9 MB each at the reference's size.  A pack is read when its
         #  frame is taken -- inside the clock, under phase_seconds["inputs"] -- and dropped once its row is reset)
         self.inputs = {} if args.frames_dir else {frame: synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts),
-                                                                                instances_of(frame, args.instance_counts), args.height, args.width) for frame in mine}
+                                                                                instances_of(frame, args.instance_counts), args.height, args.width, args.label_views) for frame in mine}
         self.slots, self.batch = queue.Queue(), None
         self.setup_seconds, self.graphs_per_slot, self.unsuitable_founders = 0.0, 0, []
         # the frames a slot or batch may be founded on: this rank's own (static), or the head of the job's queue (dynamic: built here, once)
@@ -415,7 +437,8 @@ class _RenderWork:
                     mixed, mixed_views = len(set(args.instance_counts)) > 1, len(set(args.view_counts)) > 1
                     self.batch = optimization.FrameBatch(founders, self.optimization_config(), self.device,
                                                          max_instances=max(args.instance_counts) if mixed else None,
-                                                         max_views=max(args.view_counts) if mixed_views else None)
+                                                         max_views=max(args.view_counts) if mixed_views else None,
+                                                         max_label_views=args.label_view_capacity)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
                     tail = len(mine) % args.frame_batch if mine else 0                   # a static queue's last group is known now: capture it too
                     self.graphs_per_slot = self.batch.capture_all(actives=sorted({args.frame_batch, tail} - {0}, reverse=True))
@@ -426,7 +449,8 @@ class _RenderWork:
                 for _ in range(min(args.frames_in_flight, len(candidates))):
                     for founder in candidates:      # (a slot is founded on a frame that suits the table sampler its graphs will draw from)
                         try:
-                            loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(founder)), self.optimization_config(), self.device, graph=True, persistent=True)
+                            loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(founder)), self.optimization_config(), self.device, graph=True, persistent=True,
+                                                               max_label_views=args.label_view_capacity)
                         except optimization.UnsuitableFrameError:
                             self.unsuitable_founders.append(int(founder))
                             continue
@@ -440,7 +464,8 @@ class _RenderWork:
     def _own_loop(self, frame):
         """A frame outside the slots / the batch (--fresh-loops, or importance weights that do not suit the table sampler): a loop of its own."""
         from . import optimization
-        loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(frame)), self.optimization_config(init_seed=self.init_seed(frame)), self.device, graph=True)
+        loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(frame)), self.optimization_config(init_seed=self.init_seed(frame)), self.device, graph=True,
+                                          max_label_views=self.args.label_view_capacity)
         loss, payload, pending = self._finish_alone(frame, loop, loop.run(self.args.num_steps))
         loop.close()
         self._write_outputs(pending)
@@ -462,14 +487,16 @@ class _RenderWork:
         """The clock's keys of --predictions / --masks / --metrics (None without any of them: outside the batch path such a job has no
         clock) and the rank's report of per-frame metrics."""
         args = self.args
-        keys = [key for wanted, keys in ((args.predictions, ("labels", "labels_write")), (args.masks, ("masks", "masks_write")), (args.metrics, ("metrics",)))
+        keys = [key for wanted, keys in ((args.predictions, ("labels", "labels_write")), (getattr(args, "group_predictions", False), ("group_labels", "group_labels_write")),
+                                         (args.masks, ("masks", "masks_write")), (args.metrics, ("metrics",)))
                 if wanted for key in keys]
         self.phase_seconds, self.frame_metrics = dict.fromkeys(keys, 0.0) or None, {}
 
     def _collect(self, source, frames, payloads, active=None):
         """What the flags ask of a group of finished frames, inside the section that copies their checkpoint `payloads`: `source` is the
         loop of ONE frame, or the batch whose first `active` rows hold the `frames` = [(frame, checkpoint path)].  In this order, each ONE
-        vsrd_frame_* call for the group and its copies to the host: --predictions, the labels; --masks, the target view's predicted masks,
+        vsrd_frame_* call for the group and its copies to the host: --predictions, the labels; --group-predictions, the labels in every
+        frame's own group; --masks, the target view's predicted masks,
         and every payload's metric mask_iou (the mean over its instances); --metrics, the reference's six metrics into the payload's
         `metrics` and the rank's report, for every frame that had 3-D ground truth (a loop without it is not asked; a batch is, and its
         frames without come back with count 0 and are skipped).  Returns the pending file writes for `_write_outputs`."""
@@ -479,6 +506,9 @@ class _RenderWork:
 
         def labels(frame, folder, entry, payload):
             pending.append(("labels_write", formats.save_frame_labels, (folder, formats.to_host(entry))))
+
+        def group_labels(frame, folder, entry, payload):
+            pending.append(("group_labels_write", formats.save_frame_group_labels, (folder, formats.to_host(entry))))
 
         def masks(frame, folder, entry, payload):
             host = formats.to_host({key: value for key, value in entry.items() if key != "soft"})
@@ -491,7 +521,7 @@ class _RenderWork:
                 payload["metrics"] = dict(payload.get("metrics") or {}, **named)
                 self.frame_metrics[int(frame)] = named
 
-        for key, wanted, each in (("labels", args.predictions, labels), ("masks", args.masks, masks),
+        for key, wanted, each in (("labels", args.predictions, labels), ("group_labels", getattr(args, "group_predictions", False), group_labels), ("masks", args.masks, masks),
                                   ("metrics", args.metrics and (active is not None or source.inputs.boxes_3d is not None), metrics)):
             if wanted:
                 t0 = time.perf_counter()
@@ -755,6 +785,14 @@ def main(argv=None):
                              "(tools/kitti_360/make_predictions.py) and labels/view_00.txt, the target view's KITTI label lines "
                              "(convert_predictions.py) -- vsrd_frame_labels, one launch per group of frames; with --frames-dir an end-to-end "
                              "auto-labelling run.  Not with --selftest")
+    parser.add_argument("--group-predictions", action="store_true",
+                        help="after a frame's steps, write its pseudo-labels in the frames of its GROUP (the frames whose instance set equals the "
+                             "target's: what tools/kitti_360/make_predictions.py labels and a detector is trained on) before its checkpoint: "
+                             "group/predictions/<id>.json and group/labels/<id>.txt for every group frame -- vsrd_frame_group_labels, one call per "
+                             "group of frames.  Needs --out and frames that carry a group: --frames-dir packs with the label_* members, or "
+                             "synthetic frames with --label-views; not with --selftest")
+    parser.add_argument("--label-views", type=int, default=0,
+                        help="synthetic frames carry a group of this many label views (synthetic.synthetic_group); packs carry their own")
     parser.add_argument("--masks", action="store_true",
                         help="after a frame's steps, render the target view's dense predicted instance masks (scripts/main.py:1011-1061: volume_masks "
                              "x surface_masks) -- vsrd_frame_masks, one launch per group of frames -- write them bit-packed to masks/view_00.npz next "
@@ -795,6 +833,16 @@ def main(argv=None):
         raise SystemExit("--masks renders the masks of optimised frames; --selftest optimises none: drop one of --selftest, --masks")
     if args.metrics and args.selftest:
         raise SystemExit("--metrics evaluates the boxes of optimised frames; --selftest optimises none: drop one of --selftest, --metrics")
+    if args.group_predictions and args.selftest:
+        raise SystemExit("--group-predictions writes the labels of optimised frames; --selftest optimises none: drop one of --selftest, --group-predictions")
+    if args.group_predictions and not args.out:
+        raise SystemExit("--group-predictions writes group/predictions/<id>.json and group/labels/<id>.txt next to every frame's checkpoint: it needs --out")
+    if not 0 <= args.label_views <= 4096:
+        raise SystemExit("--label-views must be 0..4096")
+    if args.label_views and args.frames_dir:
+        raise SystemExit("--frames-dir: the packs carry their own groups; drop --label-views")
+    if args.group_predictions and not args.frames_dir and not args.label_views:
+        raise SystemExit("--group-predictions needs frames that carry a group: --frames-dir packs with the label_* members, or synthetic frames with --label-views L")
     if args.masks and not args.out:
         raise SystemExit("--masks writes masks/view_00.npz and a mask_iou metric next to every frame's checkpoint: it needs --out")
     if args.frames_dir:
@@ -806,7 +854,9 @@ def main(argv=None):
         args.frames_dir = os.path.abspath(args.frames_dir)
         argv = argv + ["--frames-dir", args.frames_dir]
         if "RANK" not in os.environ:          # (a job nobody could run ends here, before any rank starts; rank 0 reads the counts again for the manifest)
-            scan_frames_dir(args.frames_dir, args.frames)
+            files, _ = scan_frames_dir(args.frames_dir, args.frames)
+            if args.group_predictions:
+                scan_label_views(files)
     args.height, args.width = (default if value is None else value for value, default in ((args.height, 376), (args.width, 1408)))
     args.view_counts = parse_views("17" if args.views is None else args.views)
     args.views = args.view_counts[0] if len(args.view_counts) == 1 else ",".join(str(v) for v in args.view_counts)
@@ -878,10 +928,12 @@ def _rank_main(args):
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", "29500")
             dist.init_process_group(backend="gloo", rank=rank, world_size=world)
-    packs = shapes = None
+    packs = shapes = label_views = None
     if args.frames_dir and rank == 0:        # rank 0 alone lists the directory and opens the files for their counts: the job is what ITS list says
         packs, shapes = scan_frames_dir(args.frames_dir, args.frames)
         args.frames = len(packs)
+        if args.group_predictions:
+            label_views = scan_label_views(packs)
     total = args.frames or (2 * max(args.frames_in_flight, args.frame_batch) * world if use_gpu else 4 * world)
     out_dir = args.out or (tempfile.mkdtemp(prefix="vsrd_frames_") if rank == 0 else None)
     dynamic = args.queue == "dynamic" or (args.queue == "auto" and world > 1)
@@ -893,7 +945,7 @@ def _rank_main(args):
             store = dist.TCPStore(host, 0, world, is_master=True, wait_for_workers=False)
             store_port = store.port
     manifest = broadcast_manifest(dict(frames=list(range(total)), seed=args.seed, out=out_dir, store_port=store_port, attempt=args.attempt,
-                                       packs=packs, pack_shapes=shapes) if rank == 0 else None)      # (pack_shapes: every pack's (V, H, W, N))
+                                       packs=packs, pack_shapes=shapes, pack_label_views=label_views) if rank == 0 else None)      # (pack_shapes: every pack's (V, H, W, N))
     total = len(manifest["frames"])          # (every rank sizes the job from the manifest)
     args.frame_batch = effective_frame_batch(args.frame_batch, total, world)
     if manifest.get("packs"):                # frame j's count is its pack's: instances_of(j, counts) with one entry per frame
@@ -902,6 +954,8 @@ def _rank_main(args):
         args.instances = ",".join(str(n) for n in sorted(set(args.instance_counts)))
         args.view_counts = [int(shape[0]) for shape in manifest["pack_shapes"]]
         args.views = ",".join(str(v) for v in sorted(set(args.view_counts)))
+    # the label-view capacity of every loop and row: the job's largest L with --group-predictions, else no loop keeps a group
+    args.label_view_capacity = (max(manifest["pack_label_views"]) if manifest.get("pack_label_views") else args.label_views) if args.group_predictions else 0
     if not manifest["out"]:
         raise SystemExit("no checkpoint directory (--out; the supervisor supplies one)")
     if dynamic and rank != 0:
@@ -989,6 +1043,7 @@ def _rank_main(args):
                 # where a batched rank's time went, in seconds over its frames: building inputs (dynamic queue only), resetting rows, the steps, checkpoints
                 "phase_seconds": [r.get("phase_seconds") for r in gathered],
                 **({"predictions": True} if args.predictions else {}),
+                **({"group_predictions": True} if args.group_predictions else {}),
                 **({"masks": True} if args.masks else {}),      # (--predictions: label files next to every checkpoint)
                 **(mean_frame_metrics(gathered) if args.metrics else {}),
                 "frames_outside_slots": sorted(f for r in gathered for f in r["frames_outside_slots"]),

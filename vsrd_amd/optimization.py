@@ -12,7 +12,7 @@ device memory that the kernels read (vsrd_render_config::device_schedule / devic
 Frames are independent problems (README.md:128): multi-GPU runs shard *frames* over ranks (vsrd_amd/launcher.py) and
 never exchange gradients.
 """
-from dataclasses import dataclass, field as dataclass_field
+from dataclasses import InitVar, dataclass, field as dataclass_field
 from typing import Optional, Sequence
 
 import ctypes
@@ -196,6 +196,18 @@ class FrameInputs:
     # 3-D ground truth for metrics() (main.py:877-886: target_inputs.boxes_3d and the dataset's rectification matrix), optional
     boxes_3d: Optional[torch.Tensor] = None              # [N,8,3] corners in the target's instance order, in the frame of the decoded boxes; NaN rows = no annotation
     rectification_matrix: Optional[torch.Tensor] = None  # [3,3] (None: identity)
+    # the frame's group for group_labels() (make_predictions.py:50-60: the frames that get labels, the target among them), all five or none.
+    # Keyword arguments and attributes like the fields above, but init-only: the dataclass's FIELDS stay what callers splat into it positionally
+    # (dataclasses.fields ends with the 3-D ground truth; dataclasses.replace carries these over through their defaults)
+    label_frame_ids: InitVar[Optional[torch.Tensor]] = None             # [L] int64
+    label_intrinsic_matrices: InitVar[Optional[torch.Tensor]] = None    # [L,3,3]
+    label_extrinsic_matrices: InitVar[Optional[torch.Tensor]] = None    # [L,4,4] (target-camera frame -> label view's camera frame)
+    label_boxes_2d: InitVar[Optional[torch.Tensor]] = None              # [L,N,4] (xmin, ymin, xmax, ymax) in the target's instance order, zeros where invisible
+    label_visible: InitVar[Optional[torch.Tensor]] = None               # [L,N] uint8 / bool
+
+    def __post_init__(self, label_frame_ids, label_intrinsic_matrices, label_extrinsic_matrices, label_boxes_2d, label_visible):
+        self.label_frame_ids, self.label_intrinsic_matrices, self.label_extrinsic_matrices = label_frame_ids, label_intrinsic_matrices, label_extrinsic_matrices
+        self.label_boxes_2d, self.label_visible = label_boxes_2d, label_visible
 
 
 @dataclass
@@ -421,7 +433,7 @@ class _FrameOutput:
 
 def _check_asked(name, members):
     """RuntimeError unless the loops `members` -- one loop, or the active frames of a batch -- can be asked for output `name` now."""
-    reads = _OUTPUTS[name].last_step
+    reads = _output(name).last_step
     if reads and not members[0].fused_glue:
         raise RuntimeError(f"{name}() reads the {reads} the fused glue keeps on the device (graph=True)")
     if reads and any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
@@ -508,10 +520,67 @@ def _metric_views(loop, state):
     return dict(iou_3d=state["ious"][:n, 0], iou_bev=state["ious"][:n, 1], summary=state["summary"], corners=state["corners"][:n])
 
 
+def label_view_count(inputs):
+    """L of a frame -- a frames.FramePack or a FrameInputs: the label views of its group, 0 when it has none."""
+    if isinstance(inputs, frames.FramePack):
+        return int(inputs.num_label_views)
+    ids = getattr(inputs, "label_frame_ids", None)
+    return 0 if ids is None else int(ids.shape[0])
+
+
+def _check_group(inputs, num_instances, capacity):
+    """ValueError unless the optional group of `inputs` has the shapes of its L and the frame's N, and L fits a row laid out for `capacity`
+    label views (0: the loop keeps no group, whatever the frame has): checked before a loop writes anything of the frame."""
+    count = label_view_count(inputs)
+    if count == 0 or capacity == 0:
+        return
+    if count > capacity:
+        raise ValueError(f"a frame with {count} label views in a loop laid out for {capacity} (max_label_views)")
+    shapes = dict(label_intrinsic_matrices=(count, 3, 3), label_extrinsic_matrices=(count, 4, 4), label_boxes_2d=(count, int(num_instances), 4),
+                  label_visible=(count, int(num_instances)))
+    for name, shape in shapes.items():
+        value = getattr(inputs, name, None)
+        if value is None or tuple(int(x) for x in value.shape) != shape:
+            raise ValueError(f"{name} of shape {None if value is None else tuple(value.shape)} for a group of {count} views and {int(num_instances)} "
+                             f"instances: expected {shape}")
+
+
+def _group_buffers(L, N, H, W):
+    """`L`: the label-view capacity.  The group's tables and the frame's own count (read), then vsrd_frame_group_labels' five outputs."""
+    f32 = torch.float32
+    return [("count", (1,), torch.int32, 1), ("frame_ids", (L,), torch.int64, -1), ("extrinsics", (L, 16), f32, 0.0), ("intrinsics", (L, 9), f32, 0.0),
+            ("gt_boxes", (L, N, 4), f32, 0.0), ("visible", (L, N), torch.uint8, 0), ("camera_corners", (L, N, 8, 3), f32, 0.0),
+            ("boxes_2d", (L, N, 4), f32, 0.0), ("mean_iou", (N, N), f32, 0.0), ("matched_gt", (N,), torch.int64, 0), ("confidences", (N,), f32, 0.0)]
+
+
+def _launch_group_labels(loop, state, frame, header):
+    det = loop.detector
+    return _lib.load().vsrd_frame_group_labels(
+        frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), loop.label_view_capacity,
+        state["count"].data_ptr(), _lib.ptr(state["extrinsics"]), _lib.ptr(state["intrinsics"]), _lib.ptr(state["gt_boxes"]), state["visible"].data_ptr(),
+        _lib.ptr(state["camera_corners"]), _lib.ptr(state["boxes_2d"]), _lib.ptr(state["mean_iou"]), state["matched_gt"].data_ptr(),
+        _lib.ptr(state["confidences"]), header, _lib.stream())
+
+
+def _group_views(loop, state):
+    n, l = loop.num_instances, label_view_count(loop.inputs)
+    return dict(boxes_3d=state["camera_corners"][:l, :n], boxes_2d=state["boxes_2d"][:l, :n].unflatten(-1, (2, 2)), confidences=state["confidences"][:n],
+                matched_gt=state["matched_gt"][:n], mean_iou=state["mean_iou"][:n, :n], frame_ids=state["frame_ids"][:l])
+
+
 _OUTPUTS = dict(
     labels=_FrameOutput(_label_buffers, _launch_labels, _label_views),                                        # csrc/frame_labels.h
     masks=_FrameOutput(_mask_buffers, _launch_masks, _mask_views, last_step="field block"),                   # csrc/frame_masks.h
     metrics=_FrameOutput(_metric_buffers, _launch_metrics, _metric_views, last_step="matching"))              # csrc/frame_metrics.h
+
+
+# ... and the outputs whose buffers are laid out for the LABEL-view capacity (max_label_views) instead of the row's views: a fourth entry on
+# the same path (`_output` finds either kind), in a table of its own because that one difference is all `_output_state` needs to know
+_LABEL_VIEW_OUTPUTS = dict(group_labels=_FrameOutput(_group_buffers, _launch_group_labels, _group_views))     # csrc/frame_group_labels.h
+
+
+def _output(name):
+    return _OUTPUTS[name] if name in _OUTPUTS else _LABEL_VIEW_OUTPUTS[name]
 
 
 class FrameOptimizer:
@@ -523,7 +592,7 @@ class FrameOptimizer:
     (``fused_hypernetwork = False`` keeps them with torch: the A/B reference)."""
 
     def __init__(self, inputs: FrameInputs, config: OptimizationConfig, device, graph=False, fused_glue=None, persistent=False, row=None,
-                 capacity=None, view_capacity=None):
+                 capacity=None, view_capacity=None, max_label_views=None):
         """``persistent``: the loop will be given other frames of the same shape through ``reset()`` (a frame SLOT, launcher.py): it then
         owns every buffer a captured graph holds the address of -- in particular a copy of the soft masks instead of the caller's tensor.
         ``row`` (a ``FrameRow``): the loop is one frame of a ``FrameBatch`` and keeps EVERY device buffer its kernels touch -- parameters,
@@ -534,7 +603,14 @@ class FrameOptimizer:
         inverse projections, extrinsics and intrinsics, ground-truth boxes and visibility, soft masks, sampling weights, the ray table, the
         label outputs, the prologue's scratch -- is laid out for ``view_capacity`` views; they are view-major, so the frame's own V fill a
         prefix of each, and the header carries V and V H W.  Either capacity gives the row a header; the other one is then the founder's
-        own count."""
+        own count.
+        ``max_label_views``: the label views (``FrameInputs.label_*``: the frame's group) that ``group_labels()`` lays its tables out for --
+        None: the frame's own L; a loop that ``reset()`` gives other frames needs the largest L among them.  0: the loop keeps no group."""
+        self.label_view_capacity = label_view_count(inputs) if max_label_views is None else int(max_label_views)
+        if not 0 <= self.label_view_capacity <= _lib.MAX_LABEL_VIEWS:
+            raise ValueError(f"max_label_views: 0..{_lib.MAX_LABEL_VIEWS}, got {self.label_view_capacity}")
+        if label_view_count(inputs) > self.label_view_capacity > 0:
+            raise ValueError(f"a frame with {label_view_count(inputs)} label views in a loop laid out for {self.label_view_capacity} (max_label_views)")
         self._graphs = {}
         self.persistent = bool(persistent)
         self._row = row
@@ -1193,7 +1269,8 @@ class FrameOptimizer:
                            visible=b["visible"])
         intrinsics, extrinsics = frames.camera_matrices(pack, self.device)
         return FrameInputs((H, W), intrinsics, extrinsics, self.flat_masks.view(V, H, W, stride)[..., :N],
-                           b["gt_boxes"][:, :N].unflatten(-1, (2, 2)), b["visible"][:, :N].bool(), *frames.ground_truth_3d(pack, self.device))
+                           b["gt_boxes"][:, :N].unflatten(-1, (2, 2)), b["visible"][:, :N].bool(), *frames.ground_truth_3d(pack, self.device),
+                           **frames.group_tables(pack, self.device))
 
     def reset(self, inputs: FrameInputs, init_seed=None):
         """Start ANOTHER frame of the same shape in this loop, in place: the new frame's matrices, boxes and soft masks are copied into
@@ -1210,6 +1287,7 @@ class FrameOptimizer:
         V, H, W, N = _incoming_shape(inputs, (self.num_views, *self.inputs.image_size, self.num_instances),
                                      (self.view_capacity, self.capacity) if self._headed else None)
         _check_ground_truth(inputs, N)           # (before anything of the row is overwritten)
+        _check_group(inputs, N, self.label_view_capacity)
         with _capture_lock, torch.no_grad():
             main = torch.cuda.current_stream(dev)
             main.synchronize()                                      # (replays of the previous frame have finished: nothing reads the buffers)
@@ -1229,6 +1307,8 @@ class FrameOptimizer:
             self.inputs = inputs
             if "metrics" in self._outputs:
                 self._write_ground_truth(N)      # (the row's 3-D ground truth becomes the new frame's, or none)
+            if "group_labels" in self._outputs:
+                self._write_group(N)             # (likewise the row's group)
             if N != self.num_instances:
                 # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
                 # addresses: the pointer blocks and the captured graphs stay valid)
@@ -1270,34 +1350,41 @@ class FrameOptimizer:
 
     # ---- what a frame can be asked for after its steps (_OUTPUTS) ------------------------------------------------------------------
     def _output_state(self, name):
-        """The buffers of output `name` (_OUTPUTS[name].buffers), created at first use -- in the frame's row when there is one (a
+        """The buffers of output `name` (_output(name).buffers), created at first use -- in the frame's row when there is one (a
         FrameBatch creates them in every row at once: equal offsets) -- and laid out for the capacities.  metrics() keeps the frame's 3-D
         ground truth among them: checked before anything is created, written here and by every reset()."""
         if name not in self._outputs:
             H, W = (int(x) for x in self.inputs.image_size)
-            if name == "metrics":      # (by name, like reset(): the one output with inputs in its state; a hook for it alone would be an extension point)
+            if name == "metrics":      # (by name, like reset(): the outputs with inputs in their state; a hook for the two would be an extension point)
                 _check_ground_truth(self.inputs, self.num_instances)
+            if name == "group_labels":
+                _check_group(self.inputs, self.num_instances, self.label_view_capacity)
+            views = self.label_view_capacity if name in _LABEL_VIEW_OUTPUTS else self.view_capacity      # (the group's buffers: label views along dimension 0)
             with _capture_lock, torch.no_grad():
-                self._outputs[name] = {key: self._new(*buffer) for key, *buffer in _OUTPUTS[name].buffers(self.view_capacity, self.capacity, H, W)}
+                self._outputs[name] = {key: self._new(*buffer) for key, *buffer in _output(name).buffers(views, self.capacity, H, W)}
                 if name == "metrics":
                     self._write_ground_truth(self.num_instances)
+                if name == "group_labels":
+                    self._write_group(self.num_instances)
         return self._outputs[name]
 
     def _launch_output(self, name, frames=None, **arguments):
         """ONE vsrd_frame_* call on this loop's tensors; ``frames = (B, stride)``: this loop is row 0 of a batch, as in `_fused_step`."""
         state = self._output_state(name)       # (the frame config's batch fields are this call's own: a copy of the glue's)
+        if not self.fused_glue and "frame" not in state:
+            state["frame"] = self._frame_config()      # (a loop without the fused glue has no frame config of its own)
         frame = _lib.FrameConfig.from_buffer_copy(self._frame if self.fused_glue else state["frame"])
         frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
         header = self._glue.get("header") if self.fused_glue else None
         with _capture_lock:
-            _lib.check(_OUTPUTS[name].launch(self, state, frame, None if header is None else header.data_ptr(), **arguments))
+            _lib.check(_output(name).launch(self, state, frame, None if header is None else header.data_ptr(), **arguments))
         return state
 
     def _ask(self, name, **arguments):
         """Output `name` (_OUTPUTS) of this loop: the preconditions, ONE launch on the current stream, the frame's own views."""
         _check_asked(name, [self])
         state = self._launch_output(name, **arguments)
-        return _OUTPUTS[name].views(self, state, **arguments)
+        return _output(name).views(self, state, **arguments)
 
     def labels(self):
         """The frame's pseudo-labels from its CURRENT parameters (tools/kitti_360/make_predictions.py:61-192), by one vsrd_frame_labels
@@ -1308,6 +1395,37 @@ class FrameOptimizer:
             with _capture_lock, torch.no_grad():       # (a loop without the fused glue: float32 copies of its inputs' tables and a frame config)
                 self._output_state("labels").update(tables=self._input_tables(), frame=self._frame_config())
         return self._ask("labels")
+
+    def _write_group(self, n):
+        """The row's label-view tables and count from `self.inputs`; a frame without a group leaves the count at 1 (group_labels() refuses it)."""
+        state, inp = self._outputs["group_labels"], self.inputs
+        count = label_view_count(inp)
+        state["count"].fill_(max(count, 1))
+        state["frame_ids"].fill_(-1)
+        if count:
+            n = int(n)
+            state["frame_ids"][:count].copy_(inp.label_frame_ids)
+            state["extrinsics"][:count].copy_(inp.label_extrinsic_matrices.reshape(count, 16))
+            state["intrinsics"][:count].copy_(inp.label_intrinsic_matrices.reshape(count, 9))
+            state["gt_boxes"][:count, :n].copy_(inp.label_boxes_2d.reshape(count, n, 4))
+            state["visible"][:count, :n].copy_(inp.label_visible.reshape(count, n))
+
+    def _check_has_group(self):
+        if label_view_count(self.inputs) == 0:
+            raise ValueError("group_labels() needs the frame's group: FrameInputs.label_frame_ids is None")
+        if self.label_view_capacity == 0:
+            raise ValueError("group_labels(): this loop was laid out for no label views (max_label_views)")
+
+    def group_labels(self):
+        """The frame's pseudo-labels in the views of its GROUP (``FrameInputs.label_*``; tools/kitti_360/make_predictions.py:50-192: the frames
+        whose instance set equals the target's, which are the frames a detector is trained on -- not the views the frame was optimised on,
+        which ``labels()`` serves) from its CURRENT parameters, by one vsrd_frame_group_labels call on the current stream, no host
+        synchronisation; like ``labels()`` it needs no step to have run.  A dictionary of device tensors sliced to the frame's own l label
+        views and n instances: boxes_3d [l,n,8,3], boxes_2d [l,n,2,2], confidences [n], matched_gt [n], mean_iou [n,n], frame_ids [l].
+        They are views of buffers the next call overwrites (formats.save_frame_group_labels writes them out).  ValueError when the frame has
+        no group."""
+        self._check_has_group()
+        return self._ask("group_labels")
 
     def masks(self, view=0, threshold=0.5, soft=False):
         """The frame's dense predicted instance masks of view ``view`` (0: the target view) -- what the reference renders every
@@ -1421,16 +1539,24 @@ class FrameBatch:
     Like a frame slot, a batch is built and captured once (``capture_all``) and then serves group after group of frames through
     ``reset(f, inputs, init_seed)``; a last group of fewer than B frames runs with ``active < B`` (the first ``active`` rows)."""
 
-    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None):
+    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None, max_label_views=None):
         """``max_instances`` and ``max_views`` None: every frame has ONE shape (views, height, width, instances).  ``max_instances`` an
         integer: a MIXED batch -- the frames have 1..max_instances instances each; every row is laid out for ``max_instances`` (the capacity)
         and carries its frame's own count in a header (include/vsrd_hip.h, vsrd_frame_header), and frame f still walks, bit for bit, the
         trajectory it walks in a slot of its own N, through both phases.  ``max_views`` an integer (1..32): likewise the frames have
         1..max_views views each and every row is laid out for ``max_views`` views (ABI 12).  The two combine; giving either one gives every
-        row a header, and the axis without a capacity stays uniform.  The frames always share (height, width)."""
+        row a header, and the axis without a capacity stays uniform.  The frames always share (height, width).  ``max_label_views``: the
+        label-view capacity of every row (``group_labels``; the frames' groups may differ in size whatever the other capacities are, their
+        count lives in the row) -- None: the largest L of the frames given, 0: no groups."""
         inputs = list(inputs)
         if not inputs:
             raise ValueError("FrameBatch needs at least one frame")
+        largest = max(label_view_count(i) for i in inputs)
+        self.max_label_views = largest if max_label_views is None else int(max_label_views)
+        if not 0 <= self.max_label_views <= _lib.MAX_LABEL_VIEWS:
+            raise ValueError(f"max_label_views: 0..{_lib.MAX_LABEL_VIEWS}, got {self.max_label_views}")
+        if largest > self.max_label_views > 0:
+            raise ValueError(f"a frame with {largest} label views in a batch laid out for {self.max_label_views} (max_label_views)")
         shape = tuple(int(x) for x in inputs[0].soft_masks.shape)
         self.max_instances = None if max_instances is None else int(max_instances)
         self.max_views = None if max_views is None else int(max_views)
@@ -1462,7 +1588,7 @@ class FrameBatch:
             config = dataclasses.replace(config, mlp_adjoint_item_slots=self.item_slots(self.size, config, shape[-1]))
         self.config, self.device = config, _indexed(device)
         with _capture_lock:
-            self.arena = FrameArena(self.size, self._row_bytes(shape, config), self.device)
+            self.arena = FrameArena(self.size, self._row_bytes(shape, config, self.max_label_views), self.device)
         # A row is FOUNDED on a frame that suits the table sampler its graphs will draw from (the frames a row later serves come through reset(),
         # which says so when one does not suit).  A founder that does not suit is replaced by the first one that does -- the shape is what a
         # row needs from its founder -- and listed in `unsuitable_founders`; no suitable founder at all: UnsuitableFrameError.
@@ -1476,7 +1602,7 @@ class FrameBatch:
                 row.cursor, row.layout = 0, []                           # (a founder that failed had begun to fill the row)
                 try:
                     member = FrameOptimizer(frame_inputs, cfg, self.device, graph=True, persistent=True, row=row, capacity=capacities[0],
-                                            view_capacity=capacities[1])
+                                            view_capacity=capacities[1], max_label_views=self.max_label_views)
                 except UnsuitableFrameError:
                     if position == 0:
                         self.unsuitable_founders.append(f)
@@ -1509,7 +1635,7 @@ class FrameBatch:
         return slots
 
     @staticmethod
-    def _row_bytes(shape, config):
+    def _row_bytes(shape, config, label_views=0):
         """Bytes of one frame's row: every device buffer a FrameOptimizer(row=...) creates (FrameRow.new raises if this is short)."""
         V, H, W, N = (int(x) for x in shape)
         lib = _lib.load()
@@ -1524,6 +1650,7 @@ class FrameBatch:
         total += 4 * (3 * N * _lib.MLP_WEIGHTS + 64 * N + 128 * V) + 16 * int(config.num_rays)          # the glue's tables
         total += N * H * ((W + 7) // 8) + 4 * H * W * N + 12 * N     # masks(): bit-packed masks, soft values, counts
         # (metrics(): 200 N + 68 bytes in five buffers, at most 14 KB: within the slack below)
+        total += int(label_views) * (129 * N + 108)                 # group_labels(): the label views' tables, ids, corners and boxes (the [N] outputs: slack)
         return total + (4 << 20)                                     # 256-byte alignment of ~400 buffers, step counters, rates, slack
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
@@ -1563,12 +1690,20 @@ class FrameBatch:
         if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
             raise RuntimeError(f"the frames of a batch laid their {name} buffers out differently: frame batches need equal offsets in every row")
         self.frames[0]._launch_output(name, frames=(active, self.arena.stride), **arguments)
-        return [_OUTPUTS[name].views(m, m._outputs[name], **arguments) for m in members]
+        return [_output(name).views(m, m._outputs[name], **arguments) for m in members]
 
     def labels(self, active=None):
         """The pseudo-labels of the first ``active`` frames (``FrameOptimizer.labels``) by ONE vsrd_frame_labels call for all of them: a
         list of dictionaries of device tensors, each sliced to its frame's own instance count."""
         return self._ask("labels", active)
+
+    def group_labels(self, active=None):
+        """The pseudo-labels of the first ``active`` frames in the views of their groups (``FrameOptimizer.group_labels``) by ONE
+        vsrd_frame_group_labels call for all of them, whatever their groups' sizes: a list of dictionaries of device tensors, each sliced to
+        its frame's own label views and instances.  ValueError when an active frame has no group."""
+        for m in self._members(active)[1]:
+            m._check_has_group()
+        return self._ask("group_labels", active)
 
     def masks(self, active=None, view=0, threshold=0.5, soft=False):
         """The dense predicted masks of the first ``active`` frames (``FrameOptimizer.masks``) by ONE vsrd_frame_masks call for all of
