@@ -37,18 +37,9 @@ def dev():
 def _frame_config(V, N):
     from oracle import geometry
     from vsrd_amd import _lib
-    frame = _lib.FrameConfig()
-    frame.num_boxes, frame.num_views = N, V
-    frame.height, frame.width, frame.epsilon = float(scenes.IMAGE_SIZE[0]), float(scenes.IMAGE_SIZE[1]), 1.0e-6
-    for j in range(3):
-        frame.location_lo[j], frame.location_hi[j] = geometry.LOCATION_RANGE[0][j], geometry.LOCATION_RANGE[1][j]
-        frame.dimension_lo[j], frame.dimension_hi[j] = geometry.DIMENSION_RANGE[0][j], geometry.DIMENSION_RANGE[1][j]
-    frame.num_steps = NUM_STEPS
-    frame.max_temperature, frame.min_temperature, frame.max_std, frame.min_std = 1.0, 0.1, 1.0, 0.1
-    frame.weight_iou, frame.weight_l1, frame.weight_silhouette = scenes.WEIGHTS[0], scenes.WEIGHTS[1], W_SIL
-    frame.beta1, frame.beta2, frame.adam_epsilon, frame.lr_gamma = BETAS[0], BETAS[1], ADAM_EPS, GAMMA
-    frame.num_frames, frame.frame_stride = 0, 0
-    return frame
+    return _lib.make_frame_config(N, V, scenes.IMAGE_SIZE, 1.0e-6, geometry.LOCATION_RANGE, geometry.DIMENSION_RANGE, num_steps=NUM_STEPS,
+                                  temperatures=(1.0, 0.1), std_deviations=(1.0, 0.1), loss_weights=(scenes.WEIGHTS[0], scenes.WEIGHTS[1], W_SIL),
+                                  betas=BETAS, adam_epsilon=ADAM_EPS, lr_gamma=GAMMA)
 
 
 def _is_fill(t):

@@ -12,14 +12,13 @@ is about ten float32 roundings, the sum of at most L terms <= 1 divided by its c
 in ascending order), end to end 2 x floor + that bound, exact +0.0 where the formula is 0 or no view sees the slot, the assignment scipy's on
 the device's own matrix, the confidences the matched entries bit for bit.  With a row's own views as label views nothing is bounded: the
 five outputs are vsrd_frame_labels' bits."""
-import math
-
 import pytest
 import torch
 
 import frame_glue_scenes as scenes
 import test_hip_frame_labels as labels_test
 from conftest import margin
+from frame_rows import RowArena
 from oracle import frame_glue as ref
 
 pytestmark = pytest.mark.gpu
@@ -38,30 +37,18 @@ def dev():
     return torch.device("cuda:0")
 
 
-class Arena:
-    """B rows laid out for L label views and a capacity of N boxes."""
+class Arena(RowArena):
+    """B rows laid out for L label views and a capacity of N boxes, filled with NaN bits (the int64 output with -7)."""
 
     def __init__(self, L, N, B=1):
         f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
         fields = [("loc", (N, 3), f32), ("dim", (N, 3), f32), ("ori", (N, 2), f32), ("count", (1,), i32), ("E", (L, 16), f32), ("K", (L, 9), f32),
                   ("gt", (L, N, 4), f32), ("visible", (L, N), u8), ("header", (2,), i32), ("camera_corners", (L, N, 8, 3), f32),
                   ("boxes_2d", (L, N, 4), f32), ("mean_iou", (N, N), f32), ("matched_gt", (N,), i64), ("confidences", (N,), f32)]
-        self.L, self.N, self.B, self.layout, cursor = L, N, B, {}, 0
-        for name, shape, dtype in fields:
-            nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
-            self.layout[name] = (cursor, nbytes, shape, dtype)
-            cursor = (cursor + nbytes + 255) // 256 * 256
-        self.stride = cursor + GAP
-        assert self.stride % 256 == 0
-        self.host = torch.empty(B * self.stride, dtype=torch.uint8)
-        self.host.view(torch.int32).fill_(NAN_BITS)
+        super().__init__(fields, B, NAN_BITS, GAP)
+        self.L, self.N = L, N
         for f in range(B):
             self.view("matched_gt", f).fill_(-7)
-
-    def view(self, name, f=0, host=None):
-        offset, nbytes, shape, dtype = self.layout[name]
-        start = f * self.stride + offset
-        return (self.host if host is None else host)[start:start + nbytes].view(dtype).view(shape)
 
     def put(self, f, scene, header=True, count=True):
         """Frame f's inputs: the scene's l views and n boxes in the leading corner of the row's tables (the rest keeps the fill)."""
@@ -75,8 +62,7 @@ class Arena:
         if count:
             self.view("count", f)[0] = l
         if header:
-            self.view("header", f)[0] = n
-            self.view("header", f).view(torch.float32)[1] = 1.0
+            self.write_header(f, n)
 
 
 def _call(dev, arena, header=True, count=True, frame=None, L=None, null=(), expect_ok=True):
@@ -84,8 +70,7 @@ def _call(dev, arena, header=True, count=True, frame=None, L=None, null=(), expe
     from vsrd_amd import _lib
     lib = _lib.load()
     device = arena.host.to(dev)
-    base = device.data_ptr()
-    pointer = lambda name: None if name in null else base + arena.layout[name][0]
+    pointer = arena.pointers(device, null)
     if frame is None:           # (num_views is not read: 1 would do as well as anything)
         frame = labels_test._frame_config(1, arena.N, arena.B, arena.stride if arena.B > 1 else 0)
     code = lib.vsrd_frame_group_labels(frame, pointer("loc"), pointer("dim"), pointer("ori"), arena.L if L is None else L,
@@ -224,6 +209,18 @@ def test_invalid_arguments_are_refused(dev):
         code, after = _call(dev, arena, header=False, expect_ok=False, **arguments)
         assert code == _lib.E_INVALID_ARGUMENT, label
         assert torch.equal(after, arena.host), label
+
+
+def test_a_config_without_views_or_steps_is_accepted(dev):
+    """Of its config the call reads num_boxes, the image, the guard, the ranges and the batch fields: num_views = 0 and num_steps = 0, which
+    vsrd_frame_labels and the prologues refuse, are accepted and write the bytes of the call with a fully filled config (one frame, L = 1,
+    N = 1)."""
+    arena = Arena(1, 1)
+    arena.put(0, scenes.build(1, 1, 0), header=False, count=False)
+    _, full = _call(dev, arena, header=False, count=False)
+    code, lenient = _call(dev, arena, header=False, count=False, frame=labels_test._frame_config(0, 1, num_steps=0))
+    assert code == 0 and not torch.equal(full, arena.host)
+    assert torch.equal(lenient, full)
 
 
 # ---- 6. through the loops ----------------------------------------------------------------------------------------------------------------

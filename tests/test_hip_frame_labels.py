@@ -22,6 +22,7 @@ from scipy.optimize import linear_sum_assignment
 
 import frame_glue_scenes as scenes
 from conftest import margin
+from frame_rows import RowArena
 from oracle import frame_glue as ref
 
 pytestmark = pytest.mark.gpu
@@ -41,30 +42,18 @@ def dev():
     return torch.device("cuda:0")
 
 
-class Arena:
-    """B rows laid out for V views and a capacity of N boxes."""
+class Arena(RowArena):
+    """B rows laid out for V views and a capacity of N boxes, filled with NaN bits (the int64 output with -7)."""
 
     def __init__(self, V, N, B=1):
         f32, u8, i32, i64 = torch.float32, torch.uint8, torch.int32, torch.int64
         fields = [("loc", (N, 3), f32), ("dim", (N, 3), f32), ("ori", (N, 2), f32), ("E", (V, 16), f32), ("K", (V, 9), f32), ("gt", (V, N, 4), f32),
                   ("visible", (V, N), u8), ("header", (2,), i32), ("camera_corners", (V, N, 8, 3), f32), ("boxes_2d", (V, N, 4), f32),
                   ("mean_iou", (N, N), f32), ("matched_gt", (N,), i64), ("confidences", (N,), f32)]
-        self.V, self.N, self.B, self.layout, cursor = V, N, B, {}, 0
-        for name, shape, dtype in fields:
-            nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
-            self.layout[name] = (cursor, nbytes, shape, dtype)
-            cursor = (cursor + nbytes + 255) // 256 * 256
-        self.stride = cursor + GAP
-        assert self.stride % 256 == 0
-        self.host = torch.empty(B * self.stride, dtype=torch.uint8)
-        self.host.view(torch.int32).fill_(NAN_BITS)
+        super().__init__(fields, B, NAN_BITS, GAP)
+        self.V, self.N = V, N
         for f in range(B):
             self.view("matched_gt", f).fill_(-7)
-
-    def view(self, name, f=0, host=None):
-        offset, nbytes, shape, dtype = self.layout[name]
-        start = f * self.stride + offset
-        return (self.host if host is None else host)[start:start + nbytes].view(dtype).view(shape)
 
     def put(self, f, scene, header=True):
         """Frame f's inputs: the scene's n boxes in the first n instances of the row (the pad instances keep the fill)."""
@@ -76,22 +65,13 @@ class Arena:
         self.view("gt", f)[:, :n] = scene["gt_boxes"].float()
         self.view("visible", f)[:, :n] = scene["visible"].to(torch.uint8)
         if header:
-            self.view("header", f)[0] = n
-            self.view("header", f).view(torch.float32)[1] = 1.0
+            self.write_header(f, n)
 
 
-def _frame_config(V, N, B=1, stride=0):
+def _frame_config(V, N, B=1, stride=0, num_steps=3000):
     from oracle import geometry
     from vsrd_amd import _lib
-    frame = _lib.FrameConfig()
-    frame.num_boxes, frame.num_views = N, V
-    frame.height, frame.width, frame.epsilon = float(scenes.IMAGE_SIZE[0]), float(scenes.IMAGE_SIZE[1]), 1.0e-6
-    for j in range(3):
-        frame.location_lo[j], frame.location_hi[j] = geometry.LOCATION_RANGE[0][j], geometry.LOCATION_RANGE[1][j]
-        frame.dimension_lo[j], frame.dimension_hi[j] = geometry.DIMENSION_RANGE[0][j], geometry.DIMENSION_RANGE[1][j]
-    frame.num_steps = 3000
-    frame.num_frames, frame.frame_stride = B, stride
-    return frame
+    return _lib.make_frame_config(N, V, scenes.IMAGE_SIZE, 1.0e-6, geometry.LOCATION_RANGE, geometry.DIMENSION_RANGE, num_steps=num_steps, frames=(B, stride))
 
 
 def _call(dev, arena, header=True, frame=None, null=(), expect_ok=True):
@@ -99,8 +79,7 @@ def _call(dev, arena, header=True, frame=None, null=(), expect_ok=True):
     from vsrd_amd import _lib
     lib = _lib.load()
     device = arena.host.to(dev)
-    base = device.data_ptr()
-    pointer = lambda name: None if name in null else base + arena.layout[name][0]
+    pointer = arena.pointers(device, null)
     if frame is None:
         frame = _frame_config(arena.V, arena.N, arena.B, arena.stride if arena.B > 1 else 0)
     code = lib.vsrd_frame_labels(frame, *[pointer(name) for name in INPUTS[:-1]], *[pointer(name) for name in OUTPUTS],
@@ -298,3 +277,14 @@ def test_invalid_arguments_are_refused(dev):
         code, after = _call(dev, arena, header=False, expect_ok=False, **arguments)
         assert code < 0, label
         assert torch.equal(after, arena.host), label
+
+
+def test_a_config_without_steps_is_accepted(dev):
+    """Of its config the call reads the sizes, the image, the guard, the ranges and the batch fields: num_steps = 0, which the prologues and
+    the epilogue refuse, is accepted and writes the bytes of the call with a fully filled config (one frame, V = 1, N = 1)."""
+    arena = Arena(1, 1)
+    arena.put(0, scenes.build(1, 1, 0), header=False)
+    _, full = _call(dev, arena, header=False)
+    code, lenient = _call(dev, arena, header=False, frame=_frame_config(1, 1, num_steps=0))
+    assert code == 0 and not torch.equal(full, arena.host)
+    assert torch.equal(lenient, full)

@@ -26,6 +26,7 @@ import pytest
 import torch
 
 from conftest import margin
+from frame_rows import RowArena
 
 pytestmark = pytest.mark.gpu
 
@@ -165,26 +166,15 @@ def conditioning(c1, c2):
 
 
 # ---- the C ABI by hand ----------------------------------------------------------------------------------------------------------------
-class Arena:
+class Arena(RowArena):
     """B rows laid out for a capacity of N boxes; every byte starts as the sentinel."""
 
     def __init__(self, N, B=1):
         f32, i32, i64 = torch.float32, torch.int32, torch.int64
         fields = [("loc", (N, 3), f32), ("dim", (N, 3), f32), ("ori", (N, 2), f32), ("gt", (N, 8, 3), f32), ("rect", (3, 3), f32), ("pd", (N,), i64),
                   ("gi", (N,), i64), ("header", (6,), i32), ("corners", (N, 8, 3), f32), ("ious", (N, 2), f32), ("summary", (8,), f32)]
-        self.N, self.B, self.layout, cursor = N, B, {}, 0
-        for name, shape, dtype in fields:
-            nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
-            self.layout[name] = (cursor, nbytes, shape, dtype)
-            cursor = (cursor + nbytes + 255) // 256 * 256
-        self.stride = cursor + GAP
-        self.host = torch.empty(B * self.stride, dtype=torch.uint8)
-        self.host.view(torch.int32).fill_(SENTINEL_BITS)
-
-    def view(self, name, f=0, host=None):
-        offset, nbytes, shape, dtype = self.layout[name]
-        start = f * self.stride + offset
-        return (self.host if host is None else host)[start:start + nbytes].view(dtype).view(shape)
+        super().__init__(fields, B, SENTINEL_BITS, GAP)
+        self.N = N
 
     def put(self, f, raw, gt=None, rect=None, pairs=None, header=True):
         n = len(raw)
@@ -197,22 +187,13 @@ class Arena:
             self.view("pd", f)[:n], self.view("gi", f)[:n] = torch.as_tensor(pairs[0]), torch.as_tensor(pairs[1])
         if header:
             self.view("header", f).zero_()
-            self.view("header", f)[0] = n
-            self.view("header", f).view(torch.float32)[1] = 1.0
+            self.write_header(f, n)
 
 
-def frame_config(N, B=1, stride=0):
+def frame_config(N, B=1, stride=0, num_views=1, image_size=(32.0, 64.0), num_steps=3000):
     from oracle import geometry
     from vsrd_amd import _lib
-    frame = _lib.FrameConfig()
-    frame.num_boxes, frame.num_views = N, 1
-    frame.height, frame.width, frame.epsilon = 32.0, 64.0, 1.0e-6
-    for j in range(3):
-        frame.location_lo[j], frame.location_hi[j] = geometry.LOCATION_RANGE[0][j], geometry.LOCATION_RANGE[1][j]
-        frame.dimension_lo[j], frame.dimension_hi[j] = geometry.DIMENSION_RANGE[0][j], geometry.DIMENSION_RANGE[1][j]
-    frame.num_steps = 3000
-    frame.num_frames, frame.frame_stride = B, stride
-    return frame
+    return _lib.make_frame_config(N, num_views, image_size, 1.0e-6, geometry.LOCATION_RANGE, geometry.DIMENSION_RANGE, num_steps=num_steps, frames=(B, stride))
 
 
 def launch(dev, arena, header=True, rect=True, pairs=True, null=(), frame=None, expect_ok=True):
@@ -220,9 +201,7 @@ def launch(dev, arena, header=True, rect=True, pairs=True, null=(), frame=None, 
     from vsrd_amd import _lib
     lib = _lib.load()
     device = arena.host.to(dev)
-    base = device.data_ptr()
-    skipped = set(null) | (set() if rect else {"rect"}) | (set() if pairs else {"pd", "gi"}) | (set() if header else {"header"})
-    pointer = lambda name: None if name in skipped else base + arena.layout[name][0]
+    pointer = arena.pointers(device, set(null) | (set() if rect else {"rect"}) | (set() if pairs else {"pd", "gi"}) | (set() if header else {"header"}))
     if frame is None:
         frame = frame_config(arena.N, arena.B, arena.stride if arena.B > 1 else 0)
     code = lib.vsrd_frame_metrics(frame, *[pointer(name) for name in INPUTS[:-1]], *[pointer(name) for name in OUTPUTS], pointer("header"), _lib.stream())
@@ -420,6 +399,20 @@ def test_invalid_arguments_are_refused(dev):
         assert code == _lib.E_INVALID_ARGUMENT and torch.equal(after, arena.host)
     code, after = launch(dev, arena, header=False, null=("corners",))      # (corners may be NULL)
     assert code == 0 and bool((arena.view("corners", 0, after) == SENTINEL).all()) and float(arena.view("summary", 0, after)[0]) == 0.0
+
+
+def test_a_config_of_nothing_but_boxes_and_ranges_is_accepted(dev):
+    """Of its config the call reads num_boxes, the ranges and the batch fields: num_views = 0, num_steps = 0 and an image of size zero, which
+    the other frame entry points refuse or would read, are accepted and write the bytes of the call with a fully filled config (one frame,
+    N = 1)."""
+    rng = np.random.default_rng(3)
+    raw = raw_boxes(rng, 1, ("small_yaw",))
+    arena = Arena(1)
+    arena.put(0, raw, ground_truth(exported_corners(dev, raw)[0], "small_yaw", rng)[None], header=False)
+    _, full = launch(dev, arena, header=False, rect=False, pairs=False)
+    code, lenient = launch(dev, arena, header=False, rect=False, pairs=False, frame=frame_config(1, num_views=0, image_size=(0.0, 0.0), num_steps=0))
+    assert code == 0 and not torch.equal(full, arena.host)
+    assert torch.equal(lenient, full)
 
 
 # ---- (b) end to end ----------------------------------------------------------------------------------------------------------------------

@@ -42,6 +42,23 @@ def test_header_symbols_are_exported(lib):
     assert lib.vsrd_error_string(-1) == b"invalid argument"
 
 
+def test_binding_is_read_from_the_header_and_refuses_what_it_does_not_know(monkeypatch, tmp_path):
+    """_lib.SIGNATURES is parsed from the header's prototypes at import: the types of one prototype spelled out, a parameter type outside
+    the binding's list is an error (no fall-back to a pointer or an int), and so is a missing header, by its path."""
+    from vsrd_amd import _lib
+    p = ctypes.c_void_p
+    assert _lib.SIGNATURES["vsrd_sample_rays"] == (ctypes.c_int32, [p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, p, p, ctypes.c_size_t, p, p])
+    assert _lib.SIGNATURES["vsrd_frame_epilogue"][1][5:9] == [ctypes.c_float] + [ctypes.POINTER(_lib.AdamTensors)] * 3
+    assert _lib.SIGNATURES["vsrd_error_string"] == (ctypes.c_char_p, [ctypes.c_int32]) and _lib.SIGNATURES["vsrd_abi_version"] == (ctypes.c_int32, [])
+    assert _lib.SIGNATURES["vsrd_ray_table_bytes"] == (ctypes.c_size_t, [ctypes.c_int64]) and _lib.SIGNATURES == _lib._signatures()
+    for unknown in ("double x", "float** rows", "vsrd_field* field", "const vsrd_other* other", "const int32_t count", "int16_t n", "float"):
+        with pytest.raises(_lib.VsrdHipError, match="no ctypes type"):
+            _lib._argtype(unknown)
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "include" / "vsrd_hip.h"))
+    with pytest.raises(_lib.VsrdHipError, match=re.escape(str(tmp_path / "include" / "vsrd_hip.h"))):
+        _lib._signatures()
+
+
 def test_workspace_sizes_are_the_parents(lib, monkeypatch):
     """The sizing contract of the C ABI, pinned.  Hosts size frame rows and arenas from these functions, so a change of the launch plans
     must not move a byte.  Every number below was recorded from the library of the commit BEFORE the launch planning was collapsed into
@@ -135,30 +152,139 @@ def test_workspace_sizes_are_the_parents(lib, monkeypatch):
             assert getattr(lib, name)(*args) == size, (name, args)
 
 
-def test_struct_layout_matches_header(tmp_path):
-    """The ctypes structures against the C compiler's view of include/vsrd_hip.h itself (gcc: sizeof / offsetof of every member that
-    matters), not against numbers copied into the test."""
-    import subprocess
+def test_constants_match_the_header():
+    """The literal constants of the binding against the header's #defines, both ways round: every integer VSRD_<X> the binding has a name <X>
+    for has that value, and every constant of the binding's families is defined in the header.  MAX_VIEWS, which the header does not
+    define, against the frame glue's own limit."""
     from vsrd_amd import _lib
-    members = {"vsrd_field": (_lib.Field, ["instances", "mlp_weights"]),
-               "vsrd_render_config": (_lib.RenderConfig, ["seed", "stream_offset", "flags", "device_schedule", "device_stream_offset", "ray_indices", "rays_per_origin",
-                                                          "target_columns", "target_stride", "out_distances", "out_u_fine", "num_frames", "frame_stride", "adjoint_slots_per_item"]),
-               "vsrd_frame_config": (_lib.FrameConfig, ["num_steps", "lr_gamma", "num_frames", "frame_stride"]),
-               "vsrd_adam_tensors": (_lib.AdamTensors, ["learning_rate"]),
-               "vsrd_hypernetwork": (_lib.Hypernetwork, ["embeddings", "norm_bias", "num_frames", "frame_stride"])}
+    header = open(os.path.join(ROOT, "include", "vsrd_hip.h")).read()
+    defines = {name: int(value.rstrip("u"), 0) for name, value in re.findall(r"^#define VSRD_(\w+) \(?(-?(?:0x[0-9a-fA-F]+|\d+)u?)\)?(?:\s|$)", header, flags=re.M)}
+    assert {"OK", "HYPER_WIDTH", "ABI_VERSION", "E_WORKSPACE", "FLAG_MLP_SPLIT_BF16", "MAX_LABEL_VIEWS"} <= set(defines)
+    shared = [name for name in defines if hasattr(_lib, name)]
+    for name in shared:
+        assert getattr(_lib, name) == defines[name], name
+    family = re.compile(r"(FLAG_|E_)\w+|MAX_INSTANCES|MAX_SAMPLES|MAX_LABEL_VIEWS|INSTANCE_STRIDE|MLP_WEIGHTS|HYPER_LAYERS|FRAME_HEADER_HAS_VIEWS|ABI_VERSION")
+    named = [name for name in vars(_lib) if family.fullmatch(name)]
+    assert sorted(named) == sorted(shared) and len(named) == 24
+    glue = open(os.path.join(ROOT, "vsrd_amd", "csrc", "frame_step.h")).read()
+    assert _lib.MAX_VIEWS == int(re.search(r"constexpr int kFrameMaxViews = (\d+)", glue).group(1))
+
+
+STRUCTS = {"Field": "vsrd_field", "RenderConfig": "vsrd_render_config", "FrameConfig": "vsrd_frame_config", "AdamTensors": "vsrd_adam_tensors",
+           "Hypernetwork": "vsrd_hypernetwork", "FrameHeader": "vsrd_frame_header", "FrameMasksConfig": "vsrd_frame_masks_config"}
+
+
+def _declared_members(struct):
+    """The member names of `typedef struct <struct> {...}` in the header, in declaration order (`float height, width;` and
+    `float location_lo[3], location_hi[3];` are two members each)."""
+    header = open(os.path.join(ROOT, "include", "vsrd_hip.h")).read()
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), header, flags=re.S).group(1)
+    declarations = [line for line in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";") if line.strip()]
+    return [re.search(r"(\w+)\s*(?:\[[^\]]*\])?\s*$", declarator).group(1) for line in declarations for declarator in line.split(",")]
+
+
+@pytest.fixture(scope="module")
+def compiled_layout(tmp_path_factory):
+    """The C compiler's view of include/vsrd_hip.h (gcc, one program for all structures): {"<struct>": sizeof, "<struct>.<member>":
+    (offsetof, sizeof)} for every member the header declares."""
+    import subprocess
+    folder = tmp_path_factory.mktemp("layout")
     lines = []
-    for struct, (_, names) in members.items():
-        lines.append(f'printf("{struct} %zu\\n", sizeof({struct}));')
-        lines += [f'printf("{struct}.{name} %zu\\n", offsetof({struct}, {name}));' for name in names]
-    source = tmp_path / "layout.c"
+    for struct in STRUCTS.values():
+        lines.append(f'printf("{struct} %zu 0\\n", sizeof({struct}));')
+        lines += [f'printf("{struct}.{name} %zu %zu\\n", offsetof({struct}, {name}), sizeof((({struct}*)0)->{name}));' for name in _declared_members(struct)]
+    source = folder / "layout.c"
     source.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vsrd_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(source), "-o", str(tmp_path / "layout")], check=True)
-    seen = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
-    for struct, (binding, names) in members.items():
-        assert int(seen[struct]) == ctypes.sizeof(binding), struct
-        for name in names:
-            assert int(seen[f"{struct}.{name}"]) == getattr(binding, name).offset, (struct, name)
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(source), "-o", str(folder / "layout")], check=True)
+    rows = [line.split() for line in subprocess.run([str(folder / "layout")], capture_output=True, text=True, check=True).stdout.splitlines()]
+    return {key: (int(first), int(second)) for key, first, second in rows}
+
+
+@pytest.mark.parametrize("binding", list(STRUCTS))
+def test_struct_matches_the_header(compiled_layout, binding):
+    """A ctypes structure against the C compiler's view of the header itself, not against numbers copied into the test: the member names in
+    declaration order, sizeof the structure, and offsetof and sizeof of EVERY member."""
+    from vsrd_amd import _lib
+    structure, struct = getattr(_lib, binding), STRUCTS[binding]
+    names = [name for name, _ in structure._fields_]
+    assert names == _declared_members(struct)
+    assert ctypes.sizeof(structure) == compiled_layout[struct][0]
+    for name in names:
+        member = getattr(structure, name)
+        assert (member.offset, member.size) == compiled_layout[f"{struct}.{name}"], (struct, name)
+
+
+def test_struct_layout_matches_header():
+    """The sizes the ABI has had since its version 8, as literals (the members: test_struct_matches_the_header)."""
+    from vsrd_amd import _lib
     assert ctypes.sizeof(_lib.RenderConfig) == 160 and ctypes.sizeof(_lib.FrameConfig) == 128 and ctypes.sizeof(_lib.Hypernetwork) == 24 + 24 * 40 + 16      # ABI 8
+
+
+def _frame_refusals(_lib):
+    """[(label, entry point, arguments, code)]: calls of the entry points that take a vsrd_frame_config, each refused before any HIP call.
+    Pointers are dummies that are never dereferenced."""
+    P = 0x1000
+    full = dict(num_steps=3000, temperatures=(1.0, 0.1), std_deviations=(1.0, 0.1), loss_weights=(1.0, 1.0, 1.0), betas=(0.9, 0.999), adam_epsilon=1e-8, lr_gamma=0.999)
+
+    def config(N=3, V=4, frames=None, **changes):
+        return _lib.make_frame_config(N, V, (32.0, 64.0), 1.0e-6, [[-50.0, 1.0, 0.0], [50.0, 2.0, 100.0]], [[0.7, 0.7, 1.5], [1.0, 1.0, 2.5]], frames=frames,
+                                      **dict(full, **changes))
+    adam = _lib.AdamTensors(P, P, P, P, P)
+    scratch = 4 * 3 * 36 * 4                   # vsrd_frame_scratch_bytes(4, 3)
+
+    def prologue(c, first=P, out=P, scratch_pointer=P, scratch_bytes=scratch, tail=()):
+        return [c, first, P, P, P, P, P, P, P, scratch_pointer, scratch_bytes, P, P, P, P, P, P, P, out, *tail, None]
+    draw = (P, 4096, 64, 5, None, P)           # ray_table, count, num_rays, seed, remap, ray_indices
+    entries = {          # name -> arguments(config, null first input, null required output)
+        "vsrd_frame_prologue": lambda c, first=P, out=P: prologue(c, first, out),
+        "vsrd_frame_prologue_with_header": lambda c, first=P, out=P: prologue(c, first, out, tail=(P,)),
+        "vsrd_frame_prologue_sample": lambda c, first=P, out=P: prologue(c, first, out, tail=draw),
+        "vsrd_frame_prologue_sample_with_header": lambda c, first=P, out=P: prologue(c, first, out, tail=(*draw, P)),
+        "vsrd_frame_epilogue": lambda c, first=P, out=P: [c, first, P, P, P, 0.1, adam, adam, adam, P, P, P, out, P, None],
+        "vsrd_frame_epilogue_with_header": lambda c, first=P, out=P: [c, first, P, P, P, 0.1, adam, adam, adam, P, P, P, out, P, P, None],
+        "vsrd_frame_labels": lambda c, first=P, out=P: [c, first, P, P, P, P, P, P, P, P, out, P, P, P, None],
+        "vsrd_frame_group_labels": lambda c, first=P, out=P, L=5: [c, first, P, P, L, P, P, P, P, P, P, P, out, P, P, P, None],
+        "vsrd_frame_metrics": lambda c, first=P, out=P, gi=P: [c, first, P, P, P, P, P, gi, P, P, out, P, None],
+    }
+    steps = [name for name in entries if "prologue" in name or "epilogue" in name]
+    cases = []
+    for name, arguments in entries.items():
+        for label, c in (("N = 0", config(N=0)), ("N = 65", config(N=65)), ("B = 2, stride 0", config(frames=(2, 0))), ("B = 2, stride 100", config(frames=(2, 100))),
+                         ("B = 1025, stride 256", config(frames=(1025, 256)))):
+            cases.append((label, name, arguments(c), -1))
+        cases.append(("null first input", name, arguments(config(), first=None), -1))
+        if name != "vsrd_frame_labels":            # (every output of vsrd_frame_labels may be null)
+            cases.append(("null required output", name, arguments(config(), out=None), -1))
+    for name in steps + ["vsrd_frame_labels"]:
+        cases += [("V = 0", name, entries[name](config(V=0)), -1), ("V = 33", name, entries[name](config(V=33)), -1)]
+    for name in steps:
+        cases.append(("num_steps = 0", name, entries[name](config(num_steps=0)), -1))
+    cases.append(("pd_indices without gt_indices", "vsrd_frame_metrics", entries["vsrd_frame_metrics"](config(), gi=None), -1))
+    cases += [(f"L = {L}", "vsrd_frame_group_labels", entries["vsrd_frame_group_labels"](config(), L=L), -1) for L in (0, 4097)]
+    for tail, name in (((), "vsrd_frame_prologue"), ((P,), "vsrd_frame_prologue_with_header")):
+        cases.append(("scratch one byte short", name, prologue(config(), scratch_bytes=scratch - 1, tail=tail), -4))
+        cases.append(("null scratch", name, prologue(config(), scratch_pointer=None, tail=tail), -4))
+        cases.append(("null output and scratch one byte short", name, prologue(config(), out=None, scratch_bytes=scratch - 1, tail=tail), -1))
+    # (the combined launches check the draw's arguments before the scratch: refused there, short of the LDS opt-in)
+    for tail, name in (((P, 0, 64, 5, None, P), "vsrd_frame_prologue_sample"), ((P, 0, 64, 5, None, P, P), "vsrd_frame_prologue_sample_with_header")):
+        cases.append(("count = 0 and scratch one byte short", name, prologue(config(), scratch_bytes=scratch - 1, tail=tail), -1))
+    return cases
+
+
+def test_frame_entry_points_refuse_what_the_parent_refused(lib):
+    """What each entry point that takes a vsrd_frame_config refuses, and with which code -- the contract the single reader of that struct
+    in csrc/api.hip (frame_shape / frame_args) must keep.  The rule of test_workspace_sizes_are_the_parents: every code below was recorded from
+    a library built at the commit BEFORE that reader was introduced, not from the code under test.  The box count and the batch fields are
+    refused by all nine entry points; the view count by the prologues, the epilogues and vsrd_frame_labels only; num_steps = 0 by the
+    prologues and the epilogues only (vsrd_frame_metrics reads neither and is called with such configs); in the prologues an invalid
+    argument is decided before the size of the scratch.  Every case returns before any HIP call (no GPU here); accepted calls are the GPU
+    tests' (test_hip_frame_labels.py, test_hip_frame_group_labels.py, test_hip_frame_metrics.py: the configs those calls accept)."""
+    from vsrd_amd import _lib
+    cases = _frame_refusals(_lib)
+    assert len(cases) == 93
+    for label, name, arguments, code in cases:
+        assert getattr(lib, name)(*arguments) == code, (name, label)
+    assert lib.vsrd_frame_scratch_bytes(3, 4) == 1728 and lib.vsrd_frame_scratch_bytes(33, 4) == 0
 
 
 def test_cpu_tensors_are_rejected_not_emulated(lib):

@@ -44,21 +44,15 @@ def test_abi_version_is_12():
     assert _lib.ABI_VERSION == 12 and "#define VSRD_ABI_VERSION 12" in header
 
 
-def test_frame_header_layout_matches_the_c_struct(tmp_path):
-    """The ctypes vsrd_frame_header against gcc's view of include/vsrd_hip.h (as tests/test_host_logic.py does for the other structs)."""
+def test_frame_header_layout_matches_the_c_struct():
+    """The grown vsrd_frame_header as literals (against gcc's view of the header, member by member: tests/test_host_logic.py::
+    test_struct_matches_the_header[FrameHeader]; the flag against its #define: test_constants_match_the_header)."""
     from vsrd_amd import _lib
     names = [name for name, _ in _lib.FrameHeader._fields_]
     assert names == ["num_instances", "loss_scale", "num_views", "reserved", "num_pixels"]
-    lines = ['printf("size %zu\\n", sizeof(vsrd_frame_header));', 'printf("flag %d\\n", VSRD_FRAME_HEADER_HAS_VIEWS);']
-    lines += [f'printf("{name} %zu\\n", offsetof(vsrd_frame_header, {name}));' for name in names]
-    source = tmp_path / "layout.c"
-    source.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vsrd_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(source), "-o", str(tmp_path / "layout")], check=True)
-    seen = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(seen["size"]) == ctypes.sizeof(_lib.FrameHeader) == 24
-    assert int(seen["flag"]) == _lib.FRAME_HEADER_HAS_VIEWS
-    for name in names:
-        assert int(seen[name]) == getattr(_lib.FrameHeader, name).offset, name
+    assert ctypes.sizeof(_lib.FrameHeader) == 24
+    header = open(os.path.join(ROOT, "include", "vsrd_hip.h")).read()
+    assert _lib.FRAME_HEADER_HAS_VIEWS == 0x10000 and "#define VSRD_FRAME_HEADER_HAS_VIEWS 0x10000 " in header
     assert (_lib.FrameHeader.num_instances.offset, _lib.FrameHeader.loss_scale.offset) == (0, 4)          # the ABI-9 header is its first 8 bytes
 
 

@@ -7,6 +7,7 @@ slowest, after two warm-up repetitions (one for the host path).  The comparison 
     python tools/frame_group_labels_bench.py [--out profiles/r07/frame_group_labels.txt]"""
 import argparse
 import ctypes
+import math
 import os
 import statistics
 import sys
@@ -29,20 +30,15 @@ def median_of(run, repetitions=5, warmup=2):
 
 
 def measure(N, L):
-    from vsrd_amd import _lib, formats, models, operations, synthetic
+    from vsrd_amd import _lib, formats, models, operations, optimization, synthetic
     lib, dev = _lib.load(), torch.device("cuda:0")
-    fields = (("loc", N * 12), ("dim", N * 12), ("ori", N * 8), ("E", L * 64), ("K", L * 36), ("gt", L * N * 16), ("visible", L * N),
-              ("corners", L * N * 96), ("boxes", L * N * 16), ("mean", N * N * 4), ("matched", N * 8), ("confidences", N * 4))
-    offsets, at = {}, 0
-    for name, nbytes in fields:
-        offsets[name] = (at, nbytes)
-        at = (at + nbytes + 255) // 256 * 256
-    stride = at
-    arena = torch.zeros(B, stride, dtype=torch.uint8, device=dev)
-
-    def view(f, name, shape, dtype=torch.float32):
-        offset, nbytes = offsets[name]
-        return arena[f, offset:offset + nbytes].view(dtype).view(shape)
+    f32, u8 = torch.float32, torch.uint8
+    buffers = (("loc", (N, 3), f32), ("dim", (N, 3), f32), ("ori", (N, 2), f32), ("E", (L, 16), f32), ("K", (L, 9), f32), ("gt", (L, N, 4), f32),
+               ("visible", (L, N), u8), ("corners", (L, N, 8, 3), f32), ("boxes", (L, N, 4), f32), ("mean", (N, N), f32), ("matched", (N,), torch.int64),
+               ("confidences", (N,), f32))
+    size = lambda shape, dtype: (math.prod(shape) * torch.empty((), dtype=dtype).element_size() + 255) // 256 * 256
+    arena = optimization.FrameArena(B, sum(size(shape, dtype) for _, shape, dtype in buffers), dev)
+    rows = [{name: row.new(shape, dtype, fill=0) for name, shape, dtype in buffers} for row in arena.rows]
     detector = models.BoxParameters3D(1, N).to(dev)
     groups = []
     for f in range(B):
@@ -53,17 +49,11 @@ def measure(N, L):
         group = synthetic.synthetic_group(f, HEIGHT, WIDTH, L, truth)
         groups.append(group)
         noise = 0.05 * torch.randn(N, 3, generator=torch.Generator().manual_seed(f))          # (the labelled boxes are near the truth, not on it)
-        view(f, "loc", (N, 3)).copy_(raw_loc[0] + noise); view(f, "dim", (N, 3)).copy_(raw_dim[0]); view(f, "ori", (N, 2)).copy_(raw_ori[0])
-        view(f, "E", (L, 16)).copy_(group["label_extrinsic_matrices"].reshape(L, 16)); view(f, "K", (L, 9)).copy_(group["label_intrinsic_matrices"].reshape(L, 9))
-        view(f, "gt", (L, N, 4)).copy_(group["label_boxes_2d"]); view(f, "visible", (L, N), torch.uint8).copy_(group["label_visible"])
-    frame = _lib.FrameConfig()
-    frame.num_boxes, frame.num_views = N, 1
-    frame.height, frame.width, frame.epsilon = float(HEIGHT), float(WIDTH), 1.0e-6
-    for j in range(3):
-        frame.location_lo[j], frame.location_hi[j] = float(detector.location_range[0, j]), float(detector.location_range[1, j])
-        frame.dimension_lo[j], frame.dimension_hi[j] = float(detector.dimension_range[0, j]), float(detector.dimension_range[1, j])
-    frame.num_frames, frame.frame_stride = B, stride
-    pointer = lambda name: ctypes.c_void_p(arena.data_ptr() + offsets[name][0])
+        rows[f]["loc"].copy_(raw_loc[0] + noise); rows[f]["dim"].copy_(raw_dim[0]); rows[f]["ori"].copy_(raw_ori[0])
+        rows[f]["E"].copy_(group["label_extrinsic_matrices"].reshape(L, 16)); rows[f]["K"].copy_(group["label_intrinsic_matrices"].reshape(L, 9))
+        rows[f]["gt"].copy_(group["label_boxes_2d"]); rows[f]["visible"].copy_(group["label_visible"])
+    frame = _lib.make_frame_config(N, 1, (HEIGHT, WIDTH), 1.0e-6, detector.location_range, detector.dimension_range, frames=(B, arena.stride))
+    pointer = lambda name: ctypes.c_void_p(rows[0][name].data_ptr())
 
     def launch():
         _lib.check(lib.vsrd_frame_group_labels(frame, pointer("loc"), pointer("dim"), pointer("ori"), L, None, pointer("E"), pointer("K"), pointer("gt"),
@@ -82,7 +72,7 @@ def measure(N, L):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         launch()
-        confidences = torch.stack([view(f, "confidences", (N,)) for f in range(B)]).cpu()
+        confidences = torch.stack([rows[f]["confidences"] for f in range(B)]).cpu()
         assert confidences.shape == (B, N)
         return 1000.0 * (time.perf_counter() - t0)
     tables = [[torch.where(g["label_visible"][l].bool(), torch.arange(N), torch.full((N,), -1)) for l in range(L)] for g in groups]
@@ -94,8 +84,8 @@ def measure(N, L):
         t0 = time.perf_counter()
         for f in range(B):
             with torch.no_grad():
-                detector.locations.copy_(view(f, "loc", (N, 3))[None]); detector.dimensions.copy_(view(f, "dim", (N, 3))[None])
-                detector.orientations.copy_(view(f, "ori", (N, 2))[None])
+                detector.locations.copy_(rows[f]["loc"][None]); detector.dimensions.copy_(rows[f]["dim"][None])
+                detector.orientations.copy_(rows[f]["ori"][None])
                 boxes, _ = operations.project_boxes_multi_view(detector()["boxes_3d"][0], *cameras[f], (HEIGHT, WIDTH))
             confidences, _, _ = formats.multi_view_confidences(list(boxes.cpu()), truths[f], tables[f])
             assert confidences.shape == (N,)

@@ -7,6 +7,7 @@ trace converged (the pixels (b) renders at all).
     python tools/frame_masks_bench.py [--out profiles/r07/frame_masks.txt] [--height 376 --width 1408]"""
 import argparse
 import ctypes
+import math
 import os
 import statistics
 import sys
@@ -55,23 +56,19 @@ def main():
     args = parser.parse_args()
     import __graft_entry__
     __graft_entry__.build()
-    from vsrd_amd import _lib, fields, models, rendering, synthetic
+    from vsrd_amd import _lib, fields, models, optimization, rendering, synthetic
     lib, dev = _lib.load(), torch.device("cuda:0")
     H, W = args.height, args.width
     R, row_bytes = H * W, (W + 7) // 8
     lines = [f"# tools/frame_masks_bench.py: {H} x {W}, N = {N}, S = {S}, trace {TRACE}, median of five [fastest .. slowest], ms per call for all B frames"]
     for residual in (False, True):
         for B in (1, 16):
-            offsets, at = {}, 0
-            for name, nbytes in (("instances", N * 64), ("cam", 12), ("dirs", R * 12), ("mlp", N * _lib.MLP_WEIGHTS * 4), ("inside", N * H * row_bytes)):
-                offsets[name] = (at, nbytes)
-                at = (at + nbytes + 255) // 256 * 256
-            stride = at
-            arena = torch.zeros(B, stride, dtype=torch.uint8, device=dev)
-
-            def view(f, name, dtype, shape):
-                offset, nbytes = offsets[name]
-                return arena[f, offset:offset + nbytes].view(dtype).view(shape)
+            f32 = torch.float32
+            buffers = (("instances", (N, 16), f32), ("cam", (1, 3), f32), ("dirs", (R, 3), f32), ("mlp", (N, _lib.MLP_WEIGHTS), f32), ("inside", (N, H, row_bytes), torch.uint8))
+            size = lambda shape, dtype: (math.prod(shape) * torch.empty((), dtype=dtype).element_size() + 255) // 256 * 256
+            arena = optimization.FrameArena(B, sum(size(shape, dtype) for _, shape, dtype in buffers), dev)
+            rows = [{name: row.new(shape, dtype, fill=0) for name, shape, dtype in buffers} for row in arena.rows]
+            stride = arena.stride
             for f in range(B):
                 K, E, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(f, 1, H, W, N)
                 det = models.BoxParameters3D(1, N)
@@ -79,31 +76,31 @@ def main():
                     det.locations.copy_(raw_loc); det.dimensions.copy_(raw_dim); det.orientations.copy_(raw_ori)
                     out = det()
                 cam, dirs = rendering.ray_casting((H, W), K.to(dev), E.to(dev))
-                view(f, "instances", torch.float32, (N, 16)).copy_(fields.pack_instances(out["locations"][0], out["orientations"][0], out["dimensions"][0]))
-                view(f, "cam", torch.float32, (1, 3)).copy_(cam)
-                view(f, "dirs", torch.float32, (R, 3)).copy_(dirs.reshape(-1, 3))
+                rows[f]["instances"].copy_(fields.pack_instances(out["locations"][0], out["orientations"][0], out["dimensions"][0]))
+                rows[f]["cam"].copy_(cam)
+                rows[f]["dirs"].copy_(dirs.reshape(-1, 3))
                 if residual:
-                    view(f, "mlp", torch.float32, (N, _lib.MLP_WEIGHTS)).copy_(0.05 * torch.randn(N, _lib.MLP_WEIGHTS, generator=torch.Generator().manual_seed(f)))
+                    rows[f]["mlp"].copy_(0.05 * torch.randn(N, _lib.MLP_WEIGHTS, generator=torch.Generator().manual_seed(f)))
             labels = torch.empty(R, N, device=dev)
             positions, converged = torch.empty(R, 3, device=dev), torch.empty(R, dtype=torch.uint8, device=dev)
 
             def field_of(f):
-                return _lib.Field(N, T, view(f, "instances", torch.float32, (N, 16)).data_ptr(), view(f, "mlp", torch.float32, (N, _lib.MLP_WEIGHTS)).data_ptr() if residual else None)
+                return _lib.Field(N, T, rows[f]["instances"].data_ptr(), rows[f]["mlp"].data_ptr() if residual else None)
 
             def composition():
                 for f in range(B):
-                    field, cam, dirs = field_of(f), view(f, "cam", torch.float32, (1, 3)), view(f, "dirs", torch.float32, (R, 3))
+                    field, cam, dirs = field_of(f), rows[f]["cam"], rows[f]["dirs"]
                     config = _lib.make_config(R, S, (0.0, 100.0), STD, RATIO, 1.0e-6, 0, seed=1)
                     _lib.check(lib.vsrd_render_hierarchical_forward(field, config, pointer(cam), pointer(dirs), None, None, pointer(labels), None, None, None, None, None, None, _lib.stream()))
                     _lib.check(lib.vsrd_sphere_trace(field, pointer(cam), 0, pointer(dirs), None, R, TRACE[0], TRACE[1], TRACE[2], 0, 0, pointer(positions), pointer(converged), _lib.stream()))
                     mask = (labels * converged[:, None].to(torch.float32)) > 0.5
-                    view(f, "inside", torch.uint8, (N, H, row_bytes)).copy_(packbits(mask.view(H, W, N).permute(2, 0, 1)))
+                    rows[f]["inside"].copy_(packbits(mask.view(H, W, N).permute(2, 0, 1)))
 
             def fused():
                 config = _lib.make_config(0, S, (0.0, 100.0), STD, RATIO, 1.0e-6, 3, seed=1, frames=(B, stride) if B > 1 else None)
                 masks = _lib.FrameMasksConfig(0, 1, H, W, TRACE[0], TRACE[1], TRACE[2], 0.5, N)
-                _lib.check(lib.vsrd_frame_masks(field_of(0), config, masks, pointer(view(0, "cam", torch.float32, (1, 3))), pointer(view(0, "dirs", torch.float32, (R, 3))),
-                                                None, None, None, None, pointer(view(0, "inside", torch.uint8, (N, H, row_bytes))), None, None, None, _lib.stream()))
+                _lib.check(lib.vsrd_frame_masks(field_of(0), config, masks, pointer(rows[0]["cam"]), pointer(rows[0]["dirs"]),
+                                                None, None, None, None, pointer(rows[0]["inside"]), None, None, None, _lib.stream()))
             a, b = timed(composition), timed(fused)
             share = float(converged.float().mean())
             lines.append(f"{'residual' if residual else 'box-only'} B = {B:2d}: (a) composition {a[0]:9.3f} [{a[1]:.3f} .. {a[2]:.3f}]   (b) vsrd_frame_masks {b[0]:9.3f} [{b[1]:.3f} .. {b[2]:.3f}]"

@@ -35,36 +35,24 @@ def main():
     args = parser.parse_args()
     import __graft_entry__
     __graft_entry__.build()
-    from vsrd_amd import _lib, formats, models, operations, synthetic
+    from vsrd_amd import _lib, formats, models, operations, optimization, synthetic
     lib, dev = _lib.load(), torch.device("cuda:0")
-    offsets, at = {}, 0
-    for name, nbytes in (("loc", N * 12), ("dim", N * 12), ("ori", N * 8), ("gt", N * 96), ("rect", 36), ("corners", N * 96), ("ious", N * 8), ("summary", 32)):
-        offsets[name] = (at, nbytes)
-        at = (at + nbytes + 255) // 256 * 256
-    stride = at
-    arena = torch.zeros(B, stride, dtype=torch.uint8, device=dev)
-
-    def view(f, name, shape):
-        offset, nbytes = offsets[name]
-        return arena[f, offset:offset + nbytes].view(torch.float32).view(shape)
+    buffers = (("loc", (N, 3)), ("dim", (N, 3)), ("ori", (N, 2)), ("gt", (N, 8, 3)), ("rect", (3, 3)), ("corners", (N, 8, 3)), ("ious", (N, 2)), ("summary", (8,)))
+    arena = optimization.FrameArena(B, sum((4 * math.prod(shape) + 255) // 256 * 256 for _, shape in buffers), dev)
+    rows = [{name: row.new(shape, fill=0) for name, shape in buffers} for row in arena.rows]
     detector = models.BoxParameters3D(1, N).to(dev)
     tilt = math.radians(2.0)
     rect = torch.tensor([[1.0, 0.0, 0.0], [0.0, math.cos(tilt), -math.sin(tilt)], [0.0, math.sin(tilt), math.cos(tilt)]])
     for f in range(B):
         _, _, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(f, 1, 376, 1408, N)
-        view(f, "loc", (N, 3)).copy_(raw_loc[0]); view(f, "dim", (N, 3)).copy_(raw_dim[0]); view(f, "ori", (N, 2)).copy_(raw_ori[0])
+        rows[f]["loc"].copy_(raw_loc[0]); rows[f]["dim"].copy_(raw_dim[0]); rows[f]["ori"].copy_(raw_ori[0])
         with torch.no_grad():
             detector.locations.copy_(raw_loc); detector.dimensions.copy_(raw_dim); detector.orientations.copy_(raw_ori)
             truth = detector()["boxes_3d"][0]
-        view(f, "gt", (N, 8, 3)).copy_(truth + 0.3 * torch.randn(N, 1, 3, generator=torch.Generator().manual_seed(f)).to(dev))
-        view(f, "rect", (3, 3)).copy_(rect)
-    frame = _lib.FrameConfig()
-    frame.num_boxes, frame.num_views = N, 1
-    for j in range(3):
-        frame.location_lo[j], frame.location_hi[j] = float(detector.location_range[0, j]), float(detector.location_range[1, j])
-        frame.dimension_lo[j], frame.dimension_hi[j] = float(detector.dimension_range[0, j]), float(detector.dimension_range[1, j])
-    frame.num_frames, frame.frame_stride = B, stride
-    pointer = lambda name: ctypes.c_void_p(arena.data_ptr() + offsets[name][0])
+        rows[f]["gt"].copy_(truth + 0.3 * torch.randn(N, 1, 3, generator=torch.Generator().manual_seed(f)).to(dev))
+        rows[f]["rect"].copy_(rect)
+    frame = _lib.make_frame_config(N, 1, (0.0, 0.0), 0.0, detector.location_range, detector.dimension_range, frames=(B, arena.stride))
+    pointer = lambda name: ctypes.c_void_p(rows[0][name].data_ptr())
 
     def launch():
         _lib.check(lib.vsrd_frame_metrics(frame, pointer("loc"), pointer("dim"), pointer("ori"), pointer("gt"), pointer("rect"), None, None, pointer("corners"),
@@ -82,7 +70,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         launch()
-        summaries = torch.stack([view(f, "summary", (8,)) for f in range(B)]).cpu()
+        summaries = torch.stack([rows[f]["summary"] for f in range(B)]).cpu()
         named = [formats.frame_metrics(s) for s in summaries]
         assert len(named) == B
         return 1000.0 * (time.perf_counter() - t0)
@@ -94,10 +82,10 @@ def main():
         named = []
         for f in range(B):
             with torch.no_grad():
-                detector.locations.copy_(view(f, "loc", (N, 3))[None]); detector.dimensions.copy_(view(f, "dim", (N, 3))[None])
-                detector.orientations.copy_(view(f, "ori", (N, 2))[None])
+                detector.locations.copy_(rows[f]["loc"][None]); detector.dimensions.copy_(rows[f]["dim"][None])
+                detector.orientations.copy_(rows[f]["ori"][None])
                 boxes = (detector()["boxes_3d"][0] @ rect.to(dev).T).cpu()
-            truth = (view(f, "gt", (N, 8, 3)) @ rect.to(dev).T).cpu()
+            truth = (rows[f]["gt"] @ rect.to(dev).T).cpu()
             pairs = [operations.box_3d_iou(boxes[k] @ rotation.T, truth[k] @ rotation.T) for k in range(N)]
             named.append(formats.frame_metrics(formats.frame_metrics_summary([p[0] for p in pairs], [p[1] for p in pairs])))
         return 1000.0 * (time.perf_counter() - t0)

@@ -6,6 +6,7 @@ point raises.
 """
 import ctypes
 import os
+import re
 import threading
 
 import torch
@@ -13,6 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VSRD_HIP_LIBRARY: an experiment build of the same ABI (tools/phase_timers.py, A/B macros); the product path is the in-tree default
 LIBRARY_PATH = os.environ.get("VSRD_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libvsrd_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vsrd_hip.h")
 
 ABI_VERSION = 12
 MAX_INSTANCES = 64
@@ -33,6 +35,10 @@ FLAG_YAW_GRADIENTS = 1024
 FLAG_MLP_SPLIT_BF16 = 2048
 
 c_float_p = ctypes.c_void_p  # device pointers travel as integers
+
+
+class VsrdHipError(RuntimeError):
+    pass
 
 
 class Field(ctypes.Structure):
@@ -133,7 +139,6 @@ class Hypernetwork(ctypes.Structure):
     ]
 
 
-# symbol -> (restype, argtypes); mirrors include/vsrd_hip.h one to one
 class FrameHeader(ctypes.Structure):
     """include/vsrd_hip.h::vsrd_frame_header (ABI 9, mixed batches): one frame's own instance count and silhouette normaliser; ABI 12:
     its own view count and the count of its sampling table, read when num_instances carries FRAME_HEADER_HAS_VIEWS."""
@@ -167,123 +172,48 @@ MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFra
 MAX_LABEL_VIEWS = 4096         # VSRD_MAX_LABEL_VIEWS: the label views (a frame's group) of vsrd_frame_group_labels
 
 
-SIGNATURES = {
-    "vsrd_abi_version": (ctypes.c_int32, []),
-    "vsrd_error_string": (ctypes.c_char_p, [ctypes.c_int32]),
-    "vsrd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
-    "vsrd_render_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "vsrd_ray_directions": (ctypes.c_int32, [c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_float_p, ctypes.c_void_p]),
-    "vsrd_field_eval": (ctypes.c_int32, [ctypes.POINTER(Field), c_float_p, ctypes.c_int64, c_float_p, c_float_p, c_float_p,
-                                         ctypes.c_int32, ctypes.c_void_p]),
-    "vsrd_sphere_trace": (ctypes.c_int32, [ctypes.POINTER(Field), c_float_p, ctypes.c_int32, c_float_p, ctypes.c_void_p, ctypes.c_int64,
-                                           ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
-                                           c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_polygon_soft_masks": (ctypes.c_int32, [c_float_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_void_p, ctypes.c_float, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_frame_ingest_chunk": (ctypes.c_int32, []),
-    "vsrd_frame_ingest": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                           c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_sample_stratified": (ctypes.c_int32, [ctypes.POINTER(RenderConfig), c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_sample_importance": (ctypes.c_int32, [ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_render_forward": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
-                                             ctypes.c_int32, c_float_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_render_backward": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
-                                              ctypes.c_int32, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_size_t,
-                                              c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_render_hierarchical_forward": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p,
-                                                          c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                          c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_render_silhouette_step": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
-                                                     c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
-                                                     c_float_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_residual_step_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "vsrd_render_residual_step": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
-                                                   c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
-                                                   ctypes.c_size_t, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_project_boxes_forward": (ctypes.c_int32, [c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                                    c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_field_eval_backward": (ctypes.c_int32, [ctypes.POINTER(Field), c_float_p, ctypes.c_int64, c_float_p, c_float_p, ctypes.c_int32,
-                                                  ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_sample_rays_workspace_bytes": (ctypes.c_size_t, []),
-    "vsrd_sample_rays": (ctypes.c_int32, [c_float_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_centre_mlp_weights": (ctypes.c_int32, [c_float_p, ctypes.c_int32, c_float_p, ctypes.c_void_p]),
-    "vsrd_ray_table_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "vsrd_ray_table_build": (ctypes.c_int32, [c_float_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "vsrd_sample_rays_table": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_match_boxes": (ctypes.c_int32, [c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_linear_sum_assignment": (ctypes.c_int32, [c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_frame_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
-    "vsrd_frame_prologue": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_frame_prologue_sample": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                    ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_frame_epilogue": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float,
-                                             ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors),
-                                             c_float_p, c_float_p, ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_void_p]),
-    # ABI 9: the twins of the batched entry points with a per-frame header (the header pointer before the stream)
-    "vsrd_frame_prologue_with_header": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p,
-                                                         ctypes.c_void_p]),
-    "vsrd_frame_prologue_sample_with_header": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                                c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_frame_epilogue_with_header": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float,
-                                                         ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors), ctypes.POINTER(AdamTensors),
-                                                         c_float_p, c_float_p, ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_render_silhouette_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
-                                                                 c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
-                                                                 c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_render_residual_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), c_float_p, c_float_p, c_float_p,
-                                                               c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
-                                                               ctypes.c_size_t, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_hypernetwork_forward_with_header": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p,
-                                                               ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_hypernetwork_backward_step_with_header": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p,
-                                                                     ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    # ABI 11: a frame's pseudo-labels (camera corners, clipped 2-D boxes, mean IoU, assignment, confidences); header before the stream
-    "vsrd_frame_labels": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                           ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
-                                           ctypes.c_void_p]),
-    # added within ABI 12: vsrd_frame_labels in label views of the call's own, the frame's group (L <= MAX_LABEL_VIEWS, per-frame count on the device)
-    "vsrd_frame_group_labels": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_void_p,
-                                                 c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p,
-                                                 c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # added within ABI 12: a view's dense predicted instance masks, bit-packed (+ soft values, pixel counts); header before the stream
-    "vsrd_frame_masks": (ctypes.c_int32, [ctypes.POINTER(Field), ctypes.POINTER(RenderConfig), ctypes.POINTER(FrameMasksConfig), c_float_p, c_float_p,
-                                          c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p]),
-    # added within ABI 12: a frame's 3-D / BEV IoU metrics against its ground truth (corners, IoUs per pair, summary); header before the stream
-    "vsrd_frame_metrics": (ctypes.c_int32, [ctypes.POINTER(FrameConfig), c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "vsrd_hypernetwork_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32]),
-    "vsrd_hypernetwork_forward": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_hypernetwork_backward_step": (ctypes.c_int32, [ctypes.POINTER(Hypernetwork), ctypes.c_void_p, ctypes.c_size_t, c_float_p, ctypes.c_float,
-                                                         ctypes.c_void_p]),
-    "vsrd_project_boxes_backward": (ctypes.c_int32, [c_float_p, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                     ctypes.c_int32, ctypes.c_float, c_float_p, ctypes.c_void_p, c_float_p,
-                                                     ctypes.c_void_p]),
-    "vsrd_selftest_wave": (ctypes.c_int32, [c_float_p, c_float_p, ctypes.c_void_p]),
-    "vsrd_selftest_gelu": (ctypes.c_int32, [c_float_p, ctypes.c_int32, c_float_p, ctypes.c_void_p]),
-}
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+            "size_t": ctypes.c_size_t}
+_RETURNS = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+# host structures, passed as const T*; every other pointer is device memory (vsrd_frame_header too) or the stream, and travels as an integer
+_HOST_STRUCTS = {"vsrd_field": Field, "vsrd_render_config": RenderConfig, "vsrd_frame_config": FrameConfig, "vsrd_adam_tensors": AdamTensors,
+                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig}
+_DEVICE_POINTEES = {"void", "float", "uint8_t", "int32_t", "int64_t", "uint64_t", "vsrd_frame_header"}
+
+
+def _argtype(parameter):
+    """One parameter of a prototype ("const float* origins", "size_t workspace_bytes") -> its ctypes type.  A type the binding does not know
+    is an error, never a guess."""
+    match = re.fullmatch(r"(const\s+)?(\w+)\s*(\*?)\s*\w+", parameter.strip())
+    if match:
+        const, name, star = match.groups()
+        if not star and not const and name in _SCALARS:
+            return _SCALARS[name]
+        if star and const and name in _HOST_STRUCTS:
+            return ctypes.POINTER(_HOST_STRUCTS[name])
+        if star and name in _DEVICE_POINTEES:
+            return ctypes.c_void_p
+    raise VsrdHipError(f"{HEADER_PATH}: no ctypes type for the parameter {parameter.strip()!r}")
+
+
+def _signatures():
+    """symbol -> (restype, argtypes), read from the prototypes of include/vsrd_hip.h: the header is the one place a prototype is written."""
+    if not os.path.exists(HEADER_PATH):
+        raise VsrdHipError(f"{HEADER_PATH} not found: the ctypes binding is derived from the header's prototypes")
+    with open(HEADER_PATH) as file:
+        text = re.sub(r"/\*.*?\*/", "", file.read(), flags=re.S)
+    table = {}
+    for restype, name, parameters in re.findall(r"^(int32_t|size_t|const char\*)\s+(vsrd_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        table[name] = (_RETURNS[restype], [] if parameters.strip() == "void" else [_argtype(p) for p in parameters.split(",")])
+    return table
+
+
+SIGNATURES = _signatures()
 
 E_INVALID_ARGUMENT, E_UNSUPPORTED, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4      # include/vsrd_hip.h: VSRD_E_*
 
 _lock = threading.Lock()
 _lib = None
-
-
-class VsrdHipError(RuntimeError):
-    pass
 
 
 def load():
@@ -340,6 +270,18 @@ def stream():
 def make_field(instances, temperature, mlp_weights=None):
     return Field(int(instances.shape[0]), float(temperature), ptr(instances).value,
                  None if mlp_weights is None else ptr(mlp_weights).value)
+
+
+def make_frame_config(num_boxes, num_views, image_size, epsilon, location_range, dimension_range, num_steps=0, temperatures=(0.0, 0.0),
+                      std_deviations=(0.0, 0.0), loss_weights=(0.0, 0.0, 0.0), betas=(0.0, 0.0), adam_epsilon=0.0, lr_gamma=0.0, frames=None):
+    """include/vsrd_hip.h::vsrd_frame_config.  `image_size` (height, width); `location_range` / `dimension_range` [2][3] = (lo, hi);
+    `temperatures` / `std_deviations` (max, min); `loss_weights` (iou, l1, silhouette); `frames`: optional (num_frames, frame_stride in
+    bytes).  What only the prologues and the epilogue read (from `num_steps` on) defaults to zero, as in a fresh FrameConfig."""
+    vec3 = lambda row: (ctypes.c_float * 3)(*(float(row[j]) for j in range(3)))
+    return FrameConfig(int(num_boxes), int(num_views), float(image_size[0]), float(image_size[1]), float(epsilon),
+                       vec3(location_range[0]), vec3(location_range[1]), vec3(dimension_range[0]), vec3(dimension_range[1]),
+                       int(num_steps), *map(float, temperatures), *map(float, std_deviations), *map(float, loss_weights), *map(float, betas),
+                       float(adam_epsilon), float(lr_gamma), *((0, 0) if frames is None else (int(frames[0]), int(frames[1]))))
 
 
 def make_config(num_rays, num_samples, distance_range, sdf_std_deviation, cosine_ratio, epsilon, origin_stride,

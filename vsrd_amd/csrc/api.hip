@@ -1083,22 +1083,30 @@ size_t vsrd_frame_scratch_bytes(int32_t num_views, int32_t num_boxes) {
 }
 
 namespace {
-static bool frame_args(const vsrd_frame_config* c, FrameStepArgs* a) {
-    if (!c || c->num_boxes < 1 || c->num_boxes > kFrameMaxBoxes || c->num_views < 1 || c->num_views > kFrameMaxViews || c->num_steps < 1) return false;
+// What every frame kernel reads of a vsrd_frame_config -- the sizes, the image, the projection's guard, the decode's ranges and the batch stride --
+// with the frame header: the ONE reader of those fields.  It refuses what every entry point refuses (the box count, the batch fields); the
+// view and step counts are checked by the entry points that read them.
+bool frame_shape(const vsrd_frame_config* c, const vsrd_frame_header* frame_header, FrameStepArgs* a, Frames* frames) {
+    if (!c || c->num_boxes < 1 || c->num_boxes > kFrameMaxBoxes || !frames_of(c->num_frames, c->frame_stride, frames)) return false;
+    *a = FrameStepArgs{};
     a->num_boxes = c->num_boxes; a->num_views = c->num_views;
     a->height = c->height; a->width = c->width; a->epsilon = c->epsilon;
     for (int j = 0; j < 3; ++j) {
         a->location_lo[j] = c->location_lo[j]; a->location_hi[j] = c->location_hi[j];
         a->dimension_lo[j] = c->dimension_lo[j]; a->dimension_hi[j] = c->dimension_hi[j];
     }
+    a->frame_stride = frames->stride;
+    a->header = reinterpret_cast<const FrameHeader*>(frame_header);
+    return true;
+}
+bool valid_views(const vsrd_frame_config* c) { return c->num_views >= 1 && c->num_views <= kFrameMaxViews; }
+// frame_shape and what the prologues and the epilogue alone read: the steps, the schedules, the loss weights and Adam's constants
+bool frame_args(const vsrd_frame_config* c, const vsrd_frame_header* frame_header, FrameStepArgs* a, Frames* frames) {
+    if (!frame_shape(c, frame_header, a, frames) || !valid_views(c) || c->num_steps < 1) return false;
     a->num_steps = c->num_steps;
     a->max_temperature = c->max_temperature; a->min_temperature = c->min_temperature; a->max_std = c->max_std; a->min_std = c->min_std;
     a->weight_iou = c->weight_iou; a->weight_l1 = c->weight_l1; a->weight_silhouette = c->weight_silhouette;
     a->beta1 = c->beta1; a->beta2 = c->beta2; a->adam_epsilon = c->adam_epsilon; a->lr_gamma = c->lr_gamma;
-    Frames frames;
-    if (!frames_of(c->num_frames, c->frame_stride, &frames)) return false;
-    a->frame_stride = frames.stride;
-    a->header = nullptr;
     return true;
 }
 // the buffers of a frame's prologue, none of which may be null (the scratch apart: its size is the caller's next check)
@@ -1137,14 +1145,14 @@ int32_t vsrd_frame_prologue_with_header(const vsrd_frame_config* config, const f
                                         float* instances, int64_t* pd_indices, int64_t* gt_indices, int32_t* target_columns, float* instance_weights,
                                         float* schedule, float* projection_losses, float* grad_raw, const vsrd_frame_header* frame_header, void* stream) {
     FrameStepArgs a;
-    if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
-    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
+    Frames frames;
+    if (!frame_args(config, frame_header, &a, &frames)) return VSRD_E_INVALID_ARGUMENT;
     FrameBuffers b;
     if (!frame_buffers(raw_locations, raw_dimensions, raw_orientations, extrinsics, intrinsics, gt_boxes, visible, step, scratch, instances, pd_indices, gt_indices,
                        target_columns, instance_weights, schedule, projection_losses, grad_raw, &b))
         return VSRD_E_INVALID_ARGUMENT;
     if (!scratch || scratch_bytes < vsrd_frame_scratch_bytes(a.num_views, a.num_boxes)) return VSRD_E_WORKSPACE;
-    hipLaunchKernelGGL(frame_prologue_kernel, dim3(1, config->num_frames > 1 ? config->num_frames : 1), dim3(kFrameThreads), 0, static_cast<hipStream_t>(stream), a, b);
+    hipLaunchKernelGGL(frame_prologue_kernel, dim3(1, frames.count), dim3(kFrameThreads), 0, static_cast<hipStream_t>(stream), a, b);
     return launch_status();
 }
 
@@ -1167,8 +1175,8 @@ int32_t vsrd_frame_prologue_sample_with_header(const vsrd_frame_config* config, 
                                                void* ray_table, int64_t count, int32_t num_rays, uint64_t seed, const int64_t* remap, int64_t* ray_indices,
                                                const vsrd_frame_header* frame_header, void* stream) {
     FrameStepArgs a;
-    if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
-    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
+    Frames frames;
+    if (!frame_args(config, frame_header, &a, &frames)) return VSRD_E_INVALID_ARGUMENT;
     FrameBuffers b;
     if (!frame_buffers(raw_locations, raw_dimensions, raw_orientations, extrinsics, intrinsics, gt_boxes, visible, step, scratch, instances, pd_indices, gt_indices,
                        target_columns, instance_weights, schedule, projection_losses, grad_raw, &b))
@@ -1178,7 +1186,7 @@ int32_t vsrd_frame_prologue_sample_with_header(const vsrd_frame_config* config, 
     // (a refused LDS opt-in is "this device / build cannot run the combined launch" -- VSRD_E_UNSUPPORTED, on which the caller falls back to
     //  vsrd_frame_prologue + vsrd_sample_rays_table -- and not a failed launch, which must not be mistaken for it)
     if (opt_in_lds(frame_prologue_sample_kernel, kTableLdsBytes) != VSRD_OK) return VSRD_E_UNSUPPORTED;
-    hipLaunchKernelGGL(frame_prologue_sample_kernel, dim3(2, config->num_frames > 1 ? config->num_frames : 1), dim3(kTableThreads), kTableLdsBytes, static_cast<hipStream_t>(stream), a, b,
+    hipLaunchKernelGGL(frame_prologue_sample_kernel, dim3(2, frames.count), dim3(kTableThreads), kTableLdsBytes, static_cast<hipStream_t>(stream), a, b,
                        static_cast<RayTableHeader*>(ray_table), static_cast<long long>(count), num_rays, seed, reinterpret_cast<const unsigned long long*>(step),
                        reinterpret_cast<const long long*>(remap), reinterpret_cast<long long*>(ray_indices));
     return launch_status();
@@ -1199,8 +1207,8 @@ int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const f
                                         float* other_learning_rate_0, float* other_learning_rate_1, int64_t* step,
                                         float* record, float* raw_gradients, const vsrd_frame_header* frame_header, void* stream) {
     FrameStepArgs a;
-    if (!frame_args(config, &a)) return VSRD_E_INVALID_ARGUMENT;
-    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
+    Frames frames;
+    if (!frame_args(config, frame_header, &a, &frames)) return VSRD_E_INVALID_ARGUMENT;
     if (!grad_instances || !grad_raw_projection || !projection_losses || !render_losses || !locations || !dimensions || !orientations || !step || !record)
         return VSRD_E_INVALID_ARGUMENT;
     if (!valid_adam(*locations) || !valid_adam(*dimensions) || !valid_adam(*orientations)) return VSRD_E_INVALID_ARGUMENT;
@@ -1210,7 +1218,7 @@ int32_t vsrd_frame_epilogue_with_header(const vsrd_frame_config* config, const f
     e.locations = adam_tensors(*locations); e.dimensions = adam_tensors(*dimensions); e.orientations = adam_tensors(*orientations);
     e.other_learning_rates[0] = other_learning_rate_0; e.other_learning_rates[1] = other_learning_rate_1;
     e.step = reinterpret_cast<long long*>(step); e.record = record; e.raw_gradients = raw_gradients;
-    hipLaunchKernelGGL(frame_epilogue_kernel, dim3(1, config->num_frames > 1 ? config->num_frames : 1), dim3(kFrameMaxBoxes), 0, static_cast<hipStream_t>(stream), a, e);
+    hipLaunchKernelGGL(frame_epilogue_kernel, dim3(1, frames.count), dim3(kFrameMaxBoxes), 0, static_cast<hipStream_t>(stream), a, e);
     return launch_status();
 }
 
@@ -1218,20 +1226,10 @@ int32_t vsrd_frame_labels(const vsrd_frame_config* config, const float* raw_loca
                           const float* extrinsics, const float* intrinsics, const float* gt_boxes, const uint8_t* visible,
                           float* camera_corners, float* boxes_2d, float* mean_iou, int64_t* matched_gt, float* confidences,
                           const vsrd_frame_header* frame_header, void* stream) {
-    if (!config || config->num_boxes < 1 || config->num_boxes > kFrameMaxBoxes || config->num_views < 1 || config->num_views > kFrameMaxViews)
-        return VSRD_E_INVALID_ARGUMENT;
+    FrameStepArgs a;                       // (the schedules, loss weights and Adam's constants are not read: num_steps is not checked)
     Frames frames;
-    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (!frame_shape(config, frame_header, &a, &frames) || !valid_views(config)) return VSRD_E_INVALID_ARGUMENT;
     if (!raw_locations || !raw_dimensions || !raw_orientations || !extrinsics || !intrinsics || !gt_boxes || !visible) return VSRD_E_INVALID_ARGUMENT;
-    FrameStepArgs a = {};                  // (the decode's ranges, the projection's guard and the image size: the schedules, loss weights and Adam's constants are not read)
-    a.num_boxes = config->num_boxes; a.num_views = config->num_views;
-    a.height = config->height; a.width = config->width; a.epsilon = config->epsilon;
-    for (int j = 0; j < 3; ++j) {
-        a.location_lo[j] = config->location_lo[j]; a.location_hi[j] = config->location_hi[j];
-        a.dimension_lo[j] = config->dimension_lo[j]; a.dimension_hi[j] = config->dimension_hi[j];
-    }
-    a.frame_stride = frames.stride;
-    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     LabelBuffers b;
     b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
     b.extrinsics = extrinsics; b.intrinsics = intrinsics; b.gt_boxes = gt_boxes; b.visible = visible;
@@ -1246,22 +1244,12 @@ int32_t vsrd_frame_group_labels(const vsrd_frame_config* config, const float* ra
                                 const float* label_gt_boxes, const uint8_t* label_visible, float* camera_corners, float* boxes_2d, float* mean_iou,
                                 int64_t* matched_gt, float* confidences, const vsrd_frame_header* frame_header, void* stream) {
     static_assert(kGroupMaxViews == VSRD_MAX_LABEL_VIEWS, "frame_group_labels.h and the ABI agree on the label-view capacity");
-    if (!config || config->num_boxes < 1 || config->num_boxes > kFrameMaxBoxes || num_label_views < 1 || num_label_views > kGroupMaxViews)
-        return VSRD_E_INVALID_ARGUMENT;
+    FrameStepArgs a;                       // (num_views is not read, and not checked: the label views are the call's own)
     Frames frames;
-    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (!frame_shape(config, frame_header, &a, &frames) || num_label_views < 1 || num_label_views > kGroupMaxViews) return VSRD_E_INVALID_ARGUMENT;
     if (!raw_locations || !raw_dimensions || !raw_orientations || !label_extrinsics || !label_intrinsics || !label_gt_boxes || !label_visible ||
         !boxes_2d || !mean_iou)
         return VSRD_E_INVALID_ARGUMENT;
-    FrameStepArgs a = {};                  // (the decode's ranges, the projection's guard and the image size; num_views is not read)
-    a.num_boxes = config->num_boxes;
-    a.height = config->height; a.width = config->width; a.epsilon = config->epsilon;
-    for (int j = 0; j < 3; ++j) {
-        a.location_lo[j] = config->location_lo[j]; a.location_hi[j] = config->location_hi[j];
-        a.dimension_lo[j] = config->dimension_lo[j]; a.dimension_hi[j] = config->dimension_hi[j];
-    }
-    a.frame_stride = frames.stride;
-    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     GroupLabelBuffers b;
     b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
     b.view_count = label_view_count; b.extrinsics = label_extrinsics; b.intrinsics = label_intrinsics; b.gt_boxes = label_gt_boxes; b.visible = label_visible;
@@ -1326,19 +1314,11 @@ int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* conf
 int32_t vsrd_frame_metrics(const vsrd_frame_config* config, const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
                            const float* gt_boxes_3d, const float* rectification, const int64_t* pd_indices, const int64_t* gt_indices,
                            float* corners, float* ious, float* summary, const vsrd_frame_header* frame_header, void* stream) {
-    if (!config || config->num_boxes < 1 || config->num_boxes > kFrameMaxBoxes) return VSRD_E_INVALID_ARGUMENT;
+    FrameStepArgs a;                       // (of it the kernel reads the box count, the decode's ranges and the batch fields: nothing else is checked)
     Frames frames;
-    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (!frame_shape(config, frame_header, &a, &frames)) return VSRD_E_INVALID_ARGUMENT;
     if (!raw_locations || !raw_dimensions || !raw_orientations || !gt_boxes_3d || !ious || !summary) return VSRD_E_INVALID_ARGUMENT;
     if ((pd_indices != nullptr) != (gt_indices != nullptr)) return VSRD_E_INVALID_ARGUMENT;
-    FrameStepArgs a = {};                  // (the decode's ranges and the batch fields: nothing else is read)
-    a.num_boxes = config->num_boxes;
-    for (int j = 0; j < 3; ++j) {
-        a.location_lo[j] = config->location_lo[j]; a.location_hi[j] = config->location_hi[j];
-        a.dimension_lo[j] = config->dimension_lo[j]; a.dimension_hi[j] = config->dimension_hi[j];
-    }
-    a.frame_stride = frames.stride;
-    a.header = reinterpret_cast<const FrameHeader*>(frame_header);
     MetricBuffers b;
     b.raw_locations = raw_locations; b.raw_dimensions = raw_dimensions; b.raw_orientations = raw_orientations;
     b.gt_boxes_3d = gt_boxes_3d; b.rectification = rectification;

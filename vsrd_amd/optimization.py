@@ -770,19 +770,12 @@ class FrameOptimizer:
         cfg, inp, det = self.config, self.inputs, self.detector
         V, N = self.view_capacity, self.capacity       # (a row with a header: the capacities; the frame's own counts are in the header)
         w = cfg.loss_weights
-        frame = _lib.FrameConfig()
-        frame.num_boxes, frame.num_views = N, V
-        frame.height, frame.width, frame.epsilon = float(inp.image_size[0]), float(inp.image_size[1]), 1.0e-6
-        for j in range(3):
-            frame.location_lo[j], frame.location_hi[j] = float(det.location_range[0, j]), float(det.location_range[1, j])
-            frame.dimension_lo[j], frame.dimension_hi[j] = float(det.dimension_range[0, j]), float(det.dimension_range[1, j])
-        frame.num_steps = cfg.num_steps
-        frame.max_temperature, frame.min_temperature = cfg.max_sdf_union_temperature, cfg.min_sdf_union_temperature
-        frame.max_std, frame.min_std = cfg.max_sdf_std_deviation, cfg.min_sdf_std_deviation
-        frame.weight_iou, frame.weight_l1, frame.weight_silhouette = w["iou_projection_loss"], w["l1_projection_loss"], w["silhouette_loss"]
-        betas, eps = self.optimizer.param_groups[0]["betas"], self.optimizer.param_groups[0]["eps"]      # the box tensors' Adam constants
-        frame.beta1, frame.beta2, frame.adam_epsilon, frame.lr_gamma = float(betas[0]), float(betas[1]), float(eps), cfg.lr_gamma
-        return frame
+        group = self.optimizer.param_groups[0]         # the box tensors' Adam constants
+        return _lib.make_frame_config(N, V, inp.image_size, 1.0e-6, det.location_range, det.dimension_range, num_steps=cfg.num_steps,
+                                      temperatures=(cfg.max_sdf_union_temperature, cfg.min_sdf_union_temperature),
+                                      std_deviations=(cfg.max_sdf_std_deviation, cfg.min_sdf_std_deviation),
+                                      loss_weights=(w["iou_projection_loss"], w["l1_projection_loss"], w["silhouette_loss"]),
+                                      betas=group["betas"], adam_epsilon=group["eps"], lr_gamma=cfg.lr_gamma)
 
     # ---- fused glue (csrc/frame_step.h) ---------------------------------------------------------------------------------
     def _init_fused_glue(self):
