@@ -697,6 +697,64 @@ int32_t vsrd_frame_metrics(const vsrd_frame_config* config,
                            float* corners /* [N,8,3] or NULL */, float* ious /* [N,2] */, float* summary /* [8] */,
                            const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
 
+/* Frame log (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the scalar
+ * history and the step snapshots of a frame's optimisation, kept on the device -- what the reference's loop leaves behind every
+ * `scalar_intervals` steps (the named losses, metrics, learning rates and annealed hyperparameters, scripts/main.py:870-953) and every
+ * `ckpt_intervals` steps (step_{step}.pt, main.py:1109-1121) -- in ONE launch between two replays of the step graphs, no host
+ * synchronisation, no allocation, capturable.  The call is pure gather and copy: every value is moved as the 32 bits it is (int32 sources
+ * such as pixel counts included), nothing is computed from it.
+ * EVERY pointer of the structure is device memory and addresses frame 0's buffer; num_frames / frame_stride batch the call as in
+ * vsrd_frame_config (frame f's copy of every buffer, its pointer list and its segment table included, lies f * frame_stride bytes behind).
+ * Each frame reads its own step counter `step` once -- the int64 vsrd_frame_epilogue increments: after step s it holds c = s + 1 -- and
+ * decides by it alone, so frames of one call whose counters differ each log what their own counter says:
+ *   history   if scalar_interval > 0, c > 0 and c % scalar_interval == 0: row c / scalar_interval - 1 of history
+ *             [history_capacity, VSRD_LOG_SCALARS] = (the step c - 1 as an int32 bit pattern | record[5] | *learning_rates[0..5) |
+ *             schedule[3] | summary[8], or eight quiet NaNs (0x7fc00000) when summary is NULL);
+ *   snapshot  if checkpoint_interval > 0, c > 0 and c % checkpoint_interval == 0: for every entry of `segments`, `count` 32-bit words from
+ *             `source` to word `offset` of slot c / checkpoint_interval - 1 of snapshots [snapshot_capacity, snapshot_floats], and
+ *             snapshot_steps[slot] = c - 1.  Sources and destinations that are 16-byte aligned are copied with 16-byte accesses (lay the
+ *             offsets out on multiples of four words); anything else word by word.  An entry with a NULL source, a count < 1 or a range
+ *             outside the slot is skipped.
+ * A row or slot at or beyond its capacity is dropped and counted.  counters [4] int32 = (rows_written, rows_dropped, slots_written,
+ * slots_dropped): *_written is the highest row / slot written plus one, never lowered by the call; the caller zeroes the counters when a
+ * frame starts over.  Nothing outside the written row, the written slot's segments, snapshot_steps[slot] and the counters is written.
+ * What a frame with n_f < N instances in a row laid out for N copies is the caller's choice: the table is the frame's own, so its counts
+ * cover the frame's n_f instances while its offsets are laid out for N -- the call reads nothing but what the entries name.
+ * Both intervals 0: VSRD_OK without a launch.  Refused with VSRD_E_INVALID_ARGUMENT before any launch: a negative interval or capacity;
+ * NULL step or counters; scalar_interval > 0 with NULL record, learning_rates, schedule or history; checkpoint_interval > 0 with NULL
+ * segments, snapshots or snapshot_steps, num_segments outside 0..VSRD_LOG_MAX_SEGMENTS, snapshot_floats negative or no multiple of 4, or
+ * snapshots not 16-byte aligned; num_frames / frame_stride as everywhere. */
+#define VSRD_LOG_SCALARS 22
+#define VSRD_LOG_MAX_SEGMENTS 32
+typedef struct vsrd_log_segment {   /* device memory */
+    const void* source;
+    int64_t count;                  /* 32-bit words                                                                           */
+    int64_t offset;                 /* 32-bit words from the start of a slot                                                  */
+} vsrd_log_segment;
+
+typedef struct vsrd_frame_log_config {
+    int32_t scalar_interval;        /* 0: no history                                                                          */
+    int32_t checkpoint_interval;    /* 0: no snapshots                                                                        */
+    int32_t history_capacity;       /* rows                                                                                   */
+    int32_t snapshot_capacity;      /* slots                                                                                  */
+    int64_t snapshot_floats;        /* 32-bit words per slot, a multiple of 4                                                 */
+    int32_t num_segments;
+    int32_t num_frames;             /* 0 or 1 = one frame                                                                     */
+    int64_t frame_stride;           /* bytes between the frames' copies of every buffer of the call                           */
+    const int64_t* step;            /* [1]                                                                                    */
+    const float* record;            /* [5] vsrd_frame_epilogue's record                                                       */
+    const void* learning_rates;     /* [5] device pointers (const float*), each to a [1] rate                                 */
+    const float* schedule;          /* [3]                                                                                    */
+    const float* summary;           /* [8] vsrd_frame_metrics' summary, or NULL                                               */
+    const vsrd_log_segment* segments;   /* [num_segments]                                                                     */
+    float* history;                 /* [history_capacity, VSRD_LOG_SCALARS]                                                   */
+    float* snapshots;               /* [snapshot_capacity, snapshot_floats]                                                   */
+    int32_t* snapshot_steps;        /* [snapshot_capacity]                                                                    */
+    int32_t* counters;              /* [4]                                                                                    */
+} vsrd_frame_log_config;
+
+int32_t vsrd_frame_log(const vsrd_frame_log_config* log, void* stream);
+
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]
  * -> weight_norm(Linear 256 -> 1617) = mlp_weights [N,1617].  weight_norm over dim 0: W[o,:] = g[o] v[o,:] / |v[o,:]|.

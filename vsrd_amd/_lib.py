@@ -167,6 +167,41 @@ class FrameMasksConfig(ctypes.Structure):
     ]
 
 
+class LogSegment(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_log_segment (device memory): `count` 32-bit words from `source` to word `offset` of a snapshot slot."""
+    _fields_ = [
+        ("source", ctypes.c_void_p),
+        ("count", ctypes.c_int64),
+        ("offset", ctypes.c_int64),
+    ]
+
+
+class FrameLogConfig(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_frame_log_config (added within ABI 12): the intervals, capacities and device buffers of one vsrd_frame_log call."""
+    _fields_ = [
+        ("scalar_interval", ctypes.c_int32),
+        ("checkpoint_interval", ctypes.c_int32),
+        ("history_capacity", ctypes.c_int32),
+        ("snapshot_capacity", ctypes.c_int32),
+        ("snapshot_floats", ctypes.c_int64),
+        ("num_segments", ctypes.c_int32),
+        ("num_frames", ctypes.c_int32),
+        ("frame_stride", ctypes.c_int64),
+        ("step", ctypes.c_void_p),
+        ("record", ctypes.c_void_p),
+        ("learning_rates", ctypes.c_void_p),
+        ("schedule", ctypes.c_void_p),
+        ("summary", ctypes.c_void_p),
+        ("segments", ctypes.c_void_p),
+        ("history", ctypes.c_void_p),
+        ("snapshots", ctypes.c_void_p),
+        ("snapshot_steps", ctypes.c_void_p),
+        ("counters", ctypes.c_void_p),
+    ]
+
+
+FRAME_LOG_COLUMNS = 22         # VSRD_LOG_SCALARS: (step | record 5 | learning rates 5 | schedule 3 | metrics summary 8) of a history row
+FRAME_LOG_SEGMENTS = 32        # VSRD_LOG_MAX_SEGMENTS: entries of a frame's snapshot table
 FRAME_HEADER_HAS_VIEWS = 0x10000
 MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFrameMaxViews)
 MAX_LABEL_VIEWS = 4096         # VSRD_MAX_LABEL_VIEWS: the label views (a frame's group) of vsrd_frame_group_labels
@@ -177,7 +212,7 @@ _SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ct
 _RETURNS = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
 # host structures, passed as const T*; every other pointer is device memory (vsrd_frame_header too) or the stream, and travels as an integer
 _HOST_STRUCTS = {"vsrd_field": Field, "vsrd_render_config": RenderConfig, "vsrd_frame_config": FrameConfig, "vsrd_adam_tensors": AdamTensors,
-                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig}
+                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig, "vsrd_frame_log_config": FrameLogConfig}
 _DEVICE_POINTEES = {"void", "float", "uint8_t", "int32_t", "int64_t", "uint64_t", "vsrd_frame_header"}
 
 

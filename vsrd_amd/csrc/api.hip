@@ -16,6 +16,7 @@
 #include "frame_group_labels.h"
 #include "frame_masks.h"
 #include "frame_metrics.h"
+#include "frame_log.h"
 #include "launch.h"
 
 namespace {
@@ -1325,6 +1326,39 @@ int32_t vsrd_frame_metrics(const vsrd_frame_config* config, const float* raw_loc
     b.pd_indices = reinterpret_cast<const long long*>(pd_indices); b.gt_indices = reinterpret_cast<const long long*>(gt_indices);
     b.corners = corners; b.ious = ious; b.summary = summary;
     hipLaunchKernelGGL(frame_metrics_kernel, dim3(frames.count), dim3(kWave), 0, static_cast<hipStream_t>(stream), a, b);
+    return launch_status();
+}
+
+int32_t vsrd_frame_log(const vsrd_frame_log_config* log, void* stream) {
+    static_assert(kLogScalars == VSRD_LOG_SCALARS && kLogMaxSegments == VSRD_LOG_MAX_SEGMENTS, "frame_log.h and the ABI agree on the row and the table");
+    static_assert(sizeof(LogSegment) == sizeof(vsrd_log_segment), "frame_log.h and the ABI agree on a table entry");
+    Frames frames;
+    if (!log || log->scalar_interval < 0 || log->checkpoint_interval < 0 || log->history_capacity < 0 || log->snapshot_capacity < 0 ||
+        !frames_of(log->num_frames, log->frame_stride, &frames))
+        return VSRD_E_INVALID_ARGUMENT;
+    if (!log->step || !log->counters) return VSRD_E_INVALID_ARGUMENT;
+    if (log->scalar_interval > 0 && (!log->record || !log->learning_rates || !log->schedule || !log->history)) return VSRD_E_INVALID_ARGUMENT;
+    if (log->checkpoint_interval > 0 &&
+        (!log->segments || !log->snapshots || !log->snapshot_steps || log->num_segments < 0 || log->num_segments > kLogMaxSegments ||
+         log->snapshot_floats < 0 || (log->snapshot_floats & 3) != 0 || (reinterpret_cast<uintptr_t>(log->snapshots) & 15) != 0))
+        return VSRD_E_INVALID_ARGUMENT;
+    if (log->scalar_interval == 0 && log->checkpoint_interval == 0) return VSRD_OK;
+    LogArgs a;
+    a.scalar_interval = log->scalar_interval; a.checkpoint_interval = log->checkpoint_interval;
+    a.history_capacity = log->history_capacity; a.snapshot_capacity = log->snapshot_capacity;
+    a.snapshot_floats = log->snapshot_floats; a.num_segments = log->num_segments; a.frame_stride = frames.stride;
+    a.step = reinterpret_cast<const long long*>(log->step);
+    a.record = reinterpret_cast<const unsigned*>(log->record);
+    a.learning_rates = static_cast<const unsigned* const*>(log->learning_rates);
+    a.schedule = reinterpret_cast<const unsigned*>(log->schedule); a.summary = reinterpret_cast<const unsigned*>(log->summary);
+    a.segments = reinterpret_cast<const LogSegment*>(log->segments);
+    a.history = reinterpret_cast<unsigned*>(log->history); a.snapshots = reinterpret_cast<unsigned*>(log->snapshots);
+    a.snapshot_steps = log->snapshot_steps; a.counters = log->counters;
+    // one block without snapshots; with them a block per 256 16-byte accesses of a slot, at most kLogMaxBlocks per frame (grid-stride beyond)
+    long long blocks = 1;
+    if (log->checkpoint_interval > 0) blocks = (log->snapshot_floats / 4 + kLogThreads - 1) / kLogThreads;
+    blocks = blocks < 1 ? 1 : (blocks > kLogMaxBlocks ? kLogMaxBlocks : blocks);
+    hipLaunchKernelGGL(frame_log_kernel, dim3(static_cast<unsigned>(blocks), frames.count), dim3(kLogThreads), 0, static_cast<hipStream_t>(stream), a);
     return launch_status();
 }
 

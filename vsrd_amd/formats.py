@@ -7,12 +7,18 @@ pseudo-label files derived from it.  Host-side I/O only.
   multi-view confidences    tools/kitti_360/make_predictions.py:86-176    mean box IoU over source views + Hungarian (maximise)
   KITTI label line          tools/kitti_360/convert_predictions.py:16-78
   per-frame label files     save_frame_labels: what optimization.FrameOptimizer.labels() returns (vsrd_frame_labels), as the two above
+  per-frame log             save_frame_history (history.json, the reference's scalar names, scripts/main.py:926-939), save_frame_snapshots
+                            (step_{step}.pt: step, models, metrics) and select_model (tools/select_model.py's rule -> model.pt) over what
+                            optimization.FrameOptimizer.history() / snapshots() return (vsrd_frame_log)
   per-frame metrics         frame_metrics: the summary of optimization.FrameOptimizer.metrics() (vsrd_frame_metrics) under the reference's
                             six names (scripts/main.py:908-924)
 """
 import json
 import math
+import operator
 import os
+import re
+import shutil
 
 import torch
 
@@ -228,3 +234,123 @@ def load_frame_masks(path):
     with np.load(path) as data:
         return dict(inside=data["inside"], shape=tuple(int(x) for x in data["shape"]), threshold=float(data["threshold"]), counts=data["counts"],
                     mask_iou=data["mask_iou"])
+
+
+# ---- the per-frame log: scalar history and step snapshots (optimization.FrameOptimizer.history / snapshots, vsrd_frame_log) ---------------
+HISTORY_LOSSES = ("iou_projection_loss", "l1_projection_loss", "silhouette_loss", "eikonal_loss", "loss")
+# config.optimization.param_group_names of the reference's configs, the order of the optimiser's groups (scripts/main.py:929-933)
+HISTORY_LEARNING_RATES = ("detector/locations", "detector/dimensions", "detector/orientations", "detector/embeddings", "hyper_distance_field")
+HISTORY_HYPERPARAMETERS = ("sdf_union_temperature", "sdf_std_deviation", "cosine_ratio")
+
+
+def frame_history_records(history):
+    """``FrameOptimizer.history()`` (host or device tensors) as a list of dictionaries, one per logged step, under the reference's scalar
+    names (scripts/main.py:926-939): ``step``, ``losses/<name>`` (and ``losses/loss``, the weighted total; ``losses/eikonal_loss`` is left
+    out where it is NaN -- a box-only step, for which the reference's dictionary has no such key), ``metrics/<name>`` only when the row has
+    metrics and the value is finite, ``learning_rates/<group>``, ``hyperparameters/<name>``.  Python ints and floats."""
+    host = {key: torch.as_tensor(value).detach().cpu() for key, value in history.items()}
+    records = []
+    for row in range(int(host["steps"].shape[0])):
+        record = {"step": int(host["steps"][row])}
+        for name in HISTORY_LOSSES:
+            value = float(host[name][row])
+            if name != "eikonal_loss" or not math.isnan(value):
+                record[f"losses/{name}"] = value
+        summary = [float(v) for v in host["metrics"][row].tolist()]
+        for name, value in frame_metrics(summary).items():        # (a row without metrics holds NaN, one without a pair a count of 0: neither names any)
+            if math.isfinite(value):
+                record[f"metrics/{name}"] = value
+        record.update({f"learning_rates/{name}": float(v) for name, v in zip(HISTORY_LEARNING_RATES, host["learning_rates"][row].tolist())})
+        record.update({f"hyperparameters/{name}": float(v) for name, v in zip(HISTORY_HYPERPARAMETERS, host["hyperparameters"][row].tolist())})
+        records.append(record)
+    return records
+
+
+def save_frame_history(folder, history):
+    """One frame's scalar history as ``folder/history.json``: the list of ``frame_history_records``, written under a temporary name and renamed."""
+    records = frame_history_records(history)
+    path = os.path.join(folder, "history.json")
+
+    def write(name):
+        with open(name, "w") as file:
+            json.dump(records, file, indent=1)
+    _atomic_write(path, write)
+    return path
+
+
+def snapshot_payloads(snapshots):
+    """``FrameOptimizer.snapshots()`` as checkpoint payloads in host memory: ``step`` (int), ``models`` (the state dicts, copied: a slot's
+    views change with the frame's next reset) and ``metrics`` by name -- the reference's six from the slot's summary (none when no pair had
+    ground truth) and ``mask_iou``, the mean over the instances, as the final checkpoint carries them.  What tools/select_model.py and
+    make_predictions.py read of a step_{step}.pt; optimiser and scheduler state stay with the final checkpoint.  Payloads pass through
+    unchanged (a named metric stays, the mean of one number is that number)."""
+    payloads = []
+    for snapshot in snapshots:
+        host = to_host(snapshot)
+        metrics = {name: float(value) for name, value in host["metrics"].items() if name not in ("summary", "mask_iou")}
+        if "summary" in host["metrics"]:
+            metrics.update(frame_metrics(host["metrics"]["summary"]))
+        if "mask_iou" in host["metrics"]:
+            metrics["mask_iou"] = float(torch.as_tensor(host["metrics"]["mask_iou"], dtype=torch.float32).mean())
+        models = {module: {key: value.clone() for key, value in state.items()} for module, state in host["models"].items()}
+        payloads.append(dict(step=int(host["step"]), models=models, metrics=metrics))
+    return payloads
+
+
+def save_frame_snapshots(folder, snapshots, skip_steps=()):
+    """``FrameOptimizer.snapshots()`` (or their ``snapshot_payloads``) as ``folder/step_{step}.pt`` files, each written under a temporary
+    name and renamed.  ``skip_steps``: steps whose file somebody else writes (the launcher's final checkpoint, which holds the same models
+    and metrics and marks the frame as done).  Returns the paths."""
+    paths = []
+    for payload in snapshot_payloads(snapshots):
+        if payload["step"] in skip_steps:
+            continue
+        paths.append(os.path.join(folder, f"step_{payload['step']}.pt"))
+        atomic_torch_save(payload, paths[-1])
+    return paths
+
+
+_CONSTRAINT = re.compile(r"\s*(\w+)\s*(<=|>=|==|!=|<|>)\s*([+-]?(?:\d+\.?\d*(?:[eE][+-]?\d+)?|\.\d+(?:[eE][+-]?\d+)?))\s*")
+_COMPARISONS = {"<": operator.lt, "<=": operator.le, "==": operator.eq, "!=": operator.ne, ">=": operator.ge, ">": operator.gt}
+
+
+def select_model(folder, metrics, maximum=False, constraints=(), step_range=()):
+    """The selection rule of the reference's tools/select_model.py over one frame's folder: of the ``*.pt`` checkpoints directly in
+    ``folder`` -- ``model.pt`` itself aside -- those whose ``metrics`` hold every name in ``metrics``, meet every constraint
+    (``name<op>value`` with <, <=, ==, !=, >=, >; a checkpoint lacking the constrained metric does not meet it) and whose ``step`` lies in
+    ``range(*step_range)`` (empty: any) compete; the mean over the named metrics decides, by a strict comparison (smallest, or with
+    ``maximum`` largest); the winner is copied to ``folder/model.pt`` (under a temporary name, then renamed).  One stated difference: the
+    candidates are visited in ascending step order, so a tie keeps the EARLIEST step; the reference visits them in glob order, which is
+    unspecified.  Returns (path of the winner, its named metrics), or (None, {}) when nothing competes (model.pt is then left alone)."""
+    metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+    if not metrics:
+        raise ValueError("select_model: name at least one metric")
+    tests = []
+    for constraint in constraints:
+        match = _CONSTRAINT.fullmatch(constraint)
+        if not match:
+            raise ValueError(f"constraint {constraint!r}: expected name<op>value with one of < <= == != >= >")
+        tests.append((match.group(1), _COMPARISONS[match.group(2)], float(match.group(3))))
+    candidates = []
+    for name in os.listdir(folder):
+        path = os.path.join(folder, name)
+        if not name.endswith(".pt") or name == "model.pt" or not os.path.isfile(path):
+            continue
+        checkpoint = torch.load(path, map_location="cpu", weights_only=False)
+        candidates.append((int(checkpoint.get("step", 0)), name, path, checkpoint.get("metrics") or {}))
+    better = operator.gt if maximum else operator.lt
+    best = None
+    for step, name, path, stored in sorted(candidates, key=lambda c: (c[0], c[1])):
+        if not all(metric in stored for metric in metrics):
+            continue
+        if not all(key in stored and compare(float(stored[key]), value) for key, compare, value in tests):
+            continue
+        if step_range and step not in range(*step_range):
+            continue
+        mean = sum(float(stored[metric]) for metric in metrics) / len(metrics)
+        if best is None or better(mean, best[0]):
+            best = (mean, path, {metric: float(stored[metric]) for metric in metrics})
+    if best is None:
+        return None, {}
+    _atomic_write(os.path.join(folder, "model.pt"), lambda temporary: shutil.copyfile(best[1], temporary))
+    return best[1], best[2]

@@ -11,6 +11,7 @@ barrier; here additionally rank 0 broadcasts the run manifest so every rank agre
 """
 import os
 import random
+import re
 from typing import Callable, List, Sequence
 
 import torch
@@ -123,7 +124,7 @@ def pending_frames(frames: Sequence, checkpoint_path: Callable[[object], str] = 
     return pending
 
 
-def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], str] = None, frames_in_flight: int = 1):
+def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], str] = None, frames_in_flight: int = 1, save: Callable = None):
     """Optimise this rank's frames -- a sequence, or a ``FrameQueue`` the frames are taken from one by one -- skipping every frame whose final
     checkpoint exists (main.py:134-136).
 
@@ -134,6 +135,7 @@ def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], s
     launches, graph destruction, host synchronisations -- runs during ANOTHER frame's capture, and captures (with a graph's first launch)
     run alone: optimization._CaptureGate (round 4, one box: 0.749 frames/s with one frame in flight, 0.91 with three; without the gate a
     dead rank about every tenth run of 36 frames).
+    ``save(result, path)`` writes a frame's final checkpoint (default: formats.atomic_torch_save).
     Returns the frames optimised, in the order of ``frames`` (a queue: in the order they were taken)."""
     import threading
 
@@ -171,7 +173,7 @@ def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], s
             result = optimise(frame)
             if path:
                 from .formats import atomic_torch_save
-                atomic_torch_save(result, path)   # utils.Saver.save == torch.save(dict) (vsrd/utils.py:191-198), written atomically
+                (save or atomic_torch_save)(result, path)   # utils.Saver.save == torch.save(dict) (vsrd/utils.py:191-198), written atomically
             finished.append((index, frame))
 
     if frames_in_flight <= 1:
@@ -369,6 +371,12 @@ class _RenderWork:
         self.args, self.manifest, self.device, self.queue = args, manifest, device, queue
         self.config = dict(num_steps=args.num_steps, warmup_steps=args.warmup_steps, num_rays=args.rays, num_samples=args.samples,
                            mlp_split_bf16=not args.fp32_mlp, mlp_adjoint_item_slots=args.adjoint_item_slots)
+        # --scalar-interval / --ckpt-interval / --select: the device-side log of every frame (optimization.FrameOptimizer.history / snapshots)
+        self.scalar_interval, self.ckpt_interval = int(getattr(args, "scalar_interval", 0) or 0), int(getattr(args, "ckpt_interval", 0) or 0)
+        self.select = parse_select(getattr(args, "select", "") or "")
+        self.logs = self.scalar_interval > 0 or self.ckpt_interval > 0
+        if self.logs:
+            self.config.update(scalar_interval=self.scalar_interval, checkpoint_interval=self.ckpt_interval)
 
     def path_of(self, frame):
         return os.path.join(self.manifest["out"], f"frame_{int(frame):06d}", f"step_{self.args.num_steps - 1}.pt")
@@ -439,6 +447,8 @@ class _RenderWork:
                                                          max_instances=max(args.instance_counts) if mixed else None,
                                                          max_views=max(args.view_counts) if mixed_views else None,
                                                          max_label_views=args.label_view_capacity)
+                    if self.logs:                # (before the captures: the buffers the log reads exist in every row)
+                        self.batch.log_outputs(metrics=args.metrics, masks=args.masks)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
                     tail = len(mine) % args.frame_batch if mine else 0                   # a static queue's last group is known now: capture it too
                     self.graphs_per_slot = self.batch.capture_all(actives=sorted({args.frame_batch, tail} - {0}, reverse=True))
@@ -454,6 +464,8 @@ class _RenderWork:
                         except optimization.UnsuitableFrameError:
                             self.unsuitable_founders.append(int(founder))
                             continue
+                        if self.logs:
+                            loop.log_outputs(metrics=args.metrics, masks=args.masks)
                         self.graphs_per_slot = loop.capture_all()
                         self.slots.put(loop)
                         break
@@ -466,6 +478,8 @@ class _RenderWork:
         from . import optimization
         loop = optimization.FrameOptimizer(self.materialised(self.inputs_of(frame)), self.optimization_config(init_seed=self.init_seed(frame)), self.device, graph=True,
                                           max_label_views=self.args.label_view_capacity)
+        if self.logs:
+            loop.log_outputs(metrics=self.args.metrics, masks=self.args.masks)
         loss, payload, pending = self._finish_alone(frame, loop, loop.run(self.args.num_steps))
         loop.close()
         self._write_outputs(pending)
@@ -481,7 +495,8 @@ class _RenderWork:
             if health is not None:
                 health(frame, loop)
             payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
-            return loss, payload, self._collect(loop, [(frame, self.path_of(frame))], [payload])
+            rows = [(frame, self.path_of(frame))]
+            return loss, payload, self._collect(loop, rows, [payload]) + self._collect_log(loop, rows)
 
     def _begin_outputs(self):
         """The clock's keys of --predictions / --masks / --metrics (None without any of them: outside the batch path such a job has no
@@ -490,7 +505,43 @@ class _RenderWork:
         keys = [key for wanted, keys in ((args.predictions, ("labels", "labels_write")), (getattr(args, "group_predictions", False), ("group_labels", "group_labels_write")),
                                          (args.masks, ("masks", "masks_write")), (args.metrics, ("metrics",)))
                 if wanted for key in keys]
+        keys += ["log", "log_write"] if self.logs else []
         self.phase_seconds, self.frame_metrics = dict.fromkeys(keys, 0.0) or None, {}
+
+    def _collect_log(self, source, frames, active=None):
+        """--scalar-interval / --ckpt-interval: the history and the snapshots of a group of finished frames, read from the device ONCE, here,
+        inside the section that copies their checkpoints -> the pending writes of history.json and step_*.pt (the snapshot of the LAST step
+        aside: the final checkpoint holds its models and metrics, and is what marks the frame as done).  The clock's `log`: the host time of
+        the log launches between the replays (with the metrics and masks launches in front of them) and of these copies."""
+        if not self.logs:
+            return []
+        import time
+        from . import formats
+        t0 = time.perf_counter()
+        members = [source] if active is None else source.frames[:active]
+        pending, last = [], self.args.num_steps - 1
+        for (frame, path), loop in zip(frames, members):
+            folder = os.path.dirname(path)
+            if self.scalar_interval:
+                pending.append(("log_write", formats.save_frame_history, (folder, formats.to_host(loop.history()))))
+            if self.ckpt_interval:
+                pending.append(("log_write", formats.save_frame_snapshots, (folder, formats.snapshot_payloads(loop.snapshots()), (last,))))
+            self.phase_seconds["log"] += loop.log_seconds
+            loop.log_seconds = 0.0
+        self.phase_seconds["log"] += time.perf_counter() - t0
+        return pending
+
+    def _save_final(self, payload, path):
+        """A frame's final checkpoint -- with --select: written under a pending name, so that it competes (select_model copies the winner
+        to model.pt), and renamed last: the frame counts as done only when everything else of it is there."""
+        from . import formats
+        if not self.select:
+            return formats.atomic_torch_save(payload, path)
+        folder = os.path.dirname(path)
+        pending = os.path.join(folder, "pending_" + os.path.basename(path))
+        formats.atomic_torch_save(payload, pending)
+        formats.select_model(folder, self.select[0], maximum=self.select[1])
+        os.replace(pending, path)
 
     def _collect(self, source, frames, payloads, active=None):
         """What the flags ask of a group of finished frames, inside the section that copies their checkpoint `payloads`: `source` is the
@@ -574,7 +625,7 @@ class _RenderWork:
         if self.batch is not None:
             done = self._run_batches(losses, fallbacks, health)
         else:
-            done = run_frames(self.queue, optimise, self.path_of, frames_in_flight=args.frames_in_flight)
+            done = run_frames(self.queue, optimise, self.path_of, frames_in_flight=args.frames_in_flight, save=self._save_final)
         torch.cuda.synchronize()
         taken = len(self.queue.taken)
         return dict(frames=len(done), skipped=taken - len(done), frames_done=sorted(int(f) for f in done),
@@ -616,11 +667,11 @@ class _RenderWork:
                         health(frame, batch.frames[row])
                         payloads.append(formats.checkpoint_payload(batch.frames[row], step=args.num_steps - 1, metrics={}, host=True))
                     t2 = time.perf_counter()
-                    pending = self._collect(batch, rows, payloads, active=len(rows))
+                    pending = self._collect(batch, rows, payloads, active=len(rows)) + self._collect_log(batch, rows, active=len(rows))
                 self._write_outputs(pending)
                 t3 = time.perf_counter()
                 for (frame, path), payload in zip(rows, payloads):
-                    formats.atomic_torch_save(payload, path)
+                    self._save_final(payload, path)
                     done.append(frame)
                 clock["steps"] += t1 - t0
                 clock["checkpoint_copy"] += t2 - t1
@@ -628,7 +679,7 @@ class _RenderWork:
             for frame, path in alone:
                 fallbacks.append(int(frame))
                 losses[frame], payload = self._own_loop(frame)
-                formats.atomic_torch_save(payload, path)
+                self._save_final(payload, path)
                 done.append(frame)
         return done
 
@@ -690,6 +741,17 @@ def mean_frame_metrics(reports):
     frames = [named for report in reports for named in (report.get("frame_metrics") or {}).values()]
     means = {name: sum(named[name] for named in frames) / len(frames) for name in formats.FRAME_METRIC_NAMES} if frames else {}
     return {"frame_metrics": means, "frame_metrics_frames": len(frames)}
+
+
+def parse_select(text):
+    """--select METRIC[,METRIC...][:max|:min] -> ([metrics], maximum), or None for an empty string; ValueError otherwise."""
+    if not text:
+        return None
+    names, _, order = text.partition(":")
+    metrics = [name.strip() for name in names.split(",")]
+    if order not in ("", "max", "min") or not all(re.fullmatch(r"\w+", name) for name in metrics):
+        raise ValueError(f"--select {text!r}: expected METRIC[,METRIC...][:max|:min]")
+    return metrics, order == "max"
 
 
 def parse_instances(text):
@@ -797,13 +859,26 @@ def main(argv=None):
                         help="after a frame's steps, render the target view's dense predicted instance masks (scripts/main.py:1011-1061: volume_masks "
                              "x surface_masks) -- vsrd_frame_masks, one launch per group of frames -- write them bit-packed to masks/view_00.npz next "
                              "to the frame's checkpoint and store their mean IoU against the masks the frame was fitted to as the checkpoint's "
-                             "metric `mask_iou` (tools/select_model.py --metrics mask_iou --maximum).  Needs --out; not with --selftest")
+                             "metric `mask_iou`; with --ckpt-interval every step_*.pt carries it too, and --select mask_iou:max picks among "
+                             "them.  Needs --out; not with --selftest")
     parser.add_argument("--metrics", action="store_true",
                         help="after a frame's steps, evaluate its boxes against the frame's 3-D ground truth (FrameInputs.boxes_3d / a frame pack's "
                              "boxes_3d; synthetic frames carry their true boxes) -- vsrd_frame_metrics, one launch per group of frames -- and store the "
                              "reference's iou_3d, iou_bev, accuracy_3d_25, accuracy_bev_25, accuracy_3d_50, accuracy_bev_50 (scripts/main.py:870-924) in "
-                             "the checkpoint's `metrics` (tools/select_model.py); the job's line gets their means over the frames that had ground "
+                             "the checkpoint's `metrics` (with --ckpt-interval in every step_*.pt too, for --select); the job's line gets their means over the frames that had ground "
                              "truth (`frame_metrics`, `frame_metrics_frames`); frames without it are skipped.  Not with --selftest")
+    parser.add_argument("--scalar-interval", type=int, default=0,
+                        help="every K steps log a frame's scalars on the device (the reference's scalar_intervals, 50: losses, learning rates, "
+                             "annealed hyperparameters, with --metrics the six metrics) -- vsrd_frame_log between the graph replays, read once per "
+                             "frame -- and write them to history.json next to the frame's checkpoint.  0: off.  Needs --out; not with --selftest")
+    parser.add_argument("--ckpt-interval", type=int, default=0,
+                        help="every K steps keep a snapshot of a frame's models on the device (the reference's ckpt_intervals, 500) and write them "
+                             "as step_{step}.pt (step, models, metrics: with --metrics the six metrics, with --masks mask_iou) before the frame's "
+                             "final checkpoint.  0: off.  Needs --out; not with --selftest")
+    parser.add_argument("--select", default="",
+                        help="METRIC[,METRIC...][:max|:min] (default :min): copy the frame's step_*.pt with the best mean of these metrics to "
+                             "model.pt (the rule of tools/select_model.py; a tie keeps the earliest step), which make_predictions.py "
+                             "--ckpt_filename model.pt picks up.  Needs --out; not with --selftest")
     parser.add_argument("--ranks-share-gpu", action="store_true",
                         help="TEST ONLY: every rank on cuda:0, gloo rendezvous (RCCL refuses two ranks on one device); the line says so")
     parser.add_argument("--fresh-loops", action="store_true",
@@ -833,6 +908,17 @@ def main(argv=None):
         raise SystemExit("--masks renders the masks of optimised frames; --selftest optimises none: drop one of --selftest, --masks")
     if args.metrics and args.selftest:
         raise SystemExit("--metrics evaluates the boxes of optimised frames; --selftest optimises none: drop one of --selftest, --metrics")
+    for flag, value in (("--scalar-interval", args.scalar_interval), ("--ckpt-interval", args.ckpt_interval), ("--select", args.select)):
+        if value and args.selftest:
+            raise SystemExit(f"{flag} logs optimised frames; --selftest optimises none: drop one of --selftest, {flag}")
+        if value and not args.out:
+            raise SystemExit(f"{flag} writes history.json, step_*.pt and model.pt next to every frame's checkpoint: it needs --out")
+    if args.scalar_interval < 0 or args.ckpt_interval < 0:
+        raise SystemExit("--scalar-interval and --ckpt-interval must be at least 0 (0: off)")
+    try:
+        parse_select(args.select)
+    except ValueError as error:
+        raise SystemExit(str(error))
     if args.group_predictions and args.selftest:
         raise SystemExit("--group-predictions writes the labels of optimised frames; --selftest optimises none: drop one of --selftest, --group-predictions")
     if args.group_predictions and not args.out:
@@ -1045,6 +1131,8 @@ def _rank_main(args):
                 **({"predictions": True} if args.predictions else {}),
                 **({"group_predictions": True} if args.group_predictions else {}),
                 **({"masks": True} if args.masks else {}),      # (--predictions: label files next to every checkpoint)
+                **({"frame_log": {"scalar_interval": args.scalar_interval, "ckpt_interval": args.ckpt_interval, "select": args.select}}
+                   if args.scalar_interval or args.ckpt_interval or args.select else {}),
                 **(mean_frame_metrics(gathered) if args.metrics else {}),
                 "frames_outside_slots": sorted(f for r in gathered for f in r["frames_outside_slots"]),
                 "unsuitable_founders": sorted(f for r in gathered for f in r["unsuitable_founders"]),

@@ -246,6 +246,68 @@ class OptimizationConfig:
     surface_num_iterations: int = 1000
     surface_convergence_criteria: float = 0.01
     surface_bounding_radius: float = 100.0
+    # the device-side log of the fused-glue graph loop (csrc/frame_log.h; scripts/main.py:870-953, 1109-1121 -- config.json's scalar_intervals
+    # 50 and ckpt_intervals 500): every `scalar_interval` steps a row of scalars (FrameOptimizer.history), every `checkpoint_interval` steps a
+    # snapshot of the models (FrameOptimizer.snapshots).  0: off -- no buffer, no launch, the loop as it is without them.
+    scalar_interval: int = 0
+    checkpoint_interval: int = 0
+
+    def __post_init__(self):
+        for name in ("scalar_interval", "checkpoint_interval"):
+            if int(getattr(self, name)) < 0:
+                raise ValueError(f"{name}: at least 0 (0: off), got {getattr(self, name)}")
+
+
+LOG_LOSSES = ("iou_projection_loss", "l1_projection_loss", "silhouette_loss", "eikonal_loss", "loss")       # the epilogue's record, in order
+
+
+def _align4(count):
+    return (int(count) + 3) // 4 * 4
+
+
+def _log_slot_layout(detector, hyper_distance_field, capacity):
+    """[(name, tensor or None, floats reserved)] of a snapshot slot -- every entry starts on a multiple of four floats: the detector's four
+    parameters laid out for `capacity` instances, every parameter of the hypernetwork, then the metrics summary [8] and the mask pixel counts
+    [capacity,3] (int32), whose sources exist only once those outputs do.  Works on meta modules (sizes only)."""
+    entries = [(f"detector.{name}", p, _align4(int(capacity) * p[0, 0].numel())) for name, p in detector.named_parameters()]
+    entries += [(f"hyper_distance_field.{name}", p, _align4(p.numel())) for name, p in hyper_distance_field.named_parameters()]
+    entries += [("summary", None, 8), ("counts", None, _align4(3 * int(capacity)))]
+    if len(entries) > _lib.FRAME_LOG_SEGMENTS:
+        raise ValueError(f"a snapshot of {len(entries)} tensors: vsrd_frame_log copies at most {_lib.FRAME_LOG_SEGMENTS} segments")
+    return entries
+
+
+def _steps_to_log_boundary(members):
+    """Steps until the first of `members` reaches a boundary of either interval of the log (None: no log)."""
+    cfg = members[0].config
+    gaps = [interval - m.step_index % interval for m in members for interval in (cfg.scalar_interval, cfg.checkpoint_interval) if interval > 0]
+    return min(gaps) if gaps and members[0]._log is not None else None
+
+
+def _launch_log(members, frames=None):
+    """After a step group of `members` (one loop, or the active rows of a batch whose row 0 leads the launches): when a member's step count
+    sits on a boundary of the log, the metrics launch (every boundary) and the masks launch (checkpoint boundaries) whose buffers the log
+    reads (a frame without ``boxes_3d`` gets the summary of no pair: count 0), then ONE vsrd_frame_log launch, all on the current stream -- the one the graphs replay on -- with no synchronisation.  Each row
+    decides by its own device counter what it logs (csrc/frame_log.h), so a launch that a row did not need writes nothing in that row."""
+    lead = members[0]
+    log = lead._log
+    if log is None:
+        return
+    cfg = lead.config
+    due = [any(m.step_index > 0 and m.step_index % interval == 0 for m in members) if interval > 0 else False
+           for interval in (cfg.scalar_interval, cfg.checkpoint_interval)]
+    if not any(due):
+        return
+    started = time.perf_counter()
+    if log["metrics"]:       # (always: a frame without boxes_3d has NaN ground truth in its row, so its summary comes out as count 0 -- never a
+        lead._launch_output("metrics", frames=frames)        # summary an earlier frame of the row left behind)
+    if log["masks"] and due[1]:
+        lead._launch_output("masks", frames=frames, view=0)
+    config = _lib.FrameLogConfig.from_buffer_copy(log["config"])
+    config.num_frames, config.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
+    with _capture_lock:
+        _lib.check(_lib.load().vsrd_frame_log(config, _lib.stream()))
+    lead.log_seconds += time.perf_counter() - started
 
 
 class FrameArena:
@@ -611,6 +673,10 @@ class FrameOptimizer:
             raise ValueError(f"max_label_views: 0..{_lib.MAX_LABEL_VIEWS}, got {self.label_view_capacity}")
         if label_view_count(inputs) > self.label_view_capacity > 0:
             raise ValueError(f"a frame with {label_view_count(inputs)} label views in a loop laid out for {self.label_view_capacity} (max_label_views)")
+        if config.scalar_interval > 0 or config.checkpoint_interval > 0:
+            if not (graph and fused_glue in (None, True)):
+                raise ValueError("scalar_interval / checkpoint_interval: the log is filled between the replays of the fused-glue graph loop "
+                                 "(graph=True, fused_glue on); the eager loop has no device-side log")
         self._graphs = {}
         self.persistent = bool(persistent)
         self._row = row
@@ -671,6 +737,7 @@ class FrameOptimizer:
         self.pixels_per_view = H * W
         self._prepare_rays(inputs, config, H, W, N)
         self.step_index = 0
+        self._log, self.log_seconds = None, 0.0          # (the device-side log: _init_log)
         if self.fused_glue:
             self._init_fused_glue()
 
@@ -809,6 +876,119 @@ class FrameOptimizer:
         b["picks"] = new(cfg.num_rays, torch.int64, fill=0)
         b["ray_indices"] = new(cfg.num_rays, torch.int64, fill=0)
         b["mlp_weights"], b["mlp_centred"] = new((N, _lib.MLP_WEIGHTS), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
+        if cfg.scalar_interval > 0 or cfg.checkpoint_interval > 0:
+            self._init_log()
+
+    # ---- the device-side log (csrc/frame_log.h) -----------------------------------------------------------------------------------------
+    def _init_log(self):
+        """The log's buffers, at construction (a frame of a batch: in its row, the same offsets in every row): history
+        [num_steps // scalar_interval, 22], snapshots [num_steps // checkpoint_interval, slot], the slots' steps, the four counters, the
+        list of the five rate pointers and the segment table."""
+        cfg, new = self.config, self._new
+        rows = cfg.num_steps // cfg.scalar_interval if cfg.scalar_interval > 0 else 0
+        slots = cfg.num_steps // cfg.checkpoint_interval if cfg.checkpoint_interval > 0 else 0
+        layout = _log_slot_layout(self.detector, self.hyper_distance_field, self.capacity)
+        slot_floats = sum(size for _, _, size in layout) if slots else 0
+        log = self._log = dict(rows=rows, slots=slots, slot_floats=slot_floats, metrics=False, masks=False)
+        log["history"] = new((max(rows, 1), _lib.FRAME_LOG_COLUMNS), fill=0.0)
+        log["snapshots"] = new((max(slots, 1), max(slot_floats, 4)), fill=0.0)
+        log["snapshot_steps"] = new(max(slots, 1), torch.int32, fill=-1)
+        log["counters"] = new(4, torch.int32, fill=0)
+        log["rate_pointers"] = new(5, torch.int64, fill=0)
+        log["table"] = new(_lib.FRAME_LOG_SEGMENTS * ctypes.sizeof(_lib.LogSegment), torch.uint8, fill=0)
+        log["config"] = _lib.FrameLogConfig(
+            int(cfg.scalar_interval), int(cfg.checkpoint_interval), rows, slots, slot_floats, len(layout), 1, 0, self.step_tensor.data_ptr(),
+            self._glue["record"].data_ptr(), log["rate_pointers"].data_ptr(), self.schedule.data_ptr(), None, log["table"].data_ptr(),
+            log["history"].data_ptr(), log["snapshots"].data_ptr(), log["snapshot_steps"].data_ptr(), log["counters"].data_ptr())
+        self._write_log_table()
+
+    def _write_log_table(self):
+        """The frame's own pointer list and segment table: the CURRENT tensors of the modules and the optimiser (rebind() calls this again),
+        the frame's own n instances at offsets laid out for the capacity, and the metrics / masks sources once log_outputs() has made them."""
+        log = self._log
+        log["rate_pointers"].copy_(torch.tensor([group["lr"].data_ptr() for group in self.optimizer.param_groups], dtype=torch.int64))
+        sources = {"summary": self._outputs["metrics"]["summary"] if log["metrics"] else None,
+                   "counts": self._outputs["masks"]["counts"][:self.num_instances] if log["masks"] else None}
+        table, offset = (_lib.LogSegment * _lib.FRAME_LOG_SEGMENTS)(), 0
+        log["layout"] = []
+        for index, (name, tensor, size) in enumerate(_log_slot_layout(self.detector, self.hyper_distance_field, self.capacity)):
+            tensor = sources[name] if tensor is None else tensor.data
+            if tensor is not None:
+                if not tensor.is_contiguous() or tensor.element_size() != 4 or tensor.numel() > size:
+                    raise ValueError(f"{name}: a snapshot segment is a contiguous tensor of 32-bit words within its {size} reserved")
+                table[index] = _lib.LogSegment(tensor.data_ptr(), tensor.numel(), offset)
+            log["layout"].append((name, offset, None if tensor is None else (tuple(tensor.shape), tensor.dtype)))
+            offset += size
+        log["table"].copy_(torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8))
+        log["config"].summary = sources["summary"].data_ptr() if log["metrics"] else None
+
+    def log_outputs(self, metrics=False, masks=False):
+        """What the log reads of the other outputs from now on: with ``metrics`` the summary of vsrd_frame_metrics -- launched before every
+        log launch; a frame without ``boxes_3d`` gets the summary of no pair, count 0, which names no metric -- goes into every history row and snapshot; with ``masks`` the pixel counts of
+        vsrd_frame_masks (view 0) -- launched before the log launch at checkpoint boundaries -- go into every snapshot (``mask_iou``).
+        Creates those outputs' buffers now (a FrameBatch: in every row, FrameBatch.log_outputs)."""
+        if self._log is None:
+            raise RuntimeError("log_outputs(): this loop keeps no log (OptimizationConfig.scalar_interval / checkpoint_interval)")
+        for name, wanted in (("metrics", metrics), ("masks", masks)):
+            if wanted:
+                self._output_state(name)
+            self._log[name] = bool(wanted)
+        with _capture_lock, torch.no_grad():
+            self._write_log_table()
+
+    def _require_log(self, what, interval):
+        if self._log is None or interval <= 0:
+            raise RuntimeError(f"{what}(): this loop does not log it (OptimizationConfig.scalar_interval / checkpoint_interval)")
+        return self._log
+
+    def history(self):
+        """The scalars logged so far, one row per ``scalar_interval`` steps, as device tensors sliced to the rows written (views of the
+        log's buffer; the row count follows from the step count, nothing is read back): steps [rows] int32, the five losses by name
+        (``eikonal_loss`` NaN for box-only steps, as the reference's dictionary has no such key then), learning_rates [rows,5] AFTER the
+        step's decay (``param_group["lr"]`` when main.py logs it), hyperparameters [rows,3] = (sdf_union_temperature, sdf_std_deviation,
+        cosine_ratio) of the step, metrics [rows,8] (the summary of ``metrics()`` on the parameters after the step's update; NaN when
+        log_outputs(metrics=True) was not asked for)."""
+        cfg = self.config
+        log = self._require_log("history", cfg.scalar_interval)
+        rows = min(self.step_index // cfg.scalar_interval, log["rows"])
+        table = log["history"][:rows]
+        steps = table[:, 0].view(torch.int32)
+        result = dict(steps=steps, learning_rates=table[:, 6:11], hyperparameters=table[:, 11:14], metrics=table[:, 14:22])
+        for column, name in enumerate(LOG_LOSSES, start=1):
+            result[name] = table[:, column]
+        result["eikonal_loss"] = torch.where(steps >= cfg.warmup_steps, table[:, 4], torch.full_like(table[:, 4], float("nan")))
+        return result
+
+    def snapshots(self):
+        """The snapshots taken so far, one per ``checkpoint_interval`` steps: a list of dictionaries -- step (the tensor snapshot_steps[slot],
+        int32), models (state dicts in the layout ``formats.checkpoint_payload`` gives ``models``: the parameters AFTER that step's Adam
+        update, as the reference's step_{s}.pt holds them; views of the slot) and metrics (the slot's summary [8], a view, and, with masks,
+        mask_iou [n] -- the slot holds the int32 pixel counts [n,3] that vsrd_frame_masks wrote, no device buffer holds an IoU, so this one
+        tensor is computed from the slot's counts here, by the ``mask_iou`` function that ``masks()`` uses; an empty dictionary without either)."""
+        cfg = self.config
+        log = self._require_log("snapshots", cfg.checkpoint_interval)
+        result = []
+        for slot in range(min(self.step_index // cfg.checkpoint_interval, log["slots"])):
+            words = log["snapshots"][slot]
+            models = {"detector": {}, "hyper_distance_field": {}}
+            metrics = {}
+            for name, offset, source in log["layout"]:
+                if source is None:
+                    continue
+                shape, dtype = source
+                value = words[offset:offset + math.prod(shape)].view(dtype).view(shape)
+                if name == "summary":
+                    metrics["summary"] = value
+                elif name == "counts":
+                    metrics["mask_iou"] = mask_iou(value)
+                else:
+                    module, key = name.split(".", 1)
+                    models[module][key] = value
+            for module, key, value in [("detector", k, v) for k, v in self.detector.named_buffers()] + \
+                                      [("hyper_distance_field", k, v) for k, v in self.hyper_distance_field.named_buffers()]:
+                models[module][key] = value
+            result.append(dict(step=log["snapshot_steps"][slot], models=models, metrics=metrics))
+        return result
 
     # ---- the tensors whose addresses the kernels and the captured graphs hold ----------------------------------------------------
     def _bound_tensors(self):
@@ -861,6 +1041,8 @@ class FrameOptimizer:
         # while a graph that writes through its address may still be replayed
         self._bound = self._bound_tensors()
         self._bound_signature = tuple(t.data_ptr() for t in self._bound)
+        if getattr(self, "_log", None) is not None:
+            self._write_log_table()
 
     def _check_bindings(self):
         """Before anything is launched or replayed: are the tensors the pointer blocks were built from still the ones the modules and
@@ -1043,7 +1225,10 @@ class FrameOptimizer:
         if self.graph:
             if u_coarse is not None or u_fine is not None:
                 raise ValueError("graph mode draws its uniforms in the kernels (Philox keyed by the device-side step counter)")
-            return self._graph_step(ray_indices)
+            outputs = self._graph_step(ray_indices)
+            if self._log is not None:
+                _launch_log([self])
+            return outputs
         return self._step(ray_indices, u_coarse, u_fine)
 
     # ---- hipGraph mode ---------------------------------------------------------------------------------
@@ -1117,6 +1302,9 @@ class FrameOptimizer:
                 to_boundary = remaining if residual else self.config.warmup_steps - self.step_index
                 # whole groups of `steps_per_graph` only: a tail shorter than that replays the one-step graph (every distinct k would
                 # otherwise cost a capture of its own -- a synchronisation -- for one use)
+                to_log = _steps_to_log_boundary([self])         # (no group crosses a boundary of the log: the launch follows the group)
+                if to_log is not None:
+                    to_boundary = min(to_boundary, to_log)
                 k = int(steps_per_graph) if min(remaining, to_boundary) >= int(steps_per_graph) else 1
                 if self._eager_graph_steps.get((residual, False), 0) < 3 or (residual, False) not in self._graphs:
                     k = 1            # the phase's eager warm-up steps and its one-step graph come first (step() owns that protocol)
@@ -1137,12 +1325,13 @@ class FrameOptimizer:
                         outputs = self._step(None, None, None, count=False, joins=(j == 0, j == k - 1))
                 self._graphs[key] = (graph, None, outputs)
                 graph.replay()          # (the first launch inside the capture's turn: _graph_step)
-            self.step_index += k
-            return outputs
-        graph, _, outputs = self._graphs[key]
-        with _capture_lock.replaying():
-            graph.replay()
+        else:
+            graph, _, outputs = self._graphs[key]
+            with _capture_lock.replaying():
+                graph.replay()
         self.step_index += k
+        if self._log is not None:
+            _launch_log([self])
         return outputs
 
     def _step(self, ray_indices, u_coarse, u_fine, count=True, joins=(True, True)):
@@ -1230,6 +1419,9 @@ class FrameOptimizer:
             with _capture_lock:
                 self.step_index = phase_start
                 self.step_tensor.fill_(phase_start)
+            # (a loop with the log: these steps launch it too, with the metrics and masks launches in front of it, at counters that start
+            #  from phase_start -- rows and slots of steps the founder never ran.  Harmless: the reset() below starts the log over, and every
+            #  row a real run logs is written, metrics included, by that run's own launches)
             for _ in range(min(4, phase_steps)):     # three eager steps, then the capture (and first replay) of the one-step graph
                 self.step()
             if k > 1 and phase_steps >= 4 + k:       # (run() takes the k-step graph only for whole groups of k inside a phase)
@@ -1333,6 +1525,11 @@ class FrameOptimizer:
                 b[name].zero_()
             if self._headed:
                 self._write_header()
+            if self._log is not None:            # (the log starts over; its table follows the frame's own instance count)
+                self.log_seconds = 0.0
+                self._log["counters"].zero_()
+                self._log["snapshot_steps"].fill_(-1)
+                self._write_log_table()
             suits = self._prepare_sampler(cfg)
             main.synchronize()
         return suits
@@ -1465,6 +1662,11 @@ class FrameOptimizer:
         with _capture_lock:
             incomplete = bool(self.graph and self.ray_table is not None and self.ray_table.incomplete())
             overflowed = bool(self.graph and self.workspace.sampler_overflowed(self.device))
+            dropped = self._log["counters"].tolist() if getattr(self, "_log", None) is not None else [0, 0, 0, 0]
+        if dropped[1] or dropped[3]:
+            import warnings
+            warnings.warn(f"vsrd_frame_log dropped {dropped[1]} history rows and {dropped[3]} snapshots of this frame: it ran beyond the "
+                          "capacities num_steps // interval its log was laid out for", RuntimeWarning)
         if incomplete:
             import warnings
             warnings.warn("vsrd_sample_rays_table ran out of picks in some step of this frame: those draws repeat some rays "
@@ -1644,6 +1846,11 @@ class FrameBatch:
         total += N * H * ((W + 7) // 8) + 4 * H * W * N + 12 * N     # masks(): bit-packed masks, soft values, counts
         # (metrics(): 200 N + 68 bytes in five buffers, at most 14 KB: within the slack below)
         total += int(label_views) * (129 * N + 108)                 # group_labels(): the label views' tables, ids, corners and boxes (the [N] outputs: slack)
+        if config.scalar_interval > 0 or config.checkpoint_interval > 0:        # the log: history rows, snapshot slots (the small buffers: slack)
+            with torch.device("meta"):
+                slot = sum(size for _, _, size in _log_slot_layout(*_fresh_modules(N), N))
+            total += 4 * _lib.FRAME_LOG_COLUMNS * (config.num_steps // config.scalar_interval if config.scalar_interval > 0 else 1)
+            total += 4 * slot * (config.num_steps // config.checkpoint_interval) if config.checkpoint_interval > 0 else 16
         return total + (4 << 20)                                     # 256-byte alignment of ~400 buffers, step counters, rates, slack
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
@@ -1726,18 +1933,37 @@ class FrameBatch:
                 self._graphs[key].replay()
             for m in members:
                 m.step_index += 1
-            return
-        done = self._eager.get(key, 0)
-        if done < 3:
+        elif self._eager.get(key, 0) < 3:
             with _capture_lock:
                 side = torch.cuda.Stream(device=self.device)
                 side.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(side):
                     self._step(active)
                 torch.cuda.current_stream(self.device).wait_stream(side)
-            self._eager[key] = done + 1
-            return
-        self._capture(key, active, 1)
+            self._eager[key] = self._eager.get(key, 0) + 1
+        else:
+            self._capture(key, active, 1)
+        self._log_after(members)
+
+    def _log_after(self, members):
+        """The log launch that follows a step group of `members` (the first rows of the batch) when one of them sits on a boundary."""
+        if members[0]._log is not None:
+            _launch_log(members, frames=(len(members), self.arena.stride))
+
+    def log_outputs(self, metrics=False, masks=False):
+        """``FrameOptimizer.log_outputs`` for every row (the outputs' buffers at equal offsets)."""
+        for m in self.frames:
+            m.log_outputs(metrics=metrics, masks=masks)
+        if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
+            raise RuntimeError("the frames of a batch laid their output buffers out differently: frame batches need equal offsets in every row")
+
+    def history(self, active=None):
+        """``FrameOptimizer.history`` of the first ``active`` frames: a list of dictionaries of device tensors, each sliced to its frame's own rows."""
+        return [m.history() for m in self._members(active)[1]]
+
+    def snapshots(self, active=None):
+        """``FrameOptimizer.snapshots`` of the first ``active`` frames: a list of lists, each frame's own slots and instances."""
+        return [m.snapshots() for m in self._members(active)[1]]
 
     def _capture(self, key, active, k):
         _, members = self._members(active)
@@ -1762,6 +1988,9 @@ class FrameBatch:
         while remaining > 0:
             residual = self._phase(active)
             to_boundary = remaining if residual else self.config.warmup_steps - members[0].step_index
+            to_log = _steps_to_log_boundary(members)            # (no group crosses a boundary of the log, of any row: the launch follows the group)
+            if to_log is not None:
+                to_boundary = min(to_boundary, to_log)
             k = k_many if k_many > 1 and min(remaining, to_boundary) >= k_many else 1
             if (residual, active, 1) not in self._graphs:
                 k = 1                   # the phase's eager steps and its one-step graph come first
@@ -1776,6 +2005,7 @@ class FrameBatch:
                         m.step_index += k
                 else:
                     self._capture(key, active, k)
+                self._log_after(members)
             remaining -= k
 
     def capture_all(self, steps_per_graph=4, actives=None):
@@ -1793,7 +2023,7 @@ class FrameBatch:
                     for m in members:
                         m.step_index = phase_start
                         m.step_tensor.fill_(phase_start)
-                for _ in range(min(4, phase_steps)):
+                for _ in range(min(4, phase_steps)):     # (with the log these launch it as well: FrameOptimizer.capture_all; the resets below start it over)
                     self.step(active)
                 if k > 1 and phase_steps >= 4 + k:
                     self._capture((self._phase(active), active, k), active, k)
