@@ -755,6 +755,80 @@ typedef struct vsrd_frame_log_config {
 
 int32_t vsrd_frame_log(const vsrd_frame_log_config* log, void* stream);
 
+/* Multi-view patch-correlation photometric loss (added within ABI 12; probe for the symbols -- VSRD_ABI_VERSION is unchanged, no existing
+ * struct has a new field): the homography / patch-correlation part of the reference's photometric branch (scripts/main.py:783-851) for ONE
+ * frame, forward and backward, without host synchronisation or allocation, capturable.  The arithmetic is tiny (100 rays x 17 views x 121
+ * pixels); what the calls buy is launch count -- three launches forward, two backward, where the reference issues V grid_sample calls, V R
+ * matrix chains and a Python loop with cov / diag / sqrt / topk per converged ray -- not throughput.
+ * What is computed, the reference's quirks included:
+ *   patch grid   offsets arange(pw) - pw / 2 in x and arange(ph) - ph / 2 in y (integer division: size 4 gives -2..1), x the fast index,
+ *                P = pw ph; q = (x + dx, y + dy, 1) for the ray's target pixel (x, y);
+ *   homography   for EVERY view s, the target included: H = K_s (R_s R_t^T - R_s (R_s^T t_s - R_t^T t_t) n^T / -(n.p)) K_t^-1, evaluated as
+ *                A_s + b_s (K_t^-T n)^T / (n.p) with A_s = K_s R_s R_t^T K_t^-1 and b_s = K_s R_s (R_s^T t_s - R_t^T t_t) computed once per
+ *                call in double (K_t^-1 by adjugate: no assumption about the skew); h = H q, s = h_xy / (h_z + sample_epsilon);
+ *   sampling     the reference maps [0, W-1] -> [-1, 1] (align-corners) and then calls grid_sample with align_corners=False: the sampled
+ *                pixel coordinate is s_x W / (W - 1) - 0.5 (likewise y) -- even the identity homography interpolates.  Bilinear, zeros
+ *                padding: a tap outside the image contributes 0;
+ *   correlation  per converged ray the V patches [V,P]: unbiased covariance (/ (P - 1)), c_ij = cov_ij / sqrt(cov_ii cov_jj +
+ *                correlation_epsilon) -- a constant patch has coefficient 0 with everything, itself included, not NaN --, the top_k largest
+ *                of every row (the self-coefficient is among the candidates; NaN ranks above every number, as in torch.topk; ties go to the
+ *                lowest index);
+ *   loss         (1 - nanmean(all selected coefficients of all converged rays)) / 2; unconverged rays contribute nothing.
+ * Two stated deviations from the reference:
+ *   gray first   the reference samples the three colour planes and applies 0.2989 r + 0.587 g + 0.114 b afterwards; here
+ *                vsrd_grayscale_images makes the gray planes once per frame and the loss samples those.  Both maps are linear, so the two
+ *                orders agree in exact arithmetic; they differ in rounding only, and the gathers are a third;
+ *   no ray       with no converged ray the reference adds no term; here the loss is 0 and every gradient 0 -- the same weighted sum.
+ * Hazards: a plane that passes near a source camera's centre sends sample coordinates to +-5e8 and beyond, h_z + sample_epsilon == 0 makes
+ * them non-finite.  Inside-ness is decided in floating point before any conversion to integer; a sample that is outside or non-finite reads
+ * 0 and passes no gradient.
+ * Deterministic: every reduction has a fixed order, there are no floating-point atomics.
+ * Limits, refused with VSRD_E_INVALID_ARGUMENT before any launch: 1 <= top_k <= num_views <= VSRD_PATCH_MAX_VIEWS; 1 <= patch_width,
+ * patch_height and P <= VSRD_PATCH_MAX_PIXELS; 1 <= num_rays <= VSRD_PATCH_MAX_RAYS; height, width >= 2; 0 <= target_view < num_views; a
+ * NULL config or required pointer.  A workspace smaller than vsrd_patch_correlation_workspace_bytes: VSRD_E_WORKSPACE. */
+#define VSRD_PATCH_MAX_VIEWS 32
+#define VSRD_PATCH_MAX_PIXELS 256
+#define VSRD_PATCH_MAX_RAYS 65535
+typedef struct vsrd_patch_correlation_config {
+    int32_t num_views;              /* V                                                                                      */
+    int32_t num_rays;               /* R                                                                                      */
+    int32_t height, width;          /* of every image                                                                         */
+    int32_t patch_width;            /* pw: the reference's patch_size[0]                                                      */
+    int32_t patch_height;           /* ph: patch_size[1]                                                                      */
+    int32_t top_k;                  /* the reference: 4                                                                       */
+    int32_t target_view;            /* t: the view the pixels, positions and normals belong to                                */
+    float sample_epsilon;           /* the reference: 1e-6                                                                    */
+    float correlation_epsilon;      /* the reference: 1e-12                                                                   */
+} vsrd_patch_correlation_config;
+
+/* images [V,3,H,W] -> gray [V,H,W] = fma(0.114, b, fma(0.587, g, 0.2989 r)) (torchvision's rgb_to_grayscale weights, the products fused as
+ * written here, whatever the compiler's contraction mode).  Once per frame: the images do not change over its steps.  H W need not be a
+ * multiple of 4. */
+int32_t vsrd_grayscale_images(const float* images, int32_t num_views, int32_t height, int32_t width, float* gray, void* stream);
+
+/* Bytes of the calls' workspace: the per-view constants and one (sum, count) pair per ray.  Grows with num_views and num_rays;
+ * patch_pixels is validated with them (the patches themselves live in LDS) and adds nothing today.  0 for a shape outside the limits. */
+size_t vsrd_patch_correlation_workspace_bytes(int32_t num_views, int32_t num_rays, int32_t patch_pixels);
+
+/* gray [V,H,W]; intrinsics [V,3,3] and extrinsics [V,4,4] row-major, the reference's own matrices; pixels [R,2] = (x, y) of the target
+ * view; positions, normals [R,3] in the frame of the extrinsics' input; converged [R].
+ * Out: loss [1]; stats [2] = (sum, count) of the selected non-NaN coefficients.  Optional (NULL: not written): patches [V,R,P], the
+ * reference's sampled_patches without the singleton -- of every ray, converged or not; coefficients [R,V,V] and selected [R,V] (bit j of
+ * entry (r, i): coefficient (i, j) is among row i's top_k), zero rows for unconverged rays. */
+int32_t vsrd_patch_correlation_forward(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics,
+                                       const int32_t* pixels, const float* positions, const float* normals, const uint8_t* converged,
+                                       void* workspace, size_t workspace_bytes, float* loss, float* stats,
+                                       float* patches, float* coefficients, int32_t* selected, void* stream);
+
+/* The same inputs, the forward's stats and the upstream gradient of the loss grad_loss [1] (device memory) -> grad_positions, grad_normals
+ * [R,3]; zero rows for unconverged rays.  Every ray's forward is recomputed with the forward's own device functions (the selection is the
+ * forward's bit for bit); the workspace need not be the forward's, nor keep its contents in between.  No gradient with respect to images
+ * or cameras. */
+int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics,
+                                        const int32_t* pixels, const float* positions, const float* normals, const uint8_t* converged,
+                                        void* workspace, size_t workspace_bytes, const float* stats, const float* grad_loss,
+                                        float* grad_positions, float* grad_normals, void* stream);
+
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]
  * -> weight_norm(Linear 256 -> 1617) = mlp_weights [N,1617].  weight_norm over dim 0: W[o,:] = g[o] v[o,:] / |v[o,:]|.

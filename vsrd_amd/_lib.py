@@ -200,7 +200,27 @@ class FrameLogConfig(ctypes.Structure):
     ]
 
 
-FRAME_LOG_COLUMNS = 22         # VSRD_LOG_SCALARS: (step | record 5 | learning rates 5 | schedule 3 | metrics summary 8) of a history row
+class PatchCorrelationConfig(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_patch_correlation_config (added within ABI 12): the shape and the two epsilons of one
+    vsrd_patch_correlation_forward / _backward call."""
+    _fields_ = [
+        ("num_views", ctypes.c_int32),
+        ("num_rays", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("patch_width", ctypes.c_int32),
+        ("patch_height", ctypes.c_int32),
+        ("top_k", ctypes.c_int32),
+        ("target_view", ctypes.c_int32),
+        ("sample_epsilon", ctypes.c_float),
+        ("correlation_epsilon", ctypes.c_float),
+    ]
+
+
+PATCH_VIEWS = 32               # VSRD_PATCH_MAX_VIEWS: the limits of vsrd_patch_correlation_forward / _backward
+PATCH_PIXELS = 256             # VSRD_PATCH_MAX_PIXELS
+PATCH_RAYS = 65535             # VSRD_PATCH_MAX_RAYS
+FRAME_LOG_COLUMNS = 22        # VSRD_LOG_SCALARS: (step | record 5 | learning rates 5 | schedule 3 | metrics summary 8) of a history row
 FRAME_LOG_SEGMENTS = 32        # VSRD_LOG_MAX_SEGMENTS: entries of a frame's snapshot table
 FRAME_HEADER_HAS_VIEWS = 0x10000
 MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFrameMaxViews)
@@ -212,7 +232,8 @@ _SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ct
 _RETURNS = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
 # host structures, passed as const T*; every other pointer is device memory (vsrd_frame_header too) or the stream, and travels as an integer
 _HOST_STRUCTS = {"vsrd_field": Field, "vsrd_render_config": RenderConfig, "vsrd_frame_config": FrameConfig, "vsrd_adam_tensors": AdamTensors,
-                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig, "vsrd_frame_log_config": FrameLogConfig}
+                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig, "vsrd_frame_log_config": FrameLogConfig,
+                 "vsrd_patch_correlation_config": PatchCorrelationConfig}
 _DEVICE_POINTEES = {"void", "float", "uint8_t", "int32_t", "int64_t", "uint64_t", "vsrd_frame_header"}
 
 

@@ -17,6 +17,7 @@
 #include "frame_masks.h"
 #include "frame_metrics.h"
 #include "frame_log.h"
+#include "patch_correlation.h"
 #include "launch.h"
 
 namespace {
@@ -1359,6 +1360,78 @@ int32_t vsrd_frame_log(const vsrd_frame_log_config* log, void* stream) {
     if (log->checkpoint_interval > 0) blocks = (log->snapshot_floats / 4 + kLogThreads - 1) / kLogThreads;
     blocks = blocks < 1 ? 1 : (blocks > kLogMaxBlocks ? kLogMaxBlocks : blocks);
     hipLaunchKernelGGL(frame_log_kernel, dim3(static_cast<unsigned>(blocks), frames.count), dim3(kLogThreads), 0, static_cast<hipStream_t>(stream), a);
+    return launch_status();
+}
+
+namespace {
+bool valid_patch_shape(int V, int R, int P) {
+    return V >= 1 && V <= kPatchMaxViews && R >= 1 && R <= kPatchMaxRays && P >= 1 && P <= kPatchMaxPixels;
+}
+
+// The checks the two calls share, in this order: the shape, the pointers, the workspace.
+int32_t patch_args(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics, const int32_t* pixels,
+                   const float* positions, const float* normals, const uint8_t* converged, void* workspace, size_t workspace_bytes, PatchArgs* a) {
+    static_assert(kPatchMaxViews == VSRD_PATCH_MAX_VIEWS && kPatchMaxPixels == VSRD_PATCH_MAX_PIXELS && kPatchMaxRays == VSRD_PATCH_MAX_RAYS,
+                  "patch_correlation.h and the ABI agree on the limits");
+    if (!config || config->patch_width < 1 || config->patch_height < 1 || config->patch_width > kPatchMaxPixels || config->patch_height > kPatchMaxPixels)
+        return VSRD_E_INVALID_ARGUMENT;
+    const int V = config->num_views, R = config->num_rays, P = config->patch_width * config->patch_height;
+    if (!valid_patch_shape(V, R, P) || config->top_k < 1 || config->top_k > V || config->target_view < 0 || config->target_view >= V ||
+        config->height < 2 || config->width < 2 || static_cast<int64_t>(config->height) * config->width >= (int64_t{1} << 30))
+        return VSRD_E_INVALID_ARGUMENT;
+    if (!gray || !intrinsics || !extrinsics || !pixels || !positions || !normals || !converged) return VSRD_E_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < patch_workspace_floats(V, R) * sizeof(float)) return VSRD_E_WORKSPACE;
+    a->num_views = V; a->num_rays = R; a->height = config->height; a->width = config->width;
+    a->patch_width = config->patch_width; a->patch_height = config->patch_height; a->top_k = config->top_k; a->target_view = config->target_view;
+    a->sample_epsilon = config->sample_epsilon; a->correlation_epsilon = config->correlation_epsilon;
+    a->gray = gray; a->intrinsics = intrinsics; a->extrinsics = extrinsics; a->pixels = pixels; a->positions = positions; a->normals = normals;
+    a->converged = converged;
+    a->constants = static_cast<float*>(workspace);
+    a->ray_stats = a->constants + static_cast<size_t>(V + 1) * kPatchViewFloats;
+    return VSRD_OK;
+}
+}  // namespace
+
+int32_t vsrd_grayscale_images(const float* images, int32_t num_views, int32_t height, int32_t width, float* gray, void* stream) {
+    if (!images || !gray || num_views < 1 || num_views > 65535 || height < 1 || width < 1) return VSRD_E_INVALID_ARGUMENT;
+    const long long plane = static_cast<long long>(height) * width;
+    if (plane >= (1ll << 30)) return VSRD_E_UNSUPPORTED;
+    long long blocks = (plane / 4 + 255) / 256;                  // a thread per 16 bytes of a plane, grid-stride beyond 1024 blocks
+    blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+    hipLaunchKernelGGL(patch_gray_kernel, dim3(static_cast<unsigned>(blocks), num_views), dim3(256), 0, static_cast<hipStream_t>(stream), images, gray, plane);
+    return launch_status();
+}
+
+size_t vsrd_patch_correlation_workspace_bytes(int32_t num_views, int32_t num_rays, int32_t patch_pixels) {
+    return valid_patch_shape(num_views, num_rays, patch_pixels) ? patch_workspace_floats(num_views, num_rays) * sizeof(float) : 0;
+}
+
+int32_t vsrd_patch_correlation_forward(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics,
+                                       const int32_t* pixels, const float* positions, const float* normals, const uint8_t* converged,
+                                       void* workspace, size_t workspace_bytes, float* loss, float* stats,
+                                       float* patches, float* coefficients, int32_t* selected, void* stream) {
+    PatchArgs a;
+    const int32_t status = patch_args(config, gray, intrinsics, extrinsics, pixels, positions, normals, converged, workspace, workspace_bytes, &a);
+    if (status != VSRD_OK) return status;
+    if (!loss || !stats) return VSRD_E_INVALID_ARGUMENT;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(patch_constants_kernel, dim3(1), dim3(kWave), 0, s, a);
+    hipLaunchKernelGGL(patch_correlation_forward_kernel, dim3(a.num_rays), dim3(kPatchThreads), 0, s, a, patches, coefficients, selected);
+    hipLaunchKernelGGL(patch_loss_kernel, dim3(1), dim3(kWave), 0, s, a, loss, stats);
+    return launch_status();
+}
+
+int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics,
+                                        const int32_t* pixels, const float* positions, const float* normals, const uint8_t* converged,
+                                        void* workspace, size_t workspace_bytes, const float* stats, const float* grad_loss,
+                                        float* grad_positions, float* grad_normals, void* stream) {
+    PatchArgs a;
+    const int32_t status = patch_args(config, gray, intrinsics, extrinsics, pixels, positions, normals, converged, workspace, workspace_bytes, &a);
+    if (status != VSRD_OK) return status;
+    if (!stats || !grad_loss || !grad_positions || !grad_normals) return VSRD_E_INVALID_ARGUMENT;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(patch_constants_kernel, dim3(1), dim3(kWave), 0, s, a);
+    hipLaunchKernelGGL(patch_correlation_backward_kernel, dim3(a.num_rays), dim3(kPatchThreads), 0, s, a, stats, grad_loss, grad_positions, grad_normals);
     return launch_status();
 }
 

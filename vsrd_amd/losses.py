@@ -6,6 +6,7 @@ small tensors; the heavy lifting -- rendering -- is in the HIP library).
   schedules                       scripts/main.py:420-431
   silhouette / eikonal            scripts/main.py:653-687
   weights                         configs/.../config.json:120-127
+  photometric (patch correlation) scripts/main.py:783-851   (HIP: csrc/patch_correlation.h; not used by the optimisation loop)
 """
 import math
 
@@ -105,3 +106,88 @@ def silhouette_loss(labels, targets, pd_idx=None, gt_idx=None):
 def eikonal_loss(gradients):
     """main.py:679-687."""
     return ((gradients.norm(dim=-1) - 1.0) ** 2).mean()
+
+
+# ---- photometric loss: the homography / patch-correlation part (main.py:783-851) ---------------------------------------------------
+def grayscale_images(images):
+    """images [V,3,H,W] in [0,1] -> the gray planes [V,H,W] float32 (vsrd_grayscale_images: torchvision's rgb_to_grayscale weights).
+    Once per frame: `patch_correlation_loss` takes the planes in place of the images and skips the conversion on every call."""
+    from . import _lib
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"images must be [V,3,H,W], got {tuple(images.shape)}")
+    images = images.detach().to(torch.float32).contiguous()
+    V, _, H, W = images.shape
+    gray = torch.empty(V, H, W, dtype=torch.float32, device=images.device)
+    _lib.check(_lib.load().vsrd_grayscale_images(_lib.ptr(images), V, H, W, _lib.ptr(gray), _lib.stream()))
+    return gray
+
+
+class _PatchCorrelation(torch.autograd.Function):
+    """vsrd_patch_correlation_forward / _backward: the loss as a [1] tensor (and the exported patches), gradients to positions and normals."""
+
+    @staticmethod
+    def forward(ctx, positions, normals, gray, intrinsics, extrinsics, pixels, converged, meta, want_patches):
+        from . import _lib
+        from .rendering.renderers import current_workspace
+        lib = _lib.load()
+        V, H, W = gray.shape
+        R = positions.shape[0]
+        pw, ph, top_k, target = meta
+        config = _lib.PatchCorrelationConfig(V, R, H, W, pw, ph, top_k, target, 1.0e-6, 1.0e-12)
+        positions, normals = positions.detach().contiguous(), normals.detach().contiguous()
+        workspace = current_workspace().patch_correlation(gray.device, V, R, pw * ph)
+        loss = torch.empty(1, dtype=torch.float32, device=gray.device)
+        stats = torch.empty(2, dtype=torch.float32, device=gray.device)
+        patches = torch.empty(V, R, pw * ph, dtype=torch.float32, device=gray.device) if want_patches else None
+        _lib.check(lib.vsrd_patch_correlation_forward(config, _lib.ptr(gray), _lib.ptr(intrinsics), _lib.ptr(extrinsics), _lib.iptr(pixels),
+                                                      _lib.ptr(positions), _lib.ptr(normals), converged.data_ptr(), workspace.data_ptr(),
+                                                      workspace.numel(), _lib.ptr(loss), _lib.ptr(stats), _lib.ptr(patches), None, None, _lib.stream()))
+        ctx.save_for_backward(positions, normals, gray, intrinsics, extrinsics, pixels, converged, stats)
+        ctx.config, ctx.workspace = config, workspace
+        if want_patches:
+            ctx.mark_non_differentiable(patches)
+        return loss, patches
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_patches):
+        from . import _lib
+        positions, normals, gray, intrinsics, extrinsics, pixels, converged, stats = ctx.saved_tensors
+        grad_loss = grad_loss.detach().to(torch.float32).contiguous()
+        grad_positions, grad_normals = torch.empty_like(positions), torch.empty_like(normals)
+        workspace = ctx.workspace
+        _lib.check(_lib.load().vsrd_patch_correlation_backward(
+            ctx.config, _lib.ptr(gray), _lib.ptr(intrinsics), _lib.ptr(extrinsics), _lib.iptr(pixels), _lib.ptr(positions), _lib.ptr(normals),
+            converged.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.ptr(stats), _lib.ptr(grad_loss), _lib.ptr(grad_positions),
+            _lib.ptr(grad_normals), _lib.stream()))
+        return grad_positions, grad_normals, None, None, None, None, None, None, None
+
+
+def patch_correlation_loss(images, intrinsic_matrices, extrinsic_matrices, pixel_indices, positions, normals, convergence_masks,
+                           patch_size=(11, 11), top_k=4, target_view=0, return_patches=False):
+    """main.py:783-851 in one call: the multi-view patch-correlation photometric loss of one frame (include/vsrd_hip.h has what is
+    computed, the reference's quirks and the two stated deviations: gray before interpolation, loss 0 when no ray converged).
+
+    `images` [V,3,H,W] (converted on every call) or the gray planes [V,H,W] of `grayscale_images`; `intrinsic_matrices` [V,3,3];
+    `extrinsic_matrices` [V,4,4]; `pixel_indices` the reference's flat target_ray_indices (x = i % W, y = i // W); `positions`,
+    `normals` [R,3] or with the reference's leading dimensions [1,R,3], in the frame of the extrinsics' input; `convergence_masks` [R],
+    [R,1] or [1,R,1]; `patch_size` (width, height).  Returns the loss as a 0-dim tensor with gradients to `positions` and `normals`
+    (none to images or cameras), and with `return_patches` the sampled patches [V,R,P] beside it.  The workspace is the active
+    `rendering.workspace_scope`'s."""
+    gray = images if images.dim() == 3 else grayscale_images(images)
+    gray = gray.detach().to(torch.float32).contiguous()
+    V, H, W = gray.shape
+    intrinsics = intrinsic_matrices.detach().reshape(-1, 3, 3).to(torch.float32).contiguous()
+    extrinsics = extrinsic_matrices.detach().reshape(-1, 4, 4).to(torch.float32).contiguous()
+    if intrinsics.shape[0] != V or extrinsics.shape[0] != V:
+        raise ValueError(f"{V} images need {V} intrinsic and extrinsic matrices, got {intrinsics.shape[0]} and {extrinsics.shape[0]}")
+    indices = pixel_indices.detach().reshape(-1)
+    pixels = torch.stack([indices % W, indices // W], dim=-1).to(torch.int32).contiguous()
+    R = pixels.shape[0]
+    positions, normals = positions.reshape(-1, 3).to(torch.float32), normals.reshape(-1, 3).to(torch.float32)
+    converged = convergence_masks.detach().reshape(-1).to(torch.uint8).contiguous()
+    if positions.shape[0] != R or normals.shape[0] != R or converged.shape[0] != R:
+        raise ValueError(f"{R} pixels need {R} positions, normals and convergence flags")
+    meta = (int(patch_size[0]), int(patch_size[1]), int(top_k), int(target_view))
+    loss, patches = _PatchCorrelation.apply(positions, normals, gray, intrinsics, extrinsics, pixels, converged, meta, bool(return_patches))
+    loss = loss.reshape(())
+    return (loss, patches) if return_patches else loss

@@ -40,6 +40,7 @@ class Workspace:
         self._allocate = allocate
         self._adjoint = {}      # device -> uint8 tensor
         self._sampler = {}      # device -> uint8 tensor
+        self._patch = {}        # device -> uint8 tensor
         self._retired = []      # outgrown buffers that captured graphs may still reference (only kept when asked to)
         self.keep_outgrown = False
 
@@ -64,6 +65,17 @@ class Workspace:
         """Allocate now what the largest later launch will need (a hipGraph captures the buffer's address)."""
         return self.adjoint(device, num_instances, residual, step_shape)
 
+    def patch_correlation(self, device, num_views, num_rays, patch_pixels):
+        """Scratch of vsrd_patch_correlation_forward / _backward (losses.patch_correlation_loss): its own buffer, so the adjoint scratch of
+        a render launch between the loss's forward and backward stays what it was."""
+        need = _lib.load().vsrd_patch_correlation_workspace_bytes(int(num_views), int(num_rays), int(patch_pixels))
+        buf = self._patch.get(device)
+        if buf is None or buf.numel() < need:
+            if buf is not None and self.keep_outgrown:
+                self._retired.append(buf)
+            buf = self._patch[device] = torch.empty(need, dtype=torch.uint8, device=device) if self._allocate is None else self._allocate(need)
+        return buf
+
     def sampler(self, device):
         buf = self._sampler.get(device)
         if buf is None:
@@ -81,10 +93,10 @@ class Workspace:
         return bool(buf[offset:offset + 4].view(torch.int32).item())
 
     def nbytes(self):
-        return sum(b.numel() for b in list(self._adjoint.values()) + list(self._sampler.values()) + self._retired)
+        return sum(b.numel() for b in list(self._adjoint.values()) + list(self._sampler.values()) + list(self._patch.values()) + self._retired)
 
     def release(self):
-        self._adjoint.clear(); self._sampler.clear(); self._retired.clear()
+        self._adjoint.clear(); self._sampler.clear(); self._patch.clear(); self._retired.clear()
 
 
 _default_workspace = Workspace()       # launches outside any scope (tests, the API-faithful entry points, bench.py)
