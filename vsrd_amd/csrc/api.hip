@@ -919,8 +919,17 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
             launch_hot_then_rest(hot, rest, g, s, f, field->instances, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels, partials,
                                  loss_partials, redo_flags);
         };
-        if (r.quad && r.full) launch(render_silhouette_quad_kernel<4, true, true>, render_silhouette_quad_kernel<4, false, false>);
-        else if (r.full) launch(render_silhouette_pair_kernel<4, true, true>, render_silhouette_pair_kernel<4, false, false>);
+        // (... and of those the launches with VSRD_FLAG_YAW_GRADIENTS a hot kernel that has the flag compiled in: quad_step.h, quad_phase_b.
+        //  The hot kernel runs only fields whose rotations are all about y, so the flag alone decides; -DVSRD_NO_YAW_KERNEL: the run-time test)
+#ifndef VSRD_NO_YAW_KERNEL
+        const bool yaw_only = (config->flags & VSRD_FLAG_YAW_GRADIENTS) != 0u;
+#else
+        const bool yaw_only = false;
+#endif
+        if (r.quad && r.full) for_bool(yaw_only, [&](auto y) {
+            launch(render_silhouette_quad_kernel<4, true, true, decltype(y)::value>, render_silhouette_quad_kernel<4, false, false>); });
+        else if (r.full) for_bool(yaw_only, [&](auto y) {
+            launch(render_silhouette_pair_kernel<4, true, true, decltype(y)::value>, render_silhouette_pair_kernel<4, false, false>); });
         else if (r.quad) known = for_rounds<1, 2, 4>(r.rounds, [&](auto k) {
             launch(render_silhouette_quad_kernel<decltype(k)::value, true, false>, render_silhouette_quad_kernel<decltype(k)::value, false, false>); });
         else known = for_rounds<2, 4>(r.rounds, [&](auto k) {

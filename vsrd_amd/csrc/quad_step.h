@@ -292,8 +292,17 @@ __device__ __forceinline__ int seg_count_below(const float* a, int n, float v) {
 
 // samplers.py:11-36 + renderers.py:198-210 for the lane's ray (render.h: importance_merge, per row): w[k] = coarse weight of point
 // k * 16 + col (0 beyond S - 2); on return merged[0..2S) is the sorted union of the coarse and the fine distances.
+// Merge ranks from the brackets (-DVSRD_NO_MERGE_BRACKETS: always the two searches).  Fine sample j was interpolated in the coarse bracket
+// [coarse[upper_j - 1], coarse[upper_j]].  Where the FINAL sample (after the running maximum) still lies in it, lower end included, upper
+// end excluded, the number of coarse distances <= it is upper_j itself; and where that holds for every fine sample of a ray, the number of
+// fine samples < coarse[i] is #{j : upper_j <= i} (upper_j <= i: sample_j < coarse[upper_j] <= coarse[i]; upper_j > i: sample_j >=
+// coarse[upper_j - 1] >= coarse[i]).  The brackets of such a ray do not decrease with j, so that count is j + 1 of the LAST sample of the
+// largest occupied bracket <= i: every sample that is the last of its bracket stores j + 1 at its bracket (one writer per slot) and a
+// running maximum over the slots fills the empty ones.  Integers throughout (held as floats below 2^24), so merged[] is what the searches
+// give, tie rule included (a coarse value before an equal fine one).  `votes`: the ray's merged row is used (a live ray); one ballot
+// decides for the wave, padding lanes and the other rays do not vote -- their ranks stay within the row whatever their brackets are.
 template <int kL, int kRoundsS>
-__device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, const float (&w)[kRoundsS], const RowLanes& rl) {
+__device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, const float (&w)[kRoundsS], const RowLanes& rl, bool votes) {
     float* coarse = rowbase;
     float* fine = rowbase + S;                    // holds the sorted uniforms on entry: lane j turns u[j] into fine[j] in place
     float* merged = rowbase + quad_merged_offset(S, kL);
@@ -314,8 +323,15 @@ __device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, con
     if (rl.col == 0) cdf[0] = 0.0f;
     wave_lds_sync();
     float fine_max = -3.0e38f;
+#ifndef VSRD_NO_MERGE_BRACKETS
+    int uppers[kRoundsS];
+    bool bracketed = true;
+#endif
 #pragma unroll
     for (int k = 0; k < kRoundsS; ++k) {
+#ifndef VSRD_NO_MERGE_BRACKETS
+        uppers[k] = 1;
+#endif
         if (k * kL >= S) continue;
         const int j = k * kL + rl.col;
         const bool valid = j < S;
@@ -329,10 +345,55 @@ __device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, con
         const float scan = seg_inclusive_max<kL>(valid ? sample : -3.0e38f);     // running maximum: see render.h
         sample = fmaxf(scan, fine_max);
         fine_max = fmaxf(fine_max, lane_gather(scan, rl.last));
+#ifndef VSRD_NO_MERGE_BRACKETS
+        uppers[k] = upper;                                                   // (in 1 .. S - 1 on every lane)
+        bracketed = bracketed && (!(valid && votes) || (b_lo <= sample && sample < b_hi));
+#endif
         wave_lds_sync();                                                     // (padding lanes read the last lane's uniform above)
         if (valid) fine[j] = sample;
     }
     wave_lds_sync();
+#ifndef VSRD_NO_MERGE_BRACKETS
+    if (__ballot(!bracketed) == 0ull) {                                      // wave-uniform
+        float* brackets = merged;                 // [S] upper_j        (the raw uniforms: dead)
+        float* last_of = cdf;                     // [S] j + 1 of the last sample of bracket b, 0: none   (the cdf: dead)
+#pragma unroll
+        for (int k = 0; k < kRoundsS; ++k) {
+            const int j = k * kL + rl.col;
+            if (k * kL < S && j < S) { brackets[j] = static_cast<float>(uppers[k]); last_of[j] = 0.0f; }
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int k = 0; k < kRoundsS; ++k) {
+            const int j = k * kL + rl.col;
+            if (k * kL < S && j < S) {
+                const float next = brackets[min(j + 1, S - 1)];
+                if (j == S - 1 || next != static_cast<float>(uppers[k])) last_of[uppers[k]] = static_cast<float>(j + 1);
+            }
+        }
+        wave_lds_sync();
+        int rank_a[kRoundsS], rank_b[kRoundsS];
+        float below = 0.0f;                       // fine samples in the brackets of the earlier rounds' slots
+#pragma unroll
+        for (int k = 0; k < kRoundsS; ++k) {
+            rank_a[k] = rank_b[k] = 0;
+            if (k * kL >= S) continue;
+            const int j = k * kL + rl.col;
+            const float scan = seg_inclusive_max<kL>(j < S ? last_of[j] : 0.0f);
+            rank_a[k] = j + static_cast<int>(fmaxf(scan, below));
+            rank_b[k] = j + uppers[k];
+            below = fmaxf(below, lane_gather(scan, rl.last));
+        }
+        wave_lds_sync();                          // (the slots read above lie where the merged distances go)
+#pragma unroll
+        for (int k = 0; k < kRoundsS; ++k) {
+            const int j = k * kL + rl.col;
+            if (k * kL < S && j < S) { merged[rank_a[k]] = coarse[j]; merged[rank_b[k]] = fine[j]; }
+        }
+        wave_lds_sync();
+        return;
+    }
+#endif
 #pragma unroll
     for (int k = 0; k < kRoundsS; ++k) {
         if (k * kL >= S) continue;
@@ -796,7 +857,10 @@ __device__ __forceinline__ unsigned quad_reverse_sweep(QuadAdjoint<kRounds>& st,
 // Per-instance phase for the four rays (render_kernels.h: adjoint_phase_b): instance-outer, rounds inner, one reduce-scatter butterfly
 // per (wave, instance).  G[s]: lane (row r, col c) accumulates parameter c of instance 4 s + r (four registers for N <= 16; float
 // atomics on the wave's row of the partial table instead cost 6.5 GB of L2 write-through per launch).
-template <int kL, int kRounds, bool kYaw>
+// kYawOnly (the hot full-shape step kernels of a launch with VSRD_FLAG_YAW_GRADIENTS, chosen by the host): what sh.yaw_gradients says at run
+// time is a property of the instantiation.  The five accumulators r01 r10 r11 r12 r21 are literal zeros then, in the loop and as inputs of
+// the reduce-scatter, instead of five registers held through the phase -- the same sums (the run-time test left them at zero as well).
+template <int kL, int kRounds, bool kYaw, bool kYawOnly = false>
 __device__ __forceinline__ void quad_phase_b(const QuadAdjoint<kRounds>& st, const float* __restrict__ instances, const Shading& sh, const float* rayp,
                                              unsigned flow, const float* coef_own, const float* cbuf, const float* mids, const float* c2buf, float (&G)[kL == kRowLanes ? 4 : 16], const RowLanes& rl) {
     const float inv_t = sh.inv_t;
@@ -856,7 +920,7 @@ __device__ __forceinline__ void quad_phase_b(const QuadAdjoint<kRounds>& st, con
             ad0 -= qbx; ad1 -= qby; ad2 -= qbz;
             r00 += e.relx * pbx + gwbx * e.glx; r02 += e.relx * pbz + gwbx * e.glz;
             r20 += e.relz * pbx + gwbz * e.glx; r22 += e.relz * pbz + gwbz * e.glz;
-            if (!(kYaw && sh.yaw_gradients)) {           // (wave-uniform) the entries rotation_matrix_y keeps constant: nobody reads their adjoints
+            if (!(kYaw && (kYawOnly || sh.yaw_gradients))) {           // (wave-uniform) the entries rotation_matrix_y keeps constant: nobody reads their adjoints
                 r01 += e.relx * pby + gwbx * e.gly;
                 r10 += e.rely * pbx + gwby * e.glx; r11 += e.rely * pby + gwby * e.gly; r12 += e.rely * pbz + gwby * e.glz;
                 r21 += e.relz * pby + gwbz * e.gly;
@@ -900,7 +964,7 @@ __device__ __forceinline__ void quad_phase_b(const QuadAdjoint<kRounds>& st, con
 // the running minimum; else the shift known before the instance loop, field.h); returns false -- before any side effect other than
 // LDS staging -- when the fixed shift cannot serve some round of the group: the caller then runs the group again with kRunning.
 // The three instantiations share no state, so none of it crosses a control-flow merge.
-template <int kL, int kRoundsS, bool kYaw, bool kRunning>
+template <int kL, int kRoundsS, bool kYaw, bool kRunning, bool kYawOnly = false>
 __device__ __forceinline__ bool quad_step_body(const float* __restrict__ instances, int N, int NP, const RenderArgs& c, const Shading& sh, int first_ray,
                                                const float* __restrict__ origins, const float* __restrict__ directions,
                                                const float* __restrict__ u_coarse, const float* __restrict__ u_fine, bool sorted_input,
@@ -956,7 +1020,7 @@ __device__ __forceinline__ bool quad_step_body(const float* __restrict__ instanc
     const float* merged = stage + data_row * quad_row_floats(S, kL) + quad_merged_offset(S, kL);
     float* trans_mid = rowbase;                                              // (the row's own: a shadow row's transmittances are all 1)
     if (live_lanes != 0ull) {
-        quad_importance_merge<kL, kRoundsS>(rowbase, S, w1, rl);
+        quad_importance_merge<kL, kRoundsS>(rowbase, S, w1, rl, live);
         if (c.out_distances != nullptr && live) {            // the sorted pass-2 distances of the row's own ray (the reverse sweep overwrites them later)
             float* dst = c.out_distances + static_cast<size_t>(my_ray) * (2 * S);
             const float* own = rowbase + quad_merged_offset(S, kL);
@@ -998,7 +1062,7 @@ __device__ __forceinline__ bool quad_step_body(const float* __restrict__ instanc
     const unsigned flow = quad_reverse_sweep<kL, kRounds, kYaw>(st, instances, sh, rayp, merged, num_points, live, active, lam_any, kRunning ? -1 : cached_round,
                                                             coef_own, dcache, trans_mid, rowbase + quad_merged_offset(S, kL), rl);
     VSRD_PHASE(4);
-    if (flow != 0u) quad_phase_b<kL, kRounds, kYaw>(st, instances, sh, rayp, flow, coef_own, dcache, trans_mid, rowbase + quad_merged_offset(S, kL), G, rl);
+    if (flow != 0u) quad_phase_b<kL, kRounds, kYaw, kYawOnly>(st, instances, sh, rayp, flow, coef_own, dcache, trans_mid, rowbase + quad_merged_offset(S, kL), G, rl);
     VSRD_PHASE(5);
     return true;
 }
@@ -1025,7 +1089,11 @@ __device__ __forceinline__ bool quad_step_body(const float* __restrict__ instanc
 // tables are padded to the shape's full count: every LDS offset, every loop bound of the culling pre-pass and the searches, the
 // stratification and the point counts fold into the code.  Measured on config 2: 190 -> 222 Mrays/s (S alone: 210) -- the kernel is
 // bound by VALU issue (profiles/r04), and a fifth of what it issued was address and bound arithmetic on two launch constants.
-template <int kL, int kRoundsS, bool kHot, bool kFull>
+//
+// kYawOnly (hot full-shape kernels only): the launch carries VSRD_FLAG_YAW_GRADIENTS -- the host picks this instantiation by the flag, and the
+// hot kernel runs only fields whose rotations are all about y, so sh.yaw_gradients is true wherever it is asked (quad_phase_b).  Every
+// other instantiation keeps the run-time test.  -DVSRD_NO_YAW_KERNEL (api.hip): never picked.
+template <int kL, int kRoundsS, bool kHot, bool kFull, bool kYawOnly = false>
 __device__ __forceinline__ void silhouette_rows_kernel_body(
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
     const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
@@ -1045,6 +1113,7 @@ __device__ __forceinline__ void silhouette_rows_kernel_body(
     const int wave = wave_in_block();
     const int lane0 = lane_id();
     static_assert(kHot || !kFull, "only the hot kernel is instantiated for a full shape");
+    static_assert(!kYawOnly || (kHot && kFull), "only the hot full-shape kernel is instantiated for VSRD_FLAG_YAW_GRADIENTS");
     if (kFull) c.num_samples = kL * kRoundsS;                                   // (the host launches kFull for exactly this S)
     // (these kernels take dense launches only -- no ray_indices, no target column map: vsrd_render_silhouette_step sends every other launch
     //  to the one-ray kernels -- so the three fields are compile-time nothing here)
@@ -1097,7 +1166,7 @@ __device__ __forceinline__ void silhouette_rows_kernel_body(
         const RowLanes rl = row_lanes<kL>(opaque_lane_id());
         wave_lds_sync();
         if (kHot) {
-            const bool done = quad_step_body<kL, kRoundsS, true, false>(instances, N, NP, c, sh, first_ray, origins, directions, u_coarse, u_fine, sorted_input, targets,
+            const bool done = quad_step_body<kL, kRoundsS, true, false, kYawOnly>(instances, N, NP, c, sh, first_ray, origins, directions, u_coarse, u_fine, sorted_input, targets,
                                                                         instance_weights, loss_scale, labels_out, stage, dcache, coefs, rays, G, loss_acc, rl VSRD_QUAD_CLOCK_ARG);
             if (lane0 == 0) {
                 redo_flags[group] = done ? 0 : 1;
@@ -1128,13 +1197,13 @@ __device__ __forceinline__ void silhouette_rows_kernel_body(
     if (lane0 == 0) loss_partials[wave_global] = add ? (loss_partials[wave_global] + loss_total * loss_scale) : (loss_total * loss_scale);
 }
 
-template <int kRoundsS, bool kHot, bool kFull>
+template <int kRoundsS, bool kHot, bool kFull, bool kYawOnly = false>
 __global__ __launch_bounds__(kBlockThreads, VSRD_QUAD_WAVES_PER_EU) void render_silhouette_quad_kernel(
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
     const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale,
     float* __restrict__ labels_out, float* __restrict__ partials, float* __restrict__ loss_partials, unsigned char* __restrict__ redo_flags) {
-    silhouette_rows_kernel_body<kRowLanes, kRoundsS, kHot, kFull>(f, instances, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels_out,
+    silhouette_rows_kernel_body<kRowLanes, kRoundsS, kHot, kFull, kYawOnly>(f, instances, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels_out,
                                                            partials, loss_partials, redo_flags);
 }
 
@@ -1187,7 +1256,7 @@ __device__ __forceinline__ bool rows_forward_body(const float* __restrict__ inst
         int cached_round = -1;
         QuadAdjoint<kRounds> st;
         const int data_row = live ? rl.row : (__builtin_ctzll(live_lanes) / kL);
-        quad_importance_merge<kL, kRoundsS>(rowbase, S, w1, rl);
+        quad_importance_merge<kL, kRoundsS>(rowbase, S, w1, rl, live);
         if (!quad_forward_sweep<kL, kRounds, kYaw, kRunning>(st, instances, NP, sh, rays + data_row * kRowRayFloats, coefs + data_row * quad_coef_floats(NP),
                                                               stage + data_row * quad_row_floats(S, kL) + quad_merged_offset(S, kL), num_points, live, dcache,
                                                               rowbase, label, active, cached_round, rl, real)) return false;
@@ -1467,13 +1536,13 @@ __global__ __launch_bounds__(kBlockThreads, 3) void render_backward_pair_kernel(
 #ifndef VSRD_PAIR_WAVES_PER_EU
 #define VSRD_PAIR_WAVES_PER_EU 3
 #endif
-template <int kRoundsS, bool kHot, bool kFull>
+template <int kRoundsS, bool kHot, bool kFull, bool kYawOnly = false>
 __global__ __launch_bounds__(kBlockThreads, VSRD_PAIR_WAVES_PER_EU) void render_silhouette_pair_kernel(
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
     const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale,
     float* __restrict__ labels_out, float* __restrict__ partials, float* __restrict__ loss_partials, unsigned char* __restrict__ redo_flags) {
-    silhouette_rows_kernel_body<32, kRoundsS, kHot, kFull>(f, instances, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels_out,
+    silhouette_rows_kernel_body<32, kRoundsS, kHot, kFull, kYawOnly>(f, instances, c, origins, directions, u_coarse, u_fine, targets, instance_weights, loss_scale, labels_out,
                                                     partials, loss_partials, redo_flags);
 }
 
