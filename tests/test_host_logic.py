@@ -436,6 +436,23 @@ def test_product_never_imports_the_oracle():
                 assert "/root/reference" not in text
 
 
+def test_build_switches_are_the_ones_in_the_design_table():
+    """Every VSRD_* name a preprocessor conditional of csrc/ tests has its line in DESIGN.md's "Build switches" table, and the table has
+    no line for a switch that is gone."""
+    tested = set()
+    csrc = os.path.join(ROOT, "vsrd_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        for line in open(os.path.join(csrc, name)):
+            directive = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b([^/]*)", line)
+            if directive:
+                tested.update(re.findall(r"\bVSRD_\w+", directive.group(1)))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.search(r"^## [^\n]*Build switches\n(.*?)^## ", design, flags=re.M | re.S).group(1)
+    listed = re.findall(r"^\| `(VSRD_\w+)` \|", section, flags=re.M)
+    assert len(listed) == len(set(listed))
+    assert tested and tested == set(listed)
+
+
 def test_formats_match_reference_writers():
     """N4: KITTI label lines byte-for-byte against the reference's convert_predictions.save_prediction (golden g12), the
     prediction JSON layout, the checkpoint's detector state-dict layout and the multi-view confidence voting."""

@@ -897,9 +897,6 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
     Geometry g;
     if (!plan(r.rows ? static_cast<int>(r.num_groups) : config->num_rays, r.rows ? r.lds_floats : static_cast<size_t>(wave_lds_floats(S, N)) + N + row, &g))
         return VSRD_E_UNSUPPORTED;
-#ifdef VSRD_INSTANCE_LDS
-    if (r.quad && r.full) g.lds_bytes += static_cast<size_t>(N) * kInstanceStride * sizeof(float);      // experiment: the instance block next to the waves' partitions
-#endif
     // one gradient row and one loss partial per wave, and behind them (multi-ray mappings) the groups' flags
     if (!cap_to_workspace(vsrd_workspace_bytes(N, 0), row + 1, r.flag_bytes, &g)) return VSRD_E_WORKSPACE;
     const FieldArgs f = field_args(field);
@@ -920,12 +917,8 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
                                  loss_partials, redo_flags);
         };
         // (... and of those the launches with VSRD_FLAG_YAW_GRADIENTS a hot kernel that has the flag compiled in: quad_step.h, quad_phase_b.
-        //  The hot kernel runs only fields whose rotations are all about y, so the flag alone decides; -DVSRD_NO_YAW_KERNEL: the run-time test)
-#ifndef VSRD_NO_YAW_KERNEL
+        //  The hot kernel runs only fields whose rotations are all about y, so the flag alone decides)
         const bool yaw_only = (config->flags & VSRD_FLAG_YAW_GRADIENTS) != 0u;
-#else
-        const bool yaw_only = false;
-#endif
         if (r.quad && r.full) for_bool(yaw_only, [&](auto y) {
             launch(render_silhouette_quad_kernel<4, true, true, decltype(y)::value>, render_silhouette_quad_kernel<4, false, false>); });
         else if (r.full) for_bool(yaw_only, [&](auto y) {

@@ -33,28 +33,6 @@ __device__ __forceinline__ Instance load_instance(const float* __restrict__ inst
     return v;
 }
 
-// A/B experiment (-DVSRD_INSTANCE_VGPR, box-only loops): the parameters as VGPRs (vector loads of one address) instead of SGPR
-// operands -- a VALU instruction with an SGPR operand issues in 4.3 cycles, the same one on VGPRs in 2.5 (tools/micro/pk_rate.hip).
-template <bool kVector>
-__device__ __forceinline__ Instance load_instance_as(const float* __restrict__ instances, int i) {
-#ifdef VSRD_INSTANCE_VGPR
-    if (kVector) {
-        int zero;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-        const float4* p = reinterpret_cast<const float4*>(instances + i * kInstanceStride + zero);
-        const float4 a = p[0], b = p[1], c = p[2], d = p[3];
-        Instance v;
-        v.tx = a.x; v.ty = a.y; v.tz = a.z;
-        v.r00 = a.w; v.r01 = b.x; v.r02 = b.y;
-        v.r10 = b.z; v.r11 = b.w; v.r12 = c.x;
-        v.r20 = c.y; v.r21 = c.z; v.r22 = c.w;
-        v.dx = d.x; v.dy = d.y; v.dz = d.z;
-        return v;
-    }
-#endif
-    return load_instance(instances, i);
-}
-
 // Everything phase B of the backward needs about one (sample, instance) pair.
 struct BoxEval {
     float relx, rely, relz;   // x - t
@@ -96,19 +74,11 @@ __device__ __forceinline__ BoxEval box_value(const Instance& in, float x, float 
     const float ax = fmaxf(e.qx, 0.0f), ay = fmaxf(e.qy, 0.0f), az = fmaxf(e.qz, 0.0f);
     // |v| = s rsq(s) and 1 / |v| = rsq(s): ONE transcendental per evaluation instead of v_sqrt + v_rcp (a quarter-rate instruction costs
     // three multiply-adds).  Both forms are within 1.5 ulp of the exact norm; round 4: config 2 229 -> 234 Mrays/s, config 5 30.1 -> 30.7.
-    // -DVSRD_BOX_SQRT_RCP: the form of rounds 1-3.
-#ifndef VSRD_BOX_SQRT_RCP
     const float squares = ax * ax + ay * ay + az * az + kNormEpsilon;
     e.inv = fast_rsq(squares);
     e.nrm = squares * e.inv;
-#ifndef VSRD_NO_NORM_PIN
     asm volatile("" : "+v"(e.nrm));      // (a rounded product in EVERY instantiation: without this some of them fuse it into the subtraction below,
                                          //  and kernels that differ in the last bit of a distance differ by 1e-4 in summed gradients -- see above)
-#endif
-#else
-    e.nrm = fast_sqrt(ax * ax + ay * ay + az * az + kNormEpsilon);
-    e.inv = fast_rcp(e.nrm);
-#endif
     e.qmax = fmaxf(fmaxf(e.qx, e.qy), e.qz);                            // one v_max3_f32
     e.d = e.nrm - fmaxf(-e.qmax, 0.0f);
     return e;

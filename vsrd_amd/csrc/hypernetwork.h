@@ -29,18 +29,11 @@ struct HyperAdam { float beta1, beta2, epsilon; };
 // The erf-form GELU (torch's default, hyper_distance_field.py:30-55) and its derivative through residual.h's normal cdf / pdf pair: erf
 // by Abramowitz & Stegun 7.1.26, an APPROXIMATION with |error| <= 1.5e-7 on erf -- one f32 ulp of a cdf near 1, ~17 instructions, but a
 // large RELATIVE error of the cdf in the far negative tail (a < -5, where a * cdf(a) < 2e-6 anyway).  Absolute error of the GELU and of
-// its derivative over [-8, 8]: < 4e-7 (tests/test_hip_step.py::test_hypernetwork_gelu_error_bound); -DVSRD_LIBM_ERF builds libm's erff
-// for parity runs.  libm's erff is ~300 instructions with divergent branches, and the part between two
-// linears is ONE wave's work while fifteen wait: 4 erff per lane were 4.5 of the 8 us per layer (tools/hyper_timers.py).
-#ifdef VSRD_LIBM_ERF
-__device__ __forceinline__ float erf_gelu(float a) { return 0.5f * a * (1.0f + erff(a * 0.70710678118654752f)); }
-__device__ __forceinline__ float erf_gelu_derivative(float a) {
-    return 0.5f * (1.0f + erff(a * 0.70710678118654752f)) + a * 0.39894228040143268f * expf(-0.5f * a * a);
-}
-#else
+// its derivative over [-8, 8]: < 4e-7 (tests/test_hip_step.py::test_hypernetwork_gelu_error_bound).  libm's erff is ~300
+// instructions with divergent branches, and the part between two linears is ONE wave's work while fifteen wait: 4 erff per lane were 4.5
+// of the 8 us per layer (tools/hyper_timers.py).
 __device__ __forceinline__ float erf_gelu(float a) { return a * gauss(a).cdf; }
 __device__ __forceinline__ float erf_gelu_derivative(float a) { const Gauss n = gauss(a); return n.cdf + a * n.pdf; }
-#endif
 
 __global__ void gelu_selftest_kernel(const float* __restrict__ x, int n, float* __restrict__ out) {
     const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);

@@ -79,27 +79,13 @@ __device__ __forceinline__ float seg_inclusive_sum(float v) {          // prefix
 }
 template <int kL>
 __device__ __forceinline__ float seg_inclusive_product(float v) {
-#ifndef VSRD_NO_DPP_INPLACE
     v = mul_shr8(mul_shr4(mul_shr2(mul_shr1(v))));
-#else
-    v *= dpp_move<kDppRowShr1>(1.0f, v);
-    v *= dpp_move<kDppRowShr2>(1.0f, v);
-    v *= dpp_move<kDppRowShr4>(1.0f, v);
-    v *= dpp_move<kDppRowShr8>(1.0f, v);
-#endif
     if (kL == 32) v *= dpp_move<kDppRowBcast15, 0xa>(1.0f, v);
     return v;
 }
 template <int kL>
 __device__ __forceinline__ float seg_inclusive_max(float v) {
-#ifndef VSRD_NO_DPP_INPLACE
     v = max_shr8(max_shr4(max_shr2(max_shr1(v))));
-#else
-    v = fmaxf(v, dpp_move<kDppRowShr1>(v, v));
-    v = fmaxf(v, dpp_move<kDppRowShr2>(v, v));
-    v = fmaxf(v, dpp_move<kDppRowShr4>(v, v));
-    v = fmaxf(v, dpp_move<kDppRowShr8>(v, v));
-#endif
     if (kL == 32) v = fmaxf(v, dpp_move<kDppRowBcast15, 0xa>(v, v));
     return v;
 }
@@ -132,25 +118,6 @@ __device__ __forceinline__ int opaque_lane_id() {
     return lane;
 }
 
-// Experiment (-DVSRD_INSTANCE_LDS): the hot full-shape kernel stages the instance block in the workgroup's LDS and the instance loops read
-// it with four ds_read_b128 of one address (a broadcast): the parameters are VGPR operands then -- an FMA with an SGPR operand issues in
-// 4.4 cycles, on VGPRs in 2.8 (profiles/r01/op_rates.txt), and the instance loops have ~14 of them per (sample, instance).
-__device__ __forceinline__ Instance load_instance_block(const float* __restrict__ instances, int i) {
-#ifdef VSRD_INSTANCE_LDS
-    const float4* p = reinterpret_cast<const float4*>(instances + i * kInstanceStride);
-    const float4 a = p[0], b = p[1], c = p[2], d = p[3];
-    Instance v;
-    v.tx = a.x; v.ty = a.y; v.tz = a.z;
-    v.r00 = a.w; v.r01 = b.x; v.r02 = b.y;
-    v.r10 = b.z; v.r11 = b.w; v.r12 = c.x;
-    v.r20 = c.y; v.r21 = c.z; v.r22 = c.w;
-    v.dx = d.x; v.dy = d.y; v.dz = d.z;
-    return v;
-#else
-    return load_instance(instances, i);
-#endif
-}
-
 // ---- per-wave LDS ------------------------------------------------------------------------------------------------------------------
 //   4 x [ coarse S | fine S (first the sorted uniforms) | 16 pad | merged 2S (first: raw uniforms | cdf) | 16 + 4 pad ]   the first pad takes
 //       the tail of the per-point array below when 2S - 1 points are padded to whole rounds of 16, the second the tail of C2
@@ -170,19 +137,14 @@ __host__ __device__ constexpr int quad_coef_floats(int num_instances) { return k
 __host__ __device__ constexpr int quad_rounds_s(int num_samples, int lanes = kRowLanes) {          // rounds of `lanes` coarse points: 1, 2 or 4
     return num_samples <= lanes ? 1 : (num_samples <= 2 * lanes ? 2 : 4);
 }
-#ifndef VSRD_CACHE_SLOTS
-#define VSRD_CACHE_SLOTS 22       // (what three workgroups per CU leave room for at S = 128, N = 64: 52 160 of 54 613 bytes)
-#endif
-static_assert(VSRD_CACHE_SLOTS >= 16 && VSRD_CACHE_SLOTS <= 32, "quad_label_sums gathers a survivor's rank within the 32 lanes of a ray, and the rows are reused as the [16][64] C1 / C3 area");
-constexpr int kCacheSlots = VSRD_CACHE_SLOTS;   // (>= 16: the rows also hold C1 / C3 of the eight pass-2 rounds) shapes with more instances than lanes per ray: soft-min terms of the first 16 survivors of a round
+// Shapes with more instances than lanes per ray: soft-min terms of the first kCacheSlots survivors of a round (22: what three workgroups
+// per CU leave room for at S = 128, N = 64: 52 160 of 54 613 bytes; >= 16: the rows also hold C1 / C3 of the eight pass-2 rounds)
+constexpr int kCacheSlots = 22;
+static_assert(kCacheSlots >= 16 && kCacheSlots <= 32, "quad_label_sums gathers a survivor's rank within the 32 lanes of a ray, and the rows are reused as the [16][64] C1 / C3 area");
 // Two rays per wave: the terms of survivor k of a round start at float k * kSlotStride (64 lanes + 4: rows stay 16-byte aligned and
 // sixteen lanes reading sixteen DIFFERENT rows with ds_read_b128 touch every bank once -- quad_label_sums), and one more row holds the
 // lanes' label scales.  The same floats hold C1 / C3 of the eight pass-2 rounds afterwards ([16][64]).
-#ifndef VSRD_LABEL_LOOP
 constexpr int kSlotStride = kWave + 4;
-#else
-constexpr int kSlotStride = kWave;
-#endif
 __host__ __device__ constexpr int quad_cache_floats(int num_samples, int num_instances, int lanes = kRowLanes) {   // soft-min terms of a round, later C1 / C3 of every pass-2 round ([rows][64])
     return lanes == kRowLanes ? (num_instances > 4 * quad_rounds_s(num_samples, lanes) ? num_instances : 4 * quad_rounds_s(num_samples, lanes)) * kWave
                               : (kCacheSlots + 1) * kSlotStride;
@@ -292,7 +254,7 @@ __device__ __forceinline__ int seg_count_below(const float* a, int n, float v) {
 
 // samplers.py:11-36 + renderers.py:198-210 for the lane's ray (render.h: importance_merge, per row): w[k] = coarse weight of point
 // k * 16 + col (0 beyond S - 2); on return merged[0..2S) is the sorted union of the coarse and the fine distances.
-// Merge ranks from the brackets (-DVSRD_NO_MERGE_BRACKETS: always the two searches).  Fine sample j was interpolated in the coarse bracket
+// Merge ranks from the brackets.  Fine sample j was interpolated in the coarse bracket
 // [coarse[upper_j - 1], coarse[upper_j]].  Where the FINAL sample (after the running maximum) still lies in it, lower end included, upper
 // end excluded, the number of coarse distances <= it is upper_j itself; and where that holds for every fine sample of a ray, the number of
 // fine samples < coarse[i] is #{j : upper_j <= i} (upper_j <= i: sample_j < coarse[upper_j] <= coarse[i]; upper_j > i: sample_j >=
@@ -323,15 +285,11 @@ __device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, con
     if (rl.col == 0) cdf[0] = 0.0f;
     wave_lds_sync();
     float fine_max = -3.0e38f;
-#ifndef VSRD_NO_MERGE_BRACKETS
     int uppers[kRoundsS];
     bool bracketed = true;
-#endif
 #pragma unroll
     for (int k = 0; k < kRoundsS; ++k) {
-#ifndef VSRD_NO_MERGE_BRACKETS
         uppers[k] = 1;
-#endif
         if (k * kL >= S) continue;
         const int j = k * kL + rl.col;
         const bool valid = j < S;
@@ -345,15 +303,12 @@ __device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, con
         const float scan = seg_inclusive_max<kL>(valid ? sample : -3.0e38f);     // running maximum: see render.h
         sample = fmaxf(scan, fine_max);
         fine_max = fmaxf(fine_max, lane_gather(scan, rl.last));
-#ifndef VSRD_NO_MERGE_BRACKETS
         uppers[k] = upper;                                                   // (in 1 .. S - 1 on every lane)
         bracketed = bracketed && (!(valid && votes) || (b_lo <= sample && sample < b_hi));
-#endif
         wave_lds_sync();                                                     // (padding lanes read the last lane's uniform above)
         if (valid) fine[j] = sample;
     }
     wave_lds_sync();
-#ifndef VSRD_NO_MERGE_BRACKETS
     if (__ballot(!bracketed) == 0ull) {                                      // wave-uniform
         float* brackets = merged;                 // [S] upper_j        (the raw uniforms: dead)
         float* last_of = cdf;                     // [S] j + 1 of the last sample of bracket b, 0: none   (the cdf: dead)
@@ -393,7 +348,6 @@ __device__ __forceinline__ void quad_importance_merge(float* rowbase, int S, con
         wave_lds_sync();
         return;
     }
-#endif
 #pragma unroll
     for (int k = 0; k < kRoundsS; ++k) {
         if (k * kL >= S) continue;
@@ -455,20 +409,11 @@ __device__ __forceinline__ void quad_ray_setup(const float* __restrict__ instanc
 }
 
 // The culling pre-pass of one round (field.h: cull_round_mask) in two steps, so that a round can leave between them.
-// -DVSRD_CULL_PARTIAL (round 4, NOT the default): the term of the squared centre distance that all instances share leaves the
-// per-instance work,  |x(t) - t_i|^2 = (a_i + b_i t) + (r.r) t^2 = e_i + c:  min_i e_i + c for the nearest centre and
-// e_i > reach_i^2 + (E - c)  for the test, one instruction less per (sample, instance) in either loop.  +1 % on config 2 -- but with it
-// the culling A/B of the two-rays-per-wave kernels (tests/test_hip_scale.py: pair-mid) shows rays whose labels are off by up to 6.7e-3
-// (nested form: 2.2e-4, the sampler's own conditioning), although a float32 emulation of both bound tests over every (group, round,
-// instance) of that view (tests/culling_formulations_debug.py) finds their masks equal but for 6 of 1.4e8 triples and neither ever
-// dropping an instance that matters, and the bounds of the nearest distance intact.  Not understood, so not used.
+// (Round 4 tried the bound test on partial sums e_i = a_i + b_i t, with the shared term (r.r) t^2 outside the per-instance work: +1 % on
+//  config 2, labels off by up to 6.7e-3 in the two-rays-per-wave kernels, not understood, so not used -- DESIGN.md.)
 // Step 1: the bounds of the nearest centre distance of every lane's point (RoundCull).
-__device__ __forceinline__ float centre_partial(const RayCull& rc, int i, float t) {       // e_i = a_i + b_i t
-#ifndef VSRD_CULL_PARTIAL                            // the nested form: d2_i = a_i + t (b_i + c t) itself
+__device__ __forceinline__ float centre_partial(const RayCull& rc, int i, float t) {       // d2_i = a_i + t (b_i + c t)
     return fmaf(t, rc.c2 * t + rc.coef[kCullCoefs * i + 1], rc.coef[kCullCoefs * i + 0]);
-#else
-    return fmaf(t, rc.coef[kCullCoefs * i + 1], rc.coef[kCullCoefs * i + 0]);
-#endif
 }
 __device__ __forceinline__ RoundCull quad_round_bounds(const RayCull& rc, int num_instances, float t, float margin, float inner = 0.0f) {
     float nearest = 3.0e38f;
@@ -479,23 +424,14 @@ __device__ __forceinline__ RoundCull quad_round_bounds(const RayCull& rc, int nu
         for (int j = 0; j < 4; ++j) nearest = fminf(nearest, centre_partial(rc, i + j, t));
     }
     for (; i < num_instances; ++i) nearest = fminf(nearest, centre_partial(rc, i, t));
-#ifndef VSRD_CULL_PARTIAL
     return cull_round(rc, t, nearest, margin, inner);
-#else
-    return cull_round(rc, t, fmaf(rc.c2 * t, t, nearest), margin, inner);
-#endif
 }
 // Step 2: bit i = instance i may matter on some lane (wave-uniform).  (NaN-safe: an undecidable comparison keeps the instance.)
 __device__ __forceinline__ unsigned long long quad_round_mask(const RayCull& rc, const RoundCull& cull, int num_instances, float t,
                                                               unsigned long long real = ~0ull, float widest = -1.0f) {
-#ifndef VSRD_CULL_PARTIAL
     const float shift = cull.err;
-#else
-    const float shift = cull.err - rc.c2 * t * t;                                       // E - c
-#endif
     unsigned long long mask = 0ull;
     int i = 0;
-#ifndef VSRD_CULL_PER_INSTANCE_RADIUS
     // Round 4: one threshold per lane from the WIDEST instance's bounding radius (field_bounds: max |dim|) instead of one per (lane,
     // instance): two instructions and an LDS read less per pair, a margin looser by at most max|dim| - min|dim| (1.1 m between the
     // reference's smallest and largest box against 18 T + the nearest distance) -- conservative, so nothing the tests see changes (the
@@ -518,7 +454,6 @@ __device__ __forceinline__ unsigned long long quad_round_mask(const RayCull& rc,
         for (; i < num_instances; ++i) mask |= (__ballot(!(centre_partial(rc, i, t) > threshold)) != 0ull) ? (1ull << i) : 0ull;
         return mask & real;
     }
-#endif
 #pragma unroll 4
     for (; i + 4 <= num_instances; i += 4) {
         float e[4], radius[4];
@@ -571,7 +506,7 @@ __device__ __forceinline__ UnionSums quad_union_loop(const float* __restrict__ i
     //  the copies are nearly free and the longer scalar chain between the test and the branch is not)
     for (unsigned long long todo = evaluated; todo != 0ull; todo &= todo - 1ull) {
         const int i = __builtin_ctzll(todo);
-        const Instance in = load_instance_block(instances, i);
+        const Instance in = load_instance(instances, i);
         BoxEval e = box_value<kYaw>(in, x, y, z);
         const unsigned long long near = __ballot(!(e.d - best > sh.cull));
         if (near == 0ull) { evaluated &= ~(1ull << i); continue; }
@@ -595,7 +530,7 @@ __device__ __forceinline__ float quad_cached_term(const float* __restrict__ inst
                                                   float m, float inv_t) {
     if (!kBySlot) return dcache[i * kWave + lane];
     if (slot < kCacheSlots) return dcache[slot * kSlotStride + lane];
-    const float d = box_value<kYaw>(load_instance_block(instances, i), x, y, z).d;
+    const float d = box_value<kYaw>(load_instance(instances, i), x, y, z).d;
     return kRunning ? d : fast_exp(-(d - m) * inv_t);
 }
 
@@ -657,10 +592,6 @@ __device__ __forceinline__ bool quad_pass_one(const float* __restrict__ instance
         const RoundCull cull = quad_round_bounds(rc, N, p.mid, sh.cull, sh.inner);
         if (quad_round_is_empty(rc, cull, sh, p.delta)) continue;                // alpha = 0 exactly: the transmittance passes unchanged
         unsigned long long evaluated = quad_round_mask(rc, cull, N, p.mid, real, sh.reach >= 0.0f ? sh.reach * (1.0f / (1.0f - kCullSlack)) : -1.0f);
-#ifdef VSRD_BOUND_FINER_CULLING         // (see quad_forward_sweep)
-        for (int drop = 0; drop < VSRD_BOUND_FINER_CULLING; ++drop)
-            if (__builtin_popcountll(evaluated) >= 5) evaluated &= ~(1ull << (63 - __builtin_clzll(evaluated)));
-#endif
         const float floor = cull.nearest_lo - sh.reach;
         if (!kRunning && wave_any(!((cull.nearest_hi + 1.0f - floor) * sh.inv_t <= kUnionFloorSpan))) return false;
         const UnionSums sums = quad_union_loop<false, false, kRunning, kYaw>(instances, evaluated, sh, cull, floor, p.x, p.y, p.z, nullptr, rl.lane);
@@ -725,11 +656,6 @@ __device__ __forceinline__ bool quad_forward_sweep(QuadAdjoint<kRounds>& st, con
             const RoundCull cull = quad_round_bounds(rc, N, p.mid, sh.cull, sh.inner);
             if (quad_round_is_empty(rc, cull, sh, p.delta)) continue;            // alpha = 0 exactly: no weight, no label, no adjoint
             st.near[q] = quad_round_mask(rc, cull, N, p.mid, real, sh.reach >= 0.0f ? sh.reach * (1.0f / (1.0f - kCullSlack)) : -1.0f);
-#ifdef VSRD_BOUND_FINER_CULLING         // TIMING BOUND ONLY (profiles/r06/variants.txt; wrong results): what a mapping with a finer culling granularity could
-            // buy at no cost of its own -- every pass-2 round with five or more candidate instances loses VSRD_BOUND_FINER_CULLING of them
-            for (int drop = 0; drop < VSRD_BOUND_FINER_CULLING; ++drop)
-                if (__builtin_popcountll(st.near[q]) >= 5) st.near[q] &= ~(1ull << (63 - __builtin_clzll(st.near[q])));
-#endif
             const float floor = cull.nearest_lo - sh.reach;
             if (!kRunning && wave_any(!((cull.nearest_hi + 1.0f - floor) * sh.inv_t <= kUnionFloorSpan))) return false;
             const UnionSums sums = quad_union_loop<true, (kL > kRowLanes), kRunning, kYaw>(instances, st.near[q], sh, cull, floor, p.x, p.y, p.z, dcache, rl.lane);
@@ -759,13 +685,11 @@ __device__ __forceinline__ bool quad_forward_sweep(QuadAdjoint<kRounds>& st, con
         const float scale = t * alpha * v.inv_z;
         int slot = 0;
         unsigned long long todo = st.near[q];
-#ifndef VSRD_LABEL_LOOP
         if constexpr (kL > kRowLanes && !kRunning) {                               // the cached survivors at once; the loop below: the others
             quad_label_sums(dcache, scale, st.near[q], label, rl);
             if (__builtin_popcountll(todo) <= kCacheSlots) todo = 0ull;
             for (; slot < kCacheSlots && todo != 0ull; ++slot) todo &= todo - 1ull;
         }
-#endif
         for (; todo != 0ull; todo &= todo - 1ull, ++slot) {
             const int i = __builtin_ctzll(todo);
             const float cached = quad_cached_term<(kL > kRowLanes), kRunning, kYaw>(instances, i, slot, dcache, rl.lane, px, py, pz, v.m, sh.inv_t);
@@ -797,11 +721,7 @@ __device__ __forceinline__ unsigned quad_reverse_sweep(QuadAdjoint<kRounds>& st,
         const QuadPoint p = quad_point<kL>(merged, num_points, q, rr.ray, live, rl);
         // Lambda_s / Z_s = sum_n lambda_n w_{s,n} over the instances the forward sweep evaluated (culled ones: weight < exp(-18))
         float acc = 0.0f;
-#ifdef VSRD_BOUND_CACHED_LABEL_MIX      // TIMING BOUND ONLY (profiles/r06/variants.txt; wrong results): every round's label mix at the price of the cached round's
-        if (cached_round >= 0) {
-#else
         if (q == cached_round) {                                                   // wave-uniform: the soft-min terms are still in the distance cache
-#endif
             int slot = 0;
             for (unsigned long long todo = st.near[q]; todo != 0ull; todo &= todo - 1ull, ++slot) {
                 const int i = __builtin_ctzll(todo);
@@ -811,7 +731,7 @@ __device__ __forceinline__ unsigned quad_reverse_sweep(QuadAdjoint<kRounds>& st,
         } else {
             for (unsigned long long todo = st.near[q] & lam_any; todo != 0ull; todo &= todo - 1ull) {
                 const int i = __builtin_ctzll(todo);
-                const Instance in = load_instance_block(instances, i);
+                const Instance in = load_instance(instances, i);
                 acc += coef_own[kCullCoefs * i + 3] * fast_exp(-(box_value<kYaw>(in, p.x, p.y, p.z).d - st.m[q]) * sh.inv_t);
             }
         }
@@ -870,7 +790,7 @@ __device__ __forceinline__ void quad_phase_b(const QuadAdjoint<kRounds>& st, con
     for (int q = 0; q < kRounds; ++q) todo |= ((flow >> q) & 1u) ? st.near[q] : 0ull;
     for (; todo != 0ull; todo &= todo - 1ull) {
         const int i = __builtin_ctzll(todo);
-        const Instance in = load_instance_block(instances, i);
+        const Instance in = load_instance(instances, i);
         const float lam_i = coef_own[kCullCoefs * i + 3];
         float at0 = 0, at1 = 0, at2 = 0, ad0 = 0, ad1 = 0, ad2 = 0;
         float r00 = 0, r01 = 0, r02 = 0, r10 = 0, r11 = 0, r12 = 0, r20 = 0, r21 = 0, r22 = 0;
@@ -879,14 +799,7 @@ __device__ __forceinline__ void quad_phase_b(const QuadAdjoint<kRounds>& st, con
             if (!(((st.near[q] >> i) & 1ull) && ((flow >> q) & 1u))) continue;       // wave-uniform
             const float mid = mids[q * kL + rl.col];
             const float c1 = cbuf[(2 * q) * kWave + rl.lane], c3 = cbuf[(2 * q + 1) * kWave + rl.lane], c2 = c2buf[q * kL + rl.col + 1];
-#ifndef VSRD_BOUND_FREE_SELECTORS
             const BoxEval e = eval_box<kYaw>(in, ray.ox + ray.rx * mid, ray.oy + ray.ry * mid, ray.oz + ray.rz * mid);
-#else       // TIMING BOUND ONLY (profiles/r06/variants.txt; results are wrong inside boxes): the per-instance phase as if the seven selectors of a
-            // (sample, instance) pair -- inside, first-x, first-y, three p != 0, three q > 0 -- cost nothing at all
-            BoxEval e = box_value<kYaw>(in, ray.ox + ray.rx * mid, ray.oy + ray.ry * mid, ray.oz + ray.rz * mid);
-            e.hx = fmaxf(e.qx, 0.0f) * e.inv; e.hy = fmaxf(e.qy, 0.0f) * e.inv; e.hz = fmaxf(e.qz, 0.0f) * e.inv;
-            e.glx = __builtin_copysignf(e.hx, e.px); e.gly = __builtin_copysignf(e.hy, e.py); e.glz = __builtin_copysignf(e.hz, e.pz);
-#endif
             const float ds = e.d - st.m[q];
             const float w = fast_exp(-ds * inv_t) * st.inv_z[q];
             const float cc = w * (st.s[q] - ds * inv_t);
@@ -898,24 +811,14 @@ __device__ __forceinline__ void quad_phase_b(const QuadAdjoint<kRounds>& st, con
             const float d_bar = cc * (c1 - tb) + w * (c2 - tb - c3 * lam_i);
             const float gwbx = cc * gx_, gwby = cc * gy_, gwbz = cc * gz_;
             const float glbx = cc * rgx, glby = cc * rgy, glbz = cc * rgz;
-#ifndef VSRD_BOUND_FREE_SELECTORS
             const float sx = sign_of(e.px), sy = sign_of(e.py), sz = sign_of(e.pz);
-#else
-            const float sx = __builtin_copysignf(1.0f, e.px), sy = __builtin_copysignf(1.0f, e.py), sz = __builtin_copysignf(1.0f, e.pz);
-#endif
             const float vx = sx * glbx, vy = sy * glby, vz = sz * glbz;
             const float inv_n = box_inverse_norm(e);
             const float hx = fmaxf(e.qx, 0.0f) * inv_n, hy = fmaxf(e.qy, 0.0f) * inv_n, hz = fmaxf(e.qz, 0.0f) * inv_n;
             const float hv = hx * vx + hy * vy + hz * vz;
-#ifndef VSRD_BOUND_FREE_SELECTORS
             const float qbx = d_bar * e.hx + ((e.qx > 0.0f) ? (vx - hx * hv) * inv_n : 0.0f);
             const float qby = d_bar * e.hy + ((e.qy > 0.0f) ? (vy - hy * hv) * inv_n : 0.0f);
             const float qbz = d_bar * e.hz + ((e.qz > 0.0f) ? (vz - hz * hv) * inv_n : 0.0f);
-#else
-            const float qbx = d_bar * e.hx + (vx - hx * hv) * inv_n;
-            const float qby = d_bar * e.hy + (vy - hy * hv) * inv_n;
-            const float qbz = d_bar * e.hz + (vz - hz * hv) * inv_n;
-#endif
             const float pbx = sx * qbx, pby = sy * qby, pbz = sz * qbz;
             ad0 -= qbx; ad1 -= qby; ad2 -= qbz;
             r00 += e.relx * pbx + gwbx * e.glx; r02 += e.relx * pbz + gwbx * e.glz;
@@ -1067,9 +970,24 @@ __device__ __forceinline__ bool quad_step_body(const float* __restrict__ instanc
     return true;
 }
 
-#ifndef VSRD_QUAD_WAVES_PER_EU
-#define VSRD_QUAD_WAVES_PER_EU 4
+// What the three rows-kernel bodies below start with: the launch's Shading with the field's culling bounds (sh.yaw_gradients: set by the
+// bodies that read it).
+__device__ __forceinline__ Shading quad_shading(const FieldArgs& f, const float* instances, const RenderArgs& c) {
+    Shading sh = c.sh;
+    const FieldBounds bounds = field_bounds(instances, f.num_instances, f.inv_t, false, c.flags);
+    sh.cull = bounds.margin; sh.reach = bounds.reach; sh.yaw = bounds.yaw;
+#ifdef VSRD_CULL_INNER           // (opt-in, round 6: the culling bounds from the boxes' inscribed ball, field.h: cull_round; +3 %, docs/OPTLOG.md round 6 item 7b)
+    sh.inner = bounds.inner;
+#else
+    sh.inner = 0.0f;
 #endif
+    sh.mlp_bits = 0u;
+    sh.mlp_lds = nullptr;
+    return sh;
+}
+// Does the hot kernel of a two-kernel launch run?  (wave-uniform, the same in both kernels of the launch)
+__device__ __forceinline__ bool quad_hot_runs(const Shading& sh) { return sh.reach >= 0.0f && sh.yaw; }
+
 // kL = lanes per ray: 16 (four rays per wave; N <= 16, S <= 64: BASELINE config 2) or 32 (two rays per wave; N <= 64, S <= 128: BASELINE
 // config 5, and config-2-shaped frames with more than 16 instances).
 //
@@ -1092,7 +1010,7 @@ __device__ __forceinline__ bool quad_step_body(const float* __restrict__ instanc
 //
 // kYawOnly (hot full-shape kernels only): the launch carries VSRD_FLAG_YAW_GRADIENTS -- the host picks this instantiation by the flag, and the
 // hot kernel runs only fields whose rotations are all about y, so sh.yaw_gradients is true wherever it is asked (quad_phase_b).  Every
-// other instantiation keeps the run-time test.  -DVSRD_NO_YAW_KERNEL (api.hip): never picked.
+// other instantiation keeps the run-time test.
 template <int kL, int kRoundsS, bool kHot, bool kFull, bool kYawOnly = false>
 __device__ __forceinline__ void silhouette_rows_kernel_body(
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
@@ -1126,28 +1044,11 @@ __device__ __forceinline__ void silhouette_rows_kernel_body(
     float* coefs = dcache + quad_cache_floats(S, NP, kL);
     float* rays = coefs + kRays * quad_coef_floats(NP);
     const bool sorted_input = (u_fine != nullptr) && (c.flags & 1u);
-    Shading sh = c.sh;
-    const FieldBounds bounds = field_bounds(instances, N, f.inv_t, false, c.flags);
-    sh.cull = bounds.margin; sh.reach = bounds.reach; sh.yaw = bounds.yaw;
-#ifdef VSRD_CULL_INNER           // (opt-in, round 6: the culling bounds from the boxes' inscribed ball, field.h: cull_round; +3 %, docs/OPTLOG.md round 6 item 7b)
-    sh.inner = bounds.inner;
-#else
-    sh.inner = 0.0f;
-#endif
+    Shading sh = quad_shading(f, instances, c);
     sh.yaw_gradients = sh.yaw && (c.flags & 1024u) != 0u;                       // VSRD_FLAG_YAW_GRADIENTS
-    sh.mlp_bits = 0u;
-    sh.mlp_lds = nullptr;
-    const bool hot_runs = sh.reach >= 0.0f && sh.yaw;                          // (wave-uniform, the same in both kernels of the launch)
+    const bool hot_runs = quad_hot_runs(sh);
     if (kHot && !hot_runs) return;
     if (kHot && blockIdx.x == 0 && threadIdx.x == 0) redo_summary[1] = 1u;
-#ifdef VSRD_INSTANCE_LDS
-    if (kHot && kFull && kL == kRowLanes) {                                     // (the host adds N x 16 floats behind the waves' partitions)
-        float* block = lds + waves_per_block() * quad_lds_floats(S, NP, kL);
-        for (int idx = static_cast<int>(threadIdx.x); idx < N * kInstanceStride; idx += static_cast<int>(blockDim.x)) block[idx] = instances[idx];
-        __syncthreads();
-        instances = block;
-    }
-#endif
     float loss_acc = 0.0f;
     float G[kG];
 #pragma unroll
@@ -1197,8 +1098,9 @@ __device__ __forceinline__ void silhouette_rows_kernel_body(
     if (lane0 == 0) loss_partials[wave_global] = add ? (loss_partials[wave_global] + loss_total * loss_scale) : (loss_total * loss_scale);
 }
 
+constexpr int kQuadWavesPerEu = 4;
 template <int kRoundsS, bool kHot, bool kFull, bool kYawOnly = false>
-__global__ __launch_bounds__(kBlockThreads, VSRD_QUAD_WAVES_PER_EU) void render_silhouette_quad_kernel(
+__global__ __launch_bounds__(kBlockThreads, kQuadWavesPerEu) void render_silhouette_quad_kernel(
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
     const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale,
@@ -1301,17 +1203,8 @@ __device__ __forceinline__ void hierarchical_rows_kernel_body(
     float* coefs = dcache + quad_cache_floats(S, NP, kL);
     float* rays = coefs + kRays * quad_coef_floats(NP);
     const bool sorted_input = (u_fine != nullptr) && (c.flags & 1u);
-    Shading sh = c.sh;
-    const FieldBounds bounds = field_bounds(instances, N, f.inv_t, false, c.flags);
-    sh.cull = bounds.margin; sh.reach = bounds.reach; sh.yaw = bounds.yaw;
-#ifdef VSRD_CULL_INNER           // (opt-in, round 6: the culling bounds from the boxes' inscribed ball, field.h: cull_round; +3 %, docs/OPTLOG.md round 6 item 7b)
-    sh.inner = bounds.inner;
-#else
-    sh.inner = 0.0f;
-#endif
-    sh.mlp_bits = 0u;
-    sh.mlp_lds = nullptr;
-    const bool hot_runs = sh.reach >= 0.0f && sh.yaw;                          // (wave-uniform, the same in both kernels of the launch)
+    Shading sh = quad_shading(f, instances, c);
+    const bool hot_runs = quad_hot_runs(sh);
     if (kHot && !hot_runs) return;
     const int num_waves = static_cast<int>(gridDim.x) * waves_per_block();
     const int wave_global = static_cast<int>(blockIdx.x) * waves_per_block() + wave;
@@ -1464,18 +1357,9 @@ __device__ __forceinline__ void backward_rows_kernel_body(
     float* dcache = stage + kRays * quad_row_floats(half, kL);
     float* coefs = dcache + quad_cache_floats(half, NP, kL);
     float* rays = coefs + kRays * quad_coef_floats(NP);
-    Shading sh = c.sh;
-    const FieldBounds bounds = field_bounds(instances, N, f.inv_t, false, c.flags);
-    sh.cull = bounds.margin; sh.reach = bounds.reach; sh.yaw = bounds.yaw;
-#ifdef VSRD_CULL_INNER           // (opt-in, round 6: the culling bounds from the boxes' inscribed ball, field.h: cull_round; +3 %, docs/OPTLOG.md round 6 item 7b)
-    sh.inner = bounds.inner;
-#else
-    sh.inner = 0.0f;
-#endif
+    Shading sh = quad_shading(f, instances, c);
     sh.yaw_gradients = sh.yaw && (c.flags & 1024u) != 0u;                       // VSRD_FLAG_YAW_GRADIENTS
-    sh.mlp_bits = 0u;
-    sh.mlp_lds = nullptr;
-    const bool hot_runs = sh.reach >= 0.0f && sh.yaw;                          // (wave-uniform, the same in both kernels of the launch)
+    const bool hot_runs = quad_hot_runs(sh);
     if (kHot && !hot_runs) return;
     if (kHot && blockIdx.x == 0 && threadIdx.x == 0) redo_summary[1] = 1u;
     float G[kG];
@@ -1533,11 +1417,9 @@ __global__ __launch_bounds__(kBlockThreads, 3) void render_backward_pair_kernel(
 }
 
 // Two rays per wave, 32 lanes each (kRoundsS = 2: S <= 64; 4: S <= 128).
-#ifndef VSRD_PAIR_WAVES_PER_EU
-#define VSRD_PAIR_WAVES_PER_EU 3
-#endif
+constexpr int kPairWavesPerEu = 3;
 template <int kRoundsS, bool kHot, bool kFull, bool kYawOnly = false>
-__global__ __launch_bounds__(kBlockThreads, VSRD_PAIR_WAVES_PER_EU) void render_silhouette_pair_kernel(
+__global__ __launch_bounds__(kBlockThreads, kPairWavesPerEu) void render_silhouette_pair_kernel(
     FieldArgs f, const float* __restrict__ instances, RenderArgs c, const float* __restrict__ origins, const float* __restrict__ directions,
     const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale,

@@ -540,7 +540,7 @@ __device__ __forceinline__ void adjoint_label_mix(RayAdjoint<kRounds>& st, const
             for (unsigned long long todo = st.near_any[k]; todo != 0ull; todo &= todo - 1ull) {   // the instances the forward sweep evaluated
                 const int i = __builtin_ctzll(todo);
                 if (lam[i] == 0.0f) continue;                               // wave-uniform
-                const Instance in = load_instance_as<!kResidual>(instances, i);
+                const Instance in = load_instance(instances, i);
                 float d = box_value<kYaw>(in, st.sa[k].x, st.sa[k].y, st.sa[k].z).d;
                 if (kResidual) d += load_jet<kRounds>(rcache, N, k, i, lane).x;
                 acc += lam[i] * fast_exp(-(d - st.sa[k].m) * inv_t);
@@ -600,7 +600,7 @@ __device__ __forceinline__ void adjoint_phase_b(const RayAdjoint<kRounds>& st, c
             else sink.masks8[at] = 0;
         }
         if (!any_active) continue;                                            // negligible for this ray (field.h culling)
-        const Instance in = load_instance_as<!kResidual>(instances, i);
+        const Instance in = load_instance(instances, i);
         const float lam_i = lam[i];
         float at0 = 0, at1 = 0, at2 = 0, ad0 = 0, ad1 = 0, ad2 = 0;
         float r00 = 0, r01 = 0, r02 = 0, r10 = 0, r11 = 0, r12 = 0, r20 = 0, r21 = 0, r22 = 0;
@@ -922,11 +922,9 @@ __host__ __device__ constexpr int residual_step_lds_floats(int num_samples, int 
     return (kMlpWbarFloats + kMlpLdsFloats + kMlpBatch * 4 * num_instances + wave_lds_floats(num_samples, num_instances) + num_instances + num_instances * kGradStride + 3) & ~3;
 }
 
-#ifndef VSRD_RESIDUAL_WAVES_PER_EU
-#define VSRD_RESIDUAL_WAVES_PER_EU 1
-#endif
+constexpr int kResidualWavesPerEu = 1;
 template <int kRounds>
-__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(VSRD_RESIDUAL_WAVES_PER_EU, VSRD_RESIDUAL_WAVES_PER_EU))) void render_residual_step_kernel(
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(kResidualWavesPerEu, kResidualWavesPerEu))) void render_residual_step_kernel(
     FieldArgs f, const float* __restrict__ instances, const float* __restrict__ mlp, RenderArgs c,
     const float* __restrict__ origins, const float* __restrict__ directions, const float* __restrict__ u_coarse, const float* __restrict__ u_fine,
     const float* __restrict__ targets, const float* __restrict__ instance_weights, float loss_scale, float eikonal_scale, float eikonal_norm,

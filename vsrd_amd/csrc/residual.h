@@ -54,12 +54,8 @@ __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return (a[0] * b[0] + 
 // Rounds 2-4 used ONE fp32 MFMA with an all-ones A operand instead (D[i][m] = sum_k 1 * B[k][m], k = row) on the assumption that the
 // matrix instruction runs beside the vector ones.  It does not (tools/micro/mfma_valu_interleave.hip: 32.5 cycles alone, ~42 in a stream
 // of vector instructions, nothing hidden), and the swaps cost ~18: round 5, same box, same build otherwise: config 3 3.05 -> 3.13 Mrays/s,
-// the native residual step 0.838 -> 0.820 ms.  -DVSRD_ROWS_SUM_MFMA: the matrix form.
-#ifndef VSRD_ROWS_SUM_MFMA
+// the native residual step 0.838 -> 0.820 ms.
 __device__ __forceinline__ float rows_sum(float v) { return add_xor32(add_xor16(v)); }
-#else
-__device__ __forceinline__ float rows_sum(float v) { return mfma4(1.0f, v, f32x4{0.0f, 0.0f, 0.0f, 0.0f})[0]; }
-#endif
 
 // Value of lane 16 q + (lane & 15): row q broadcast to all four rows.  `start` (wave-uniform): the rows are counted from lane `start`
 // on, cyclically (residual_forward with rotated tiles; ds_bpermute takes the lane index modulo 64 by itself).
@@ -75,15 +71,11 @@ __device__ __forceinline__ float rotate_lanes(float v, int byte_address) {
 // which shares its exponential exp(-y^2 / 2) with the pdf: ~17 instructions for (cdf, pdf) instead of ~60 through erff.
 struct Gauss { float cdf, pdf; };
 __device__ __forceinline__ Gauss gauss(float y) {
-#ifdef VSRD_LIBM_ERF
-    return {0.5f * (1.0f + erff(y * 0.7071067811865476f)), fast_exp(-0.5f * y * y) * 0.3989422804014327f};
-#else
     const float e = fast_exp(-0.5f * y * y);
     const float t = fast_rcp(1.0f + 0.3275911f * 0.7071067811865476f * fabsf(y));
     const float poly = ((((1.061405429f * t - 1.453152027f) * t + 1.421413741f) * t - 0.284496736f) * t + 0.254829592f) * t;
     const float half_erfc = 0.5f * poly * e;                      // 0.5 erfc(|y| / sqrt 2)
     return {(y < 0.0f) ? half_erfc : 1.0f - half_erfc, e * 0.3989422804014327f};
-#endif
 }
 
 // One 16-point tile of a 16-channel jet: value and the three tangents d/d(folded, scaled local position).
@@ -164,9 +156,6 @@ __device__ __forceinline__ void load_forward_weights(GlobalWeights w, int lane, 
 // are fp32-exact), Taylor polynomials on |pi r| <= pi / 4 (truncation 1.8e-9 / 2.4e-8), quadrant fix-up by n mod 4.
 // ~24 instructions for the pair instead of ~47 through sinpif + cospif.
 __device__ __forceinline__ void sincospi(float x, float& sine, float& cosine) {
-#ifdef VSRD_LIBM_SINCOS
-    sine = sinpif(x); cosine = cospif(x);
-#else
     const float n = rintf(2.0f * x);
     const float r = fmaf(n, -0.5f, x);
     const int quadrant = static_cast<int>(n);
@@ -177,7 +166,6 @@ __device__ __forceinline__ void sincospi(float x, float& sine, float& cosine) {
     const unsigned s_bits = __float_as_uint(odd ? cr : sr) ^ ((static_cast<unsigned>(quadrant) & 2u) << 30);          // n mod 4 in {2, 3}: -
     const unsigned c_bits = __float_as_uint(odd ? sr : cr) ^ ((static_cast<unsigned>(quadrant + 1) & 2u) << 30);      // n mod 4 in {1, 2}: -
     sine = __uint_as_float(s_bits); cosine = __uint_as_float(c_bits);
-#endif
 }
 
 // Encoder features of one tile: row g evaluates octaves 2 g and 2 g + 1 of every coordinate, i.e. features 4 g .. 4 g + 3
@@ -577,27 +565,12 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
     return r;
 }
 // {hi(x0, x1), hi(x2, x3), lo(x0, x1), lo(x2, x3)}
-#ifdef VSRD_SPLIT_TRUNCATE
-// Experiment (round 6, VERDICT r05 item 3 "cut the VALU count"; profiles/r06_c3_bf16/variants.txt): both parts TRUNCATED to bfloat16 -- the high
-// half-words picked by v_perm_b32, no v_cvt_pk_bf16_f32 (a double-rate instruction: 5.6 cycles against 2.9, profiles/r05/split_rates.txt): six
-// full-rate instructions per pair of values instead of two conversions + four; |x - hi - lo| <= 2^-16 |x| instead of 2^-18.  Measured: +2.9 % on
-// config 3, +3.0 % on the batched native residual step, goldens inside their tolerances -- NOT the default: four times the product error for 3 %.
-__device__ __forceinline__ unsigned pack_high_halves(float lo, float hi) {        // {bits 31..16 of lo, bits 31..16 of hi} as one word, lo in the low half
-    return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
-}
-__device__ __forceinline__ u32x4 split4(float x0, float x1, float x2, float x3) {
-    const float r0 = x0 - __uint_as_float(__float_as_uint(x0) & 0xffff0000u), r1 = x1 - __uint_as_float(__float_as_uint(x1) & 0xffff0000u);
-    const float r2 = x2 - __uint_as_float(__float_as_uint(x2) & 0xffff0000u), r3 = x3 - __uint_as_float(__float_as_uint(x3) & 0xffff0000u);
-    return u32x4{pack_high_halves(x0, x1), pack_high_halves(x2, x3), pack_high_halves(r0, r1), pack_high_halves(r2, r3)};
-}
-#else
 __device__ __forceinline__ u32x4 split4(float x0, float x1, float x2, float x3) {
     const unsigned h01 = cvt_pk_bf16(x0, x1), h23 = cvt_pk_bf16(x2, x3);
     const float r0 = x0 - __uint_as_float(h01 << 16), r1 = x1 - __uint_as_float(h01 & 0xffff0000u);
     const float r2 = x2 - __uint_as_float(h23 << 16), r3 = x3 - __uint_as_float(h23 & 0xffff0000u);
     return u32x4{h01, h23, cvt_pk_bf16(r0, r1), cvt_pk_bf16(r2, r3)};
 }
-#endif
 __device__ __forceinline__ u32x4 split4(f32x4 x) { return split4(x[0], x[1], x[2], x[3]); }
 __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -605,23 +578,10 @@ __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
 // c += W x, W = an image operand, x = the split `s` = [x_hi | x_lo] of the lane's four channels.  The operand comes in both orders of
 // its halves, a = [w_hi | w_lo] and swapped = [w_lo | w_hi] (the same 16 bytes of the image read a second time, half by half: no second
 // image): a . s = w_hi x_hi + w_lo x_lo, swapped . s = w_lo x_hi + w_hi x_lo -- all four partial products with the split used AS IT IS.
-// kDup: the first form, a . [x_hi | x_hi] + a . [x_lo | x_lo], whose two activation operands cost four register moves per product (144 of
-// the 1 930 vector instructions of an adjoint tile) but which needs four registers less per live operand.
-// -DVSRD_SPLIT_DUP: that form everywhere; -DVSRD_SPLIT_DUP_FORWARD: in the forward tiles of the front kernels only.
+// (The first form, a . [x_hi | x_hi] + a . [x_lo | x_lo], needed four registers less per live operand, but its two activation operands cost
+// four register moves per product: 144 of the 1 930 vector instructions of an adjoint tile.)
 struct SplitOperand { u32x4 a, swapped; };
-#ifdef VSRD_SPLIT_DUP
-constexpr bool kSplitDupForward = true, kSplitDupAdjoint = true;
-#elif defined(VSRD_SPLIT_DUP_FORWARD)
-constexpr bool kSplitDupForward = true, kSplitDupAdjoint = false;
-#else
-constexpr bool kSplitDupForward = false, kSplitDupAdjoint = false;
-#endif
-template <bool kDup>
 __device__ __forceinline__ f32x4 mfma_split(const SplitOperand& w, u32x4 s, f32x4 c) {
-    if (kDup) {
-        c = mfma_bf16(w.a, u32x4{s[0], s[1], s[0], s[1]}, c);
-        return mfma_bf16(w.a, u32x4{s[2], s[3], s[2], s[3]}, c);
-    }
     c = mfma_bf16(w.a, s, c);
     return mfma_bf16(w.swapped, s, c);
 }
@@ -655,12 +615,10 @@ __device__ __forceinline__ void pack_mlp_image(const LdsFloats w, unsigned* __re
 struct SplitWeights {
     LdsWords image;    // the staged operand image of the instance
     int lane, g;
-    template <bool kDup>
     __device__ __forceinline__ SplitOperand operand(int p) const {
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         const __attribute__((address_space(3))) u32x2* at = reinterpret_cast<const __attribute__((address_space(3))) u32x2*>(image + p * kImgOperandWords + 4 * lane);
         const u32x2 hi = at[0], lo = at[1];
-        if (kDup) return {u32x4{hi[0], hi[1], lo[0], lo[1]}, u32x4{0u, 0u, 0u, 0u}};
         // The swapped operand: a second pair of reads through addresses the optimiser cannot see through -- otherwise it keeps the first
         // pair and builds the swapped operand with four register moves, the moves this form is there to avoid; each half through its
         // own address, because a merged ds_read2_b64 returns the halves in address order and the moves are back.
@@ -696,9 +654,9 @@ __device__ __forceinline__ void forward_tile_split(const SplitWeights& wt, const
     f32x4 x[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const SplitOperand a = wt.operand<kSplitDupForward>(kImgFirst + c);
-        z = mfma_split<kSplitDupForward>(a, split4(e.f[c]), z);
-        x[c] = mfma_split<kSplitDupForward>(a, split4(e.d[c]), splat4(0.0f));
+        const SplitOperand a = wt.operand(kImgFirst + c);
+        z = mfma_split(a, split4(e.f[c]), z);
+        x[c] = mfma_split(a, split4(e.d[c]), splat4(0.0f));
     }
     f32x4 y[4], g1[4];
     float inv_s[4];
@@ -715,7 +673,7 @@ __device__ __forceinline__ void forward_tile_split(const SplitWeights& wt, const
             a[j] = y[l][j] * n.cdf;
             g1[l][j] = n.cdf + y[l][j] * n.pdf;
         }
-        if (l < 3) z = mfma_split<kSplitDupForward>(wt.operand<kSplitDupForward>(kImgHidden + l), split4(a), wt.b(l));
+        if (l < 3) z = mfma_split(wt.operand(kImgHidden + l), split4(a), wt.b(l));
         else v = rows_sum(dot4(wt.w4(), a)) + wt.b4();
     }
     f32x4 a_bar = wt.w4(), z_bar;
@@ -725,7 +683,7 @@ __device__ __forceinline__ void forward_tile_split(const SplitWeights& wt, const
         const float m = rows_sum(hsum4(u)) * (1.0f / kMlpHidden);
         const float my = rows_sum(dot4(u, y[l])) * (1.0f / kMlpHidden);
         z_bar = (u - splat4(m) - y[l] * splat4(my)) * splat4(inv_s[l]);
-        if (l > 0) a_bar = mfma_split<kSplitDupForward>(wt.operand<kSplitDupForward>(kImgHiddenT + l - 1), split4(z_bar), splat4(0.0f));
+        if (l > 0) a_bar = mfma_split(wt.operand(kImgHiddenT + l - 1), split4(z_bar), splat4(0.0f));
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) t[c] = rows_sum(dot4(z_bar, x[c]));
@@ -747,11 +705,6 @@ VSRD_RESIDUAL_FN Residual residual_forward(const float* w_in, float px, float py
 #endif
     stage_centred_weights_wave(staged, uniform_weights_generic(w_in), (tiles & kMlpCentredBit) != 0u, lane);
     wave_lds_order();
-#ifdef VSRD_PROBE_STAGE_TWICE          // probe: what one staging costs (the difference to the normal build)
-    asm volatile("" ::: "memory");
-    stage_centred_weights_wave(staged, uniform_weights_generic(w_in) + (tiles >> 30), (tiles & kMlpCentredBit) != 0u, lane);
-    wave_lds_order();
-#endif
     const LdsWeights wt = {staged, g, lane & 15};
 #ifdef VSRD_SPLIT_BF16
     const SplitWeights swt = {(LdsWords)weights_lds, lane, g};
@@ -801,14 +754,12 @@ __device__ __forceinline__ TilePlan tile_plan(unsigned long long need) {
     p.start = 0;
     p.tiles = ((need & 0xFFFFull) ? 1u : 0u) | ((need & 0xFFFF0000ull) ? 2u : 0u) | ((need & 0xFFFF00000000ull) ? 4u : 0u) |
               ((need & 0xFFFF000000000000ull) ? 8u : 0u);
-#ifndef VSRD_NO_TILE_PACKING
     if (need != 0ull) {
         const int first = __builtin_ctzll(need);
         const int run = 64 - __builtin_clzll(need) - first;
         const int packed = (run + 15) >> 4;
         if (packed < __builtin_popcount(p.tiles)) { p.start = first; p.tiles = (1u << packed) - 1u; }
     }
-#endif
     return p;
 }
 
@@ -1051,11 +1002,7 @@ __device__ __forceinline__ f32x4 mfma_outer(const SplitPair& x, const SplitPair&
     acc = mfma_bf16(x.hi, y.hi, acc);
     acc = mfma_bf16(x.hi, y.lo, acc);
     acc = mfma_bf16(x.lo, y.hi, acc);
-#ifdef VSRD_SPLIT_OUTER_3        // experiment (round 6, profiles/r06_c3_bf16/variants.txt): without the lo.lo partial product (2^-16 of the term)
-    return acc;
-#else
     return mfma_bf16(x.lo, y.lo, acc);
-#endif
 }
 
 __device__ __forceinline__ ResidualAdjoint mlp_adjoint_points_split(MlpAdjoint& s, const SplitWeights& wt, float px, float py, float pz, float res_bar,
@@ -1086,16 +1033,16 @@ __device__ __forceinline__ ResidualAdjoint mlp_adjoint_points_split(MlpAdjoint& 
             z.t = splat4(0.0f);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const SplitOperand a = wt.operand<kSplitDupAdjoint>(kImgFirst + c);
-                z.v = mfma_split<kSplitDupAdjoint>(a, split4(e.f[c]), z.v);
-                z.t = mfma_split<kSplitDupAdjoint>(a, split4(e.d[c] * splat4(delta[c])), z.t);
+                const SplitOperand a = wt.operand(kImgFirst + c);
+                z.v = mfma_split(a, split4(e.f[c]), z.v);
+                z.t = mfma_split(a, split4(e.d[c] * splat4(delta[c])), z.t);
             }
 #pragma unroll
             for (int l = 0; l < 3; ++l) {
                 tile_state(z, st[l]);
-                const SplitOperand a = wt.operand<kSplitDupAdjoint>(kImgHidden + l);
-                z.v = mfma_split<kSplitDupAdjoint>(a, split4(st[l].a), wt.b(l));
-                z.t = mfma_split<kSplitDupAdjoint>(a, split4(st[l].da()), splat4(0.0f));
+                const SplitOperand a = wt.operand(kImgHidden + l);
+                z.v = mfma_split(a, split4(st[l].a), wt.b(l));
+                z.t = mfma_split(a, split4(st[l].da()), splat4(0.0f));
             }
             tile_state(z, st[3]);
         }
@@ -1125,9 +1072,9 @@ __device__ __forceinline__ ResidualAdjoint mlp_adjoint_points_split(MlpAdjoint& 
                 s.acc_w[l] = mfma_outer(x, y, s.acc_w[l]);
             }
             wave_lds_order();
-            const SplitOperand at = wt.operand<kSplitDupAdjoint>(kImgHiddenT + l);
-            const f32x4 a_bar = mfma_split<kSplitDupAdjoint>(at, split4(zb.v), splat4(0.0f));
-            const f32x4 da_bar = mfma_split<kSplitDupAdjoint>(at, split4(zb.t), splat4(0.0f));
+            const SplitOperand at = wt.operand(kImgHiddenT + l);
+            const f32x4 a_bar = mfma_split(at, split4(zb.v), splat4(0.0f));
+            const f32x4 da_bar = mfma_split(at, split4(zb.t), splat4(0.0f));
             TileJet1 zin_bar;
             gelu_norm_adjoint_tile(st[l], a_bar, da_bar, zin_bar);
             zb = zin_bar;
@@ -1154,9 +1101,9 @@ __device__ __forceinline__ ResidualAdjoint mlp_adjoint_points_split(MlpAdjoint& 
             // d feat / d f = e.d;  d (delta dfeat) / d f = -delta omega^2 feat
             const f32x4 second = {-delta[c] * omega[0] * omega[0] * e.f[c][0], -delta[c] * omega[0] * omega[0] * e.f[c][1],
                                   -delta[c] * omega[1] * omega[1] * e.f[c][2], -delta[c] * omega[1] * omega[1] * e.f[c][3]};
-            const SplitOperand a = wt.operand<kSplitDupAdjoint>(kImgFirst + c);
-            const f32x4 x1 = mfma_split<kSplitDupAdjoint>(a, split4(e.d[c]), splat4(0.0f));
-            const f32x4 x2 = mfma_split<kSplitDupAdjoint>(a, split4(second), splat4(0.0f));
+            const SplitOperand a = wt.operand(kImgFirst + c);
+            const f32x4 x1 = mfma_split(a, split4(e.d[c]), splat4(0.0f));
+            const f32x4 x2 = mfma_split(a, split4(second), splat4(0.0f));
             f_bar[c] = rows_sum(dot4(zb.v, x1) + dot4(zb.t, x2));
         }
         if (g == q) { mine.px = f_bar[0] * tfold * inv; mine.py = f_bar[1] * inv; mine.pz = f_bar[2] * inv; }

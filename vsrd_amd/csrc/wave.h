@@ -109,8 +109,7 @@ __device__ __forceinline__ float dpp_move(float identity, float v) {
 // In-place scan steps "v = v op v[lane - n]" inside a row of 16 as ONE DPP instruction: a lane whose source lies outside its row is
 // disabled by the instruction itself (no bound_ctrl) and keeps its value, so no identity register is needed -- the compiler's form of
 // `v *= dpp_move(1.0f, v)` is v_mov 1.0 + v_mov_dpp + v_mul (and for fmaxf two canonicalising v_max on top).  The wait states a VALU
-// write needs before a DPP read are in the string (-DVSRD_NO_DPP_INPLACE: the compiler's form).
-#ifndef VSRD_NO_DPP_INPLACE
+// write needs before a DPP read are in the string.
 #define VSRD_DPP_STEP(NAME, OP, CTRL)                                                                              \
     __device__ __forceinline__ float NAME(float v) {                                                               \
         asm volatile("s_nop 1\n\t" OP " %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(v));                \
@@ -125,10 +124,6 @@ VSRD_DPP_STEP(max_shr4, "v_max_f32_dpp", "row_shr:4") VSRD_DPP_STEP(max_shr8, "v
 // whenever the compiler cannot prove them canonical, e.g. a value carried around a loop)
 __device__ __forceinline__ float min_raw(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float max_raw(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-#else
-__device__ __forceinline__ float min_raw(float a, float b) { return fminf(a, b); }
-__device__ __forceinline__ float max_raw(float a, float b) { return fmaxf(a, b); }
-#endif
 
 constexpr int kDppQuadXor1 = 0xB1;       // quad_perm:[1,0,3,2]
 constexpr int kDppQuadXor2 = 0x4E;       // quad_perm:[2,3,0,1]
