@@ -596,6 +596,35 @@ def test_capture_gate_keeps_captures_alone():
             pass
 
 
+def test_steps_in_next_group_takes_whole_groups_inside_every_bound():
+    """optimization._steps_in_next_group, the one rule by which FrameOptimizer.run and FrameBatch.run size their next graph launch: a whole
+    group of ``steps_per_graph`` steps where the run, the phase and the log all leave room for one and the phase's one-step graph is held,
+    a single step everywhere else."""
+    import itertools
+    from vsrd_amd.optimization import _steps_in_next_group
+    grid = itertools.product(range(1, 15), [None, *range(1, 10)], [None, *range(1, 6)], (1, 2, 4), (False, True))
+    for remaining, to_phase_end, to_log, steps_per_graph, held in grid:
+        case = (remaining, to_phase_end, to_log, steps_per_graph, held)
+        k = _steps_in_next_group(*case)
+        bounds = [b for b in (remaining, to_phase_end, to_log) if b is not None]
+        assert k in (1, steps_per_graph), case
+        assert all(k <= b for b in bounds), case
+        if not held:
+            assert k == 1, case
+        if held and all(steps_per_graph <= b for b in bounds):
+            assert k == steps_per_graph, case
+    # one walk by hand: 23 steps, the phase switch after 9, groups of 4, no log; a phase's one-step graph is held after its first four
+    # single steps (three eager ones and the capture)
+    warmup, position, singles, groups = 9, 0, {False: 0, True: 0}, []
+    while position < 23:
+        residual = position >= warmup
+        k = _steps_in_next_group(23 - position, None if residual else warmup - position, None, 4, singles[residual] >= 4)
+        singles[residual] += k == 1
+        groups.append(k)
+        position += k
+    assert groups == [1, 1, 1, 1, 4, 1, 1, 1, 1, 1, 4, 4, 1, 1] and position == 23
+
+
 def test_to_host_rebuilds_containers_and_leaves_the_rest():
     """formats.to_host: what launcher.main hands to torch.save for a frame optimised next to others -- every tensor a host copy, dicts /
     lists / tuples rebuilt with their types, everything else untouched."""

@@ -310,6 +310,86 @@ def _launch_log(members, frames=None):
     lead.log_seconds += time.perf_counter() - started
 
 
+def _steps_in_next_group(remaining, to_phase_end, to_log, steps_per_graph, one_step_graph_held):
+    """How many steps the next graph launch of a ``run()`` takes: ``steps_per_graph`` or 1.  Whole groups only: a tail shorter than a group
+    replays the one-step graph (every distinct k would otherwise cost a capture of its own -- a synchronisation -- for one use).  No group
+    crosses the end of its phase (``to_phase_end``; None: the residual phase, which ends with the run) or a boundary of the log (``to_log``;
+    None: no log -- the log's launch follows the group), and the phase's eager warm-up steps and its one-step graph come first."""
+    k = int(steps_per_graph)
+    room = min(bound for bound in (remaining, to_phase_end, to_log) if bound is not None)
+    return k if k > 1 and one_step_graph_held and room >= k else 1
+
+
+def _advance(owner, key, k, body, static=None):
+    """THE capture/replay protocol of graph mode: ``k`` steps of ``owner`` (a FrameOptimizer, a FrameBatch) under ``key`` of its ``_graphs``.
+    Three eager steps per one-step key on a side stream warm the allocator and the lazy initialisations -- they run the same device-side
+    code, so they are ordinary optimisation steps -- then the step is captured once and replayed; a k-step graph is captured at its first
+    use.  ``body(static, count=False, joins=...)`` launches one step and does not count it: the caller counts the k steps afterwards.
+    ``static``: a tensor of the caller's that the body reads (explicit ray indices): an eager step reads it as it is, a capture reads a
+    clone that the graph keeps, and every replay copies the caller's values into that clone first.  Returns the body's last result (of the
+    capture, for a replay: device tensors that every replay rewrites)."""
+    device = owner.device
+    if key in owner._graphs:
+        graph, kept, outputs = owner._graphs[key]
+        with _capture_lock.replaying():      # (the copy too: nothing of a frame calls into HIP during another frame's capture)
+            if kept is not None:
+                kept.copy_(static)
+            graph.replay()
+        return outputs
+    done = owner._eager_graph_steps.get(key, 0)
+    if k == 1 and done < 3:
+        with _capture_lock:          # (a phase's three eager steps too: nothing of a frame calls into HIP next to another frame's capture)
+            side = torch.cuda.Stream(device=device)
+            side.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.stream(side):
+                outputs = body(static, count=False, joins=(True, True))
+            torch.cuda.current_stream(device).wait_stream(side)
+        owner._eager_graph_steps[key] = done + 1
+        return outputs
+    kept = static.clone() if static is not None else None
+    graph = torch.cuda.CUDAGraph()
+    # an own capture stream per owner: torch keys the rocBLAS / hipBLASLt workspaces by stream, and its default capture stream is
+    # shared by every capture -- two loops replayed at the same time would then run their GEMMs in one workspace
+    if owner._capture_stream is None:
+        owner._capture_stream = torch.cuda.Stream(device=device)
+    # stream capture is a process-wide mode: one capture at a time, and thread-local error checking so that another frame's
+    # thread (launcher.run_frames(frames_in_flight=2)) may keep replaying its own graph meanwhile
+    # (no device-wide synchronisation out here: while ANOTHER frame's thread captures, HIP refuses it -- "operation not permitted when
+    #  stream is capturing"; torch.cuda.graph synchronises by itself once this thread holds the lock and nobody captures)
+    with _capture_lock.capture():
+        with torch.cuda.graph(graph, stream=owner._capture_stream, capture_error_mode="thread_local"):
+            for j in range(k):  # the hypernetwork's branch is joined to the step's stream only at the ends of the graph: between two
+                # steps the next prologue (which needs the epilogue only) overlaps the hypernetwork's backward and forward
+                outputs = body(kept, count=False, joins=(j == 0, j == k - 1))
+        owner._graphs[key] = (graph, kept, outputs)
+        # capture does not execute: this replay IS the step(s).  A graph's FIRST launch stays inside the capture's turn: next to another
+        # thread's launch it died inside hipGraphLaunch (one 36-frame run in twelve; later launches of an uploaded graph have not)
+        graph.replay()
+    return outputs
+
+
+def _capture_phases(members, k, step, group):
+    """The walk of ``capture_all()`` over ``members`` (the loops that step together): in each phase ``step()`` four times -- three eager
+    steps, then the capture (and first replay) of the one-step graph -- and ``group()``, the k-step group as ``run()`` takes it, where
+    ``run()`` would (whole groups of k inside a phase, behind the one-step graph).
+    (With the log these steps launch it too, with the metrics and masks launches in front of it, at counters that start from phase_start
+    -- rows and slots of steps the founder never ran.  Harmless: the caller's reset() starts the log over, and every row a real run logs is
+    written, metrics included, by that run's own launches.)"""
+    cfg = members[0].config
+    for phase_start in sorted({0, min(cfg.warmup_steps, cfg.num_steps)}):
+        phase_steps = (cfg.warmup_steps if phase_start < cfg.warmup_steps else cfg.num_steps) - phase_start
+        if phase_steps <= 0:
+            continue
+        with _capture_lock:
+            for m in members:
+                m.step_index = phase_start
+                m.step_tensor.fill_(phase_start)
+        for _ in range(min(4, phase_steps)):
+            step()
+        if k > 1 and phase_steps >= 4 + k:
+            group()
+
+
 class FrameArena:
     """Device memory of a BATCH of frames (include/vsrd_hip.h, "frame batches"): one row of ``row_bytes`` per frame, and every buffer a
     frame's kernels touch sits at the SAME offset of its frame's row -- frame f's copy of a buffer is ``stride`` bytes x f behind frame 0's,
@@ -1225,10 +1305,7 @@ class FrameOptimizer:
         if self.graph:
             if u_coarse is not None or u_fine is not None:
                 raise ValueError("graph mode draws its uniforms in the kernels (Philox keyed by the device-side step counter)")
-            outputs = self._graph_step(ray_indices)
-            if self._log is not None:
-                _launch_log([self])
-            return outputs
+            return self._graph_advance(1, ray_indices)
         return self._step(ray_indices, u_coarse, u_fine)
 
     # ---- hipGraph mode ---------------------------------------------------------------------------------
@@ -1240,51 +1317,18 @@ class FrameOptimizer:
         self.schedule.copy_(torch.cat([anneal * (cfg.max_sdf_union_temperature - cfg.min_sdf_union_temperature) + cfg.min_sdf_union_temperature,
                                        anneal * (cfg.max_sdf_std_deviation - cfg.min_sdf_std_deviation) + cfg.min_sdf_std_deviation, x]))
 
-    def _graph_step(self, ray_indices):
-        """Three eager steps per (phase, ray source) on a side stream warm the allocator and the lazy initialisations, then the step is
-        captured once and replayed.  The eager steps run the same device-side code, so they are ordinary optimisation steps."""
+    def _graph_advance(self, k, ray_indices=None):
+        """``k`` steps of graph mode (``_advance``) and what is this loop's own around them: its checks, its key -- (phase, ray source) for a
+        single step, (phase, False, k) for a group -- its step count and its log."""
         if ray_indices is not None and int(ray_indices.numel()) > self.config.num_rays:
             # the captured graphs hold the address of scratch sized for config.num_rays rays; a larger launch would outgrow it
             raise ValueError(f"graph mode replays steps of at most config.num_rays = {self.config.num_rays} rays, got {int(ray_indices.numel())}")
         self._check_bindings()
         residual = self.step_index >= self.config.warmup_steps
-        key = (residual, ray_indices is not None)
-        if key in self._graphs:
-            graph, static_rays, outputs = self._graphs[key]
-            with _capture_lock.replaying():      # (the copy too: nothing of a frame calls into HIP during another frame's capture)
-                if static_rays is not None:
-                    static_rays.copy_(ray_indices)
-                graph.replay()
-            self.step_index += 1
-            return outputs
-        done = self._eager_graph_steps.get(key, 0)
-        if done < 3:
-            with _capture_lock:          # (a phase's three eager steps too: nothing of a frame calls into HIP next to another frame's capture)
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):
-                    outputs = self._step(ray_indices, None, None)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-            self._eager_graph_steps[key] = done + 1
-            return outputs
-        static_rays = ray_indices.clone() if ray_indices is not None else None
-        graph = torch.cuda.CUDAGraph()
-        # an own capture stream per loop: torch keys the rocBLAS / hipBLASLt workspaces by stream, and its default capture stream is
-        # shared by every capture -- two loops replayed at the same time would then run their GEMMs in one workspace
-        if self._capture_stream is None:
-            self._capture_stream = torch.cuda.Stream(device=self.device)
-        # stream capture is a process-wide mode: one capture at a time, and thread-local error checking so that another frame's
-        # thread (launcher.run_frames(frames_in_flight=2)) may keep replaying its own graph meanwhile
-        # (no device-wide synchronisation out here: while ANOTHER frame's thread captures, HIP refuses it -- "operation not permitted when
-        #  stream is capturing"; torch.cuda.graph synchronises by itself once this thread holds the lock and nobody captures)
-        with _capture_lock.capture():
-            with torch.cuda.graph(graph, stream=self._capture_stream, capture_error_mode="thread_local"):
-                outputs = self._step(static_rays, None, None, count=False)
-            self._graphs[key] = (graph, static_rays, outputs)
-            # capture does not execute: this replay IS the step.  A graph's FIRST launch stays inside the capture's turn: next to another
-            # thread's launch it died inside hipGraphLaunch (one 36-frame run in twelve; later launches of an uploaded graph have not)
-            graph.replay()
-        self.step_index += 1
+        key = (residual, ray_indices is not None) if k == 1 else (residual, False, k)
+        outputs = _advance(self, key, k, lambda rays, **how: self._step(rays, None, None, **how), static=ray_indices)
+        self.step_index += k
+        _launch_log([self])
         return outputs
 
     def run(self, num_steps, steps_per_graph=4):
@@ -1297,41 +1341,12 @@ class FrameOptimizer:
         remaining = int(num_steps)
         while remaining > 0:
             k = 1
-            if self.graph and self.fused_glue and steps_per_graph > 1:
+            if self.graph and self.fused_glue:
                 residual = self.step_index >= self.config.warmup_steps
-                to_boundary = remaining if residual else self.config.warmup_steps - self.step_index
-                # whole groups of `steps_per_graph` only: a tail shorter than that replays the one-step graph (every distinct k would
-                # otherwise cost a capture of its own -- a synchronisation -- for one use)
-                to_log = _steps_to_log_boundary([self])         # (no group crosses a boundary of the log: the launch follows the group)
-                if to_log is not None:
-                    to_boundary = min(to_boundary, to_log)
-                k = int(steps_per_graph) if min(remaining, to_boundary) >= int(steps_per_graph) else 1
-                if self._eager_graph_steps.get((residual, False), 0) < 3 or (residual, False) not in self._graphs:
-                    k = 1            # the phase's eager warm-up steps and its one-step graph come first (step() owns that protocol)
-            outputs = self._graph_replay_many(k) if k > 1 else self.step()
+                k = _steps_in_next_group(remaining, None if residual else self.config.warmup_steps - self.step_index, _steps_to_log_boundary([self]),
+                                         steps_per_graph, (residual, False) in self._graphs)
+            outputs = self._graph_advance(k) if k > 1 else self.step()
             remaining -= k
-        return outputs
-
-    def _graph_replay_many(self, k):
-        self._check_bindings()
-        residual = self.step_index >= self.config.warmup_steps
-        key = (residual, False, k)
-        if key not in self._graphs:
-            graph = torch.cuda.CUDAGraph()
-            with _capture_lock.capture():
-                with torch.cuda.graph(graph, stream=self._capture_stream, capture_error_mode="thread_local"):
-                    for j in range(k):  # the hypernetwork's branch is joined to the step's stream only at the ends of the graph: between two
-                        # steps the next prologue (which needs the epilogue only) overlaps the hypernetwork's backward and forward
-                        outputs = self._step(None, None, None, count=False, joins=(j == 0, j == k - 1))
-                self._graphs[key] = (graph, None, outputs)
-                graph.replay()          # (the first launch inside the capture's turn: _graph_step)
-        else:
-            graph, _, outputs = self._graphs[key]
-            with _capture_lock.replaying():
-                graph.replay()
-        self.step_index += k
-        if self._log is not None:
-            _launch_log([self])
         return outputs
 
     def _step(self, ray_indices, u_coarse, u_fine, count=True, joins=(True, True)):
@@ -1410,22 +1425,8 @@ class FrameOptimizer:
         happens next to another frame's work again.  Returns the number of graphs held."""
         if not (self.graph and self.fused_glue and self.persistent):
             raise ValueError("capture_all() belongs to a persistent graph-mode loop (FrameOptimizer(..., graph=True, persistent=True))")
-        cfg = self.config
         k = int(steps_per_graph)
-        for phase_start in sorted({0, min(cfg.warmup_steps, cfg.num_steps)}):
-            phase_steps = (cfg.warmup_steps if phase_start < cfg.warmup_steps else cfg.num_steps) - phase_start
-            if phase_steps <= 0:
-                continue
-            with _capture_lock:
-                self.step_index = phase_start
-                self.step_tensor.fill_(phase_start)
-            # (a loop with the log: these steps launch it too, with the metrics and masks launches in front of it, at counters that start
-            #  from phase_start -- rows and slots of steps the founder never ran.  Harmless: the reset() below starts the log over, and every
-            #  row a real run logs is written, metrics included, by that run's own launches)
-            for _ in range(min(4, phase_steps)):     # three eager steps, then the capture (and first replay) of the one-step graph
-                self.step()
-            if k > 1 and phase_steps >= 4 + k:       # (run() takes the k-step graph only for whole groups of k inside a phase)
-                self._graph_replay_many(k)
+        _capture_phases([self], k, self.step, lambda: self._graph_advance(k))
         with _capture_lock:
             torch.cuda.current_stream(self.device).synchronize()
         self.reset(self.inputs)
@@ -1813,7 +1814,7 @@ class FrameBatch:
             if row.layout != lead:
                 raise RuntimeError("the frames of a batch laid their buffers out differently: frame batches need equal offsets in every row")
         self._graphs = {}
-        self._eager = {}
+        self._eager_graph_steps = {}
         self._capture_stream = None
 
     @staticmethod
@@ -1925,30 +1926,17 @@ class FrameBatch:
 
     def step(self, active=None):
         """One optimisation step of the first ``active`` frames: three eager steps per (phase, active) warm the lazy initialisations, then the
-        step is captured once and replayed (the protocol of ``FrameOptimizer._graph_step``)."""
-        active, members = self._members(active)
-        key = (self._phase(active), active, 1)
-        if key in self._graphs:
-            with _capture_lock.replaying():
-                self._graphs[key].replay()
-            for m in members:
-                m.step_index += 1
-        elif self._eager.get(key, 0) < 3:
-            with _capture_lock:
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):
-                    self._step(active)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-            self._eager[key] = self._eager.get(key, 0) + 1
-        else:
-            self._capture(key, active, 1)
-        self._log_after(members)
+        step is captured once and replayed (``_advance``)."""
+        self._graph_advance(1, active)
 
-    def _log_after(self, members):
-        """The log launch that follows a step group of `members` (the first rows of the batch) when one of them sits on a boundary."""
-        if members[0]._log is not None:
-            _launch_log(members, frames=(len(members), self.arena.stride))
+    def _graph_advance(self, k, active=None):
+        """``k`` steps of the first ``active`` frames (``_advance``) under the batch's key (phase, active, k), then the members' step counts
+        and the log launch that follows a step group when one of them sits on a boundary."""
+        active, members = self._members(active)
+        _advance(self, (self._phase(active), active, k), k, lambda _, **how: self._step(active, **how))
+        for m in members:
+            m.step_index += k
+        _launch_log(members, frames=(active, self.arena.stride))
 
     def log_outputs(self, metrics=False, masks=False):
         """``FrameOptimizer.log_outputs`` for every row (the outputs' buffers at equal offsets)."""
@@ -1965,68 +1953,24 @@ class FrameBatch:
         """``FrameOptimizer.snapshots`` of the first ``active`` frames: a list of lists, each frame's own slots and instances."""
         return [m.snapshots() for m in self._members(active)[1]]
 
-    def _capture(self, key, active, k):
-        _, members = self._members(active)
-        graph = torch.cuda.CUDAGraph()
-        if self._capture_stream is None:
-            self._capture_stream = torch.cuda.Stream(device=self.device)
-        with _capture_lock.capture():
-            with torch.cuda.graph(graph, stream=self._capture_stream, capture_error_mode="thread_local"):
-                for j in range(k):      # (the hypernetwork's branch joins the step's stream at the ends of the graph only: FrameOptimizer._graph_replay_many)
-                    self._step(active, count=False, joins=(j == 0, j == k - 1))
-            self._graphs[key] = graph
-            graph.replay()              # capture does not execute: this replay IS the step(s); a graph's first launch stays inside the capture's turn
-        for m in members:
-            m.step_index += k
-
     def run(self, num_steps, steps_per_graph=4, active=None):
-        """``num_steps`` steps of the first ``active`` frames; whole groups of ``steps_per_graph`` steps inside a phase replay ONE hipGraph
-        (``FrameOptimizer.run``)."""
+        """``num_steps`` steps of the first ``active`` frames; whole groups of ``steps_per_graph`` steps inside a phase replay ONE hipGraph."""
         active, members = self._members(active)
         remaining = int(num_steps)
-        k_many = int(steps_per_graph)
         while remaining > 0:
             residual = self._phase(active)
-            to_boundary = remaining if residual else self.config.warmup_steps - members[0].step_index
-            to_log = _steps_to_log_boundary(members)            # (no group crosses a boundary of the log, of any row: the launch follows the group)
-            if to_log is not None:
-                to_boundary = min(to_boundary, to_log)
-            k = k_many if k_many > 1 and min(remaining, to_boundary) >= k_many else 1
-            if (residual, active, 1) not in self._graphs:
-                k = 1                   # the phase's eager steps and its one-step graph come first
-            if k == 1:
-                self.step(active)
-            else:
-                key = (residual, active, k)
-                if key in self._graphs:
-                    with _capture_lock.replaying():
-                        self._graphs[key].replay()
-                    for m in members:
-                        m.step_index += k
-                else:
-                    self._capture(key, active, k)
-                self._log_after(members)
+            # (no group crosses a boundary of the log, of any row)
+            k = _steps_in_next_group(remaining, None if residual else self.config.warmup_steps - members[0].step_index, _steps_to_log_boundary(members),
+                                     steps_per_graph, (residual, active, 1) in self._graphs)
+            self._graph_advance(k, active)
             remaining -= k
 
     def capture_all(self, steps_per_graph=4, actives=None):
         """Every eager warm-up step and every capture ``run()`` would meet -- both phases, the one-step and the ``steps_per_graph``-step graph,
         for every frame count in ``actives`` (default: the full batch) -- now, then every frame is reset.  Returns the number of graphs."""
-        cfg = self.config
         k = int(steps_per_graph)
         for active in (actives or [self.size]):
-            _, members = self._members(active)
-            for phase_start in sorted({0, min(cfg.warmup_steps, cfg.num_steps)}):
-                phase_steps = (cfg.warmup_steps if phase_start < cfg.warmup_steps else cfg.num_steps) - phase_start
-                if phase_steps <= 0:
-                    continue
-                with _capture_lock:
-                    for m in members:
-                        m.step_index = phase_start
-                        m.step_tensor.fill_(phase_start)
-                for _ in range(min(4, phase_steps)):     # (with the log these launch it as well: FrameOptimizer.capture_all; the resets below start it over)
-                    self.step(active)
-                if k > 1 and phase_steps >= 4 + k:
-                    self._capture((self._phase(active), active, k), active, k)
+            _capture_phases(self._members(active)[1], k, lambda: self.step(active), lambda: self._graph_advance(k, active))
         with _capture_lock:
             torch.cuda.current_stream(self.device).synchronize()
         for m in self.frames:
