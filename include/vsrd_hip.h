@@ -329,13 +329,29 @@ int32_t vsrd_field_eval(const vsrd_field* field, const float* positions /* [P,3]
 
 /* Adjoint of vsrd_field_eval w.r.t. the field parameters and the positions: the reference's closure call is differentiable
  * (autograd), e.g. sphere_tracing(differentiable=True) (renderers.py:59-72).  grad_distances [P] and/or grad_labels [P,N] (soft
- * union only) may be NULL; the analytic normal output of vsrd_field_eval is NOT differentiated (second order).
+ * union only) may be NULL.  This entry takes no cotangent of the `gradients` output: it is vsrd_field_eval_adjoint (below) with
+ * grad_gradients = NULL, bit for bit, except that it also accepts a call without any cotangent (all gradients are zero then).
  * Needs vsrd_workspace_bytes(N, residual) of scratch.  grad_positions [P,3] or NULL; grad_instances [N,16];
  * grad_mlp_weights [N,1617] (required for residual fields). */
 int32_t vsrd_field_eval_backward(const vsrd_field* field, const float* positions, int64_t num_points,
                                  const float* grad_distances, const float* grad_labels, int32_t hard_union,
                                  void* workspace, size_t workspace_bytes, float* grad_positions,
                                  float* grad_instances, float* grad_mlp_weights, void* stream);
+
+/* The full adjoint of vsrd_field_eval, the analytic normal included (second order): the reference's surface_normal
+ * (renderers.py:100-109) takes the normal with create_graph, so the normal is differentiable w.r.t. the boxes, the residual-MLP
+ * weights and the positions, and the photometric term (scripts/main.py:747-851) reaches the box rotations through it.
+ * grad_gradients [P,3] is the cotangent of vsrd_field_eval's `gradients` output (the UN-normalised union gradient; soft union: through
+ * the soft-min weights and every member's gradient, hard union: through the arg-min member's gradient); the box Hessian and the MLP's
+ * second-order adjoint are taken where they exist -- the kinks of the box SDF (sign(p), the interior arg max, relu(q) = 0, the hard
+ * arg min) contribute nothing, as in autograd.  Contract of vsrd_field_eval_backward: same workspace, same refusals, no allocation, no
+ * host synchronisation, deterministic; in addition at least one of grad_distances, grad_labels, grad_gradients must be non-NULL.
+ * Added within ABI 12: probe for the symbol. */
+int32_t vsrd_field_eval_adjoint(const vsrd_field* field, const float* positions, int64_t num_points,
+                                const float* grad_distances /* [P] or NULL */, const float* grad_labels /* [P,N] or NULL, soft only */,
+                                const float* grad_gradients /* [P,3] or NULL: cotangent of vsrd_field_eval's `gradients` */,
+                                int32_t hard_union, void* workspace, size_t workspace_bytes,
+                                float* grad_positions, float* grad_instances, float* grad_mlp_weights, void* stream);
 
 /* vsrd.rendering.sphere_tracing, non-differentiable part (renderers.py:21-59): march each ray by the union distance until
  * |sdf| < convergence_criteria, it leaves the bounding sphere, or num_iterations is reached.

@@ -78,11 +78,21 @@ __global__ __launch_bounds__(256) void field_eval_kernel(FieldArgs f, const floa
 //   hard:  d_bar_i = u_bar [i = argmin]                                                                          adjoint with g_bar = 0)
 // then the box adjoint of d_i (and the residual MLP's) and  x_bar = sum_i d_bar_i grad d_i.  One wave = 64 points, the instance
 // loop is wave-uniform; per-wave partial rows + reduce_partials_kernel as in the render adjoint (deterministic).
-template <bool kResidual>
+// kGamma: a cotangent gamma [P,3] of the analytic normal as well (surface_normal with create_graph, renderers.py:100-109) -- phase B of
+// the renderer's adjoint (adjoint_phase_b) with g_bar = gamma and no opacity chain:
+//   soft:  d_bar_i += (-beta_i c_i + w_i A - beta_i w_i + c_i B) / T,  beta_i = gamma . grad d_i,  A = gamma . g,  B = gamma . sum_j w_j grad d_j;
+//          member i's world-gradient adjoint is c_i gamma
+//   hard:  the world-gradient adjoint gamma goes to the arg-min member alone, d_bar is unchanged
+//   member: gl_bar = R^T gw_bar;  q_bar += 1[q > 0] (v - h (h . v)) / |relu(q)|_eps,  v = sign(p) gl_bar;  R_bar += gw_bar (x) gl;  the residual
+//          MLP takes gl_bar as its local-gradient adjoint;  x_bar = sum_i (d_bar_i grad d_i + R_i (p_bar_i's second-order part)), for residual
+//          fields sum_i R_i p_bar_i (residual_backward returns both orders of its position adjoint in one).
+// Everything kGamma adds is behind `if (kGamma)`, and grad_gradients is the last argument: the kGamma = false instantiations are the kernels
+// of before (vsrd_field_eval_backward, and vsrd_field_eval_adjoint without a normal cotangent).
+template <bool kResidual, bool kGamma = false>
 __global__ __launch_bounds__(kBlockThreads) void field_eval_backward_kernel(
     FieldArgs f, const float* __restrict__ instances, const float* __restrict__ mlp, const float* __restrict__ positions, long long num_points,
     const float* __restrict__ grad_distances, const float* __restrict__ grad_labels, int hard_union,
-    float* __restrict__ grad_positions, float* __restrict__ partials, float* __restrict__ mlp_partials) {
+    float* __restrict__ grad_positions, float* __restrict__ partials, float* __restrict__ mlp_partials, const float* __restrict__ grad_gradients) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float forward_weights_all[kResidual ? kMaxWavesPerBlock * kMlpWbarFloats : 1];      // residual_forward's staged weights
     float* forward_weights = forward_weights_all + (kResidual ? wave_in_block() * kMlpWbarFloats : 0);
@@ -108,43 +118,108 @@ __global__ __launch_bounds__(kBlockThreads) void field_eval_backward_kernel(
         const float u_bar = (valid && grad_distances) ? grad_distances[idx] : 0.0f;
         // ---- forward quantities of the union ------------------------------------------------------------------------------
         UnionSums sums = union_init();
+        UnionSums gsums = union_init();                                       // kGamma: the sums the union's gradient needs (below)
         float best = 3.0e38f;
         int best_index = 0;
         for (int i = 0; i < N; ++i) {
             const BoxEval e = eval_instance<kResidual>(load_instance(instances, i), kResidual ? mlp + i * kMlpWeights : nullptr, x, y, z, forward_weights);
             const float lambda = (valid && grad_labels && !hard_union) ? grad_labels[idx * N + i] : 0.0f;
             union_accumulate(sums, e.d, e.gwx, e.gwy, e.gwz, lambda, f.inv_t);
+            if (kGamma) {
+                // Without gamma the gradient sums of `sums` are dead and its scalar sums (Z, S1, L) are fused by the compiler as
+                // single-use products; with them alive the products have a second use, fuse otherwise, and u, w_i, c_i -- hence every
+                // d_bar -- come out with other last bits than without gamma.  So the gradient sums are kept in a second set, fed from
+                // a copy of d_i the compiler cannot see through: `sums` is compiled as it is without gamma.
+                float d_copy = e.d;
+                asm volatile("" : "+v"(d_copy));
+                union_accumulate<true, false>(gsums, d_copy, e.gwx, e.gwy, e.gwz, 0.0f, f.inv_t);
+            }
             if (e.d < best) { best = e.d; best_index = i; }                   // argmin: first minimum
         }
         const UnionValue v = union_finish(sums, f.inv_t);
         const float lam_z = sums.L * v.inv_z;
+        float gmx = 0.0f, gmy = 0.0f, gmz = 0.0f, gamma_a = 0.0f, gamma_b = 0.0f;
+        if (kGamma) {
+            if (valid && grad_gradients) { gmx = grad_gradients[idx * 3 + 0]; gmy = grad_gradients[idx * 3 + 1]; gmz = grad_gradients[idx * 3 + 2]; }
+            const UnionValue gv = union_finish(gsums, f.inv_t);
+            gamma_a = gmx * gv.gx + gmy * gv.gy + gmz * gv.gz;                   // A = gamma . g
+            gamma_b = gmx * gv.b0x + gmy * gv.b0y + gmz * gv.b0z;                // B = gamma . sum_j w_j grad d_j
+        }
         // ---- per instance ------------------------------------------------------------------------------------------------------
         float xb = 0.0f, yb = 0.0f, zb = 0.0f;
         for (int i = 0; i < N; ++i) {
             const Instance in = load_instance(instances, i);
             const BoxEval e = eval_instance<kResidual>(in, kResidual ? mlp + i * kMlpWeights : nullptr, x, y, z, forward_weights);
             float d_bar;
+            float share = 0.0f, rgx = 0.0f, rgy = 0.0f, rgz = 0.0f;          // kGamma: this member's share of gamma, and R^T gamma
+            if (kGamma) {
+                rgx = fmaf(in.r20, gmz, fmaf(in.r10, gmy, in.r00 * gmx));
+                rgy = fmaf(in.r21, gmz, fmaf(in.r11, gmy, in.r01 * gmx));
+                rgz = fmaf(in.r22, gmz, fmaf(in.r12, gmy, in.r02 * gmx));
+            }
             if (hard_union) {
                 d_bar = (i == best_index) ? u_bar : 0.0f;
+                if (kGamma) share = (i == best_index) ? 1.0f : 0.0f;
             } else {
                 const float ds = e.d - v.m;
                 const float w = fast_exp(-ds * f.inv_t) * v.inv_z;
                 const float cc = w * (1.0f - (ds - v.us) * f.inv_t);
                 const float lambda = (valid && grad_labels) ? grad_labels[idx * N + i] : 0.0f;
                 d_bar = u_bar * cc - f.inv_t * w * (lambda - lam_z);
+                if (kGamma) {
+                    // (d_bar's first-order part rounded on its own, as without gamma: left open, the addition below changes which of its
+                    //  products the compiler fuses, and gamma = 0 gives other bits than no gamma)
+                    asm volatile("" : "+v"(d_bar));
+                    const float beta = rgx * e.glx + rgy * e.gly + rgz * e.glz;       // gamma . grad d_i = (R^T gamma) . gl
+                    d_bar += f.inv_t * (-beta * cc + w * gamma_a - beta * w + cc * gamma_b);
+                    share = cc;
+                }
             }
-            xb += d_bar * e.gwx; yb += d_bar * e.gwy; zb += d_bar * e.gwz;
+            if (!(kGamma && kResidual)) { xb += d_bar * e.gwx; yb += d_bar * e.gwy; zb += d_bar * e.gwz; }
             // box adjoint of d_i with no gradient adjoint: q_bar = d_bar h, p_bar = sign(p) q_bar (+ the residual's)
-            const float qbx = d_bar * e.hx, qby = d_bar * e.hy, qbz = d_bar * e.hz;
+            float qbx = d_bar * e.hx, qby = d_bar * e.hy, qbz = d_bar * e.hz;
             float pbx = sign_of(e.px) * qbx, pby = sign_of(e.py) * qby, pbz = sign_of(e.pz) * qbz;
-            if (kResidual) {
-                const ResidualAdjoint ra = residual_backward(mlp + i * kMlpWeights, e.px, e.py, e.pz, d_bar, 0.0f, 0.0f, 0.0f, wbar, lane, 0xFu);
-                pbx += ra.px; pby += ra.py; pbz += ra.pz;
+            float glbx = 0.0f, glby = 0.0f, glbz = 0.0f, gwbx = 0.0f, gwby = 0.0f, gwbz = 0.0f;
+            if (kGamma) {
+                // the member's gradient adjoint in both frames, and the box Hessian's part of q_bar (adjoint_phase_b); the interior one-hot
+                // term of h and sign(p) have no derivative
+                gwbx = share * gmx; gwby = share * gmy; gwbz = share * gmz;
+                glbx = share * rgx; glby = share * rgy; glbz = share * rgz;
+                const float sx = sign_of(e.px), sy = sign_of(e.py), sz = sign_of(e.pz);
+                const float vx = sx * glbx, vy = sy * glby, vz = sz * glbz;
+                const float inv_n = box_inverse_norm(e);
+                const float hx = fmaxf(e.qx, 0.0f) * inv_n, hy = fmaxf(e.qy, 0.0f) * inv_n, hz = fmaxf(e.qz, 0.0f) * inv_n;
+                const float hv = hx * vx + hy * vy + hz * vz;
+                const float ex = (e.qx > 0.0f) ? (vx - hx * hv) * inv_n : 0.0f;
+                const float ey = (e.qy > 0.0f) ? (vy - hy * hv) * inv_n : 0.0f;
+                const float ez = (e.qz > 0.0f) ? (vz - hz * hv) * inv_n : 0.0f;
+                qbx += ex; qby += ey; qbz += ez;
+                pbx = sx * qbx; pby = sy * qby; pbz = sz * qbz;
+                if (!kResidual) {       // x_bar: the first-order part as without gamma (above), the Hessian's part through R
+                    const float ox = sx * ex, oy = sy * ey, oz = sz * ez;
+                    xb += in.r00 * ox + in.r01 * oy + in.r02 * oz;
+                    yb += in.r10 * ox + in.r11 * oy + in.r12 * oz;
+                    zb += in.r20 * ox + in.r21 * oy + in.r22 * oz;
+                }
             }
-            const float packed[16] = {-(in.r00 * pbx + in.r01 * pby + in.r02 * pbz), -(in.r10 * pbx + in.r11 * pby + in.r12 * pbz),
-                                      -(in.r20 * pbx + in.r21 * pby + in.r22 * pbz),
-                                      e.relx * pbx, e.relx * pby, e.relx * pbz, e.rely * pbx, e.rely * pby, e.rely * pbz,
-                                      e.relz * pbx, e.relz * pby, e.relz * pbz, -qbx, -qby, -qbz, 0.0f};
+            if (kResidual) {
+                const ResidualAdjoint ra = residual_backward(mlp + i * kMlpWeights, e.px, e.py, e.pz, d_bar, glbx, glby, glbz, wbar, lane, 0xFu);
+                pbx += ra.px; pby += ra.py; pbz += ra.pz;
+                if (kGamma) {           // the MLP returns both orders of its position adjoint in one: x_bar = R p_bar
+                    xb += in.r00 * pbx + in.r01 * pby + in.r02 * pbz;
+                    yb += in.r10 * pbx + in.r11 * pby + in.r12 * pbz;
+                    zb += in.r20 * pbx + in.r21 * pby + in.r22 * pbz;
+                }
+            }
+            float packed[16] = {-(in.r00 * pbx + in.r01 * pby + in.r02 * pbz), -(in.r10 * pbx + in.r11 * pby + in.r12 * pbz),
+                                -(in.r20 * pbx + in.r21 * pby + in.r22 * pbz),
+                                e.relx * pbx, e.relx * pby, e.relx * pbz, e.rely * pbx, e.rely * pby, e.rely * pbz,
+                                e.relz * pbx, e.relz * pby, e.relz * pbz, -qbx, -qby, -qbz, 0.0f};
+            if (kGamma) {               // R_bar += gw_bar (x) gl  (gl: the member's local gradient, the residual's included)
+                packed[3] += gwbx * e.glx; packed[4] += gwbx * e.gly; packed[5] += gwbx * e.glz;
+                packed[6] += gwby * e.glx; packed[7] += gwby * e.gly; packed[8] += gwby * e.glz;
+                packed[9] += gwbz * e.glx; packed[10] += gwbz * e.gly; packed[11] += gwbz * e.glz;
+            }
             const float mine = wave_reduce16_scatter(packed, lane);
             if (lane < kGradStride) G[i * kGradStride + lane] += mine;
             if (kResidual) {

@@ -445,8 +445,9 @@ def hierarchical_volumetric_rendering(
 
 
 class _EvaluateField(torch.autograd.Function):
-    """vsrd_field_eval / vsrd_field_eval_backward: the closure call of scripts/main.py:433-509, differentiable w.r.t. the field
-    parameters and the positions through the distances and the labels (the analytic normal output is not differentiated)."""
+    """vsrd_field_eval / vsrd_field_eval_adjoint: the closure call of scripts/main.py:433-509, differentiable w.r.t. the field
+    parameters and the positions through the distances, the labels and the analytic normal (second order: what the reference's
+    surface_normal gets from autograd.grad(..., create_graph=True), renderers.py:100-109)."""
 
     @staticmethod
     def forward(ctx, instances, mlp_weights, positions, temperature, hard, want_gradients, want_labels):
@@ -465,17 +466,20 @@ class _EvaluateField(torch.autograd.Function):
         ctx.meta = (temperature, hard)
         ctx.set_materialize_grads(False)
         outs = (distances, labels if want_labels else distances.new_empty(0), gradients if want_gradients else distances.new_empty(0))
-        ctx.mark_non_differentiable(outs[2])
+        if not want_gradients:
+            ctx.mark_non_differentiable(outs[2])
         return outs
 
     @staticmethod
-    def backward(ctx, grad_distances, grad_labels, _grad_normals):
+    def backward(ctx, grad_distances, grad_labels, grad_normals):
         lib = _lib.load()
         instances, positions, *rest = ctx.saved_tensors
         mlp_weights = rest[0] if rest else None
         temperature, hard = ctx.meta
         if grad_labels is not None and grad_labels.numel() == 0:
             grad_labels = None
+        if grad_normals is not None and grad_normals.numel() == 0:
+            grad_normals = None
         P, N = positions.shape[0], instances.shape[0]
         grad_distances = None if grad_distances is None else grad_distances.to(torch.float32).contiguous()
         grad_labels = None if grad_labels is None else grad_labels.to(torch.float32).contiguous()
@@ -484,16 +488,25 @@ class _EvaluateField(torch.autograd.Function):
         grad_mlp = None if mlp_weights is None else torch.empty_like(mlp_weights)
         workspace = _workspace(positions.device, N, mlp_weights is not None)
         field = _lib.make_field(instances, temperature, mlp_weights)
-        _lib.check(lib.vsrd_field_eval_backward(field, _lib.ptr(positions), P, _lib.ptr(grad_distances), _lib.ptr(grad_labels), 1 if hard else 0,
-                                                workspace.data_ptr(), workspace.numel(), _lib.ptr(grad_positions), _lib.ptr(grad_instances),
-                                                _lib.ptr(grad_mlp), _lib.stream()))
+        if grad_normals is None:      # no cotangent of the normal: the call (and its bits) of before
+            _lib.check(lib.vsrd_field_eval_backward(field, _lib.ptr(positions), P, _lib.ptr(grad_distances), _lib.ptr(grad_labels), 1 if hard else 0,
+                                                    workspace.data_ptr(), workspace.numel(), _lib.ptr(grad_positions), _lib.ptr(grad_instances),
+                                                    _lib.ptr(grad_mlp), _lib.stream()))
+        else:
+            if not hasattr(lib, "vsrd_field_eval_adjoint"):
+                raise _lib.VsrdHipError("libvsrd_hip has no vsrd_field_eval_adjoint: the normal of this field cannot be differentiated")
+            grad_normals = grad_normals.to(torch.float32).contiguous()
+            _lib.check(lib.vsrd_field_eval_adjoint(field, _lib.ptr(positions), P, _lib.ptr(grad_distances), _lib.ptr(grad_labels), _lib.ptr(grad_normals),
+                                                   1 if hard else 0, workspace.data_ptr(), workspace.numel(), _lib.ptr(grad_positions),
+                                                   _lib.ptr(grad_instances), _lib.ptr(grad_mlp), _lib.stream()))
         return grad_instances, grad_mlp, grad_positions, None, None, None, None
 
 
 def evaluate_field(distance_field, positions, with_gradients=False, with_labels=None):
     """What calling the reference closure does (main.py:477-509): soft union -> (distances [...,1], labels [...,N]);
     hard union / plain sdfs -> distances [...,1].  ``with_gradients`` adds the analytic normal [...,3].
-    Distances and labels are autograd-connected to the field parameters and to ``positions`` (vsrd_field_eval_backward)."""
+    Distances, labels and the normal are autograd-connected to the field parameters and to ``positions`` (vsrd_field_eval_adjoint):
+    with grad mode on and an input that requires grad, the normal is attached to the graph."""
     block = flatten(distance_field)
     one_hot = None
     if with_labels is None:  # the soft union returns (distances, features); plain sdfs / hard unions distances only
@@ -538,10 +551,10 @@ def sphere_tracing(distance_field, ray_positions, ray_directions, num_iterations
     positions, converged = positions.reshape(*lead, 3), converged.to(torch.bool).reshape(*lead, 1)
     if differentiable:
         # renderers.py:59-72: one Newton step along the ray at the traced point; the step length -sdf / (grad sdf . r) carries the
-        # dependence on the field parameters (the normal enters as a constant, exactly as the reference's autograd.grad without
-        # create_graph leaves it)
+        # dependence on the field parameters.  The normal enters as a constant, exactly as the reference's autograd.grad without
+        # create_graph leaves it: evaluate_field's normal is attached to the graph, so it is detached here.
         out = evaluate_field(distance_field, positions, with_gradients=True, with_labels=False)
-        sdf, normals = out[0], out[-1]
+        sdf, normals = out[0], out[-1].detach()
         step = -sdf / (normals * ray_directions.to(normals.dtype)).sum(dim=-1, keepdim=True)
         positions = torch.where(converged, positions + ray_directions * step, positions)
     return positions, converged
@@ -586,7 +599,10 @@ def shadow_rendering(distance_field, surface_positions, surface_normals, light_d
 
 def surface_normal(distance_field, surface_positions, finite_difference_epsilon=None):
     """Drop-in for vsrd.rendering.surface_normal (renderers.py:76-113): unit normals of the field at the given points
-    (analytic gradient, or central differences when finite_difference_epsilon is given).  Not differentiable w.r.t. the field."""
+    (analytic gradient, or central differences when finite_difference_epsilon is given).  Differentiable w.r.t. the boxes, the residual-MLP
+    weights and the positions, as the reference's (autograd.grad with create_graph = torch.is_grad_enabled(), renderers.py:100-109): the
+    analytic branch through vsrd_field_eval_adjoint, the finite-difference branch through the distances.  Under torch.no_grad() no graph is
+    built."""
     if finite_difference_epsilon:
         eps = float(finite_difference_epsilon)
         offsets = torch.eye(3, device=surface_positions.device, dtype=surface_positions.dtype) * eps
