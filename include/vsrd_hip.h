@@ -353,8 +353,16 @@ int32_t vsrd_field_eval_adjoint(const vsrd_field* field, const float* positions,
                                 int32_t hard_union, void* workspace, size_t workspace_bytes,
                                 float* grad_positions, float* grad_instances, float* grad_mlp_weights, void* stream);
 
-/* vsrd.rendering.sphere_tracing, non-differentiable part (renderers.py:21-59): march each ray by the union distance until
- * |sdf| < convergence_criteria, it leaves the bounding sphere, or num_iterations is reached.
+/* vsrd.rendering.sphere_tracing, non-differentiable part (renderers.py:21-59): the reference's loop without its batch-wide early exit,
+ * so that a ray's outputs depend on that ray alone -- not on its place in the launch nor on the other rays (the loop with and without
+ * that exit gives identical output on every fixture: tests/test_sphere_trace_reference.py).  Per iteration: evaluate the
+ * union distance d at the position; move by d along the direction if the ray is foreground and was not converged by the previous
+ * iteration; clear foreground (for good) once the position is on or beyond the bounding sphere; set converged = |d| < convergence_criteria.
+ * converged is overwritten in every iteration: a converged ray stays put for one iteration and is judged again by the distance at the
+ * point it reached; a ray that stepped past a rim un-converges and marches on.  A ray is finished, before num_iterations, only once
+ * it is stationary (it did not move and may not move next).  A ray that is not foreground never moves; its flag is |d| < criteria at
+ * its position.  A position that is not finite is never converged.  num_iterations = 0: positions are the origins (or entry points),
+ * converged 0.
  * origins [R,3] (origin_stride 3) or [3] (stride 0); foreground [R] uint8 or NULL (= all finite origins);
  * bounding_radius <= 0: none; initialise != 0: start from the bounding-sphere entry point (renderers.py:36-43).
  * Outputs: positions [R,3], converged [R] uint8 (the reference's convergence_masks). */

@@ -184,6 +184,26 @@ class InstanceUnion:
     def distance(self, positions):
         return self.evaluate(positions)[0]
 
+    def instance_distances(self, positions):
+        """Per-instance distance [N,...] alone, without the gradients of instance_terms: what a march evaluates at every step."""
+        lead = (self.num_instances,) + (1,) * (positions.dim() - 1)
+        rel = positions.unsqueeze(0) - self.locations.reshape(*lead, 3)
+        local = (rel.unsqueeze(-2) @ self.orientations.reshape(*lead, 3, 3)).squeeze(-2)
+        q = local.abs() - self.dimensions.reshape(*lead, 3)
+        outside = F.relu(q)
+        d = torch.sqrt((outside * outside).sum(-1) + NORM_EPSILON) - F.relu(-q.max(dim=-1).values)
+        if self.mlp_weights is not None:
+            folded = torch.stack([local[..., 0].abs(), local[..., 1], local[..., 2]], dim=-1) / POSITION_SCALE
+            d = d + torch.sigmoid(instance_mlp(self.mlp_weights.reshape(*lead, -1), sinusoidal_features(folded)) - 1.0)
+        return d
+
+    def union_distance(self, positions, hard=False):
+        """The soft (or hard) union's distance from instance_distances: evaluate()[0] / hard_distance() without their gradients."""
+        d = self.instance_distances(positions)
+        if hard:
+            return d.min(dim=0).values
+        return (torch.softmax(-d / self.temperature, dim=0) * d).sum(0)
+
     def hard_distance(self, positions):
         """main.py:494-509 hard union (arg-min instance)."""
         d, _ = self.instance_terms(positions)

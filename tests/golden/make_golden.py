@@ -467,6 +467,64 @@ def golden_sphere_tracing(ref):
          temperature=np.array(0.1, dtype=np.float32), surface_positions=pos, convergence_masks=conv, surface_normals=normals.detach())
 
 
+GRAZING_TEMPERATURES = (0.3, 0.05)     # the third field of G19 is the hard union
+GRAZING_TRACE = (64, 0.01, 100.0)      # iterations, convergence criterion, bounding radius
+GRAZING_RAYS = 1000                    # per field: no multiple of the wave size
+
+
+def make_hard_union(fields):
+    # scripts/main.py:494-509, distances only
+    def field(positions):
+        distances = torch.stack([f(positions)[0] for f in fields])
+        return torch.gather(distances, index=torch.argmin(distances, dim=0, keepdim=True), dim=0).squeeze(0)
+    return field
+
+
+def golden_sphere_tracing_grazing(ref):
+    """G19: rays that graze a rim.  A ray whose closest approach is a little under the convergence criterion converges, steps past the
+    closest point and un-converges in the next iteration (renderers.py:56 overwrites the mask every iteration); it then leaves the
+    sphere or hits what stands behind.  Candidates: a 96 x 320 pinhole image (focal 200) of the three boxes of
+    tests/test_hip_frame_masks.py::scene; kept per field: every candidate on which a march that stops at the first convergence
+    (oracle.tracing, float32) differs from the reference's output -- the mask, or the position by more than 1 m -- and an even subsample
+    of the others."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT_DIR)))
+    from oracle import fields as ofields, tracing as otracing
+    H, W, focal = 96, 320, 200.0
+    loc = torch.tensor([[-2.0, 0.3, 10.0], [-1.0, 0.1, 16.0], [3.0, 0.2, 9.0]])
+    dims = torch.tensor([[0.9, 0.45, 1.8], [1.0, 0.6, 2.0], [0.8, 0.5, 1.6]])
+    rot = torch.stack([rotation_y(a) for a in (0.3, -0.4, 1.1)])
+    y, x = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    candidates = nn.functional.normalize(torch.stack([(x - (W - 1) / 2) / focal, (y - (H - 1) / 2) / focal, torch.ones_like(x)], -1), dim=-1).reshape(-1, 3)
+    origin = torch.zeros(3)
+    members = [ref.sdfs.translation(ref.sdfs.rotation(make_instance_field(ref.sdfs.box(dims[i]), i, 3), rot[i]), loc[i]) for i in range(3)]
+    oracle_union = [ofields.InstanceUnion(loc, rot, dims, t) for t in GRAZING_TEMPERATURES] + [ofields.InstanceUnion(loc, rot, dims, 1.0)]
+    iterations, criteria, radius = GRAZING_TRACE
+    directions, positions, masks, flags = [], [], [], []
+    for k in range(3):
+        hard = k == len(GRAZING_TEMPERATURES)
+        union = make_hard_union(members) if hard else make_soft_union(members, GRAZING_TEMPERATURES[k])
+        field = union if hard else (lambda p, union=union: union(p)[0])
+        with torch.no_grad():
+            pos, conv = ref.renderers.sphere_tracing(field, origin.expand_as(candidates), candidates, num_iterations=iterations,
+                                                     convergence_criteria=criteria, bounding_radius=radius, initialization=False)
+        conv = conv[:, 0]
+        retired = otracing.trace(oracle_union[k].hard_distance if hard else oracle_union[k].distance, origin, candidates, iterations, criteria,
+                                 bounding_radius=radius, initialise=False, stop_at_first_convergence=True)
+        differs = (retired.converged != conv) | ((retired.positions - pos).norm(dim=-1) > 1.0)
+        chosen = torch.nonzero(differs)[:, 0]
+        assert len(chosen) < GRAZING_RAYS
+        rest = torch.nonzero(~differs)[:, 0]
+        rest = rest[torch.linspace(0, len(rest) - 1, GRAZING_RAYS - len(chosen)).round().long()]
+        keep = torch.sort(torch.cat([chosen, rest])).values
+        assert len(torch.unique(keep)) == GRAZING_RAYS
+        print(f"  g19 field {k} ({'hard' if hard else 'T = %g' % GRAZING_TEMPERATURES[k]}): {int(conv.sum())} of {len(conv)} candidates converged, "
+              f"{len(chosen)} differ under the retired rule")
+        directions.append(candidates[keep]); positions.append(pos[keep]); masks.append(conv[keep]); flags.append(differs[keep])
+    save("g19_sphere_tracing_grazing", locations=loc, dimensions=dims, orientations=rot, temperatures=np.array(GRAZING_TEMPERATURES, dtype=np.float32),
+         trace=np.array(GRAZING_TRACE, dtype=np.float32), directions=torch.stack(directions), surface_positions=torch.stack(positions),
+         convergence_masks=torch.stack(masks), discriminating=torch.stack(flags))
+
+
 def golden_soft_rasterizer():
     """N2: SoftRasterizer.make_distance_map + the soft-mask formula (geometric_transforms.py:265-317).
     The module imports torchvision / cv2 / skimage at the top; empty placeholder modules let the import through and are
@@ -652,6 +710,10 @@ def main():
     if "--loss-library-rest" in sys.argv:  # only G18
         golden_loss_library_rest()
         return
+    if "--grazing" in sys.argv:            # only G19
+        golden_sphere_tracing_grazing(ref)
+        return
+    golden_sphere_tracing_grazing(ref)
     golden_rendering_bench_shapes(ref)
     golden_loss_library_rest()
     golden_rendering_helpers(ref)

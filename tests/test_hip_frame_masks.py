@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import fields as ofields, rendering as orendering
+from conftest import load_golden
+from oracle import fields as ofields, rendering as orendering, tracing as otracing
 
 pytestmark = pytest.mark.gpu
 
@@ -58,18 +59,19 @@ def pointer(t):
 
 
 def run_masks(dev, instances, W, cam, dirs, mlp=None, u=None, targets=None, columns=None, view=0, soft=True, header=None, frames=None, out=None,
-              flags=0, stream_offset=0, seed=0, stride=None, trace=TRACE, num_samples=S, capacity=None):
+              flags=0, stream_offset=0, seed=0, stride=None, trace=TRACE, num_samples=S, capacity=None, height=None):
     """One vsrd_frame_masks call -> (code, dict of outputs).  `out`: pre-made output tensors (batches); else sentinel-filled ones."""
+    rows = H if height is None else height
     from vsrd_amd import _lib
     lib = _lib.load()
     N = int(instances.shape[0]) if capacity is None else capacity
     V = int(cam.shape[0])
     field = _lib.Field(N, T, instances.data_ptr(), None if mlp is None else mlp.data_ptr())
     config = _lib.make_config(0, num_samples, RANGE, STD, RATIO, 1.0e-6, 3, seed=seed, stream_offset=stream_offset, flags=flags, frames=frames)
-    masks = _lib.FrameMasksConfig(view, V, H, W, trace[0], trace[1], trace[2], THRESHOLD, N if stride is None else stride)
+    masks = _lib.FrameMasksConfig(view, V, rows, W, trace[0], trace[1], trace[2], THRESHOLD, N if stride is None else stride)
     if out is None:
-        out = dict(inside=torch.full((N, H, (W + 7) // 8 + 3), SENTINEL, dtype=torch.uint8, device=dev)[:, :, :(W + 7) // 8].contiguous(),
-                   soft=torch.full((H * W, N), float("nan"), device=dev) if soft else None,
+        out = dict(inside=torch.full((N, rows, (W + 7) // 8 + 3), SENTINEL, dtype=torch.uint8, device=dev)[:, :, :(W + 7) // 8].contiguous(),
+                   soft=torch.full((rows * W, N), float("nan"), device=dev) if soft else None,
                    counts=torch.full((N, 3), -7, dtype=torch.int32, device=dev) if targets is not None else None)
     code = lib.vsrd_frame_masks(field, config, masks, pointer(cam), pointer(dirs), pointer(None if u is None else u[0]), pointer(None if u is None else u[1]),
                                 pointer(targets), pointer(columns), pointer(out["inside"]), pointer(out["soft"]), pointer(out["counts"]),
@@ -163,22 +165,10 @@ def test_against_the_existing_entry_points(dev, residual, golden):
 
 
 def oracle_trace(union, origin, directions):
-    """sphere_tracing(initialization=False, differentiable=False) in float64 (renderers.py:21-59) -> converged, |sdf| of the last evaluation."""
-    positions = origin.expand_as(directions).clone()
-    foreground = torch.ones(len(directions), dtype=torch.bool)
-    converged = torch.zeros(len(directions), dtype=torch.bool)
-    last = torch.full((len(directions),), float("inf"), dtype=torch.float64)
-    for _ in range(TRACE[0]):
-        active = foreground & ~converged
-        if not bool(active.any()):
-            break
-        sd = union.distance(positions)
-        positions = torch.where(active[:, None], positions + directions * sd[:, None], positions)
-        inside = positions.norm(dim=-1) < TRACE[2]
-        last = torch.where(active, sd.abs(), last)
-        converged = torch.where(active, sd.abs() < TRACE[1], converged)
-        foreground = torch.where(active, foreground & inside, foreground)
-    return converged, last
+    """sphere_tracing(initialization=False, differentiable=False) in float64 (renderers.py:21-59) without its batch-wide exit (oracle.tracing)
+    -> converged, borderline: a decision anywhere along the ray's path within 1e-4 relative of its threshold."""
+    out = otracing.trace(union.distance, origin, directions, TRACE[0], TRACE[1], bounding_radius=TRACE[2], initialise=False, early_exit=False)
+    return out.converged, otracing.borderline(out, TRACE[1], TRACE[2])
 
 
 def test_against_the_float64_oracle(dev):
@@ -189,14 +179,13 @@ def test_against_the_float64_oracle(dev):
     u = uniforms(W)
     origin = cam[0].double()
     with torch.no_grad():
-        converged, last = oracle_trace(union, origin, dirs.double())
+        converged, borderline = oracle_trace(union, origin, dirs.double())
         labels = orendering.hierarchical_render(union, origin.expand(H * W, 3), dirs.double(), RANGE, S, STD, RATIO, u[0].double(), u[1].double()).labels
     want = labels * converged[:, None]
     code, out = run_masks(dev, instances_of(dev, N), W, cam.to(dev), dirs.to(dev), u=[t.to(dev) for t in u])
     assert code == 0
     torch.cuda.synchronize()
     soft = out["soft"].cpu().double()
-    borderline = (last - TRACE[1]).abs() <= 1.0e-4 * TRACE[1]
     mine = (soft != 0).any(-1) | converged & (want == 0).all(-1)
     assert not ((mine != converged) & ~borderline).any()
     assert int(borderline.sum()) <= 0.01 * H * W
@@ -206,6 +195,47 @@ def test_against_the_float64_oracle(dev):
     assert error < LABEL_TOL
     decided = ((want - THRESHOLD).abs() > LABEL_TOL) & agreed[:, None]
     bits = torch.from_numpy(np.unpackbits(out["inside"].cpu().numpy(), axis=-1)[:, :, :W]).bool().permute(1, 2, 0).reshape(H * W, N)
+    assert torch.equal(bits[decided], (want > THRESHOLD)[decided])
+
+
+def test_grazing_rays_against_the_reference(dev):
+    """G19's T = 0.3 rays (tests/golden/make_golden.py: rays that converge at a rim, step past it and un-converge) as an 8 x 125 image:
+    where the trace phase converged -- soft's zero pattern, and no bit outside it -- against the reference's own convergence masks, and the
+    labels against the float64 oracle, off the borderline set.  A trace that stops at the first convergence fails here on the
+    discriminating rays."""
+    g = load_golden("g19_sphere_tracing_grazing")
+    height, W, N = 8, 125, 3
+    dirs, want_converged, flagged = g["directions"][0], g["convergence_masks"][0], g["discriminating"][0]
+    loc, dim, rot = g["locations"], g["dimensions"], g["orientations"]
+    union = ofields.InstanceUnion(loc.double(), rot.double(), dim.double(), T)
+    origin = torch.zeros(3, dtype=torch.float64)
+    gen = torch.Generator().manual_seed(19)
+    u = torch.rand(height * W, S, generator=gen), torch.rand(height * W, S, generator=gen)
+    with torch.no_grad():
+        converged, borderline = oracle_trace(union, origin, dirs.double())
+        labels = orendering.hierarchical_render(union, origin.expand(height * W, 3), dirs.double(), RANGE, S, STD, RATIO, u[0].double(), u[1].double()).labels
+    keep = ~borderline
+    assert int(borderline.sum()) <= 0.01 * height * W
+    assert torch.equal(converged[keep], want_converged[keep])                      # the oracle is the reference here
+    from vsrd_amd import fields
+    instances = fields.pack_instances(loc, rot, dim).to(dev)
+    code, out = run_masks(dev, instances, W, torch.zeros(1, 3, device=dev), dirs.to(dev).contiguous(), u=[t.to(dev) for t in u], height=height)
+    assert code == 0
+    torch.cuda.synchronize()
+    soft = out["soft"].cpu().double()
+    want = labels * want_converged[:, None]
+    mine = (soft != 0).any(-1) | want_converged & (want == 0).all(-1)
+    wrong = (mine != want_converged) & keep
+    print(f"converged {int(want_converged.sum())} of {height * W}, discriminating {int(flagged.sum())}, borderline {int(borderline.sum())}, wrong {int(wrong.sum())}")
+    assert not wrong.any(), torch.nonzero(wrong)[:, 0].tolist()
+    assert int((flagged & keep).sum()) >= 16
+    bits = torch.from_numpy(np.unpackbits(out["inside"].cpu().numpy(), axis=-1)[:, :, :W]).bool().permute(1, 2, 0).reshape(height * W, N)
+    assert not (bits.any(-1) & ~want_converged & keep).any()                       # no bit where the reference did not converge
+    agreed = mine == want_converged
+    error = (soft - want).abs()[agreed].max()
+    print(f"max |soft - oracle| = {float(error):.3e} over {int(agreed.sum())} pixels")
+    assert error < LABEL_TOL
+    decided = ((want - THRESHOLD).abs() > LABEL_TOL) & agreed[:, None]
     assert torch.equal(bits[decided], (want > THRESHOLD)[decided])
 
 

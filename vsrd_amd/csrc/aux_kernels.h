@@ -256,9 +256,13 @@ __device__ __forceinline__ float union_distance(const FieldArgs& f, const float*
     return hard_union ? m : (m + S1 * fast_rcp(Z));
 }
 
-// vsrd.rendering.sphere_tracing (renderers.py:21-59, the non-differentiable part), one thread per ray.  The reference
-// evaluates every ray until ALL have stopped (a host sync per iteration, :57); a stopped ray no longer moves, so stopping
-// each thread on its own condition gives identical positions and masks.
+// vsrd.rendering.sphere_tracing (renderers.py:21-59, the non-differentiable part), one thread per ray: the reference's loop without
+// its batch-wide exit (a host sync per iteration, :57), so that a ray's result depends on that ray alone.  The reference overwrites the
+// convergence mask in EVERY iteration (:56): a ray converged by iteration k stays put in k + 1 and is judged again by the distance at the
+// point it was moved to in k; a ray that stepped past a rim un-converges and walks on.  A lane is therefore finished only once it is
+// stationary: it did not move in this iteration and may not move in the next (not foreground, or converged).  From then on the same point
+// gives the same distance and the same flags for ever.  A non-foreground ray gets the one evaluation its flag reflects, a converged ray
+// one confirming evaluation.  A position that is not finite (a NaN or inf origin) is never converged: the reference's distance is NaN there.
 //   origins: origin_stride 3 (per ray) or 0 (shared); foreground [R] (uint8, in/out semantics of `foreground_masks`)
 //   bounding_radius <= 0: no bounding sphere.  initialise != 0: start at the sphere entry point (renderers.py:36-43).
 template <bool kResidual>
@@ -293,10 +297,11 @@ __global__ __launch_bounds__(256) void sphere_trace_kernel(FieldArgs f, const fl
         for (int it = 0; it < num_iterations; ++it) {
             const float sd = union_distance<kResidual>(f, instances, mlp, px, py, pz, hard_union, forward_weights);     // all lanes, stopped or not
             if (!done) {
-                if (fg && !conv) { px += dx * sd; py += dy * sd; pz += dz * sd; }
+                const bool moved = fg && !conv;
+                if (moved) { px += dx * sd; py += dy * sd; pz += dz * sd; }
                 if (bounding_radius > 0.0f) fg = fg && (sqrtf(px * px + py * py + pz * pz) < bounding_radius);
-                conv = fabsf(sd) < criteria;
-                done = !fg || conv;
+                conv = fabsf(sd) < criteria && isfinite(px) && isfinite(py) && isfinite(pz);      // (the box distance's fmaxf drops a NaN; the reference's relu keeps it)
+                done = !moved && !(fg && !conv);                   // stationary
             }
             if (!wave_any(!done)) break;
         }

@@ -4,7 +4,8 @@
 // One wave owns a run of 64 horizontally consecutive pixels of one image row of one frame:
 //
 //   1. trace     one lane per pixel: the march of sphere_trace_kernel (aux_kernels.h) with the soft union, foreground = finite origin, no
-//                initialisation -> `converged` per lane, its ballot per run
+//                initialisation; a lane is finished once it is stationary, not at its first convergence (a ray that steps past a rim
+//                un-converges, as in the reference) -> `converged` per lane, its ballot per run
 //   2. render    only the converged pixels of the run, one ray at a time with the whole wave: the body of render_hierarchical_kernel
 //                (render_kernels.h: cull_ray_setup, stage_ray_samples, render_pass, importance_merge, render_pass); a run without a
 //                converged pixel renders nothing.  Ray p = y W + x reads row p of the recorded uniforms, or the Philox stream keyed by p
@@ -89,10 +90,11 @@ __global__ __launch_bounds__(kBlockThreads) void frame_masks_kernel(
         for (int it = 0; it < m.num_iterations; ++it) {
             const float sd = union_distance<kResidual>(f, instances, mlp, px, py, pz, 0, mine);       // all lanes, stopped or not
             if (!done) {
-                if (fg && !conv) { px += dx * sd; py += dy * sd; pz += dz * sd; }
+                const bool moved = fg && !conv;
+                if (moved) { px += dx * sd; py += dy * sd; pz += dz * sd; }
                 if (m.bounding_radius > 0.0f) fg = fg && (sqrtf(px * px + py * py + pz * pz) < m.bounding_radius);
-                conv = fabsf(sd) < m.criteria;
-                done = !fg || conv;
+                conv = fabsf(sd) < m.criteria && isfinite(px) && isfinite(py) && isfinite(pz);
+                done = !moved && !(fg && !conv);                   // stationary (aux_kernels.h)
             }
             if (!wave_any(!done)) break;
         }
