@@ -853,6 +853,28 @@ int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* con
                                         void* workspace, size_t workspace_bytes, const float* stats, const float* grad_loss,
                                         float* grad_positions, float* grad_normals, void* stream);
 
+/* Box decode (added within ABI 12; probe for the symbols -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the forward
+ * of the reference's BoxParameters3D (vsrd/models/detectors/box_parameters.py:16-146) for ONE frame and its autograd backward, one launch
+ * each, without host synchronisation or allocation, capturable.  The arithmetic is tiny; what the calls buy is launch count on the
+ * optimisation step's dependent chain (eager torch: ~35 element-wise launches per step).  It is torch's arithmetic op for op -- sigmoid as
+ * 1 / (1 + exp(-x)), lerp in ATen's two-sided form, F.normalize with its 1e-12 clamp, the rotation about y with exact 0 and 1 entries,
+ * corners (u_k * dim) R^T + loc -- and the backward chains the cotangents as torch's autograd does.
+ * In: raw_locations, raw_dimensions [N,3], raw_orientations [N,2]; location_range, dimension_range [2,3] (lower | upper bounds), device memory.
+ * Out: instances [N,16] = location | rotation row-major | dimensions | 0 (a vsrd_field's instances); locations, dimensions [N,3];
+ * orientations [N,3,3]; boxes_3d [N,8,3].  Every pointer is required.
+ * N outside 1..VSRD_MAX_INSTANCES or a NULL pointer: VSRD_E_INVALID_ARGUMENT before any launch, nothing written. */
+int32_t vsrd_box_decode_forward(const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                                const float* location_range, const float* dimension_range, int32_t num_instances,
+                                float* instances, float* locations, float* dimensions, float* orientations, float* boxes_3d, void* stream);
+
+/* The same inputs and the cotangents of the five outputs -- each may be NULL: that output was not used -- -> grad_raw_locations,
+ * grad_raw_dimensions [N,3], grad_raw_orientations [N,2] (required; written, not accumulated).  The forward is recomputed. */
+int32_t vsrd_box_decode_backward(const float* raw_locations, const float* raw_dimensions, const float* raw_orientations,
+                                 const float* location_range, const float* dimension_range, int32_t num_instances,
+                                 const float* grad_instances, const float* grad_locations, const float* grad_dimensions,
+                                 const float* grad_orientations, const float* grad_boxes_3d,
+                                 float* grad_raw_locations, float* grad_raw_dimensions, float* grad_raw_orientations, void* stream);
+
 /* ---- the hypernetwork that generates the residual MLPs' weights (vsrd/models/fields/hyper_distance_field.py:27-55, 75-77) --------
  * embeddings [N,256] -> (VSRD_HYPER_LAYERS - 1) x [weight_norm(Linear 256 -> 256) -> LayerNorm(256, affine) -> exact GELU]
  * -> weight_norm(Linear 256 -> 1617) = mlp_weights [N,1617].  weight_norm over dim 0: W[o,:] = g[o] v[o,:] / |v[o,:]|.

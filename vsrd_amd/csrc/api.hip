@@ -276,6 +276,25 @@ bool cap_to_workspace(size_t bytes, int width, size_t flag_bytes, Geometry* g) {
     return true;
 }
 
+// The reduction behind a rows launch: reduce_partials_kernel, led by reduce_partials_residues_kernel (render_kernels.h: coalesced reads,
+// the same additions in the same order) whenever the tail of the workspace holds the 256 x (row + row2) residues behind the waves' rows
+// and the flags' two summary words.  The groups' flag bytes may lie there: both kernels that read them have run by then.  (A launch
+// whose rows and flags fill the buffer and whose flags are fewer than the residues -- N = 16: 64 k to 263 k groups -- keeps the one kernel.)
+void launch_reduce_rows(const float* partials, int num_waves, int row, float* out, const float* partials2, int row2, float* out2, void* workspace,
+                        size_t bytes, hipStream_t s) {
+    const size_t rows_end = (static_cast<size_t>(num_waves) * (row + row2) * sizeof(float) + 16 + 15) & ~static_cast<size_t>(15);
+    const size_t residue_bytes = (static_cast<size_t>(kReduceResidues) * (row + row2) * sizeof(float) + 15) & ~static_cast<size_t>(15);
+    if (rows_end + residue_bytes > bytes) {
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + row2), dim3(256), 0, s, partials, num_waves, row, out, nullptr, partials2, row2, out2);
+        return;
+    }
+    float* residues = reinterpret_cast<float*>(static_cast<char*>(workspace) + ((bytes - residue_bytes) & ~static_cast<size_t>(15)));
+    float* residues2 = residues + static_cast<size_t>(kReduceResidues) * row;
+    hipLaunchKernelGGL(reduce_partials_residues_kernel, dim3(kReduceResidues, (row + 255) / 256 + (row2 > 0 ? 1 : 0)), dim3(256), 0, s, partials, num_waves, row,
+                       partials2, row2, residues, residues2);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + row2), dim3(256), 0, s, residues, kReduceResidues, row, out, nullptr, row2 > 0 ? residues2 : nullptr, row2, out2);
+}
+
 // two kernels on one grid (quad_step.h): the hot body (rotations about y, fixed soft-min shift), then everything it left over
 template <typename Kernel, typename... Args>
 void launch_hot_then_rest(Kernel hot, Kernel rest, const Geometry& g, hipStream_t s, Args... args) {
@@ -740,7 +759,7 @@ int32_t vsrd_render_backward(const vsrd_field* field, const vsrd_render_config* 
             else launch(render_backward_pair_kernel<true, decltype(full)::value>, render_backward_pair_kernel<false, false>);
         });
         if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, partials, num_waves, row, grad_instances);
+        launch_reduce_rows(partials, num_waves, row, grad_instances, nullptr, 0, nullptr, workspace, workspace_bytes, s);
         return launch_status();
     }
     if (!plan(config->num_rays, static_cast<size_t>(backward_lds_floats(num_distances, N, residual)), &g)) return VSRD_E_UNSUPPORTED;
@@ -964,7 +983,7 @@ int32_t vsrd_render_silhouette_step_with_header(const vsrd_field* field, const v
     if (!known) return VSRD_E_UNSUPPORTED;
     if (status != VSRD_OK) return status;
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row + 1), dim3(256), 0, s, partials, num_waves, row, grad_instances, nullptr, loss_partials, 1, loss);
+    launch_reduce_rows(partials, num_waves, row, grad_instances, loss_partials, 1, loss, workspace, vsrd_workspace_bytes(N, 0), s);
     return launch_status();
 }
 
@@ -1462,6 +1481,8 @@ int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* con
     hipLaunchKernelGGL(patch_correlation_backward_kernel, dim3(a.num_rays), dim3(kPatchThreads), 0, s, a, stats, grad_loss, grad_positions, grad_normals);
     return launch_status();
 }
+
+// (vsrd_box_decode_forward / _backward: box_decode.hip, a translation unit of its own for its floating-point contraction mode)
 
 namespace {
 struct HyperPlan {

@@ -19,6 +19,7 @@
 #pragma once
 #include "matching.h"
 #include "projection.h"
+#include "box_decode.h"
 
 namespace vsrd {
 
@@ -44,12 +45,7 @@ __host__ __device__ constexpr size_t frame_scratch_floats(int num_views, int num
     return static_cast<size_t>(num_views) * num_boxes * (4 + 4 + 4 + 24);
 }
 
-__device__ __forceinline__ float lerp_torch(float a, float b, float w) {           // ATen's lerp kernel
-    const float diff = b - a;
-    return (fabsf(w) < 0.5f) ? (a + w * diff) : (b - diff * (1.0f - w));
-}
-__device__ __forceinline__ float sigmoid_precise(float x) { return 1.0f / (1.0f + expf(-x)); }
-
+// (lerp_torch, sigmoid_precise, unit_corner: box_decode.h, shared with the module path's decode kernels)
 struct DecodedBox {
     float sig_l[3], sig_d[3];
     float loc[3], dim[3];
@@ -69,12 +65,6 @@ __device__ __forceinline__ DecodedBox decode_box(const FrameStepArgs& a, const f
     b.c = raw_ori[0] / b.norm;
     b.s = raw_ori[1] / b.norm;
     return b;
-}
-
-// box_parameters.py:78-90: corner k = R_y (u_k * dim) + loc
-__device__ __forceinline__ void unit_corner(int k, float* u) {
-    const int table[8][3] = {{-1, -1, 1}, {1, -1, 1}, {1, -1, -1}, {-1, -1, -1}, {-1, 1, 1}, {1, 1, 1}, {1, 1, -1}, {-1, 1, -1}};
-    u[0] = static_cast<float>(table[k][0]); u[1] = static_cast<float>(table[k][1]); u[2] = static_cast<float>(table[k][2]);
 }
 
 // d max(a, b) / d a with torch.maximum's tie rule (half each); d min(a, b) / d a likewise

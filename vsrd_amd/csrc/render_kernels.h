@@ -1806,4 +1806,35 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
     }
 }
 
+// The same sums with coalesced reads, for tables of many rows (the dense box step: 64 k rows): reduce_partials_kernel's thread t owns
+// the rows t, t + 256, ... of its column, so a wave's load touches 64 rows for four bytes each.  Here workgroup (t, tile) forms thread t's
+// sequential sum for 256 neighbouring columns at once -- a wave's load is 256 contiguous bytes of one row -- and writes it to row t of a
+// 256-row table of residues ([256][row], [256][row2]).  reduce_partials_kernel over THAT table (num_waves = 256: thread t reads
+// 0.0f + residue t, which is residue t, the sums start from +0 and never are -0) then runs the old wave_sum tree and the old four-term
+// sum on the old operands: every output bit is what the one-kernel form gives.  blockIdx.y past the first table's tiles: the second table.
+constexpr int kReduceResidues = 256;
+constexpr int kReduceDepth = 16;           // loads in flight per lane (one wave per SIMD: the latency has to be covered by the wave itself)
+__global__ __launch_bounds__(256) void reduce_partials_residues_kernel(const float* __restrict__ partials, int num_waves, int row,
+                                                                       const float* __restrict__ partials2, int row2,
+                                                                       float* __restrict__ residues, float* __restrict__ residues2) {
+    const int tiles = (row + 255) >> 8;
+    const bool second = static_cast<int>(blockIdx.y) >= tiles;
+    const float* table = second ? partials2 : partials;
+    const int pitch = second ? row2 : row;
+    const int idx = (second ? 0 : static_cast<int>(blockIdx.y) << 8) + static_cast<int>(threadIdx.x);
+    if (idx >= pitch) return;
+    table += idx;
+    float acc = 0.0f;
+    int w = blockIdx.x;
+    for (; w + (kReduceDepth - 1) * kReduceResidues < num_waves; w += kReduceDepth * kReduceResidues) {
+        float v[kReduceDepth];
+#pragma unroll
+        for (int k = 0; k < kReduceDepth; ++k) v[k] = table[static_cast<size_t>(w + k * kReduceResidues) * pitch];
+#pragma unroll
+        for (int k = 0; k < kReduceDepth; ++k) acc += v[k];
+    }
+    for (; w < num_waves; w += kReduceResidues) acc += table[static_cast<size_t>(w) * pitch];
+    (second ? residues2 : residues)[static_cast<size_t>(blockIdx.x) * pitch + idx] = acc;
+}
+
 }  // namespace vsrd

@@ -1,5 +1,5 @@
-"""The optimised parameters of the hot path as torch modules (they stay on PyTorch: a handful of
-element-wise ops on [N,3] tensors per step).
+"""The optimised parameters of the hot path as torch modules.  BoxParameters3D decodes through the library's
+two box-decode kernels on a HIP device (csrc/box_decode.h) and through the same handful of torch ops as the reference elsewhere.
 
   BoxParameters3D      reference: vsrd/models/detectors/box_parameters.py:16-146
   SinusoidalEncoder    reference: vsrd/models/encoders/sinusoidal_encoder.py:8-19
@@ -10,6 +10,8 @@ import math
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _lib
 
 _UNIT_CORNERS = [[-1, -1, 1], [1, -1, 1], [1, -1, -1], [-1, -1, -1], [-1, 1, 1], [1, 1, 1], [1, 1, -1], [-1, 1, -1]]
 
@@ -29,6 +31,35 @@ def _unit_corners(like):
     if key not in _corner_cache:
         _corner_cache[key] = torch.tensor(_UNIT_CORNERS, dtype=like.dtype, device=like.device)
     return _corner_cache[key]
+
+
+class _BoxDecode(torch.autograd.Function):
+    """BoxParameters3D.forward() of one frame as ONE launch, its backward as one more (vsrd_box_decode_forward / _backward: torch's
+    arithmetic op for op).  Returns the packed instance block [N,16] of fields.pack_instances next to the module's four tensors."""
+
+    @staticmethod
+    def forward(ctx, raw_locations, raw_dimensions, raw_orientations, location_range, dimension_range):
+        lib = _lib.load()
+        n = raw_locations.shape[1]
+        raws = [t.detach().contiguous() for t in (raw_locations, raw_dimensions, raw_orientations, location_range, dimension_range)]
+        new = raws[0].new_empty
+        block, locations, dimensions, orientations, boxes_3d = new(n, 16), new(1, n, 3), new(1, n, 3), new(1, n, 3, 3), new(1, n, 8, 3)
+        _lib.check(lib.vsrd_box_decode_forward(*(_lib.ptr(t) for t in raws), n, _lib.ptr(block), _lib.ptr(locations), _lib.ptr(dimensions),
+                                               _lib.ptr(orientations), _lib.ptr(boxes_3d), _lib.stream()))
+        ctx.save_for_backward(raw_locations, raw_dimensions, raw_orientations, location_range, dimension_range)
+        ctx.set_materialize_grads(False)          # an output nobody used: a null pointer, not a tensor of zeros
+        return block, locations, dimensions, orientations, boxes_3d
+
+    @staticmethod
+    def backward(ctx, *cotangents):
+        lib = _lib.load()
+        raws = [t.detach().contiguous() for t in ctx.saved_tensors]
+        n = raws[0].shape[1]
+        cotangents = [None if g is None else g.to(torch.float32).contiguous() for g in cotangents]
+        grads = [torch.empty_like(t) for t in raws[:3]]
+        _lib.check(lib.vsrd_box_decode_backward(*(_lib.ptr(t) for t in raws), n, *(_lib.ptr(g) for g in cotangents), *(_lib.ptr(g) for g in grads),
+                                                _lib.stream()))
+        return grads[0], grads[1], grads[2], None, None
 
 
 class BoxParameters3D(nn.Module):
@@ -71,7 +102,20 @@ class BoxParameters3D(nn.Module):
         heading = F.normalize(forward[..., [2, 0]], dim=-1)
         return locations, half, yaw_matrix(heading[..., 0], heading[..., 1])
 
+    def _native(self):
+        """One frame of float32 parameters on a HIP device: the library's decode kernels.  Everything else (the CPU, other dtypes, batches)
+        runs the torch ops below."""
+        tensors = (self.locations, self.dimensions, self.orientations, self.location_range, self.dimension_range)
+        return (self.locations.is_cuda and self.locations.shape[0] == 1 and 1 <= self.locations.shape[1] <= _lib.MAX_INSTANCES
+                and all(t.dtype == torch.float32 and t.device == self.locations.device for t in tensors))
+
     def forward(self):
+        if self._native():
+            block, locations, dimensions, orientations, boxes_3d = _BoxDecode.apply(*(
+                self.locations, self.dimensions, self.orientations, self.location_range, self.dimension_range))
+            # fields.pack_instances(locations[0], orientations[0], dimensions[0]) is `block`: it hands it out instead of launching a cat
+            locations._vsrd_packed = (block, orientations, dimensions)
+            return dict(boxes_3d=boxes_3d, locations=locations, dimensions=dimensions, orientations=orientations, embeddings=self.embeddings)
         locations = self.decode_location(self.locations)
         dimensions = self.decode_dimension(self.dimensions)
         orientations = self.decode_orientation(self.orientations)
