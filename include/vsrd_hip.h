@@ -853,6 +853,64 @@ int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* con
                                         void* workspace, size_t workspace_bytes, const float* stats, const float* grad_loss,
                                         float* grad_positions, float* grad_normals, void* stream);
 
+/* Frame photometric term (added within ABI 12; probe for the symbols -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field):
+ * the multi-view patch-correlation term of ONE frame's optimisation step (scripts/main.py:689-853), forward and backward, in ONE call between
+ * the step's render launch and its epilogue -- no host synchronisation, no allocation, capturable.  In stream order, R = patch->num_rays rays:
+ *   gather      directions[r] = ray_directions[ray_indices[r]], pixels[r] = (index % W, index / W);
+ *   trace       vsrd_sphere_trace from camera_position along the directions, HARD union, initialise = 0 -> p0, converged;
+ *   evaluate    vsrd_field_eval at p0 (hard) -> d0, g0;
+ *   newton      p1 = converged ? p0 + r * (-d0 / (g0 . r)) : p0 (renderers.py:59-72, g0 a constant);
+ *   evaluate    vsrd_field_eval at p1 (hard) -> g1;
+ *   normalise   n = g1 / max(|g1|, 1e-12) (F.normalize);
+ *   forward     vsrd_patch_correlation_forward(pixels, p1, n, converged) -> loss, stats;
+ *   backward    vsrd_patch_correlation_backward with grad_loss = 1 -> p1_bar, n_bar;
+ *   adjoints    gamma = (n_bar - n (n . n_bar)) / max(|g1|, 1e-12); vsrd_field_eval_adjoint at p1 with grad_gradients = gamma -> x_bar, G_a, M_a;
+ *               d_bar = converged ? -((p1_bar + x_bar) . r) / (g0 . r) : 0; vsrd_field_eval_backward at p0 with grad_distances = d_bar -> G_b, M_b;
+ *   accumulate  photometric_grad_instances [N,16] = G_a + G_b and photometric_grad_mlp [N,1617] = M_a + M_b (the term's own gradients), then
+ *               grad_instances += scale * photometric_grad_instances and grad_mlp += scale * photometric_grad_mlp IN PLACE (one fused
+ *               multiply-add per element) on the buffers the render step has written.  Those are in units of the silhouette term -- the
+ *               epilogue and vsrd_hypernetwork_backward_step multiply them by the silhouette weight -- so scale = photometric weight /
+ *               silhouette weight, as eikonal_ratio is.
+ * The glue between the library's launches repeats torch's roundings operator by operator: given the same field and rays, p1, converged, n,
+ * the loss and stats carry the bits of the autograd composition sphere_tracing(differentiable=True) -> surface_normal ->
+ * patch_correlation_loss.  The field evaluations of this call use the exact-fp32 products of the per-instance MLP: the second-order adjoint
+ * exists in that form only (the step's render launch may still use VSRD_FLAG_MLP_SPLIT_BF16).
+ * No converged ray: loss 0, stats (0, 0), both photometric_grad_* all zero, grad_instances / grad_mlp keep their bits (the stated deviation of
+ * vsrd_patch_correlation_forward).  Deterministic: every reduction has a fixed order, there are no floating-point atomics.
+ *   field              the field as the step's render launch sees it: the row's instances and, in the residual phase, the centred MLP weights;
+ *   camera_position    [3], the origin of every ray; ray_directions [H W,3], the target view's slice;
+ *   gray, intrinsics, extrinsics, patch   as for vsrd_patch_correlation_forward; patch->num_rays is R;
+ *   ray_indices        [R] int64, pixel indices of the target view, each in 0 .. H W - 1 (not checked: device memory);
+ *   workspace          vsrd_frame_photometric_workspace_bytes(N, residual, V, R, patch pixels) bytes, 256-byte aligned;
+ *   loss [1], stats [2]; photometric_grad_mlp and grad_mlp are required for residual fields and ignored otherwise;
+ *   positions [R,3] = p1, normals [R,3] = n, converged [R]: optional outputs (NULL: kept in the workspace).
+ * Refused with VSRD_E_INVALID_ARGUMENT before any launch: a NULL config, patch, field or required pointer; N outside 1..VSRD_MAX_INSTANCES;
+ * R outside 1..VSRD_PHOTOMETRIC_MAX_RAYS (the table sampler's limit); top_k > V, V > VSRD_PATCH_MAX_VIEWS, patch pixels >
+ * VSRD_PATCH_MAX_PIXELS and the other limits of vsrd_patch_correlation_forward; num_iterations < 0.  A workspace that is too small:
+ * VSRD_E_WORKSPACE.  num_frames >= 2: VSRD_E_UNSUPPORTED before any launch (the fields are there so that batching can follow). */
+#define VSRD_PHOTOMETRIC_MAX_RAYS 2048
+typedef struct vsrd_frame_photometric_config {
+    int32_t num_iterations;         /* of the trace (config.json: surface_num_iterations)                                     */
+    float convergence_criteria;
+    float bounding_radius;          /* <= 0: none                                                                             */
+    float scale;                    /* photometric weight / silhouette weight                                                 */
+    int32_t num_frames;             /* 0 or 1 = one frame; >= 2: VSRD_E_UNSUPPORTED                                           */
+    int64_t frame_stride;
+} vsrd_frame_photometric_config;
+
+/* 0 for a shape outside the limits. */
+size_t vsrd_frame_photometric_workspace_bytes(int32_t num_instances, int32_t residual, int32_t num_views, int32_t num_rays, int32_t patch_pixels);
+
+int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
+                               const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
+                               const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
+                               float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
+                               float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged, void* stream);
+
+/* After vsrd_frame_epilogue: record[4] += weight * loss (the product rounded, then the sum), one single-lane launch; with no converged ray
+ * (stats[1] == 0) record keeps its bits.  loss, stats: vsrd_frame_photometric's outputs; record [5]: the epilogue's. */
+int32_t vsrd_frame_photometric_finish(const float* loss, const float* stats, float weight, float* record, void* stream);
+
 /* Box decode (added within ABI 12; probe for the symbols -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the forward
  * of the reference's BoxParameters3D (vsrd/models/detectors/box_parameters.py:16-146) for ONE frame and its autograd backward, one launch
  * each, without host synchronisation or allocation, capturable.  The arithmetic is tiny; what the calls buy is launch count on the

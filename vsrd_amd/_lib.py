@@ -217,7 +217,21 @@ class PatchCorrelationConfig(ctypes.Structure):
     ]
 
 
-PATCH_VIEWS = 32               # VSRD_PATCH_MAX_VIEWS: the limits of vsrd_patch_correlation_forward / _backward
+class FramePhotometricConfig(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_frame_photometric_config (added within ABI 12): the trace's constants, the term's weight relative to the
+    silhouette term and the batch fields of one vsrd_frame_photometric call."""
+    _fields_ = [
+        ("num_iterations", ctypes.c_int32),
+        ("convergence_criteria", ctypes.c_float),
+        ("bounding_radius", ctypes.c_float),
+        ("scale", ctypes.c_float),
+        ("num_frames", ctypes.c_int32),
+        ("frame_stride", ctypes.c_int64),
+    ]
+
+
+PHOTOMETRIC_RAYS = 2048        # VSRD_PHOTOMETRIC_MAX_RAYS: the rays of one vsrd_frame_photometric call (the table sampler's limit)
+PATCH_VIEWS = 32              # VSRD_PATCH_MAX_VIEWS: the limits of vsrd_patch_correlation_forward / _backward
 PATCH_PIXELS = 256             # VSRD_PATCH_MAX_PIXELS
 PATCH_RAYS = 65535             # VSRD_PATCH_MAX_RAYS
 FRAME_LOG_COLUMNS = 22        # VSRD_LOG_SCALARS: (step | record 5 | learning rates 5 | schedule 3 | metrics summary 8) of a history row
@@ -233,7 +247,7 @@ _RETURNS = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t, "const char*":
 # host structures, passed as const T*; every other pointer is device memory (vsrd_frame_header too) or the stream, and travels as an integer
 _HOST_STRUCTS = {"vsrd_field": Field, "vsrd_render_config": RenderConfig, "vsrd_frame_config": FrameConfig, "vsrd_adam_tensors": AdamTensors,
                  "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig, "vsrd_frame_log_config": FrameLogConfig,
-                 "vsrd_patch_correlation_config": PatchCorrelationConfig}
+                 "vsrd_patch_correlation_config": PatchCorrelationConfig, "vsrd_frame_photometric_config": FramePhotometricConfig}
 _DEVICE_POINTEES = {"void", "float", "uint8_t", "int32_t", "int64_t", "uint64_t", "vsrd_frame_header"}
 
 

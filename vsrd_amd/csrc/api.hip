@@ -18,6 +18,7 @@
 #include "frame_metrics.h"
 #include "frame_log.h"
 #include "patch_correlation.h"
+#include "frame_photometric.h"
 #include "launch.h"
 
 namespace {
@@ -1479,6 +1480,122 @@ int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* con
     const hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(patch_constants_kernel, dim3(1), dim3(kWave), 0, s, a);
     hipLaunchKernelGGL(patch_correlation_backward_kernel, dim3(a.num_rays), dim3(kPatchThreads), 0, s, a, stats, grad_loss, grad_positions, grad_normals);
+    return launch_status();
+}
+
+namespace {
+// The workspace of vsrd_frame_photometric, in floats: the per-ray arrays (each padded to a multiple of 4 rays), the four parameter-gradient
+// blocks of the two field adjoints, the patch correlation's workspace, then -- 256-byte aligned -- the field adjoints' own workspace.
+struct PhotometricWorkspace {
+    float *directions, *p0, *d0, *g0, *slopes, *p1, *g1, *lengths, *normals, *grad_p1, *grad_normals, *gamma, *grad_x, *grad_d0, *one;
+    int* pixels;
+    unsigned char* converged;
+    float *first_instances, *second_instances, *first_mlp, *second_mlp;
+    float* patch;
+    size_t patch_bytes;
+    void* field;
+    size_t field_bytes;
+    size_t total_bytes;
+};
+size_t padded4(size_t n) { return (n + 3) & ~static_cast<size_t>(3); }
+PhotometricWorkspace photometric_workspace(void* workspace, int N, bool residual, int V, int R) {
+    PhotometricWorkspace w;
+    float* base = static_cast<float*>(workspace);
+    size_t at = 0;
+    const size_t rays = padded4(static_cast<size_t>(R));
+    auto take = [&](size_t floats) { float* p = base + at; at += padded4(floats); return p; };
+    w.directions = take(3 * rays); w.p0 = take(3 * rays); w.d0 = take(rays); w.g0 = take(3 * rays); w.slopes = take(rays);
+    w.p1 = take(3 * rays); w.g1 = take(3 * rays); w.lengths = take(rays); w.normals = take(3 * rays);
+    w.grad_p1 = take(3 * rays); w.grad_normals = take(3 * rays); w.gamma = take(3 * rays); w.grad_x = take(3 * rays); w.grad_d0 = take(rays);
+    w.one = take(4);
+    w.pixels = reinterpret_cast<int*>(take(2 * rays));
+    w.converged = reinterpret_cast<unsigned char*>(take(rays / 4));
+    w.first_instances = take(static_cast<size_t>(N) * kGradStride); w.second_instances = take(static_cast<size_t>(N) * kGradStride);
+    w.first_mlp = take(residual ? static_cast<size_t>(N) * kMlpWeights : 0); w.second_mlp = take(residual ? static_cast<size_t>(N) * kMlpWeights : 0);
+    w.patch_bytes = patch_workspace_floats(V, R) * sizeof(float);
+    w.patch = take(patch_workspace_floats(V, R));
+    at = (at + 63) & ~static_cast<size_t>(63);
+    w.field = base + at;
+    w.field_bytes = vsrd_workspace_bytes(N, residual);
+    w.total_bytes = at * sizeof(float) + w.field_bytes;
+    return w;
+}
+}  // namespace
+
+size_t vsrd_frame_photometric_workspace_bytes(int32_t num_instances, int32_t residual, int32_t num_views, int32_t num_rays, int32_t patch_pixels) {
+    if (num_instances < 1 || num_instances > VSRD_MAX_INSTANCES || num_rays > kPhotometricMaxRays || !valid_patch_shape(num_views, num_rays, patch_pixels)) return 0;
+    return photometric_workspace(nullptr, num_instances, residual != 0, num_views, num_rays).total_bytes;
+}
+
+int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
+                               const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
+                               const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
+                               float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
+                               float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged, void* stream) {
+    static_assert(kPhotometricMaxRays == VSRD_PHOTOMETRIC_MAX_RAYS, "frame_photometric.h and the ABI agree on the limit");
+    Frames frames;
+    if (!config || !frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    if (frames.count > 1) return VSRD_E_UNSUPPORTED;
+    if (!patch || !valid_field(field) || config->num_iterations < 0) return VSRD_E_INVALID_ARGUMENT;
+    const int N = field->num_instances, V = patch->num_views, R = patch->num_rays;
+    const bool residual = field->mlp_weights != nullptr;
+    if (R < 1 || R > kPhotometricMaxRays || patch->patch_width < 1 || patch->patch_height < 1 || patch->patch_width > kPatchMaxPixels ||
+        patch->patch_height > kPatchMaxPixels || !valid_patch_shape(V, R, patch->patch_width * patch->patch_height) || patch->top_k < 1 ||
+        patch->top_k > V || patch->target_view < 0 || patch->target_view >= V || patch->height < 2 || patch->width < 2 ||
+        static_cast<int64_t>(patch->height) * patch->width >= (int64_t{1} << 30))
+        return VSRD_E_INVALID_ARGUMENT;
+    if (!camera_position || !ray_directions || !gray || !intrinsics || !extrinsics || !ray_indices || !loss || !stats || !photometric_grad_instances ||
+        !grad_instances || (residual && (!photometric_grad_mlp || !grad_mlp)))
+        return VSRD_E_INVALID_ARGUMENT;
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return workspace ? VSRD_E_INVALID_ARGUMENT : VSRD_E_WORKSPACE;
+    PhotometricWorkspace w = photometric_workspace(workspace, N, residual, V, R);
+    if (workspace_bytes < w.total_bytes) return VSRD_E_WORKSPACE;
+    if (positions) w.p1 = positions;
+    if (normals) w.normals = normals;
+    if (converged) w.converged = converged;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((R + kPhotometricThreads - 1) / kPhotometricThreads), block(kPhotometricThreads);
+    int32_t status;
+    hipLaunchKernelGGL(photometric_gather_kernel, grid, block, 0, s, R, patch->width, reinterpret_cast<const long long*>(ray_indices), ray_directions,
+                       w.directions, w.pixels, w.one);
+    if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+    status = vsrd_sphere_trace(field, camera_position, 0, w.directions, nullptr, R, config->num_iterations, config->convergence_criteria,
+                               config->bounding_radius, 0, 1, w.p0, w.converged, stream);
+    if (status != VSRD_OK) return status;
+    status = vsrd_field_eval(field, w.p0, R, w.d0, w.g0, nullptr, 1, stream);
+    if (status != VSRD_OK) return status;
+    hipLaunchKernelGGL(photometric_newton_kernel, grid, block, 0, s, R, w.p0, w.converged, w.d0, w.g0, w.directions, w.p1, w.slopes);
+    if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+    status = vsrd_field_eval(field, w.p1, R, nullptr, w.g1, nullptr, 1, stream);
+    if (status != VSRD_OK) return status;
+    hipLaunchKernelGGL(photometric_normalise_kernel, grid, block, 0, s, R, w.g1, w.normals, w.lengths);
+    if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+    status = vsrd_patch_correlation_forward(patch, gray, intrinsics, extrinsics, w.pixels, w.p1, w.normals, w.converged, w.patch, w.patch_bytes,
+                                            loss, stats, nullptr, nullptr, nullptr, stream);
+    if (status != VSRD_OK) return status;
+    status = vsrd_patch_correlation_backward(patch, gray, intrinsics, extrinsics, w.pixels, w.p1, w.normals, w.converged, w.patch, w.patch_bytes,
+                                             stats, w.one, w.grad_p1, w.grad_normals, stream);
+    if (status != VSRD_OK) return status;
+    hipLaunchKernelGGL(photometric_normal_adjoint_kernel, grid, block, 0, s, R, w.converged, w.normals, w.lengths, w.grad_normals, w.gamma);
+    if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+    status = vsrd_field_eval_adjoint(field, w.p1, R, nullptr, nullptr, w.gamma, 1, w.field, w.field_bytes, w.grad_x, w.first_instances,
+                                     residual ? w.first_mlp : nullptr, stream);
+    if (status != VSRD_OK) return status;
+    hipLaunchKernelGGL(photometric_newton_adjoint_kernel, grid, block, 0, s, R, w.converged, w.grad_p1, w.grad_x, w.directions, w.slopes, w.grad_d0);
+    if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
+    status = vsrd_field_eval_backward(field, w.p0, R, w.grad_d0, nullptr, 1, w.field, w.field_bytes, nullptr, w.second_instances,
+                                      residual ? w.second_mlp : nullptr, stream);
+    if (status != VSRD_OK) return status;
+    const int count_instances = N * kGradStride, count_mlp = residual ? N * kMlpWeights : 0;
+    const int blocks = std::min((count_instances + count_mlp + kPhotometricThreads - 1) / kPhotometricThreads, 1024);
+    hipLaunchKernelGGL(photometric_accumulate_kernel, dim3(blocks), block, 0, s, stats, config->scale, count_instances, count_mlp, w.first_instances,
+                       w.second_instances, w.first_mlp, w.second_mlp, photometric_grad_instances, photometric_grad_mlp, grad_instances, grad_mlp);
+    return launch_status();
+}
+
+int32_t vsrd_frame_photometric_finish(const float* loss, const float* stats, float weight, float* record, void* stream) {
+    if (!loss || !stats || !record) return VSRD_E_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(photometric_finish_kernel, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), loss, stats, weight, record);
     return launch_status();
 }
 

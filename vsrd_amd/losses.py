@@ -6,7 +6,7 @@ small tensors; the heavy lifting -- rendering -- is in the HIP library).
   schedules                       scripts/main.py:420-431
   silhouette / eikonal            scripts/main.py:653-687
   weights                         configs/.../config.json:120-127
-  photometric (patch correlation) scripts/main.py:783-851   (HIP: csrc/patch_correlation.h; not used by the optimisation loop)
+  photometric (patch correlation) scripts/main.py:783-851   (HIP: csrc/patch_correlation.h; FrameOptimizer applies it when its weight is non-zero)
 """
 import math
 

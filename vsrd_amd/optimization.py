@@ -204,10 +204,13 @@ class FrameInputs:
     label_extrinsic_matrices: InitVar[Optional[torch.Tensor]] = None    # [L,4,4] (target-camera frame -> label view's camera frame)
     label_boxes_2d: InitVar[Optional[torch.Tensor]] = None              # [L,N,4] (xmin, ymin, xmax, ymax) in the target's instance order, zeros where invisible
     label_visible: InitVar[Optional[torch.Tensor]] = None               # [L,N] uint8 / bool
+    # the views' colour images for the photometric term (main.py:689-853: target_inputs.images / source_inputs.images), init-only like the group
+    images: InitVar[Optional[torch.Tensor]] = None                      # [V,3,H,W] float32 in 0..1
 
-    def __post_init__(self, label_frame_ids, label_intrinsic_matrices, label_extrinsic_matrices, label_boxes_2d, label_visible):
+    def __post_init__(self, label_frame_ids, label_intrinsic_matrices, label_extrinsic_matrices, label_boxes_2d, label_visible, images=None):
         self.label_frame_ids, self.label_intrinsic_matrices, self.label_extrinsic_matrices = label_frame_ids, label_intrinsic_matrices, label_extrinsic_matrices
         self.label_boxes_2d, self.label_visible = label_boxes_2d, label_visible
+        self.images = images
 
 
 @dataclass
@@ -246,6 +249,12 @@ class OptimizationConfig:
     surface_num_iterations: int = 1000
     surface_convergence_criteria: float = 0.01
     surface_bounding_radius: float = 100.0
+    # the photometric term (scripts/main.py:689-853; live when loss_weights["photometric_loss"] is non-zero, in the steps >= warmup_steps): the
+    # rays drawn from the target view's hard masks per step and the patch of the correlation (config.json:216-225), the literal 4 of main.py:845;
+    # its trace takes the three surface_* constants above
+    surface_num_rays: int = 100
+    surface_patch_size: Sequence[int] = (11, 11)
+    surface_top_k: int = 4
     # the device-side log of the fused-glue graph loop (csrc/frame_log.h; scripts/main.py:870-953, 1109-1121 -- config.json's scalar_intervals
     # 50 and ckpt_intervals 500): every `scalar_interval` steps a row of scalars (FrameOptimizer.history), every `checkpoint_interval` steps a
     # snapshot of the models (FrameOptimizer.snapshots).  0: off -- no buffer, no launch, the loop as it is without them.
@@ -725,6 +734,49 @@ def _output(name):
     return _OUTPUTS[name] if name in _OUTPUTS else _LABEL_VIEW_OUTPUTS[name]
 
 
+def photometric_weight(config):
+    """The weight of the photometric term, 0.0 when it is off: the reference tests the weight's truthiness (scripts/main.py:689)."""
+    return float(config.loss_weights.get("photometric_loss", 0.0) or 0.0)
+
+
+def _check_loss_weights(config):
+    """ValueError for a loss weight the loops do not know: a term that nothing applies would otherwise be dropped without a word."""
+    unknown = sorted(set(config.loss_weights) - set(losses.LOSS_WEIGHTS))
+    if unknown:
+        raise ValueError(f"loss_weights: unknown terms {unknown}; the loop applies {sorted(losses.LOSS_WEIGHTS)}")
+
+
+def _check_photometric(inputs, config, num_views, num_instances):
+    """ValueError unless a frame -- a frames.FramePack or a FrameInputs -- can be optimised with the photometric term of `config` (off: nothing
+    is checked): its images, a silhouette weight to scale by, the limits of vsrd_frame_photometric and enough pixels in the target view's
+    hard-mask union for a draw.  Needs no device: checked before a loop writes anything of the frame (construction, FrameOptimizer.reset)."""
+    if photometric_weight(config) == 0.0:
+        return
+    if not float(config.loss_weights.get("silhouette_loss", 0.0) or 0.0):
+        raise ValueError("the photometric term's gradients are accumulated in units of the silhouette term (csrc/frame_step.h): "
+                         "loss_weights['silhouette_loss'] must not be 0")
+    V, N, rays, k = int(num_views), int(num_instances), int(config.surface_num_rays), int(config.surface_top_k)
+    patch = tuple(int(x) for x in config.surface_patch_size)
+    if not 1 <= rays <= _lib.PHOTOMETRIC_RAYS:
+        raise ValueError(f"surface_num_rays: 1..{_lib.PHOTOMETRIC_RAYS} (the table sampler's limit), got {rays}")
+    if not 1 <= k <= V <= _lib.PATCH_VIEWS:
+        raise ValueError(f"the photometric term needs 1 <= surface_top_k <= views <= {_lib.PATCH_VIEWS}, got top_k {k} and {V} views")
+    if len(patch) != 2 or min(patch) < 1 or patch[0] * patch[1] > _lib.PATCH_PIXELS:
+        raise ValueError(f"surface_patch_size: (width, height) of at most {_lib.PATCH_PIXELS} pixels, got {patch}")
+    if not 1 <= N <= _lib.MAX_INSTANCES:
+        raise ValueError(f"the photometric term serves 1..{_lib.MAX_INSTANCES} instances, got {N}")
+    images = getattr(inputs, "images", None)
+    if images is None:
+        raise ValueError("loss_weights['photometric_loss'] is non-zero: the frame needs its images (FrameInputs.images [V,3,H,W]; frame packs carry none)")
+    H, W = (int(x) for x in inputs.image_size)
+    if tuple(int(x) for x in images.shape) != (V, 3, H, W):
+        raise ValueError(f"images of shape {tuple(images.shape)} for a frame of {V} views of {H} x {W}: expected {(V, 3, H, W)}")
+    hard = int((inputs.soft_masks[0].amax(dim=-1) > 0.5).sum())
+    if hard < rays:
+        raise ValueError(f"only {hard} pixels of the target view lie in a hard mask, fewer than surface_num_rays = {rays} "
+                         "(torch.multinomial without replacement raises in the reference as well)")
+
+
 class FrameOptimizer:
     """``graph=True``: the step is captured in a hipGraph and replayed.  ``fused_glue`` (default: on in graph mode): everything around
     the render launch that concerns the boxes -- decode, projection, matching, projection losses and their gradients, schedules,
@@ -748,6 +800,8 @@ class FrameOptimizer:
         own count.
         ``max_label_views``: the label views (``FrameInputs.label_*``: the frame's group) that ``group_labels()`` lays its tables out for --
         None: the frame's own L; a loop that ``reset()`` gives other frames needs the largest L among them.  0: the loop keeps no group."""
+        _check_loss_weights(config)
+        _check_photometric(inputs, config, inputs.soft_masks.shape[0], inputs.soft_masks.shape[-1])
         self.label_view_capacity = label_view_count(inputs) if max_label_views is None else int(max_label_views)
         if not 0 <= self.label_view_capacity <= _lib.MAX_LABEL_VIEWS:
             raise ValueError(f"max_label_views: 0..{_lib.MAX_LABEL_VIEWS}, got {self.label_view_capacity}")
@@ -818,8 +872,11 @@ class FrameOptimizer:
         self._prepare_rays(inputs, config, H, W, N)
         self.step_index = 0
         self._log, self.log_seconds = None, 0.0          # (the device-side log: _init_log)
+        self._photometric = None                         # (the photometric term's buffers: _init_photometric)
         if self.fused_glue:
             self._init_fused_glue()
+        if photometric_weight(config) != 0.0:
+            self._init_photometric()
 
     def _new(self, shape, dtype=torch.float32, fill=None):
         """A device buffer of this loop: in the frame's row of the batch's arena when there is one."""
@@ -958,6 +1015,97 @@ class FrameOptimizer:
         b["mlp_weights"], b["mlp_centred"] = new((N, _lib.MLP_WEIGHTS), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
         if cfg.scalar_interval > 0 or cfg.checkpoint_interval > 0:
             self._init_log()
+
+    # ---- the photometric term (csrc/frame_photometric.h; scripts/main.py:689-853) ------------------------------------------------------
+    def _init_photometric(self):
+        """The term's buffers, at construction and only when it is live (a loop without it has none of them): the gray planes, the target
+        view's hard-mask union as sampling weights with its ray table (graph mode), the drawn rays, and for the fused glue the workspace and
+        outputs of vsrd_frame_photometric -- all by the one placement rule (`_new`)."""
+        cfg, new, lib = self.config, self._new, _lib.load()
+        H, W = (int(x) for x in self.inputs.image_size)
+        N, rays = self.capacity, int(cfg.surface_num_rays)
+        p = self._photometric = dict(table=None)
+        p["gray"] = new((self.view_capacity, H, W), fill=0.0)
+        p["hard_weights"] = new(H * W, fill=0.0)
+        p["ray_indices"] = new(rays, torch.int64, fill=0)
+        if self.fused_glue:
+            pw, ph = (int(x) for x in cfg.surface_patch_size)
+            p["workspace"] = new(lib.vsrd_frame_photometric_workspace_bytes(N, 1, self.view_capacity, rays, pw * ph), torch.uint8)
+            p["loss"], p["stats"] = new(1, fill=0.0), new(2, fill=0.0)
+            p["grad_instances"], p["grad_mlp"] = new((N, 16), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
+        if not self._write_photometric():
+            raise UnsuitableFrameError("the hard masks of this frame's target view do not suit the table sampler (rendering.RayTable.suits): it "
+                                       "cannot found a frame slot -- optimise it in a loop of its own (persistent=False)")
+
+    def _write_photometric(self):
+        """What the term keeps of the CURRENT frame (construction and every reset()): the gray planes of its images (vsrd_grayscale_images,
+        once per frame) and the hard-mask union of view 0, soft_masks[0].amax(-1) > 0.5, taken from the row's own masks, as the weights of
+        the term's draw; graph mode (re)builds their ray table in place.  False: the weights do not suit the table sampler a slot's graphs
+        were captured with."""
+        cfg, p, V, N = self.config, self._photometric, self.num_views, self.num_instances
+        H, W = (int(x) for x in self.inputs.image_size)
+        images = self.inputs.images.to(device=self.device, dtype=torch.float32).contiguous()
+        _lib.check(_lib.load().vsrd_grayscale_images(_lib.ptr(images), V, H, W, _lib.ptr(p["gray"]), _lib.stream()))
+        p["hard_weights"].copy_(self.flat_masks[:H * W, :N].amax(dim=-1) > 0.5)
+        if not (self.graph and self.device.type == "cuda"):
+            return True
+        had_table = p["table"] is not None
+        if had_table:
+            p["table"].rebuild(p["hard_weights"])
+        table = p["table"] if had_table else rendering.RayTable(p["hard_weights"], allocate=None if self._row is None else self._row.bytes)
+        if table.suits(int(cfg.surface_num_rays)):
+            p["table"] = table
+            return True
+        # (as for the step's own rays, _prepare_sampler: a slot's graphs are captured with ONE sampler; a loop of one frame keeps vsrd_sample_rays)
+        return not (had_table or self.persistent)
+
+    def _draw_surface_rays(self):
+        """Graph mode's draw of the term's rays (pixel indices of the target view) from the hard-mask union, keyed by (seed + 2, step counter)."""
+        cfg, p = self.config, self._photometric
+        if p["table"] is not None:
+            return p["table"].sample(int(cfg.surface_num_rays), seed=cfg.seed + 2, stream_offset=self.step_tensor, out=p["ray_indices"])
+        return rendering.sample_rays(p["hard_weights"], int(cfg.surface_num_rays), seed=cfg.seed + 2, stream_offset=self.step_tensor, out=p["ray_indices"])
+
+    def _surface_rays(self, surface_ray_indices):
+        """The term's rays of this step: the caller's (parity runs), or a draw -- torch.multinomial on the hard-mask union in the eager loop
+        (the reference's stream, main.py:700-705), the device sampler in graph mode."""
+        if surface_ray_indices is not None:
+            return surface_ray_indices.contiguous()
+        if self.graph:
+            return self._draw_surface_rays()
+        return torch.multinomial(self._photometric["hard_weights"], int(self.config.surface_num_rays), replacement=False)
+
+    def _photometric_loss(self, block, surface_ray_indices):
+        """The term as the autograd composition (the eager loop's; the fused call's parity reference): the target view's rays traced against
+        the HARD union of the step's field block, one Newton step, the attached normals, the patch correlation (main.py:747-851)."""
+        cfg, p = self.config, self._photometric
+        indices = self._surface_rays(surface_ray_indices)
+        hard = fields.FieldBlock(block.instances, block.temperature, block.mlp_weights, None, hard=True, yaw_gradients=block.yaw_gradients)
+        directions = self.ray_directions[indices]
+        positions, converged = rendering.sphere_tracing(hard, self.camera_positions[0], directions, cfg.surface_num_iterations, cfg.surface_convergence_criteria,
+                                                        bounding_radius=cfg.surface_bounding_radius, initialization=False, differentiable=True)
+        normals = rendering.surface_normal(hard, positions)
+        V = self.num_views
+        return losses.patch_correlation_loss(p["gray"][:V], self.inputs.intrinsic_matrices.to(self.device), self.inputs.extrinsic_matrices.to(self.device),
+                                             indices, positions, normals, converged, tuple(cfg.surface_patch_size), int(cfg.surface_top_k))
+
+    def _launch_photometric(self, field, surface_ray_indices, stream):
+        """vsrd_frame_photometric on the step's field, after the render launch has written grad_instances / grad_mlp and before anything reads them."""
+        cfg, b, p, lib = self.config, self._glue, self._photometric, _lib.load()
+        H, W = (int(x) for x in self.inputs.image_size)
+        indices = self._surface_rays(surface_ray_indices)
+        rays = int(indices.numel())
+        if rays != int(cfg.surface_num_rays):
+            raise ValueError(f"surface_ray_indices: config.surface_num_rays = {cfg.surface_num_rays} rays (the term's buffers are laid out for them), got {rays}")
+        weights = cfg.loss_weights
+        pw, ph = (int(x) for x in cfg.surface_patch_size)
+        patch = _lib.PatchCorrelationConfig(self.num_views, rays, H, W, pw, ph, int(cfg.surface_top_k), 0, 1.0e-6, 1.0e-12)
+        config = _lib.FramePhotometricConfig(int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria), float(cfg.surface_bounding_radius),
+                                             photometric_weight(cfg) / float(weights["silhouette_loss"]), 1, 0)
+        _lib.check(lib.vsrd_frame_photometric(config, patch, field, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), _lib.ptr(p["gray"]),
+                                              _lib.ptr(b["intrinsics"]), _lib.ptr(b["extrinsics"]), indices.data_ptr(), p["workspace"].data_ptr(),
+                                              p["workspace"].numel(), _lib.ptr(p["loss"]), _lib.ptr(p["stats"]), _lib.ptr(p["grad_instances"]),
+                                              _lib.ptr(p["grad_mlp"]), _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_mlp"]), None, None, None, stream))
 
     # ---- the device-side log (csrc/frame_log.h) -----------------------------------------------------------------------------------------
     def _init_log(self):
@@ -1142,7 +1290,7 @@ class FrameOptimizer:
                 torch.cuda.synchronize(self.device)      # replays that still write through the old addresses finish first
             self.rebind()
 
-    def _fused_step(self, ray_indices, count=True, joins=(True, True), frames=None):
+    def _fused_step(self, ray_indices, count=True, joins=(True, True), frames=None, surface_ray_indices=None):
         """One step with the box-side glue in frame_step.h.  Same arithmetic as `_step_in_scope` (the eager torch path is its
         parity reference: tests/test_hip_step.py).  ``frames = (B, stride)``: this loop is frame 0 of a batch (``FrameBatch``) and
         every launch of the step covers the B frames whose buffers lie ``stride`` bytes apart (include/vsrd_hip.h, "frame batches")."""
@@ -1243,6 +1391,13 @@ class FrameOptimizer:
                                                                    _lib.ptr(b["masks"]), _lib.ptr(b["instance_weights"]), loss_scale,
                                                                    workspace.data_ptr(), workspace.numel(), _lib.ptr(b["render_losses"]),
                                                                    _lib.ptr(b["grad_instances"]), None, header, stream))
+        photometric = residual and self._photometric is not None
+        if photometric:
+            if batch[0] > 1:
+                raise RuntimeError("the photometric term is not batched over frames (vsrd_frame_photometric: one frame per call)")
+            # on the step's own stream: the call ends in the accumulation into grad_instances / grad_mlp, which the render launch has just
+            # written and which the hypernetwork's backward and the epilogue read next -- no stretch of it is free of both
+            self._launch_photometric(field, surface_ray_indices, stream)
         if fused_net:     # branch: backward through the hypernetwork, Adam on it and on the embeddings, both rates decayed (next to the epilogue)
             net_branch.wait_stream(main)
             with torch.cuda.stream(net_branch):
@@ -1256,6 +1411,9 @@ class FrameOptimizer:
                          float(eikonal_ratio), self._adam[0], self._adam[1], self._adam[2], others[0], others[1], self.step_tensor.data_ptr(),
                          _lib.ptr(b["record"]), _lib.ptr(b["raw_gradients"]))
         _lib.check(lib.vsrd_frame_epilogue_with_header(*epilogue_args, header, stream))
+        if photometric:   # record[4], which the epilogue has just written, gains the term
+            p = self._photometric
+            _lib.check(lib.vsrd_frame_photometric_finish(_lib.ptr(p["loss"]), _lib.ptr(p["stats"]), photometric_weight(cfg), _lib.ptr(b["record"]), stream))
         if residual and not fused_net:    # autograd + torch.optim.Adam (the box tensors have no .grad: skipped)
             mlp_weights.backward(b["grad_mlp"] * weights["silhouette_loss"])
             self.optimizer.step()
@@ -1275,6 +1433,8 @@ class FrameOptimizer:
                       raw_gradients=[raw[:, 0:3].unsqueeze(0), raw[:, 3:6].unsqueeze(0), raw[:, 6:8].unsqueeze(0)])
         if residual:
             result["eikonal_loss"] = record[3]
+            if self._photometric is not None:
+                result["photometric_loss"] = self._photometric["loss"][0]
         return result
 
     # ------------------------------------------------------------------------------------------------
@@ -1298,15 +1458,19 @@ class FrameOptimizer:
         return fields.FieldBlock(fields.pack_instances(outputs["locations"][0], outputs["orientations"][0], outputs["dimensions"][0]),
                                  float(temperature), mlp_weights, None, yaw_gradients=True)      # (BoxParameters3D: rotation_matrix_y)
 
-    def step(self, ray_indices: Optional[torch.Tensor] = None, u_coarse=None, u_fine=None):
+    def step(self, ray_indices: Optional[torch.Tensor] = None, u_coarse=None, u_fine=None, surface_ray_indices: Optional[torch.Tensor] = None):
         """One optimisation step.  Steps < warmup_steps optimise the boxes only; later steps add the per-instance residual MLP
         (hypernetwork on the embeddings, main.py:525-578) and the eikonal loss (main.py:679-687).
-        ray_indices / uniforms may be supplied for reproducible parity runs."""
+        ray_indices / uniforms may be supplied for reproducible parity runs, and so may surface_ray_indices, the photometric term's rays (pixel
+        indices of the target view; used by the steps in which the term is live).  With the term live the dictionary gains
+        ``photometric_loss`` and ``loss`` includes it."""
+        if surface_ray_indices is not None and self._photometric is None:
+            raise ValueError("surface_ray_indices: the photometric term is off (loss_weights['photometric_loss'])")
         if self.graph:
             if u_coarse is not None or u_fine is not None:
                 raise ValueError("graph mode draws its uniforms in the kernels (Philox keyed by the device-side step counter)")
-            return self._graph_advance(1, ray_indices)
-        return self._step(ray_indices, u_coarse, u_fine)
+            return self._graph_advance(1, ray_indices, surface_ray_indices)
+        return self._step(ray_indices, u_coarse, u_fine, surface_ray_indices=surface_ray_indices)
 
     # ---- hipGraph mode ---------------------------------------------------------------------------------
     def _device_schedule(self):
@@ -1317,16 +1481,25 @@ class FrameOptimizer:
         self.schedule.copy_(torch.cat([anneal * (cfg.max_sdf_union_temperature - cfg.min_sdf_union_temperature) + cfg.min_sdf_union_temperature,
                                        anneal * (cfg.max_sdf_std_deviation - cfg.min_sdf_std_deviation) + cfg.min_sdf_std_deviation, x]))
 
-    def _graph_advance(self, k, ray_indices=None):
+    def _graph_advance(self, k, ray_indices=None, surface_ray_indices=None):
         """``k`` steps of graph mode (``_advance``) and what is this loop's own around them: its checks, its key -- (phase, ray source) for a
-        single step, (phase, False, k) for a group -- its step count and its log."""
+        single step, with "surface" behind it when the photometric term's rays are the caller's too, (phase, False, k) for a group -- its step
+        count and its log."""
         if ray_indices is not None and int(ray_indices.numel()) > self.config.num_rays:
             # the captured graphs hold the address of scratch sized for config.num_rays rays; a larger launch would outgrow it
             raise ValueError(f"graph mode replays steps of at most config.num_rays = {self.config.num_rays} rays, got {int(ray_indices.numel())}")
         self._check_bindings()
         residual = self.step_index >= self.config.warmup_steps
         key = (residual, ray_indices is not None) if k == 1 else (residual, False, k)
-        outputs = _advance(self, key, k, lambda rays, **how: self._step(rays, None, None, **how), static=ray_indices)
+        if surface_ray_indices is None:
+            outputs = _advance(self, key, k, lambda rays, **how: self._step(rays, None, None, **how), static=ray_indices)
+        else:
+            # static rays are part of the graph's key; `_advance` keeps ONE static tensor: the step's rays (if given) and the term's, end to end
+            n = 0 if ray_indices is None else int(ray_indices.numel())
+            surface = surface_ray_indices.reshape(-1).to(torch.int64)
+            packed = surface if n == 0 else torch.cat([ray_indices.reshape(-1).to(torch.int64), surface])
+            outputs = _advance(self, (*key, "surface"), k,
+                               lambda rays, **how: self._step(rays[:n] if n else None, None, None, surface_ray_indices=rays[n:], **how), static=packed)
         self.step_index += k
         _launch_log([self])
         return outputs
@@ -1349,15 +1522,15 @@ class FrameOptimizer:
             remaining -= k
         return outputs
 
-    def _step(self, ray_indices, u_coarse, u_fine, count=True, joins=(True, True)):
+    def _step(self, ray_indices, u_coarse, u_fine, count=True, joins=(True, True), surface_ray_indices=None):
         with rendering.workspace_scope(self.workspace):
             if self.fused_glue:
                 if not torch.cuda.is_current_stream_capturing():
                     self._check_bindings()
-                return self._fused_step(ray_indices, count, joins)
-            return self._step_in_scope(ray_indices, u_coarse, u_fine, count)
+                return self._fused_step(ray_indices, count, joins, surface_ray_indices=surface_ray_indices)
+            return self._step_in_scope(ray_indices, u_coarse, u_fine, count, surface_ray_indices)
 
-    def _step_in_scope(self, ray_indices, u_coarse, u_fine, count):
+    def _step_in_scope(self, ray_indices, u_coarse, u_fine, count, surface_ray_indices=None):
         cfg, inp = self.config, self.inputs
         step = self.step_index
         residual = step >= cfg.warmup_steps
@@ -1400,6 +1573,9 @@ class FrameOptimizer:
             terms["eikonal_loss"] = eikonal
         # main.py:855: sum of weighted terms; `rendered` already is silhouette (+ eikonal_ratio * eikonal)
         total = weights["iou_projection_loss"] * iou_loss + weights["l1_projection_loss"] * l1_loss + weights["silhouette_loss"] * rendered
+        if residual and self._photometric is not None:       # main.py:689-853, on the hard union of the step's field block
+            terms["photometric_loss"] = self._photometric_loss(block, surface_ray_indices)
+            total = total + photometric_weight(cfg) * terms["photometric_loss"]
         total.backward()
         raw_gradients = [p.grad.detach().clone() for p in (self.detector.locations, self.detector.dimensions, self.detector.orientations)]
         self.optimizer.step()
@@ -1474,6 +1650,7 @@ class FrameOptimizer:
                                      (self.view_capacity, self.capacity) if self._headed else None)
         _check_ground_truth(inputs, N)           # (before anything of the row is overwritten)
         _check_group(inputs, N, self.label_view_capacity)
+        _check_photometric(inputs, cfg, V, N)
         with _capture_lock, torch.no_grad():
             main = torch.cuda.current_stream(dev)
             main.synchronize()                                      # (replays of the previous frame have finished: nothing reads the buffers)
@@ -1532,6 +1709,10 @@ class FrameOptimizer:
                 self._log["snapshot_steps"].fill_(-1)
                 self._write_log_table()
             suits = self._prepare_sampler(cfg)
+            if self._photometric is not None:    # (the new frame's gray planes and hard masks, in the buffers the graphs read)
+                for name in ("loss", "stats", "grad_instances", "grad_mlp"):
+                    self._photometric[name].zero_()
+                suits = self._write_photometric() and suits
             main.synchronize()
         return suits
 
@@ -1678,6 +1859,8 @@ class FrameOptimizer:
                           "(many equal importance weights in one histogram bin); see csrc/ray_sampling.h", RuntimeWarning)
         _destroy_graphs(self._graphs)
         self.ray_table = None                  # (43 MB per frame at the reference's size: the table and its guide)
+        if getattr(self, "_photometric", None) is not None:
+            self._photometric["table"] = None
         self.workspace.release()
 
     def __del__(self):
@@ -1747,6 +1930,10 @@ class FrameBatch:
         inputs = list(inputs)
         if not inputs:
             raise ValueError("FrameBatch needs at least one frame")
+        _check_loss_weights(config)
+        if photometric_weight(config) != 0.0:
+            raise ValueError("loss_weights['photometric_loss'] is non-zero: the photometric term is not batched over frames yet "
+                             "(vsrd_frame_photometric serves one frame per call) -- optimise such frames in FrameOptimizer loops")
         largest = max(label_view_count(i) for i in inputs)
         self.max_label_views = largest if max_label_views is None else int(max_label_views)
         if not 0 <= self.max_label_views <= _lib.MAX_LABEL_VIEWS:
