@@ -40,9 +40,9 @@ def _config(split_bf16):
                                            mlp_split_bf16=split_bf16)
 
 
-def _inputs(dev, frame, views, n, height=128, width=128):
+def _inputs(dev, frame, views, n, height=128, width=128, label_views=0):
     from vsrd_amd import launcher
-    return launcher.synthetic_frame_inputs(dev, frame, views, n, height=height, width=width)
+    return launcher.synthetic_frame_inputs(dev, frame, views, n, height=height, width=width, label_views=label_views)
 
 
 def _state(loop):
@@ -170,6 +170,49 @@ def test_frames_of_different_view_counts_walk_their_own_trajectories(dev, split_
     for outside in (0, 33):
         with pytest.raises(ValueError, match="max_views: 1..32"):
             optimization.FrameBatch(frames[:2], config, dev, max_instances=CAPACITY, max_views=outside)
+
+
+ROWS = [  # (shapes (views, instances) of the two frames, width, label views of each frame's group, log, the batch's capacities)
+    pytest.param([(2, 2), (3, 3)], 128, 2, True, dict(max_instances=4, max_views=3, max_label_views=2), id="capacities_group_log"),
+    pytest.param([(3, 3), (3, 3)], 128, 0, False, {}, id="one_shape"),
+    pytest.param([(3, 3), (3, 3)], 100, 0, False, {}, id="width_100"),         # (the bit-packed masks round the width up to 13 bytes)
+]
+
+
+@pytest.mark.parametrize("shapes, width, label_views, log, capacities", ROWS)
+def test_a_row_is_exactly_as_large_as_planned(dev, shapes, width, label_views, log, capacities):
+    """FrameBatch._row_bytes is the sum over the declarations the rows are allocated from: once every output a row can hold has been asked
+    for -- no step, no capture -- every row's cursor stands exactly at the size the arena was planned with, nothing to spare and nothing
+    short, and the rows' layouts are equal."""
+    import dataclasses
+    from vsrd_amd import optimization
+    config = _config(True)
+    if log:
+        config = dataclasses.replace(config, scalar_interval=5, checkpoint_interval=20)
+    for first in range(100, 180, 10):          # (a batch needs ONE frame that suits the table sampler to found its rows on)
+        frames = [_inputs(dev, first + k, views, n, width=width, label_views=label_views) for k, (views, n) in enumerate(shapes)]
+        try:
+            batch = optimization.FrameBatch(frames, config, dev, **capacities)
+        except optimization.UnsuitableFrameError:
+            continue
+        break
+    else:
+        pytest.fail("no frame that suits the table sampler")
+    if log:
+        batch.log_outputs(metrics=True, masks=True)
+    names = ["labels", "masks", "metrics"] + (["group_labels"] if label_views else [])
+    for member in batch.frames:
+        for name in names:
+            member._output_state(name)
+    founder = batch.frames[0]
+    planned = optimization.FrameBatch._row_bytes((founder.view_capacity, 128, width, founder.capacity), batch.config, batch.max_label_views,
+                                                 headed=bool(capacities))
+    assert batch.arena.stride == optimization.FrameArena.aligned(planned)
+    for row in batch.arena.rows:
+        print(f"row {row.index}: cursor {row.cursor}, planned {planned}, {len(row.layout)} buffers")
+        assert row.cursor == planned
+        assert row.layout == batch.arena.rows[0].layout
+    batch.close()
 
 
 # ---- the kernels under a header, through the C ABI with buffers of the test's own -------------------------------------------------------

@@ -70,7 +70,10 @@ def test_workspace_sizes_are_the_parents(lib, monkeypatch):
     R = 30000: 58 -> 32) and 64 (N = 16, R = 100000: 195 -> 64).  NOT visible through these functions, and pinned only as the floor: the
     pair kernel on and off at two rounds (R = 2048 / 2049: 7 MB of seeds per instance against a floor of 74 MB), and the front kernels' LDS
     refusal at N = 64, S = 128 (the one-wave-per-ray plan is refused, the pair plan is taken and has the size the refused one would have).
-    R = 0, N = 1 at one ray and the invalid arguments (0) complete the table."""
+    R = 0, N = 1 at one ray and the invalid arguments (0) complete the table.
+    The patch correlation's and the photometric term's workspaces -- smallest and largest valid shapes, residual on and off, ray counts that
+    are and are not multiples of four, and a count outside each limit (0) -- were recorded from the library of the commit BEFORE their
+    sizes came out of the functions that carve them (patch_workspace, one_kernel_workspace in csrc/api.hip), likewise not from the code under test."""
     forced = [name for name in ("VSRD_PAIR_MAX_RAYS", "VSRD_SLOTS_PER_ITEM") if os.environ.get(name) is not None]
     for name in forced:
         monkeypatch.delenv(name)
@@ -145,6 +148,31 @@ def test_workspace_sizes_are_the_parents(lib, monkeypatch):
             ((0, 1), 0),
             ((33, 1), 0),
             ((1, 65), 0),
+        ],
+        "vsrd_patch_correlation_workspace_bytes": [          # (views, rays, patch pixels)
+            ((1, 1, 1), 104),
+            ((32, 65535, 256), 525864),
+            ((4, 512, 49), 4336),
+            ((3, 1000, 35), 8192),
+            ((0, 10, 9), 0),
+            ((33, 10, 9), 0),
+            ((2, 0, 9), 0),
+            ((2, 65536, 9), 0),
+            ((2, 10, 257), 0),
+        ],
+        "vsrd_frame_photometric_workspace_bytes": [          # (instances, residual, views, rays, patch pixels)
+            ((1, 0, 1, 1, 1), 4195328),
+            ((1, 1, 1, 1, 1), 73762304),
+            ((64, 0, 32, 2048, 256), 268758784),
+            ((64, 1, 32, 2048, 256), 4721053952),
+            ((8, 1, 4, 512, 49), 590171136),
+            ((8, 0, 4, 513, 49), 33634816),
+            ((3, 1, 2, 1001, 35), 221438464),
+            ((0, 0, 2, 10, 9), 0),
+            ((65, 1, 2, 10, 9), 0),
+            ((8, 1, 33, 10, 9), 0),
+            ((8, 1, 2, 2049, 9), 0),
+            ((8, 0, 2, 10, 257), 0),
         ],
     }
     for name, rows in expected.items():

@@ -204,35 +204,32 @@ int rounds_for(int points) {
 constexpr int kResidualWaves = 2;
 constexpr int kMaxBlocksResidual = 512;     // residual adjoint: one wave per SIMD resident; more workgroups than CUs = load balancing (each wave owns N x 1617 partials)
 
-// Residual adjoint, per wave: the residual jets (value + local gradient) the forward sweep leaves for the per-instance phase
-// [round <= 4][N][64] float4 + a word per (round, instance) (render_kernels.h: jet_wave_float4s), and the seeds that phase leaves for the MLP adjoint [ray of batch][round <= 4][N][7][64].
-size_t residual_jet_floats(int num_instances, bool residual) {
-    return residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * jet_wave_float4s(4, num_instances) * 4 : 0;
-}
-size_t residual_cache_floats(int num_instances, bool residual) {
-    return residual_jet_floats(num_instances, residual) +
-           (residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * kMlpBatch * 4 * num_instances * kSeedFloats * kWave : 0);
-}
+// A workspace carved into regions of floats, in order.  `base` may be null (a *_workspace_bytes call): `at`, the floats taken so far, is
+// then all that means anything -- so each workspace below is sized by the function that lays it out.
+struct Carver {
+    float* base;
+    size_t at = 0;
+    float* take(size_t floats) { float* p = base ? base + at : nullptr; at += floats; return p; }
+};
 
-size_t partial_floats(int num_instances, bool residual) {
-    const size_t box = static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * num_instances * kGradStride;
-    const size_t mlp = residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * num_instances * kMlpWeights : 0;
-    return box + mlp + residual_cache_floats(num_instances, residual);
-}
-
-
-// The workspace of the one-kernel forms (vsrd_workspace_bytes): the box partials of the largest grid, then -- residual fields -- the MLP
-// partials, the jets and the seeds of kMaxBlocksResidual x kResidualWaves waves (partial_floats).
+// The workspace of the one-kernel forms (`bytes`: vsrd_workspace_bytes): the box partials of the largest grid, then -- residual fields --
+// per wave of kMaxBlocksResidual x kResidualWaves the MLP
+// partials, the residual jets (value + local gradient) the forward sweep leaves for the per-instance phase [round <= 4][N][64] float4 + a
+// word per (round, instance) (render_kernels.h: jet_wave_float4s), and the seeds that phase leaves for the MLP adjoint
+// [ray of batch][round <= 4][N][7][64].
 struct OneKernelWorkspace {
     float* partials; float* mlp_partials; float4* jets; float* seeds;
+    size_t bytes;
 };
 OneKernelWorkspace one_kernel_workspace(void* workspace, int num_instances, bool residual) {
+    Carver c{static_cast<float*>(workspace)};
+    const size_t waves = residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves : 0;
     OneKernelWorkspace w;
-    w.partials = static_cast<float*>(workspace);
-    w.mlp_partials = w.partials + static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * num_instances * kGradStride;
-    float* jets = w.mlp_partials + (residual ? static_cast<size_t>(kMaxBlocksResidual) * kResidualWaves * num_instances * kMlpWeights : 0);
-    w.jets = reinterpret_cast<float4*>(jets);
-    w.seeds = jets + residual_jet_floats(num_instances, residual);
+    w.partials = c.take(static_cast<size_t>(kMaxBlocks) * kMaxWavesPerBlock * num_instances * kGradStride);
+    w.mlp_partials = c.take(waves * num_instances * kMlpWeights);
+    w.jets = reinterpret_cast<float4*>(c.take(waves * jet_wave_float4s(4, num_instances) * 4));
+    w.seeds = c.take(waves * kMlpBatch * 4 * num_instances * kSeedFloats * kWave);
+    w.bytes = c.at * sizeof(float);
     return w;
 }
 
@@ -546,7 +543,7 @@ const char* vsrd_error_string(int32_t code) {
 
 size_t vsrd_workspace_bytes(int32_t num_instances, int32_t residual) {
     if (num_instances < 1 || num_instances > VSRD_MAX_INSTANCES) return 0;
-    return partial_floats(num_instances, residual != 0) * sizeof(float);
+    return one_kernel_workspace(nullptr, num_instances, residual != 0).bytes;
 }
 
 int32_t vsrd_ray_directions(const float* inverse_projection, int32_t num_views, int32_t height, int32_t width,
@@ -1416,26 +1413,44 @@ bool valid_patch_shape(int V, int R, int P) {
     return V >= 1 && V <= kPatchMaxViews && R >= 1 && R <= kPatchMaxRays && P >= 1 && P <= kPatchMaxPixels;
 }
 
+// What the patch calls and vsrd_frame_photometric refuse of a patch config (each side within the pixel limit before their product is formed).
+bool valid_patch_config(const vsrd_patch_correlation_config* c) {
+    if (!c || c->patch_width < 1 || c->patch_height < 1 || c->patch_width > kPatchMaxPixels || c->patch_height > kPatchMaxPixels) return false;
+    const int V = c->num_views;
+    return valid_patch_shape(V, c->num_rays, c->patch_width * c->patch_height) && c->top_k >= 1 && c->top_k <= V && c->target_view >= 0 &&
+           c->target_view < V && c->height >= 2 && c->width >= 2 && static_cast<int64_t>(c->height) * c->width < (int64_t{1} << 30);
+}
+
+// The patch calls' workspace (patch_correlation.h: PatchArgs; `bytes`: vsrd_patch_correlation_workspace_bytes): the views' constants
+// [V,12] + K_t^-1 [9] (padded to 12), then the rays' (sum, count) [R,2].
+struct PatchWorkspace {
+    float* constants; float* ray_stats;
+    size_t bytes;
+};
+PatchWorkspace patch_workspace(void* workspace, int V, int R) {
+    Carver c{static_cast<float*>(workspace)};
+    PatchWorkspace w;
+    w.constants = c.take(static_cast<size_t>(V + 1) * kPatchViewFloats);
+    w.ray_stats = c.take(static_cast<size_t>(R) * 2);
+    w.bytes = c.at * sizeof(float);
+    return w;
+}
+
 // The checks the two calls share, in this order: the shape, the pointers, the workspace.
 int32_t patch_args(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics, const int32_t* pixels,
                    const float* positions, const float* normals, const uint8_t* converged, void* workspace, size_t workspace_bytes, PatchArgs* a) {
     static_assert(kPatchMaxViews == VSRD_PATCH_MAX_VIEWS && kPatchMaxPixels == VSRD_PATCH_MAX_PIXELS && kPatchMaxRays == VSRD_PATCH_MAX_RAYS,
                   "patch_correlation.h and the ABI agree on the limits");
-    if (!config || config->patch_width < 1 || config->patch_height < 1 || config->patch_width > kPatchMaxPixels || config->patch_height > kPatchMaxPixels)
-        return VSRD_E_INVALID_ARGUMENT;
-    const int V = config->num_views, R = config->num_rays, P = config->patch_width * config->patch_height;
-    if (!valid_patch_shape(V, R, P) || config->top_k < 1 || config->top_k > V || config->target_view < 0 || config->target_view >= V ||
-        config->height < 2 || config->width < 2 || static_cast<int64_t>(config->height) * config->width >= (int64_t{1} << 30))
-        return VSRD_E_INVALID_ARGUMENT;
+    if (!valid_patch_config(config)) return VSRD_E_INVALID_ARGUMENT;
     if (!gray || !intrinsics || !extrinsics || !pixels || !positions || !normals || !converged) return VSRD_E_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < patch_workspace_floats(V, R) * sizeof(float)) return VSRD_E_WORKSPACE;
-    a->num_views = V; a->num_rays = R; a->height = config->height; a->width = config->width;
+    const PatchWorkspace w = patch_workspace(workspace, config->num_views, config->num_rays);
+    if (!workspace || workspace_bytes < w.bytes) return VSRD_E_WORKSPACE;
+    a->num_views = config->num_views; a->num_rays = config->num_rays; a->height = config->height; a->width = config->width;
     a->patch_width = config->patch_width; a->patch_height = config->patch_height; a->top_k = config->top_k; a->target_view = config->target_view;
     a->sample_epsilon = config->sample_epsilon; a->correlation_epsilon = config->correlation_epsilon;
     a->gray = gray; a->intrinsics = intrinsics; a->extrinsics = extrinsics; a->pixels = pixels; a->positions = positions; a->normals = normals;
     a->converged = converged;
-    a->constants = static_cast<float*>(workspace);
-    a->ray_stats = a->constants + static_cast<size_t>(V + 1) * kPatchViewFloats;
+    a->constants = w.constants; a->ray_stats = w.ray_stats;
     return VSRD_OK;
 }
 }  // namespace
@@ -1451,7 +1466,7 @@ int32_t vsrd_grayscale_images(const float* images, int32_t num_views, int32_t he
 }
 
 size_t vsrd_patch_correlation_workspace_bytes(int32_t num_views, int32_t num_rays, int32_t patch_pixels) {
-    return valid_patch_shape(num_views, num_rays, patch_pixels) ? patch_workspace_floats(num_views, num_rays) * sizeof(float) : 0;
+    return valid_patch_shape(num_views, num_rays, patch_pixels) ? patch_workspace(nullptr, num_views, num_rays).bytes : 0;
 }
 
 int32_t vsrd_patch_correlation_forward(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics,
@@ -1500,10 +1515,9 @@ struct PhotometricWorkspace {
 size_t padded4(size_t n) { return (n + 3) & ~static_cast<size_t>(3); }
 PhotometricWorkspace photometric_workspace(void* workspace, int N, bool residual, int V, int R) {
     PhotometricWorkspace w;
-    float* base = static_cast<float*>(workspace);
-    size_t at = 0;
+    Carver c{static_cast<float*>(workspace)};
     const size_t rays = padded4(static_cast<size_t>(R));
-    auto take = [&](size_t floats) { float* p = base + at; at += padded4(floats); return p; };
+    auto take = [&](size_t floats) { return c.take(padded4(floats)); };
     w.directions = take(3 * rays); w.p0 = take(3 * rays); w.d0 = take(rays); w.g0 = take(3 * rays); w.slopes = take(rays);
     w.p1 = take(3 * rays); w.g1 = take(3 * rays); w.lengths = take(rays); w.normals = take(3 * rays);
     w.grad_p1 = take(3 * rays); w.grad_normals = take(3 * rays); w.gamma = take(3 * rays); w.grad_x = take(3 * rays); w.grad_d0 = take(rays);
@@ -1512,12 +1526,12 @@ PhotometricWorkspace photometric_workspace(void* workspace, int N, bool residual
     w.converged = reinterpret_cast<unsigned char*>(take(rays / 4));
     w.first_instances = take(static_cast<size_t>(N) * kGradStride); w.second_instances = take(static_cast<size_t>(N) * kGradStride);
     w.first_mlp = take(residual ? static_cast<size_t>(N) * kMlpWeights : 0); w.second_mlp = take(residual ? static_cast<size_t>(N) * kMlpWeights : 0);
-    w.patch_bytes = patch_workspace_floats(V, R) * sizeof(float);
-    w.patch = take(patch_workspace_floats(V, R));
-    at = (at + 63) & ~static_cast<size_t>(63);
-    w.field = base + at;
+    w.patch_bytes = patch_workspace(nullptr, V, R).bytes;
+    w.patch = take(w.patch_bytes / sizeof(float));
+    c.at = (c.at + 63) & ~static_cast<size_t>(63);
     w.field_bytes = vsrd_workspace_bytes(N, residual);
-    w.total_bytes = at * sizeof(float) + w.field_bytes;
+    w.field = c.take(w.field_bytes / sizeof(float));
+    w.total_bytes = c.at * sizeof(float);
     return w;
 }
 }  // namespace
@@ -1539,11 +1553,7 @@ int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, cons
     if (!patch || !valid_field(field) || config->num_iterations < 0) return VSRD_E_INVALID_ARGUMENT;
     const int N = field->num_instances, V = patch->num_views, R = patch->num_rays;
     const bool residual = field->mlp_weights != nullptr;
-    if (R < 1 || R > kPhotometricMaxRays || patch->patch_width < 1 || patch->patch_height < 1 || patch->patch_width > kPatchMaxPixels ||
-        patch->patch_height > kPatchMaxPixels || !valid_patch_shape(V, R, patch->patch_width * patch->patch_height) || patch->top_k < 1 ||
-        patch->top_k > V || patch->target_view < 0 || patch->target_view >= V || patch->height < 2 || patch->width < 2 ||
-        static_cast<int64_t>(patch->height) * patch->width >= (int64_t{1} << 30))
-        return VSRD_E_INVALID_ARGUMENT;
+    if (R > kPhotometricMaxRays || !valid_patch_config(patch)) return VSRD_E_INVALID_ARGUMENT;
     if (!camera_position || !ray_directions || !gray || !intrinsics || !extrinsics || !ray_indices || !loss || !stats || !photometric_grad_instances ||
         !grad_instances || (residual && (!photometric_grad_mlp || !grad_mlp)))
         return VSRD_E_INVALID_ARGUMENT;

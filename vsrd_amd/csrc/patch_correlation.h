@@ -58,10 +58,6 @@ struct PatchArgs {
     float* ray_stats;                        // workspace: [R,2] = (sum, count) of the ray's selected non-NaN coefficients
 };
 
-__host__ __device__ inline size_t patch_workspace_floats(int V, int R) {
-    return static_cast<size_t>(V + 1) * kPatchViewFloats + static_cast<size_t>(R) * 2;
-}
-
 // ---- grayscale ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float patch_gray(float r, float g, float b) {
     return __fmaf_rn(0.114f, b, __fmaf_rn(0.587f, g, __fmul_rn(0.2989f, r)));

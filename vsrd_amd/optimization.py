@@ -407,10 +407,19 @@ class FrameArena:
 
     ALIGNMENT = 256
 
+    @staticmethod
+    def aligned(nbytes):
+        """`nbytes` rounded up to where the next buffer of a row starts: the ONE alignment rule of rows, strides and FrameBatch._row_bytes."""
+        return (int(nbytes) + FrameArena.ALIGNMENT - 1) // FrameArena.ALIGNMENT * FrameArena.ALIGNMENT
+
     def __init__(self, num_frames, row_bytes, device):
-        self.stride = (int(row_bytes) + self.ALIGNMENT - 1) // self.ALIGNMENT * self.ALIGNMENT
+        self.stride = self.aligned(row_bytes)
         self.buffer = torch.empty(int(num_frames), self.stride, dtype=torch.uint8, device=device)
         self.rows = [FrameRow(self, f) for f in range(int(num_frames))]
+
+
+def _buffer_bytes(shape, dtype):
+    return math.prod(int(x) for x in shape) * torch.empty((), dtype=dtype).element_size()
 
 
 class FrameRow:
@@ -427,16 +436,13 @@ class FrameRow:
         end = offset + nbytes
         if end > self.arena.stride:
             raise RuntimeError(f"frame arena row of {self.arena.stride} bytes exhausted ({end} needed): FrameBatch._row_bytes is too small")
-        self.cursor = (end + FrameArena.ALIGNMENT - 1) // FrameArena.ALIGNMENT * FrameArena.ALIGNMENT
+        self.cursor = FrameArena.aligned(end)
         self.layout.append((offset, nbytes))
         return self.arena.buffer[self.index, offset:end]
 
     def new(self, shape, dtype=torch.float32, fill=None):
         shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
-        count = 1
-        for x in shape:
-            count *= x
-        view = self.bytes(count * torch.empty((), dtype=dtype).element_size()).view(dtype).view(shape)
+        view = self.bytes(_buffer_bytes(shape, dtype)).view(dtype).view(shape)
         if fill is not None:
             view.fill_(fill)
         return view
@@ -734,6 +740,73 @@ def _output(name):
     return _OUTPUTS[name] if name in _OUTPUTS else _LABEL_VIEW_OUTPUTS[name]
 
 
+# ---- what a graph-mode loop keeps besides its outputs, declared as they are: plain functions of the capacities and the config ->
+# [(name, shape, dtype, fill)] in the order of allocation, no device.  FrameOptimizer allocates from them (`_buffers`) and
+# FrameBatch._row_bytes sums over them, so a buffer added to a family is in the size of a row
+def _parameter_buffers(N):
+    """The modules' parameters (the detector's laid out for N instances), then Adam's state of each as adam_state_tensors creates it."""
+    with torch.device("meta"):               # (no memory, no random numbers drawn)
+        named = [(f"{module}.{name}", tuple(p.shape)) for module, m in zip(("detector", "hyper_distance_field"), _fresh_modules(N))
+                 for name, p in m.named_parameters()]
+    f32 = torch.float32
+    state = [[(f"{name}.step", (), f32, 0.0), (f"{name}.exp_avg", shape, f32, 0.0), (f"{name}.exp_avg_sq", shape, f32, 0.0)] for name, shape in named]
+    return [(name, shape, f32, None) for name, shape in named] + sum(state, [])
+
+
+def _scalar_buffers(config):
+    """The learning rates of the optimiser's five groups and its default rate, the step counter (= Philox counter) and the schedule
+    (temperature, std, cosine_ratio)."""
+    rates = zip(("locations", "dimensions", "orientations", "embeddings", "hypernetwork", "default"), _initial_rates(config) + [config.learning_rate])
+    return [(f"lr.{name}", (), torch.float32, value) for name, value in rates] + [("step_tensor", (1,), torch.int64, 0), ("schedule", (3,), torch.float32, 1.0)]
+
+
+def _ray_buffers(V, N, H, W):
+    """The rays of every view, the soft masks [V H W, N] (the kernels read the targets with target_stride = N) and the importance weights."""
+    f32, pixels = torch.float32, V * H * W
+    return [("camera_positions", (V, 3), f32, 0.0), ("ray_directions", (pixels, 3), f32, 0.0), ("flat_masks", (pixels, N), f32, 0.0),
+            ("sampling_weights", (pixels,), f32, 0.0)]
+
+
+def _table_buffers(V, N):
+    """The frame's cameras, ground-truth boxes and visibility as the kernels read them."""
+    f32 = torch.float32
+    return [("extrinsics", (V, 16), f32, 0.0), ("intrinsics", (V, 9), f32, 0.0), ("gt_boxes", (V, N, 4), f32, 0.0), ("visible", (V, N), torch.uint8, 0)]
+
+
+def _glue_buffers(V, N, config, headed):
+    """The fused glue's (csrc/frame_step.h): the input tables, what the prologue, the render launch and the epilogue hand each other, with
+    `headed` the row's vsrd_frame_header, and from `hyper_workspace` on what is created after the parameters' Adam state (rebind)."""
+    lib, rays = _lib.load(), int(config.num_rays)
+    f32, i32, i64, u8 = torch.float32, torch.int32, torch.int64, torch.uint8
+    return _table_buffers(V, N) + [
+        ("scratch", (lib.vsrd_frame_scratch_bytes(V, N),), u8, None), ("instances", (N, 16), f32, 0.0), ("pd_indices", (N,), i64, 0),
+        ("gt_indices", (N,), i64, 0), ("target_columns", (N,), i32, 0), ("instance_weights", (N,), f32, 1.0), ("projection_losses", (2,), f32, 0.0),
+        ("render_losses", (2,), f32, 0.0), ("grad_raw", (N, 8), f32, 0.0), ("raw_gradients", (N, 8), f32, 0.0), ("grad_instances", (N, 16), f32, 0.0),
+        ("grad_mlp", (N, _lib.MLP_WEIGHTS), f32, 0.0), ("record", (5,), f32, 0.0)] + \
+        ([("header", (ctypes.sizeof(_lib.FrameHeader),), u8, 0)] if headed else []) + [
+        ("hyper_workspace", (lib.vsrd_hypernetwork_workspace_bytes(N),), u8, None), ("picks", (rays,), i64, 0), ("ray_indices", (rays,), i64, 0),
+        ("mlp_weights", (N, _lib.MLP_WEIGHTS), f32, 0.0), ("mlp_centred", (N, _lib.MLP_WEIGHTS), f32, 0.0)]
+
+
+def _log_capacity(N, config):
+    """(history rows, snapshot slots, floats of a slot) of the log of a loop laid out for N instances."""
+    rows = config.num_steps // config.scalar_interval if config.scalar_interval > 0 else 0
+    slots = config.num_steps // config.checkpoint_interval if config.checkpoint_interval > 0 else 0
+    with torch.device("meta"):
+        layout = _log_slot_layout(*_fresh_modules(N), N)
+    return rows, slots, sum(size for _, _, size in layout) if slots else 0
+
+
+def _log_buffers(N, config):
+    """The device-side log's (csrc/frame_log.h): history [rows, 22], snapshots [slots, slot], the slots' steps, the four counters, the list
+    of the five rate pointers and the segment table."""
+    rows, slots, slot_floats = _log_capacity(N, config)
+    f32, i32 = torch.float32, torch.int32
+    return [("history", (max(rows, 1), _lib.FRAME_LOG_COLUMNS), f32, 0.0), ("snapshots", (max(slots, 1), max(slot_floats, 4)), f32, 0.0),
+            ("snapshot_steps", (max(slots, 1),), i32, -1), ("counters", (4,), i32, 0), ("rate_pointers", (5,), torch.int64, 0),
+            ("table", (_lib.FRAME_LOG_SEGMENTS * ctypes.sizeof(_lib.LogSegment),), torch.uint8, 0)]
+
+
 def photometric_weight(config):
     """The weight of the photometric term, 0.0 when it is off: the reference tests the weight's truthiness (scripts/main.py:689)."""
     return float(config.loss_weights.get("photometric_loss", 0.0) or 0.0)
@@ -850,14 +923,14 @@ class FrameOptimizer:
                 p.data = _instance_prefix(self._place(p.data, (1, self.capacity, *p.shape[2:]), p.dtype), N)
             for p in self.hyper_distance_field.parameters():
                 p.data = self._place(p.data, p.shape, p.dtype)
-        def rate(value):   # graph mode: learning rates are device tensors decayed in place inside the captured step
-            return self._new((), fill=value) if self.graph else value
-        groups = [dict(params=params, lr=rate(value)) for params, value in zip(self._module_parameters(), _initial_rates(config))]
-        self.optimizer = torch.optim.Adam(groups, lr=rate(config.learning_rate), capturable=self.graph)
+        # graph mode: learning rates are device tensors decayed in place inside the captured step
+        scalars = _scalar_buffers(config)
+        *rates, default = (self._buffers(scalars[:-2]) if self.graph else {name: value for name, _, _, value in scalars[:-2]}).values()
+        groups = [dict(params=params, lr=lr) for params, lr in zip(self._module_parameters(), rates)]
+        self.optimizer = torch.optim.Adam(groups, lr=default, capturable=self.graph)
         self.scheduler = None if self.graph else torch.optim.lr_scheduler.ExponentialLR(self.optimizer, gamma=config.lr_gamma)
         # per-step scalars on the device (graph mode): step index = Philox counter, (temperature, std, cosine_ratio)
-        self.step_tensor = self._new(1, torch.int64, fill=0)
-        self.schedule = self._new(3, torch.float32, fill=1.0)
+        self.step_tensor, self.schedule = self._buffers(scalars[-2:]).values()
         # this frame's own scratch (frames may be optimised concurrently on other streams); freed with the optimizer.  Graph mode
         # sizes it for the residual phase up front: a captured graph holds the buffer's address
         self.workspace = rendering.Workspace(allocate=None if self._row is None else self._row.bytes)
@@ -890,13 +963,19 @@ class FrameOptimizer:
         """`tensor` as this loop's buffer of the full `shape` (module-level `_place`): in the frame's row, a slot's own, or the tensor itself."""
         return _place(tensor.to(self.device), shape, dtype, self._row, self.persistent)
 
+    def _buffers(self, declared, contents=None):
+        """The buffers of a declaration -- [(name, shape, dtype, fill)]: _FrameOutput.buffers and the families above -- by name, created in
+        its order by the one placement rule: the tensors of `contents` (by name) go into the leading corner of theirs (`_place`)."""
+        contents = contents or {}
+        return {name: self._place(contents[name], shape, dtype) if name in contents else self._new(shape, dtype, fill)
+                for name, shape, dtype, fill in declared}
+
     def _input_tables(self):
         """The frame's cameras, ground-truth boxes and visibility as the kernels read them, laid out for the capacities."""
-        inp, V, N, views = self.inputs, self.num_views, self.num_instances, self.view_capacity
-        return dict(extrinsics=self._place(inp.extrinsic_matrices.reshape(V, 16), (views, 16)),
-                    intrinsics=self._place(inp.intrinsic_matrices.reshape(V, 9), (views, 9)),
-                    gt_boxes=self._place(inp.boxes_2d.reshape(V, N, 4), (views, self.capacity, 4)),
-                    visible=self._place(inp.visible_masks, (views, self.capacity), torch.uint8))
+        inp, V, N = self.inputs, self.num_views, self.num_instances
+        return self._buffers(_table_buffers(self.view_capacity, self.capacity),
+                             dict(extrinsics=inp.extrinsic_matrices.reshape(V, 16), intrinsics=inp.intrinsic_matrices.reshape(V, 9),
+                                  gt_boxes=inp.boxes_2d.reshape(V, N, 4), visible=inp.visible_masks))
 
     def _set_views(self, V):
         """The loop's per-view tensors are the first V views of its buffers (`self._full`: laid out for the view capacity) -- view-major,
@@ -924,10 +1003,8 @@ class FrameOptimizer:
         # [view capacity x H W, instance capacity] soft masks (the kernels read the targets with target_stride = capacity) and every other
         # per-view buffer laid out for the view capacity; the frame fills their leading corners.  (A slot's graphs read the masks through
         # this address for every later frame; a loop of one frame reads the caller's own tensor.)
-        views, pixels = self.view_capacity, self.view_capacity * H * W
-        self._full = dict(camera_positions=self._place(cam, (views, 3)), ray_directions=self._place(dirs.reshape(-1, 3), (pixels, 3)),
-                          flat_masks=self._place(inputs.soft_masks.reshape(-1, N), (pixels, self.capacity)),
-                          sampling_weights=self._new(pixels, fill=0.0))
+        self._full = self._buffers(_ray_buffers(self.view_capacity, self.capacity, H, W),
+                                   dict(camera_positions=cam, ray_directions=dirs.reshape(-1, 3), flat_masks=inputs.soft_masks.reshape(-1, N)))
         self._set_views(self.num_views)
         torch.amax(self.flat_masks[:, :N], dim=-1, out=self.sampling_weights)                                             # main.py:620-624
         self.ray_table = self.ray_remap = None
@@ -984,35 +1061,24 @@ class FrameOptimizer:
     # ---- fused glue (csrc/frame_step.h) ---------------------------------------------------------------------------------
     def _init_fused_glue(self):
         cfg, dev = self.config, self.device
-        N = self.capacity          # (every per-instance buffer is laid out for the capacity)
-        lib = _lib.load()
         self._frame = self._frame_config()
         b = self._glue = {}
-        self._full.update(self._input_tables())
+        tables = self._input_tables()
+        self._full.update(tables)
         self._set_views(self.num_views)         # (the glue's tables and b["masks"]: the first V views of the full buffers)
-        new = self._new            # (a frame of a batch: everything below lives in the frame's row of the arena)
-        b["scratch"] = new(lib.vsrd_frame_scratch_bytes(self.view_capacity, N), torch.uint8)
-        b["instances"] = new((N, 16), fill=0.0)
-        b["pd_indices"], b["gt_indices"] = new(N, torch.int64, fill=0), new(N, torch.int64, fill=0)
-        b["target_columns"] = new(N, torch.int32, fill=0)
-        b["instance_weights"] = new(N, fill=1.0)
-        b["projection_losses"], b["render_losses"] = new(2, fill=0.0), new(2, fill=0.0)
-        b["grad_raw"], b["raw_gradients"] = new((N, 8), fill=0.0), new((N, 8), fill=0.0)
-        b["grad_instances"], b["grad_mlp"] = new((N, 16), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
-        b["record"] = new(5, fill=0.0)
+        # (a frame of a batch: everything below lives in the frame's row of the arena, every per-instance buffer laid out for the capacity)
+        declared = _glue_buffers(self.view_capacity, self.capacity, cfg, self._headed)[len(tables):]
+        after_state = [name for name, *_ in declared].index("hyper_workspace")
+        b.update(self._buffers(declared[:after_state]))
         if self._headed:
-            b["header"] = new(ctypes.sizeof(_lib.FrameHeader), torch.uint8, fill=0)          # vsrd_frame_header
             self._write_header()
         self.fused_hypernetwork = True
         self.rebind()
-        b["hyper_workspace"] = new(lib.vsrd_hypernetwork_workspace_bytes(N), torch.uint8)
+        b.update(self._buffers(declared[after_state:]))
         # the three things a step needs before its render launch -- its rays, the boxes' side (prologue) and the generated MLP weights --
         # do not depend on each other: they run as three branches (two side streams, forked from and joined to the step's stream), and
         # so do the two things after it (epilogue, hypernetwork backward).  Captured, they become parallel branches of the hipGraph
         self._branches = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
-        b["picks"] = new(cfg.num_rays, torch.int64, fill=0)
-        b["ray_indices"] = new(cfg.num_rays, torch.int64, fill=0)
-        b["mlp_weights"], b["mlp_centred"] = new((N, _lib.MLP_WEIGHTS), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
         if cfg.scalar_interval > 0 or cfg.checkpoint_interval > 0:
             self._init_log()
 
@@ -1112,20 +1178,13 @@ class FrameOptimizer:
         """The log's buffers, at construction (a frame of a batch: in its row, the same offsets in every row): history
         [num_steps // scalar_interval, 22], snapshots [num_steps // checkpoint_interval, slot], the slots' steps, the four counters, the
         list of the five rate pointers and the segment table."""
-        cfg, new = self.config, self._new
-        rows = cfg.num_steps // cfg.scalar_interval if cfg.scalar_interval > 0 else 0
-        slots = cfg.num_steps // cfg.checkpoint_interval if cfg.checkpoint_interval > 0 else 0
-        layout = _log_slot_layout(self.detector, self.hyper_distance_field, self.capacity)
-        slot_floats = sum(size for _, _, size in layout) if slots else 0
+        cfg = self.config
+        rows, slots, slot_floats = _log_capacity(self.capacity, cfg)
+        segments = len(_log_slot_layout(self.detector, self.hyper_distance_field, self.capacity))
         log = self._log = dict(rows=rows, slots=slots, slot_floats=slot_floats, metrics=False, masks=False)
-        log["history"] = new((max(rows, 1), _lib.FRAME_LOG_COLUMNS), fill=0.0)
-        log["snapshots"] = new((max(slots, 1), max(slot_floats, 4)), fill=0.0)
-        log["snapshot_steps"] = new(max(slots, 1), torch.int32, fill=-1)
-        log["counters"] = new(4, torch.int32, fill=0)
-        log["rate_pointers"] = new(5, torch.int64, fill=0)
-        log["table"] = new(_lib.FRAME_LOG_SEGMENTS * ctypes.sizeof(_lib.LogSegment), torch.uint8, fill=0)
+        log.update(self._buffers(_log_buffers(self.capacity, cfg)))
         log["config"] = _lib.FrameLogConfig(
-            int(cfg.scalar_interval), int(cfg.checkpoint_interval), rows, slots, slot_floats, len(layout), 1, 0, self.step_tensor.data_ptr(),
+            int(cfg.scalar_interval), int(cfg.checkpoint_interval), rows, slots, slot_floats, segments, 1, 0, self.step_tensor.data_ptr(),
             self._glue["record"].data_ptr(), log["rate_pointers"].data_ptr(), self.schedule.data_ptr(), None, log["table"].data_ptr(),
             log["history"].data_ptr(), log["snapshots"].data_ptr(), log["snapshot_steps"].data_ptr(), log["counters"].data_ptr())
         self._write_log_table()
@@ -1733,7 +1792,7 @@ class FrameOptimizer:
                 _check_group(self.inputs, self.num_instances, self.label_view_capacity)
             views = self.label_view_capacity if name in _LABEL_VIEW_OUTPUTS else self.view_capacity      # (the group's buffers: label views along dimension 0)
             with _capture_lock, torch.no_grad():
-                self._outputs[name] = {key: self._new(*buffer) for key, *buffer in _output(name).buffers(views, self.capacity, H, W)}
+                self._outputs[name] = self._buffers(_output(name).buffers(views, self.capacity, H, W))
                 if name == "metrics":
                     self._write_ground_truth(self.num_instances)
                 if name == "group_labels":
@@ -1971,7 +2030,7 @@ class FrameBatch:
             config = dataclasses.replace(config, mlp_adjoint_item_slots=self.item_slots(self.size, config, shape[-1]))
         self.config, self.device = config, _indexed(device)
         with _capture_lock:
-            self.arena = FrameArena(self.size, self._row_bytes(shape, config, self.max_label_views), self.device)
+            self.arena = FrameArena(self.size, self._row_bytes(shape, config, self.max_label_views, headed=capacities != (None, None)), self.device)
         # A row is FOUNDED on a frame that suits the table sampler its graphs will draw from (the frames a row later serves come through reset(),
         # which says so when one does not suit).  A founder that does not suit is replaced by the first one that does -- the shape is what a
         # row needs from its founder -- and listed in `unsuitable_founders`; no suitable founder at all: UnsuitableFrameError.
@@ -2018,28 +2077,25 @@ class FrameBatch:
         return slots
 
     @staticmethod
-    def _row_bytes(shape, config, label_views=0):
-        """Bytes of one frame's row: every device buffer a FrameOptimizer(row=...) creates (FrameRow.new raises if this is short)."""
+    def _row_bytes(shape, config, label_views=0, headed=False):
+        """Bytes of one frame's row: the aligned sizes of everything a FrameOptimizer(row=...) creates there, summed over the declarations it
+        allocates from and the regions the library sizes, in the order of allocation (Adam's state, declared with the parameters, comes
+        amid the glue) -- every output included, so a row is exactly full once each has been asked for.  `headed`: rows with a header."""
         V, H, W, N = (int(x) for x in shape)
-        lib = _lib.load()
-        pixels = V * H * W
-        with torch.device("meta"):               # (no memory, no random numbers drawn)
-            parameters = sum(p.numel() for module in _fresh_modules(N) for p in module.parameters())
-        workspace = max(lib.vsrd_workspace_bytes(N, 1), lib.vsrd_residual_step_workspace_bytes(N, int(config.num_samples), int(config.num_rays)))
-        total = 4 * 3 * parameters                                   # parameters, exp_avg, exp_avg_sq
-        total += pixels * (12 + 4 * N + 4) + 12 * V                  # ray directions, soft masks, importance weights, camera positions
-        total += lib.vsrd_ray_table_bytes(pixels)
-        total += workspace + lib.vsrd_hypernetwork_workspace_bytes(N) + lib.vsrd_frame_scratch_bytes(V, N)
-        total += 4 * (3 * N * _lib.MLP_WEIGHTS + 64 * N + 128 * V) + 16 * int(config.num_rays)          # the glue's tables
-        total += N * H * ((W + 7) // 8) + 4 * H * W * N + 12 * N     # masks(): bit-packed masks, soft values, counts
-        # (metrics(): 200 N + 68 bytes in five buffers, at most 14 KB: within the slack below)
-        total += int(label_views) * (129 * N + 108)                 # group_labels(): the label views' tables, ids, corners and boxes (the [N] outputs: slack)
-        if config.scalar_interval > 0 or config.checkpoint_interval > 0:        # the log: history rows, snapshot slots (the small buffers: slack)
-            with torch.device("meta"):
-                slot = sum(size for _, _, size in _log_slot_layout(*_fresh_modules(N), N))
-            total += 4 * _lib.FRAME_LOG_COLUMNS * (config.num_steps // config.scalar_interval if config.scalar_interval > 0 else 1)
-            total += 4 * slot * (config.num_steps // config.checkpoint_interval) if config.checkpoint_interval > 0 else 16
-        return total + (4 << 20)                                     # 256-byte alignment of ~400 buffers, step counters, rates, slack
+        def sizes(declared):
+            return [_buffer_bytes(shape, dtype) for _, shape, dtype, _ in declared]
+        parts = sizes(_parameter_buffers(N) + _scalar_buffers(config))
+        parts += [rendering.Workspace.adjoint_bytes(N, True, (config.num_samples, config.num_rays))]
+        parts += sizes(_ray_buffers(V, N, H, W)) + [_lib.load().vsrd_ray_table_bytes(V * H * W)]
+        parts += sizes(_glue_buffers(V, N, config, headed))
+        if config.scalar_interval > 0 or config.checkpoint_interval > 0:
+            parts += sizes(_log_buffers(N, config))
+        for output in _OUTPUTS.values():
+            parts += sizes(output.buffers(V, N, H, W))
+        if label_views > 0:
+            for output in _LABEL_VIEW_OUTPUTS.values():
+                parts += sizes(output.buffers(int(label_views), N, H, W))
+        return sum(FrameArena.aligned(nbytes) for nbytes in parts)
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
     def _members(self, active):

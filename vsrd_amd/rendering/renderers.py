@@ -44,14 +44,21 @@ class Workspace:
         self._retired = []      # outgrown buffers that captured graphs may still reference (only kept when asked to)
         self.keep_outgrown = False
 
-    def adjoint(self, device, num_instances, residual=False, step_shape=None, backward_shape=None):
-        """``step_shape = (num_samples, num_rays)``: scratch of vsrd_render_residual_step for that launch (seeds of a chunk of rays);
+    @staticmethod
+    def adjoint_bytes(num_instances, residual=False, step_shape=None, backward_shape=None):
+        """The bytes ``adjoint()`` allocates for these arguments (no device: whoever lays a frame's row out sums it in beforehand).
+        ``step_shape = (num_samples, num_rays)``: scratch of vsrd_render_residual_step for that launch (seeds of a chunk of rays);
         ``backward_shape = (num_distances, num_rays)``: scratch with which vsrd_render_backward runs its two-kernel form on residual fields."""
         need = _lib.load().vsrd_workspace_bytes(int(num_instances), 1 if residual else 0)
         if residual and step_shape is not None:
             need = max(need, _lib.load().vsrd_residual_step_workspace_bytes(int(num_instances), int(step_shape[0]), int(step_shape[1])))
         if residual and backward_shape is not None:
             need = max(need, _lib.load().vsrd_render_backward_workspace_bytes(int(num_instances), 1, int(backward_shape[0]), int(backward_shape[1])))
+        return need
+
+    def adjoint(self, device, num_instances, residual=False, step_shape=None, backward_shape=None):
+        """The adjoint launches' scratch, grown to ``adjoint_bytes`` of these arguments."""
+        need = self.adjoint_bytes(num_instances, residual, step_shape, backward_shape)
         buf = self._adjoint.get(device)
         if buf is None or buf.numel() < need:
             if buf is not None and self.keep_outgrown:
