@@ -887,15 +887,16 @@ int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* con
  * Refused with VSRD_E_INVALID_ARGUMENT before any launch: a NULL config, patch, field or required pointer; N outside 1..VSRD_MAX_INSTANCES;
  * R outside 1..VSRD_PHOTOMETRIC_MAX_RAYS (the table sampler's limit); top_k > V, V > VSRD_PATCH_MAX_VIEWS, patch pixels >
  * VSRD_PATCH_MAX_PIXELS and the other limits of vsrd_patch_correlation_forward; num_iterations < 0.  A workspace that is too small:
- * VSRD_E_WORKSPACE.  num_frames >= 2: VSRD_E_UNSUPPORTED before any launch (the fields are there so that batching can follow). */
+ * VSRD_E_WORKSPACE.  num_frames >= 2: VSRD_E_UNSUPPORTED before any launch -- a batch of frames goes through
+ * vsrd_frame_photometric_with_header below. */
 #define VSRD_PHOTOMETRIC_MAX_RAYS 2048
 typedef struct vsrd_frame_photometric_config {
     int32_t num_iterations;         /* of the trace (config.json: surface_num_iterations)                                     */
     float convergence_criteria;
     float bounding_radius;          /* <= 0: none                                                                             */
     float scale;                    /* photometric weight / silhouette weight                                                 */
-    int32_t num_frames;             /* 0 or 1 = one frame; >= 2: VSRD_E_UNSUPPORTED                                           */
-    int64_t frame_stride;
+    int32_t num_frames;             /* 0 or 1 = one frame; >= 2: vsrd_frame_photometric_with_header only (here VSRD_E_UNSUPPORTED) */
+    int64_t frame_stride;           /* bytes between the frames' copies of every buffer of the call                           */
 } vsrd_frame_photometric_config;
 
 /* 0 for a shape outside the limits. */
@@ -910,6 +911,42 @@ int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, cons
 /* After vsrd_frame_epilogue: record[4] += weight * loss (the product rounded, then the sum), one single-lane launch; with no converged ray
  * (stats[1] == 0) record keeps its bits.  loss, stats: vsrd_frame_photometric's outputs; record [5]: the epilogue's. */
 int32_t vsrd_frame_photometric_finish(const float* loss, const float* stats, float weight, float* record, void* stream);
+
+/* The photometric term over a batch of frames (added within ABI 12; probe for the symbols): vsrd_frame_photometric for every frame of a
+ * batch in the SAME number of launches -- every launch of the call is B copies of its one-frame grid stacked along blockIdx.y ("frame
+ * batches" above), so the frames' traces run side by side instead of one after the other.  The arguments are vsrd_frame_photometric's, and
+ * config->num_frames / frame_stride are honoured: every device pointer -- the arguments, the members of `field`, the workspace and the three
+ * optional outputs -- addresses frame 0's buffer, frame f's lies f * frame_stride bytes behind it (a positive multiple of 256), by-value
+ * arguments are shared; workspace_bytes is the size of ONE frame's workspace (vsrd_frame_photometric_workspace_bytes stays per frame).
+ * frame_header (device memory, frame_stride apart like every buffer; may be NULL: every frame has field->num_instances instances and
+ * patch->num_views views) makes field->num_instances the capacity and the stride of every instance axis and patch->num_views the capacity
+ * of every view axis; the frame's own n_f and v_f come from its header (n_f clamped to [1, N]; v_f read when num_instances carries
+ * VSRD_FRAME_HEADER_HAS_VIEWS, 0 = V, clamped to [1, V]).  Instances n_f .. N-1 and views v_f .. V-1 of every input and output are neither
+ * read nor written; the patch correlation is the one over the frame's own v_f views.
+ * Frame f's loss, stats, own gradients, accumulated totals, positions, normals and converged flags carry the bits of a one-frame call on
+ * frame f laid out for its own n_f and v_f; a call with one frame and a NULL header issues the launches of vsrd_frame_photometric.
+ * Refused before any launch: everything vsrd_frame_photometric refuses (VSRD_E_UNSUPPORTED for a batch excepted), and a malformed batch
+ * (num_frames > 1024, a frame_stride that is not a positive multiple of 256): VSRD_E_INVALID_ARGUMENT.  top_k > v_f cannot be seen from
+ * the host side of the call (the header is device memory): such a frame gets loss 0, stats (0, 0), zero own gradients and untouched
+ * totals, exactly as a frame without a converged ray. */
+int32_t vsrd_frame_photometric_with_header(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
+                                           const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
+                                           const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
+                                           float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
+                                           float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged,
+                                           const vsrd_frame_header* frame_header, void* stream);
+
+/* vsrd_frame_photometric_finish for every frame of a batch in one launch (grid y is the frame): loss, stats and record address frame 0's,
+ * frame f's lie f * frame_stride bytes behind; the weight is shared.  A malformed batch: VSRD_E_INVALID_ARGUMENT. */
+int32_t vsrd_frame_photometric_finish_with_header(const float* loss, const float* stats, float weight, float* record, int32_t num_frames,
+                                                  int64_t frame_stride, void* stream);
+
+/* vsrd_sample_rays_table for every frame of a batch in one launch (grid y is the frame): frame f draws num_samples indices from ITS table
+ * (built over `count` weights, like every frame's), keyed by (seed, ITS step counter *device_stream_offset), into ITS indices -- the
+ * indices vsrd_sample_rays_table gives it alone.  table, device_stream_offset (required) and indices address frame 0's, frame f's lie
+ * f * frame_stride bytes behind.  No remap.  Refusals as for vsrd_sample_rays_table, and a malformed batch: VSRD_E_INVALID_ARGUMENT. */
+int32_t vsrd_sample_rays_table_frames(void* table, int64_t count, int32_t num_samples, uint64_t seed, const uint64_t* device_stream_offset,
+                                      int64_t* indices, int32_t num_frames, int64_t frame_stride, void* stream);
 
 /* Box decode (added within ABI 12; probe for the symbols -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the forward
  * of the reference's BoxParameters3D (vsrd/models/detectors/box_parameters.py:16-146) for ONE frame and its autograd backward, one launch

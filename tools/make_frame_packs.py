@@ -81,8 +81,8 @@ def even_odd_mask(polygon, height, width):
     return mask
 
 
-def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, vertices=0, label_views=0):
-    """The FramePack of synthetic frame number `frame`."""
+def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, vertices=0, label_views=0, images=False):
+    """The FramePack of synthetic frame number `frame`; `images`: with the views' colour images (synthetic.synthetic_images)."""
     from vsrd_amd import frames, models, synthetic
     K, E, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(int(frame), views, height, width, instances)
     detector = models.BoxParameters3D(1, instances)
@@ -119,10 +119,10 @@ def make_pack(frame, views, height, width, instances, drop=(), shuffle=False, ve
     return frames.FramePack((height, width), K.numpy().astype(np.float32), E.numpy().astype(np.float32), np.asarray(view_offsets, dtype=np.int64),
                             np.asarray(ids, dtype=np.int64), polygon_offsets.astype(np.int64), np.concatenate(polygons).astype(np.int32), np.stack(masks),
                             boxes_3d=corners.numpy().astype(np.float32),      # (the true boxes in the target's instance order: ground truth for --metrics)
-                            **group)
+                            images=synthetic.synthetic_images(frame, views, height, width).numpy() if images else None, **group)
 
 
-def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), drop=(), shuffle=False, vertices=0, label_views=0):
+def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), drop=(), shuffle=False, vertices=0, label_views=0, images=False):
     """Packs frame_000000.npz .. of frames 0..count-1 in `out`; returns their paths.  `views`: one count, or a list cycled over the frames
     like `instances` (frame j gets views[j % len(views)], each list with its own length)."""
     from vsrd_amd import frames
@@ -130,7 +130,7 @@ def write_packs(out, count, views=17, height=376, width=1408, instances=(8,), dr
     paths = []
     views = [int(views)] if isinstance(views, int) else [int(v) for v in views]
     for frame in range(int(count)):
-        pack = make_pack(frame, views[frame % len(views)], height, width, int(instances[frame % len(instances)]), drop, shuffle, vertices, label_views)
+        pack = make_pack(frame, views[frame % len(views)], height, width, int(instances[frame % len(instances)]), drop, shuffle, vertices, label_views, images)
         paths.append(os.path.join(out, f"frame_{frame:06d}.npz"))
         frames.save_pack(paths[-1], pack)
     return paths
@@ -148,9 +148,11 @@ def main(argv=None):
     parser.add_argument("--vertices", type=int, default=0, help="subdivide every polygon to about this many vertices (real contours have hundreds)")
     parser.add_argument("--shuffle", action="store_true", help="source views list their entries in a seeded random order")
     parser.add_argument("--label-views", type=int, default=0, help="give every pack a group of this many label views (default: none)")
+    parser.add_argument("--images", action="store_true",
+                        help="give every pack the views' colour images ([V,3,H,W] uint8: the launcher's --photometric needs them; 27 MB per pack at 17 x 376 x 1408)")
     args = parser.parse_args(argv)
     drop = [tuple(int(x) for x in item.split(":")) for item in args.drop.split(",") if item]
-    paths = write_packs(args.out, args.count, [int(x) for x in args.views.split(",")], args.height, args.width, [int(x) for x in args.instances.split(",")], drop, args.shuffle, args.vertices, args.label_views)
+    paths = write_packs(args.out, args.count, [int(x) for x in args.views.split(",")], args.height, args.width, [int(x) for x in args.instances.split(",")], drop, args.shuffle, args.vertices, args.label_views, args.images)
     print(f"{len(paths)} packs in {args.out}")
     return 0
 

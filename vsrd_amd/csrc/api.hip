@@ -482,7 +482,8 @@ int32_t render_backward_split(const vsrd_field* field, const vsrd_render_config*
 int32_t field_eval_adjoint(const vsrd_field* field, const float* positions, int64_t num_points,
                            const float* grad_distances, const float* grad_labels, const float* grad_gradients, int32_t hard_union,
                            void* workspace, size_t workspace_bytes, float* grad_positions,
-                           float* grad_instances, float* grad_mlp_weights, void* stream) {
+                           float* grad_instances, float* grad_mlp_weights, void* stream, const Frames& frames = {1, 0},
+                           const FrameHeader* header = nullptr) {
     if (!valid_field(field) || !grad_instances || num_points < 0 || (!positions && num_points > 0)) return VSRD_E_INVALID_ARGUMENT;
     if (hard_union && grad_labels) return VSRD_E_INVALID_ARGUMENT;
     const bool residual = field->mlp_weights != nullptr;
@@ -491,7 +492,9 @@ int32_t field_eval_adjoint(const vsrd_field* field, const float* positions, int6
     if (!workspace || workspace_bytes < vsrd_workspace_bytes(N, residual)) return VSRD_E_WORKSPACE;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int row = N * kGradStride, mlp_row = N * kMlpWeights;
+    const bool batched = frames.stride != 0 || header != nullptr;     // the kFrames kernels (aux_kernels.h); the callers hand a batch points
     if (num_points == 0) {
+        if (batched) return VSRD_E_UNSUPPORTED;
         if (residual && hipMemsetAsync(grad_mlp_weights, 0, mlp_row * sizeof(float), s) != hipSuccess) return VSRD_E_LAUNCH;
         return hipMemsetAsync(grad_instances, 0, row * sizeof(float), s) == hipSuccess ? VSRD_OK : VSRD_E_LAUNCH;
     }
@@ -504,20 +507,65 @@ int32_t field_eval_adjoint(const vsrd_field* field, const float* positions, int6
     const FieldArgs f = field_args(field);
     for_bool(residual, [&](auto res) {
         constexpr bool kRes = decltype(res)::value;
-        if (grad_gradients)
-            hipLaunchKernelGGL((field_eval_backward_kernel<kRes, true>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights,
-                               positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union, grad_positions, w.partials, w.mlp_partials,
-                               grad_gradients);
-        else
-            hipLaunchKernelGGL((field_eval_backward_kernel<kRes, false>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances, field->mlp_weights,
-                               positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union, grad_positions, w.partials, w.mlp_partials,
-                               grad_gradients);
+        for_bool(grad_gradients != nullptr, [&](auto gamma) {
+            constexpr bool kGamma = decltype(gamma)::value;
+            if (batched)
+                hipLaunchKernelGGL((field_eval_backward_kernel<kRes, kGamma, true>), dim3(g.blocks, frames.count), dim3(g.threads), g.lds_bytes, s, f,
+                                   field->instances, field->mlp_weights, positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union,
+                                   grad_positions, w.partials, w.mlp_partials, grad_gradients, frames.stride, header);
+            else
+                hipLaunchKernelGGL((field_eval_backward_kernel<kRes, kGamma>), dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, f, field->instances,
+                                   field->mlp_weights, positions, static_cast<long long>(num_points), grad_distances, grad_labels, hard_union, grad_positions,
+                                   w.partials, w.mlp_partials, grad_gradients);
+        });
     });
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
     const int num_waves = g.blocks * (g.threads / kWave);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row), dim3(256), 0, s, w.partials, num_waves, row, grad_instances);
+    // (a batch: the partial rows are the capacity's, rows n_f .. N-1 zeros.  The instance sums stop at the frame's own n_f -- the kernel's
+    //  header rule is the [capacity][kGradStride] layout's; the MLP sums cover the capacity and land in a buffer of that size, of which the
+    //  caller reads the leading n_f blocks)
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(row, frames.count), dim3(256), 0, s, w.partials, num_waves, row, grad_instances, nullptr, nullptr, 0, nullptr,
+                       frames.stride, header);
     if (residual)
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row), dim3(256), 0, s, w.mlp_partials, num_waves, mlp_row, grad_mlp_weights);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(mlp_row, frames.count), dim3(256), 0, s, w.mlp_partials, num_waves, mlp_row, grad_mlp_weights, nullptr,
+                           nullptr, 0, nullptr, frames.stride, nullptr);
+    return launch_status();
+}
+
+// vsrd_field_eval and vsrd_sphere_trace behind their checks, over a batch of frames (aux_kernels.h: the kFrames kernels) or, with one frame
+// and no header, as the launches of before.
+int32_t launch_field_eval(const vsrd_field* field, const float* positions, int64_t num_points, float* distances, float* gradients, float* labels,
+                          int32_t hard_union, const Frames& frames, const FrameHeader* header, hipStream_t s) {
+    const int blocks = static_cast<int>(std::min<int64_t>((num_points + 255) / 256, 8192));
+    const bool batched = frames.stride != 0 || header != nullptr;
+    for_bool(field->mlp_weights != nullptr, [&](auto residual) {
+        constexpr bool kRes = decltype(residual)::value;
+        if (batched)
+            hipLaunchKernelGGL((field_eval_kernel<kRes, true>), dim3(blocks, frames.count), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights,
+                               positions, static_cast<long long>(num_points), distances, gradients, labels, hard_union, frames.stride, header);
+        else
+            hipLaunchKernelGGL(field_eval_kernel<kRes>, dim3(blocks), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights, positions,
+                               static_cast<long long>(num_points), distances, gradients, labels, hard_union);
+    });
+    return launch_status();
+}
+
+int32_t launch_sphere_trace(const vsrd_field* field, const float* origins, int32_t origin_stride, const float* directions, const uint8_t* foreground,
+                            int64_t num_rays, int32_t num_iterations, float convergence_criteria, float bounding_radius, int32_t initialise,
+                            int32_t hard_union, float* positions, uint8_t* converged, const Frames& frames, const FrameHeader* header, hipStream_t s) {
+    const int blocks = static_cast<int>(std::min<int64_t>((num_rays + 255) / 256, 16384));
+    const bool batched = frames.stride != 0 || header != nullptr;
+    for_bool(field->mlp_weights != nullptr, [&](auto residual) {
+        constexpr bool kRes = decltype(residual)::value;
+        if (batched)
+            hipLaunchKernelGGL((sphere_trace_kernel<kRes, true>), dim3(blocks, frames.count), dim3(256), 0, s, field_args(field), field->instances,
+                               field->mlp_weights, origins, origin_stride, directions, foreground, static_cast<long long>(num_rays), num_iterations,
+                               convergence_criteria, bounding_radius, initialise, hard_union, positions, converged, frames.stride, header);
+        else
+            hipLaunchKernelGGL(sphere_trace_kernel<kRes>, dim3(blocks), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights, origins,
+                               origin_stride, directions, foreground, static_cast<long long>(num_rays), num_iterations, convergence_criteria, bounding_radius,
+                               initialise, hard_union, positions, converged);
+    });
     return launch_status();
 }
 
@@ -561,12 +609,7 @@ int32_t vsrd_field_eval(const vsrd_field* field, const float* positions, int64_t
     if (!valid_field(field) || (!positions && num_points > 0) || num_points < 0) return VSRD_E_INVALID_ARGUMENT;
     if (hard_union && labels) return VSRD_E_INVALID_ARGUMENT;
     if (num_points == 0) return VSRD_OK;
-    const int blocks = static_cast<int>(std::min<int64_t>((num_points + 255) / 256, 8192));
-    for_bool(field->mlp_weights != nullptr, [&](auto residual) {
-        hipLaunchKernelGGL(field_eval_kernel<decltype(residual)::value>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), field_args(field),
-                           field->instances, field->mlp_weights, positions, static_cast<long long>(num_points), distances, gradients, labels, hard_union);
-    });
-    return launch_status();
+    return launch_field_eval(field, positions, num_points, distances, gradients, labels, hard_union, {1, 0}, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int32_t vsrd_field_eval_backward(const vsrd_field* field, const float* positions, int64_t num_points,
@@ -593,14 +636,8 @@ int32_t vsrd_sphere_trace(const vsrd_field* field, const float* origins, int32_t
     if (!valid_field(field) || num_rays < 0 || num_iterations < 0 || (origin_stride != 0 && origin_stride != 3)) return VSRD_E_INVALID_ARGUMENT;
     if (num_rays == 0) return VSRD_OK;
     if (!origins || !directions || !positions || !converged) return VSRD_E_INVALID_ARGUMENT;
-    const int blocks = static_cast<int>(std::min<int64_t>((num_rays + 255) / 256, 16384));
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    for_bool(field->mlp_weights != nullptr, [&](auto residual) {
-        hipLaunchKernelGGL(sphere_trace_kernel<decltype(residual)::value>, dim3(blocks), dim3(256), 0, s, field_args(field), field->instances, field->mlp_weights,
-                           origins, origin_stride, directions, foreground, static_cast<long long>(num_rays), num_iterations,
-                           convergence_criteria, bounding_radius, initialise, hard_union, positions, converged);
-    });
-    return launch_status();
+    return launch_sphere_trace(field, origins, origin_stride, directions, foreground, num_rays, num_iterations, convergence_criteria, bounding_radius,
+                               initialise, hard_union, positions, converged, {1, 0}, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int32_t vsrd_polygon_soft_masks(const float* polygons, const int32_t* counts, int32_t num_polygons, int32_t max_vertices,
@@ -1451,7 +1488,36 @@ int32_t patch_args(const vsrd_patch_correlation_config* config, const float* gra
     a->gray = gray; a->intrinsics = intrinsics; a->extrinsics = extrinsics; a->pixels = pixels; a->positions = positions; a->normals = normals;
     a->converged = converged;
     a->constants = w.constants; a->ray_stats = w.ray_stats;
+    a->view_capacity = config->num_views; a->frame_stride = 0; a->header = nullptr;
     return VSRD_OK;
+}
+
+// The launches of the two patch calls behind their checks, over a batch of frames (patch_correlation.h: the kFrames kernels, the frame
+// along blockIdx.y) or, with one frame and no header, as the launches of before.
+int32_t launch_patch_forward(PatchArgs a, float* loss, float* stats, float* patches, float* coefficients, int32_t* selected, const Frames& frames,
+                             const FrameHeader* header, hipStream_t s) {
+    a.frame_stride = frames.stride; a.header = header;
+    for_bool(frames.stride != 0 || header != nullptr, [&](auto batched) {
+        constexpr bool kFrames = decltype(batched)::value;
+        const unsigned count = kFrames ? frames.count : 1;
+        hipLaunchKernelGGL(patch_constants_kernel<kFrames>, dim3(1, count), dim3(kWave), 0, s, a);
+        hipLaunchKernelGGL(patch_correlation_forward_kernel<kFrames>, dim3(a.num_rays, count), dim3(kPatchThreads), 0, s, a, patches, coefficients, selected);
+        hipLaunchKernelGGL(patch_loss_kernel<kFrames>, dim3(1, count), dim3(kWave), 0, s, a, loss, stats);
+    });
+    return launch_status();
+}
+
+int32_t launch_patch_backward(PatchArgs a, const float* stats, const float* grad_loss, float* grad_positions, float* grad_normals, const Frames& frames,
+                              const FrameHeader* header, hipStream_t s) {
+    a.frame_stride = frames.stride; a.header = header;
+    for_bool(frames.stride != 0 || header != nullptr, [&](auto batched) {
+        constexpr bool kFrames = decltype(batched)::value;
+        const unsigned count = kFrames ? frames.count : 1;
+        hipLaunchKernelGGL(patch_constants_kernel<kFrames>, dim3(1, count), dim3(kWave), 0, s, a);
+        hipLaunchKernelGGL(patch_correlation_backward_kernel<kFrames>, dim3(a.num_rays, count), dim3(kPatchThreads), 0, s, a, stats, grad_loss, grad_positions,
+                           grad_normals);
+    });
+    return launch_status();
 }
 }  // namespace
 
@@ -1477,11 +1543,7 @@ int32_t vsrd_patch_correlation_forward(const vsrd_patch_correlation_config* conf
     const int32_t status = patch_args(config, gray, intrinsics, extrinsics, pixels, positions, normals, converged, workspace, workspace_bytes, &a);
     if (status != VSRD_OK) return status;
     if (!loss || !stats) return VSRD_E_INVALID_ARGUMENT;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(patch_constants_kernel, dim3(1), dim3(kWave), 0, s, a);
-    hipLaunchKernelGGL(patch_correlation_forward_kernel, dim3(a.num_rays), dim3(kPatchThreads), 0, s, a, patches, coefficients, selected);
-    hipLaunchKernelGGL(patch_loss_kernel, dim3(1), dim3(kWave), 0, s, a, loss, stats);
-    return launch_status();
+    return launch_patch_forward(a, loss, stats, patches, coefficients, selected, {1, 0}, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* config, const float* gray, const float* intrinsics, const float* extrinsics,
@@ -1492,10 +1554,7 @@ int32_t vsrd_patch_correlation_backward(const vsrd_patch_correlation_config* con
     const int32_t status = patch_args(config, gray, intrinsics, extrinsics, pixels, positions, normals, converged, workspace, workspace_bytes, &a);
     if (status != VSRD_OK) return status;
     if (!stats || !grad_loss || !grad_positions || !grad_normals) return VSRD_E_INVALID_ARGUMENT;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(patch_constants_kernel, dim3(1), dim3(kWave), 0, s, a);
-    hipLaunchKernelGGL(patch_correlation_backward_kernel, dim3(a.num_rays), dim3(kPatchThreads), 0, s, a, stats, grad_loss, grad_positions, grad_normals);
-    return launch_status();
+    return launch_patch_backward(a, stats, grad_loss, grad_positions, grad_normals, {1, 0}, nullptr, static_cast<hipStream_t>(stream));
 }
 
 namespace {
@@ -1541,15 +1600,19 @@ size_t vsrd_frame_photometric_workspace_bytes(int32_t num_instances, int32_t res
     return photometric_workspace(nullptr, num_instances, residual != 0, num_views, num_rays).total_bytes;
 }
 
-int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
-                               const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
-                               const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
-                               float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
-                               float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged, void* stream) {
+namespace {
+// vsrd_frame_photometric and its _with_header twin: one set of refusals, one sequence of launches.  `batches` false (the first symbol):
+// num_frames >= 2 is VSRD_E_UNSUPPORTED.  With one frame and no header every launch is the one-frame launch of before.
+int32_t frame_photometric(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
+                          const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
+                          const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
+                          float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
+                          float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged,
+                          const FrameHeader* header, bool batches, void* stream) {
     static_assert(kPhotometricMaxRays == VSRD_PHOTOMETRIC_MAX_RAYS, "frame_photometric.h and the ABI agree on the limit");
     Frames frames;
     if (!config || !frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
-    if (frames.count > 1) return VSRD_E_UNSUPPORTED;
+    if (frames.count > 1 && !batches) return VSRD_E_UNSUPPORTED;
     if (!patch || !valid_field(field) || config->num_iterations < 0) return VSRD_E_INVALID_ARGUMENT;
     const int N = field->num_instances, V = patch->num_views, R = patch->num_rays;
     const bool residual = field->mlp_weights != nullptr;
@@ -1564,48 +1627,81 @@ int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, cons
     if (normals) w.normals = normals;
     if (converged) w.converged = converged;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((R + kPhotometricThreads - 1) / kPhotometricThreads), block(kPhotometricThreads);
-    int32_t status;
+    const dim3 grid((R + kPhotometricThreads - 1) / kPhotometricThreads, frames.count), block(kPhotometricThreads);
+    PatchArgs a;
+    int32_t status = patch_args(patch, gray, intrinsics, extrinsics, w.pixels, w.p1, w.normals, w.converged, w.patch, w.patch_bytes, &a);
+    if (status != VSRD_OK) return status;
     hipLaunchKernelGGL(photometric_gather_kernel, grid, block, 0, s, R, patch->width, reinterpret_cast<const long long*>(ray_indices), ray_directions,
-                       w.directions, w.pixels, w.one);
+                       w.directions, w.pixels, w.one, frames.stride);
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    status = vsrd_sphere_trace(field, camera_position, 0, w.directions, nullptr, R, config->num_iterations, config->convergence_criteria,
-                               config->bounding_radius, 0, 1, w.p0, w.converged, stream);
+    status = launch_sphere_trace(field, camera_position, 0, w.directions, nullptr, R, config->num_iterations, config->convergence_criteria,
+                                 config->bounding_radius, 0, 1, w.p0, w.converged, frames, header, s);
     if (status != VSRD_OK) return status;
-    status = vsrd_field_eval(field, w.p0, R, w.d0, w.g0, nullptr, 1, stream);
+    status = launch_field_eval(field, w.p0, R, w.d0, w.g0, nullptr, 1, frames, header, s);
     if (status != VSRD_OK) return status;
-    hipLaunchKernelGGL(photometric_newton_kernel, grid, block, 0, s, R, w.p0, w.converged, w.d0, w.g0, w.directions, w.p1, w.slopes);
+    hipLaunchKernelGGL(photometric_newton_kernel, grid, block, 0, s, R, w.p0, w.converged, w.d0, w.g0, w.directions, w.p1, w.slopes, frames.stride);
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    status = vsrd_field_eval(field, w.p1, R, nullptr, w.g1, nullptr, 1, stream);
+    status = launch_field_eval(field, w.p1, R, nullptr, w.g1, nullptr, 1, frames, header, s);
     if (status != VSRD_OK) return status;
-    hipLaunchKernelGGL(photometric_normalise_kernel, grid, block, 0, s, R, w.g1, w.normals, w.lengths);
+    hipLaunchKernelGGL(photometric_normalise_kernel, grid, block, 0, s, R, w.g1, w.normals, w.lengths, frames.stride);
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    status = vsrd_patch_correlation_forward(patch, gray, intrinsics, extrinsics, w.pixels, w.p1, w.normals, w.converged, w.patch, w.patch_bytes,
-                                            loss, stats, nullptr, nullptr, nullptr, stream);
+    status = launch_patch_forward(a, loss, stats, nullptr, nullptr, nullptr, frames, header, s);
     if (status != VSRD_OK) return status;
-    status = vsrd_patch_correlation_backward(patch, gray, intrinsics, extrinsics, w.pixels, w.p1, w.normals, w.converged, w.patch, w.patch_bytes,
-                                             stats, w.one, w.grad_p1, w.grad_normals, stream);
+    status = launch_patch_backward(a, stats, w.one, w.grad_p1, w.grad_normals, frames, header, s);
     if (status != VSRD_OK) return status;
-    hipLaunchKernelGGL(photometric_normal_adjoint_kernel, grid, block, 0, s, R, w.converged, w.normals, w.lengths, w.grad_normals, w.gamma);
+    hipLaunchKernelGGL(photometric_normal_adjoint_kernel, grid, block, 0, s, R, w.converged, w.normals, w.lengths, w.grad_normals, w.gamma, frames.stride);
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    status = vsrd_field_eval_adjoint(field, w.p1, R, nullptr, nullptr, w.gamma, 1, w.field, w.field_bytes, w.grad_x, w.first_instances,
-                                     residual ? w.first_mlp : nullptr, stream);
+    status = field_eval_adjoint(field, w.p1, R, nullptr, nullptr, w.gamma, 1, w.field, w.field_bytes, w.grad_x, w.first_instances,
+                                residual ? w.first_mlp : nullptr, stream, frames, header);
     if (status != VSRD_OK) return status;
-    hipLaunchKernelGGL(photometric_newton_adjoint_kernel, grid, block, 0, s, R, w.converged, w.grad_p1, w.grad_x, w.directions, w.slopes, w.grad_d0);
+    hipLaunchKernelGGL(photometric_newton_adjoint_kernel, grid, block, 0, s, R, w.converged, w.grad_p1, w.grad_x, w.directions, w.slopes, w.grad_d0,
+                       frames.stride);
     if (launch_status() != VSRD_OK) return VSRD_E_LAUNCH;
-    status = vsrd_field_eval_backward(field, w.p0, R, w.grad_d0, nullptr, 1, w.field, w.field_bytes, nullptr, w.second_instances,
-                                      residual ? w.second_mlp : nullptr, stream);
+    status = field_eval_adjoint(field, w.p0, R, w.grad_d0, nullptr, nullptr, 1, w.field, w.field_bytes, nullptr, w.second_instances,
+                                residual ? w.second_mlp : nullptr, stream, frames, header);
     if (status != VSRD_OK) return status;
     const int count_instances = N * kGradStride, count_mlp = residual ? N * kMlpWeights : 0;
     const int blocks = std::min((count_instances + count_mlp + kPhotometricThreads - 1) / kPhotometricThreads, 1024);
-    hipLaunchKernelGGL(photometric_accumulate_kernel, dim3(blocks), block, 0, s, stats, config->scale, count_instances, count_mlp, w.first_instances,
-                       w.second_instances, w.first_mlp, w.second_mlp, photometric_grad_instances, photometric_grad_mlp, grad_instances, grad_mlp);
+    hipLaunchKernelGGL(photometric_accumulate_kernel, dim3(blocks, frames.count), block, 0, s, stats, config->scale, count_instances, count_mlp, w.first_instances,
+                       w.second_instances, w.first_mlp, w.second_mlp, photometric_grad_instances, photometric_grad_mlp, grad_instances, grad_mlp, N,
+                       frames.stride, header);
     return launch_status();
+}
+}  // namespace
+
+int32_t vsrd_frame_photometric(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
+                               const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
+                               const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
+                               float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
+                               float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged, void* stream) {
+    return frame_photometric(config, patch, field, camera_position, ray_directions, gray, intrinsics, extrinsics, ray_indices, workspace, workspace_bytes,
+                             loss, stats, photometric_grad_instances, photometric_grad_mlp, grad_instances, grad_mlp, positions, normals, converged,
+                             nullptr, false, stream);
+}
+
+int32_t vsrd_frame_photometric_with_header(const vsrd_frame_photometric_config* config, const vsrd_patch_correlation_config* patch, const vsrd_field* field,
+                                           const float* camera_position, const float* ray_directions, const float* gray, const float* intrinsics,
+                                           const float* extrinsics, const int64_t* ray_indices, void* workspace, size_t workspace_bytes,
+                                           float* loss, float* stats, float* photometric_grad_instances, float* photometric_grad_mlp,
+                                           float* grad_instances, float* grad_mlp, float* positions, float* normals, uint8_t* converged,
+                                           const vsrd_frame_header* frame_header, void* stream) {
+    return frame_photometric(config, patch, field, camera_position, ray_directions, gray, intrinsics, extrinsics, ray_indices, workspace, workspace_bytes,
+                             loss, stats, photometric_grad_instances, photometric_grad_mlp, grad_instances, grad_mlp, positions, normals, converged,
+                             reinterpret_cast<const FrameHeader*>(frame_header), true, stream);
 }
 
 int32_t vsrd_frame_photometric_finish(const float* loss, const float* stats, float weight, float* record, void* stream) {
     if (!loss || !stats || !record) return VSRD_E_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(photometric_finish_kernel, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), loss, stats, weight, record);
+    hipLaunchKernelGGL(photometric_finish_kernel, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), loss, stats, weight, record, 0ll);
+    return launch_status();
+}
+
+int32_t vsrd_frame_photometric_finish_with_header(const float* loss, const float* stats, float weight, float* record, int32_t num_frames,
+                                                  int64_t frame_stride, void* stream) {
+    Frames frames;
+    if (!loss || !stats || !record || !frames_of(num_frames, frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(photometric_finish_kernel, dim3(1, frames.count), dim3(kWave), 0, static_cast<hipStream_t>(stream), loss, stats, weight, record,
+                       frames.stride);
     return launch_status();
 }
 
@@ -1800,6 +1896,19 @@ int32_t vsrd_sample_rays_table(void* table, int64_t count, int32_t num_samples, 
     hipLaunchKernelGGL(sample_table_kernel, dim3(1), dim3(kTableThreads), kTableLdsBytes, static_cast<hipStream_t>(stream), static_cast<RayTableHeader*>(table),
                        static_cast<long long>(count), num_samples, seed, stream_offset, reinterpret_cast<const unsigned long long*>(device_stream_offset),
                        reinterpret_cast<const long long*>(remap), reinterpret_cast<long long*>(indices));
+    return launch_status();
+}
+
+int32_t vsrd_sample_rays_table_frames(void* table, int64_t count, int32_t num_samples, uint64_t seed, const uint64_t* device_stream_offset,
+                                      int64_t* indices, int32_t num_frames, int64_t frame_stride, void* stream) {
+    Frames frames;
+    if (!table || !indices || !device_stream_offset || count < 1 || count >= 0xffffffffll || num_samples < 1 || num_samples > kSampleMax ||
+        !frames_of(num_frames, frame_stride, &frames))
+        return VSRD_E_INVALID_ARGUMENT;
+    if (opt_in_lds(sample_table_frames_kernel, kTableLdsBytes) != VSRD_OK) return VSRD_E_LAUNCH;
+    hipLaunchKernelGGL(sample_table_frames_kernel, dim3(1, frames.count), dim3(kTableThreads), kTableLdsBytes, static_cast<hipStream_t>(stream),
+                       static_cast<RayTableHeader*>(table), static_cast<long long>(count), num_samples, seed,
+                       reinterpret_cast<const unsigned long long*>(device_stream_offset), reinterpret_cast<long long*>(indices), frames.stride);
     return launch_status();
 }
 

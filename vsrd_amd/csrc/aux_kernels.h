@@ -30,11 +30,23 @@ __global__ __launch_bounds__(256) void ray_directions_kernel(const float* __rest
 
 // The distance_field closure evaluated at arbitrary points (main.py:477-509) plus its analytic normal.
 // One thread per point; the instance loop is still wave-uniform (scalar parameter loads).
-template <bool kResidual>
+// kFrames: a batch of frames (wave.h) -- frame blockIdx.y, every pointer moved by its frame's shift, the instance loops over the frame's own
+// count n_f (frame_header; null: the capacity f.num_instances, which stays the stride of `labels`).  Everything it adds is behind
+// `if (kFrames)` and its two arguments are the last: the kFrames = false instantiations are the kernels of before.  The same holds for
+// field_eval_backward_kernel and sphere_trace_kernel below.
+template <bool kResidual, bool kFrames = false>
 __global__ __launch_bounds__(256) void field_eval_kernel(FieldArgs f, const float* __restrict__ instances, const float* __restrict__ mlp,
                                                          const float* __restrict__ positions, long long num_points,
                                                          float* __restrict__ distances, float* __restrict__ gradients,
-                                                         float* __restrict__ labels, int hard_union) {
+                                                         float* __restrict__ labels, int hard_union,
+                                                         long long frame_stride = 0, const FrameHeader* __restrict__ frame_header = nullptr) {
+    const int capacity = f.num_instances;
+    if (kFrames) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(instances, shift); VSRD_OF_FRAME(mlp, shift); VSRD_OF_FRAME_NONNULL(positions, shift);
+        VSRD_OF_FRAME(distances, shift); VSRD_OF_FRAME(gradients, shift); VSRD_OF_FRAME(labels, shift);
+        f.num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, capacity);
+    }
     // residual fields: this wave's staging area for residual_forward's weight operands (static LDS: 4 waves x 6.5 KB)
     __shared__ float forward_weights_all[kResidual ? (256 / kWave) * kMlpWbarFloats : 1];
     float* forward_weights = forward_weights_all + (kResidual ? wave_in_block() * kMlpWbarFloats : 0);
@@ -65,7 +77,7 @@ __global__ __launch_bounds__(256) void field_eval_kernel(FieldArgs f, const floa
         if (labels) {
             for (int i = 0; i < f.num_instances; ++i) {
                 const BoxEval e = eval_instance<kResidual>(load_instance(instances, i), kResidual ? mlp + i * kMlpWeights : nullptr, x, y, z, forward_weights);
-                if (valid) labels[idx * f.num_instances + i] = fast_exp(-(e.d - v.m) * f.inv_t) * v.inv_z;
+                if (valid) labels[idx * capacity + i] = fast_exp(-(e.d - v.m) * f.inv_t) * v.inv_z;
             }
         }
     }
@@ -88,11 +100,22 @@ __global__ __launch_bounds__(256) void field_eval_kernel(FieldArgs f, const floa
 //          fields sum_i R_i p_bar_i (residual_backward returns both orders of its position adjoint in one).
 // Everything kGamma adds is behind `if (kGamma)`, and grad_gradients is the last argument: the kGamma = false instantiations are the kernels
 // of before (vsrd_field_eval_backward, and vsrd_field_eval_adjoint without a normal cotangent).
-template <bool kResidual, bool kGamma = false>
+// kFrames (field_eval_kernel above): N stays the capacity -- the stride of grad_labels and of the partial rows, whose rows n_f .. N-1 are
+// written as zeros -- and the instance loops run over the frame's own n_f.
+template <bool kResidual, bool kGamma = false, bool kFrames = false>
 __global__ __launch_bounds__(kBlockThreads) void field_eval_backward_kernel(
     FieldArgs f, const float* __restrict__ instances, const float* __restrict__ mlp, const float* __restrict__ positions, long long num_points,
     const float* __restrict__ grad_distances, const float* __restrict__ grad_labels, int hard_union,
-    float* __restrict__ grad_positions, float* __restrict__ partials, float* __restrict__ mlp_partials, const float* __restrict__ grad_gradients) {
+    float* __restrict__ grad_positions, float* __restrict__ partials, float* __restrict__ mlp_partials, const float* __restrict__ grad_gradients,
+    long long frame_stride = 0, const FrameHeader* __restrict__ frame_header = nullptr) {
+    int own_instances = f.num_instances;
+    if (kFrames) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(instances, shift); VSRD_OF_FRAME(mlp, shift); VSRD_OF_FRAME_NONNULL(positions, shift);
+        VSRD_OF_FRAME(grad_distances, shift); VSRD_OF_FRAME(grad_labels, shift); VSRD_OF_FRAME(grad_positions, shift);
+        VSRD_OF_FRAME_NONNULL(partials, shift); VSRD_OF_FRAME(mlp_partials, shift); VSRD_OF_FRAME(grad_gradients, shift);
+        own_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, f.num_instances);
+    }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float forward_weights_all[kResidual ? kMaxWavesPerBlock * kMlpWbarFloats : 1];      // residual_forward's staged weights
     float* forward_weights = forward_weights_all + (kResidual ? wave_in_block() * kMlpWbarFloats : 0);
@@ -121,7 +144,7 @@ __global__ __launch_bounds__(kBlockThreads) void field_eval_backward_kernel(
         UnionSums gsums = union_init();                                       // kGamma: the sums the union's gradient needs (below)
         float best = 3.0e38f;
         int best_index = 0;
-        for (int i = 0; i < N; ++i) {
+        for (int i = 0; i < own_instances; ++i) {
             const BoxEval e = eval_instance<kResidual>(load_instance(instances, i), kResidual ? mlp + i * kMlpWeights : nullptr, x, y, z, forward_weights);
             const float lambda = (valid && grad_labels && !hard_union) ? grad_labels[idx * N + i] : 0.0f;
             union_accumulate(sums, e.d, e.gwx, e.gwy, e.gwz, lambda, f.inv_t);
@@ -147,7 +170,7 @@ __global__ __launch_bounds__(kBlockThreads) void field_eval_backward_kernel(
         }
         // ---- per instance ------------------------------------------------------------------------------------------------------
         float xb = 0.0f, yb = 0.0f, zb = 0.0f;
-        for (int i = 0; i < N; ++i) {
+        for (int i = 0; i < own_instances; ++i) {
             const Instance in = load_instance(instances, i);
             const BoxEval e = eval_instance<kResidual>(in, kResidual ? mlp + i * kMlpWeights : nullptr, x, y, z, forward_weights);
             float d_bar;
@@ -265,13 +288,22 @@ __device__ __forceinline__ float union_distance(const FieldArgs& f, const float*
 // one confirming evaluation.  A position that is not finite (a NaN or inf origin) is never converged: the reference's distance is NaN there.
 //   origins: origin_stride 3 (per ray) or 0 (shared); foreground [R] (uint8, in/out semantics of `foreground_masks`)
 //   bounding_radius <= 0: no bounding sphere.  initialise != 0: start at the sphere entry point (renderers.py:36-43).
-template <bool kResidual>
+//   kFrames: a batch of frames, as in field_eval_kernel above (frame blockIdx.y, the union over the frame's own n_f instances).
+template <bool kResidual, bool kFrames = false>
 __global__ __launch_bounds__(256) void sphere_trace_kernel(FieldArgs f, const float* __restrict__ instances, const float* __restrict__ mlp,
                                                            const float* __restrict__ origins, int origin_stride,
                                                            const float* __restrict__ directions, const unsigned char* __restrict__ foreground,
                                                            long long num_rays, int num_iterations, float criteria, float bounding_radius,
                                                            int initialise, int hard_union,
-                                                           float* __restrict__ positions, unsigned char* __restrict__ converged) {
+                                                           float* __restrict__ positions, unsigned char* __restrict__ converged,
+                                                           long long frame_stride = 0, const FrameHeader* __restrict__ frame_header = nullptr) {
+    if (kFrames) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(instances, shift); VSRD_OF_FRAME(mlp, shift); VSRD_OF_FRAME_NONNULL(origins, shift);
+        VSRD_OF_FRAME_NONNULL(directions, shift); VSRD_OF_FRAME(foreground, shift); VSRD_OF_FRAME_NONNULL(positions, shift);
+        VSRD_OF_FRAME_NONNULL(converged, shift);
+        f.num_instances = frame_count_of(frame_header, frame_stride, blockIdx.y, f.num_instances);
+    }
     // residual fields: this wave's staging area for residual_forward's weight operands (static LDS: 4 waves x 6.5 KB)
     __shared__ float forward_weights_all[kResidual ? (256 / kWave) * kMlpWbarFloats : 1];
     float* forward_weights = forward_weights_all + (kResidual ? wave_in_block() * kMlpWbarFloats : 0);

@@ -11,6 +11,9 @@
 // components is taken as ATen's reduction takes it for an inner dimension of 3 -- two lanes per output, lane 0 (x0 + x2), lane 1 x1, then
 // the two partial sums: (x0 + x2) + x1.  Division and square root are the correctly rounded ones on both sides.
 // The adjoint glue follows autograd's formulas; its roundings are free (its results are held to float64 bounds, not to bits).
+//
+// A batch of frames (vsrd_frame_photometric_with_header; wave.h): B copies of the one-frame grid along blockIdx.y, every pointer moved by
+// frame_stride bytes per frame when frame_stride != 0, as in the step kernels.  Nothing else differs between the copies.
 #pragma once
 #include "frame_metrics.h"
 
@@ -28,7 +31,12 @@ __device__ __forceinline__ float dot3_as_aten(const float* a, const float* b) {
 // directions[r] = ray_directions[idx], pixels[r] = (idx % W, idx / W); lane 0 of the launch writes the backward's grad_loss = 1.
 __global__ __launch_bounds__(kPhotometricThreads) void photometric_gather_kernel(int num_rays, int width, const long long* __restrict__ ray_indices,
                                                                                  const float* __restrict__ ray_directions, float* __restrict__ directions,
-                                                                                 int* __restrict__ pixels, float* __restrict__ one) {
+                                                                                 int* __restrict__ pixels, float* __restrict__ one, long long frame_stride) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(ray_indices, shift); VSRD_OF_FRAME_NONNULL(ray_directions, shift); VSRD_OF_FRAME_NONNULL(directions, shift);
+        VSRD_OF_FRAME_NONNULL(pixels, shift); VSRD_OF_FRAME_NONNULL(one, shift);
+    }
     const int r = static_cast<int>(blockIdx.x * kPhotometricThreads + threadIdx.x);
     if (r == 0) one[0] = 1.0f;
     if (r >= num_rays) return;
@@ -42,7 +50,13 @@ __global__ __launch_bounds__(kPhotometricThreads) void photometric_gather_kernel
 // g0 . r for the adjoint.
 __global__ __launch_bounds__(kPhotometricThreads) void photometric_newton_kernel(int num_rays, const float* __restrict__ p0, const unsigned char* __restrict__ converged,
                                                                                  const float* __restrict__ d0, const float* __restrict__ g0,
-                                                                                 const float* __restrict__ directions, float* __restrict__ p1, float* __restrict__ slopes) {
+                                                                                 const float* __restrict__ directions, float* __restrict__ p1, float* __restrict__ slopes,
+                                                                                 long long frame_stride) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(p0, shift); VSRD_OF_FRAME_NONNULL(converged, shift); VSRD_OF_FRAME_NONNULL(d0, shift); VSRD_OF_FRAME_NONNULL(g0, shift);
+        VSRD_OF_FRAME_NONNULL(directions, shift); VSRD_OF_FRAME_NONNULL(p1, shift); VSRD_OF_FRAME_NONNULL(slopes, shift);
+    }
     const int r = static_cast<int>(blockIdx.x * kPhotometricThreads + threadIdx.x);
     if (r >= num_rays) return;
     const float slope = dot3_as_aten(g0 + 3 * r, directions + 3 * r);
@@ -57,7 +71,11 @@ __global__ __launch_bounds__(kPhotometricThreads) void photometric_newton_kernel
 
 // F.normalize: n = g1 / clamp_min(sqrt(sum(g1 * g1)), 1e-12) (a NaN norm stays NaN, as clamp_min leaves it).  `lengths` keeps the clamped norm.
 __global__ __launch_bounds__(kPhotometricThreads) void photometric_normalise_kernel(int num_rays, const float* __restrict__ g1, float* __restrict__ normals,
-                                                                                    float* __restrict__ lengths) {
+                                                                                    float* __restrict__ lengths, long long frame_stride) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(g1, shift); VSRD_OF_FRAME_NONNULL(normals, shift); VSRD_OF_FRAME_NONNULL(lengths, shift);
+    }
     const int r = static_cast<int>(blockIdx.x * kPhotometricThreads + threadIdx.x);
     if (r >= num_rays) return;
     const float norm = sqrtf(dot3_as_aten(g1 + 3 * r, g1 + 3 * r));
@@ -69,7 +87,13 @@ __global__ __launch_bounds__(kPhotometricThreads) void photometric_normalise_ker
 // The adjoint of F.normalize: gamma = (n_bar - n (n . n_bar)) / max(|g1|, 1e-12); zero for a ray that did not converge (its n_bar is zero).
 __global__ __launch_bounds__(kPhotometricThreads) void photometric_normal_adjoint_kernel(int num_rays, const unsigned char* __restrict__ converged,
                                                                                          const float* __restrict__ normals, const float* __restrict__ lengths,
-                                                                                         const float* __restrict__ grad_normals, float* __restrict__ gamma) {
+                                                                                         const float* __restrict__ grad_normals, float* __restrict__ gamma,
+                                                                                         long long frame_stride) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(converged, shift); VSRD_OF_FRAME_NONNULL(normals, shift); VSRD_OF_FRAME_NONNULL(lengths, shift);
+        VSRD_OF_FRAME_NONNULL(grad_normals, shift); VSRD_OF_FRAME_NONNULL(gamma, shift);
+    }
     const int r = static_cast<int>(blockIdx.x * kPhotometricThreads + threadIdx.x);
     if (r >= num_rays) return;
     const float* n = normals + 3 * r;
@@ -84,7 +108,12 @@ __global__ __launch_bounds__(kPhotometricThreads) void photometric_normal_adjoin
 __global__ __launch_bounds__(kPhotometricThreads) void photometric_newton_adjoint_kernel(int num_rays, const unsigned char* __restrict__ converged,
                                                                                          const float* __restrict__ grad_p1, const float* __restrict__ grad_x,
                                                                                          const float* __restrict__ directions, const float* __restrict__ slopes,
-                                                                                         float* __restrict__ grad_d0) {
+                                                                                         float* __restrict__ grad_d0, long long frame_stride) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(converged, shift); VSRD_OF_FRAME_NONNULL(grad_p1, shift); VSRD_OF_FRAME_NONNULL(grad_x, shift);
+        VSRD_OF_FRAME_NONNULL(directions, shift); VSRD_OF_FRAME_NONNULL(slopes, shift); VSRD_OF_FRAME_NONNULL(grad_d0, shift);
+    }
     const int r = static_cast<int>(blockIdx.x * kPhotometricThreads + threadIdx.x);
     if (r >= num_rays) return;
     float along = 0.0f;
@@ -94,12 +123,26 @@ __global__ __launch_bounds__(kPhotometricThreads) void photometric_newton_adjoin
 
 // own[i] = first[i] + second[i] (the two field adjoints' parameter gradients), then total[i] = fma(scale, own[i], total[i]); with no converged
 // ray (stats[1] == 0) own is zero and total keeps its bits.  One launch covers the instance block [count_instances] and, for residual
-// fields, the MLP block [count_mlp].
+// fields, the MLP block [count_mlp].  In a batch with headers the counts are those of the capacity `num_instances`, and a frame covers the
+// leading blocks of its own n_f instances: the rows n_f .. capacity - 1 of own and total are not touched.
 __global__ __launch_bounds__(kPhotometricThreads) void photometric_accumulate_kernel(const float* __restrict__ stats, float scale, int count_instances, int count_mlp,
                                                                                      const float* __restrict__ first_instances, const float* __restrict__ second_instances,
                                                                                      const float* __restrict__ first_mlp, const float* __restrict__ second_mlp,
                                                                                      float* __restrict__ own_instances, float* __restrict__ own_mlp,
-                                                                                     float* __restrict__ total_instances, float* __restrict__ total_mlp) {
+                                                                                     float* __restrict__ total_instances, float* __restrict__ total_mlp,
+                                                                                     int num_instances, long long frame_stride,
+                                                                                     const FrameHeader* __restrict__ frame_header) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(stats, shift); VSRD_OF_FRAME_NONNULL(first_instances, shift); VSRD_OF_FRAME_NONNULL(second_instances, shift);
+        VSRD_OF_FRAME(first_mlp, shift); VSRD_OF_FRAME(second_mlp, shift); VSRD_OF_FRAME_NONNULL(own_instances, shift); VSRD_OF_FRAME(own_mlp, shift);
+        VSRD_OF_FRAME_NONNULL(total_instances, shift); VSRD_OF_FRAME(total_mlp, shift);
+    }
+    if (frame_header != nullptr) {
+        const int own = frame_count_of(frame_header, frame_stride, blockIdx.y, num_instances);
+        count_instances = count_instances / num_instances * own;
+        count_mlp = count_mlp / num_instances * own;
+    }
     const bool any = stats[1] != 0.0f;
     const int stride = static_cast<int>(gridDim.x) * kPhotometricThreads;
     for (int i = static_cast<int>(blockIdx.x * kPhotometricThreads + threadIdx.x); i < count_instances + count_mlp; i += stride) {
@@ -117,7 +160,13 @@ __global__ __launch_bounds__(kPhotometricThreads) void photometric_accumulate_ke
 }
 
 // record[4] += weight * loss (the product rounded, then the sum: the eager loop's total + weight * loss); untouched when no ray converged.
-__global__ void photometric_finish_kernel(const float* __restrict__ loss, const float* __restrict__ stats, float weight, float* __restrict__ record) {
+// A batch: frame blockIdx.y.
+__global__ void photometric_finish_kernel(const float* __restrict__ loss, const float* __restrict__ stats, float weight, float* __restrict__ record,
+                                          long long frame_stride) {
+    if (frame_stride != 0) {
+        const long long shift = frame_shift(frame_stride, blockIdx.y);
+        VSRD_OF_FRAME_NONNULL(loss, shift); VSRD_OF_FRAME_NONNULL(stats, shift); VSRD_OF_FRAME_NONNULL(record, shift);
+    }
     if (threadIdx.x != 0 || blockIdx.x != 0 || stats[1] == 0.0f) return;
     record[4] = rounded(record[4] + rounded(weight * loss[0]));
 }

@@ -56,7 +56,25 @@ struct PatchArgs {
     const unsigned char* converged;          // [R]
     float* constants;                        // workspace: [V,12] + K_t^-1 [9] (padded to 12)
     float* ray_stats;                        // workspace: [R,2] = (sum, count) of the ray's selected non-NaN coefficients
+    int view_capacity;                       // the extent of every per-view array: num_views, and in a batch with headers the by-value V
+    long long frame_stride;                  // a batch of frames (wave.h; the kFrames kernels): bytes between the frames' buffers
+    const FrameHeader* header;               // ... and the frames' own view counts, or null: every frame has view_capacity views
 };
+
+// The kFrames kernels (a batch of frames, wave.h): the frame is blockIdx.y (the one-frame grids are 1-D), every pointer of `a` moves by its
+// frame's shift and num_views becomes the frame's own v_f; view_capacity stays the by-value V, behind whose constants K_t^-1 lies.
+// Returns the shift, for the kernel's other pointers.  A frame with fewer views than top_k is not served: the host cannot see v_f, so such
+// a frame is treated as a frame without a converged ray (loss 0, stats (0, 0), zero gradients).
+__device__ __forceinline__ long long patch_of_frame(PatchArgs& a) {
+    const long long shift = frame_shift(a.frame_stride, blockIdx.y);
+    a.gray = of_frame_nonnull(a.gray, shift); a.intrinsics = of_frame_nonnull(a.intrinsics, shift); a.extrinsics = of_frame_nonnull(a.extrinsics, shift);
+    a.pixels = of_frame_nonnull(a.pixels, shift); a.positions = of_frame_nonnull(a.positions, shift); a.normals = of_frame_nonnull(a.normals, shift);
+    a.converged = of_frame_nonnull(a.converged, shift); a.constants = of_frame_nonnull(a.constants, shift); a.ray_stats = of_frame_nonnull(a.ray_stats, shift);
+    a.num_views = frame_views(a.header ? of_frame_nonnull(a.header, shift) : nullptr, a.view_capacity);
+    return shift;
+}
+template <bool kFrames>
+__device__ __forceinline__ bool patch_served(const PatchArgs& a) { return !kFrames || a.top_k <= a.num_views; }
 
 // ---- grayscale ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float patch_gray(float r, float g, float b) {
@@ -89,8 +107,10 @@ __global__ __launch_bounds__(256) void patch_gray_kernel(const float* __restrict
 __device__ __forceinline__ double patch_k(const PatchArgs& a, int v, int i, int j) { return a.intrinsics[9 * v + 3 * i + j]; }
 __device__ __forceinline__ double patch_r(const PatchArgs& a, int v, int i, int j) { return a.extrinsics[16 * v + 4 * i + j]; }
 
+template <bool kFrames = false>
 __global__ __launch_bounds__(kWave) void patch_constants_kernel(PatchArgs a) {
     __shared__ double inverse[9];
+    if (kFrames) patch_of_frame(a);
     const int lane = static_cast<int>(threadIdx.x), t = a.target_view;
     if (lane < 9) {                                              // inverse[i][j] = cofactor[j][i] / det: any skew
         const int i = lane / 3, j = lane % 3;
@@ -100,7 +120,7 @@ __global__ __launch_bounds__(kWave) void patch_constants_kernel(PatchArgs a) {
                                    patch_k(a, t, 0, 1) * (patch_k(a, t, 1, 0) * patch_k(a, t, 2, 2) - patch_k(a, t, 1, 2) * patch_k(a, t, 2, 0)) +
                                    patch_k(a, t, 0, 2) * (patch_k(a, t, 1, 0) * patch_k(a, t, 2, 1) - patch_k(a, t, 1, 1) * patch_k(a, t, 2, 0));
         inverse[lane] = cofactor / determinant;
-        a.constants[a.num_views * kPatchViewFloats + lane] = static_cast<float>(inverse[lane]);
+        a.constants[a.view_capacity * kPatchViewFloats + lane] = static_cast<float>(inverse[lane]);
     }
     __syncthreads();
     for (int e = lane; e < a.num_views * kPatchViewFloats; e += kWave) {
@@ -147,7 +167,7 @@ __device__ __forceinline__ PatchRay patch_load_ray(const PatchArgs& a, int ray) 
     r.x = static_cast<float>(a.pixels[2 * ray]); r.y = static_cast<float>(a.pixels[2 * ray + 1]);
     for (int i = 0; i < 3; ++i) { r.n[i] = a.normals[3 * ray + i]; r.p[i] = a.positions[3 * ray + i]; }
     r.plane = __fmaf_rn(r.n[2], r.p[2], __fmaf_rn(r.n[1], r.p[1], __fmul_rn(r.n[0], r.p[0])));
-    const float* const k_inverse = a.constants + a.num_views * kPatchViewFloats;
+    const float* const k_inverse = a.constants + a.view_capacity * kPatchViewFloats;
     for (int i = 0; i < 9; ++i) r.k_inverse[i] = k_inverse[i];
     r.scale_x = static_cast<float>(a.width) / static_cast<float>(a.width - 1);
     r.scale_y = static_cast<float>(a.height) / static_cast<float>(a.height - 1);
@@ -278,11 +298,16 @@ __device__ __forceinline__ void patch_clear_exports(const PatchArgs& a, int ray,
 
 // grid R.  patches [V,R,P], coefficients [R,V,V], selected [R,V]: optional exports.  An unconverged ray writes (0, 0) and zero
 // coefficient / selection rows; its patches are sampled only when they are exported (the reference samples every ray's).
+template <bool kFrames = false>
 __global__ __launch_bounds__(kPatchThreads) void patch_correlation_forward_kernel(PatchArgs a, float* __restrict__ patches, float* __restrict__ coefficients,
                                                                                   int* __restrict__ selected) {
     __shared__ PatchShared sh;
+    if (kFrames) {
+        const long long shift = patch_of_frame(a);
+        VSRD_OF_FRAME(patches, shift); VSRD_OF_FRAME(coefficients, shift); VSRD_OF_FRAME(selected, shift);
+    }
     const int ray = static_cast<int>(blockIdx.x);
-    const bool converged = a.converged[ray] != 0;                // (uniform over the workgroup: everybody leaves or nobody)
+    const bool converged = a.converged[ray] != 0 && patch_served<kFrames>(a);      // (uniform over the workgroup: everybody leaves or nobody)
     if (converged || patches) {
         const PatchRay r = patch_load_ray(a, ray);
         patch_ray_sample(a, r, ray, sh, patches);
@@ -304,7 +329,13 @@ __global__ __launch_bounds__(kPatchThreads) void patch_correlation_forward_kerne
 // One wave: the rays' pairs in ascending blocks of 64 (wave_sum inside a block, double across blocks).  stats = (sum, count);
 // loss = (1 - sum / count) / 2, NaN when rays converged but every selected coefficient is NaN (the reference's nanmean), and 0 when no
 // ray converged (the reference adds no term: the same weighted sum).
+template <bool kFrames = false>
 __global__ __launch_bounds__(kWave) void patch_loss_kernel(PatchArgs a, float* __restrict__ loss, float* __restrict__ stats) {
+    if (kFrames) {
+        const long long shift = patch_of_frame(a);
+        VSRD_OF_FRAME_NONNULL(loss, shift); VSRD_OF_FRAME_NONNULL(stats, shift);
+    }
+    const bool served = patch_served<kFrames>(a);
     const int lane = lane_id();
     double sum = 0.0, count = 0.0, converged = 0.0;
     for (int base = 0; base < a.num_rays; base += kWave) {
@@ -312,7 +343,7 @@ __global__ __launch_bounds__(kWave) void patch_loss_kernel(PatchArgs a, float* _
         const bool inside = ray < a.num_rays;
         sum += static_cast<double>(wave_sum(inside ? a.ray_stats[2 * ray] : 0.0f));
         count += static_cast<double>(wave_sum(inside ? a.ray_stats[2 * ray + 1] : 0.0f));
-        converged += static_cast<double>(wave_sum(inside && a.converged[ray] != 0 ? 1.0f : 0.0f));
+        converged += static_cast<double>(wave_sum(inside && served && a.converged[ray] != 0 ? 1.0f : 0.0f));
     }
     if (lane == 0) {
         stats[0] = static_cast<float>(sum); stats[1] = static_cast<float>(count);
@@ -334,14 +365,20 @@ __global__ __launch_bounds__(kWave) void patch_loss_kernel(PatchArgs a, float* _
 // so the ray needs four sums over its V P samples, T0 = sum dw g (three components) and T1 = sum dw w: lane partial sums, wave_sum, then
 // the waves in ascending order.  grad_n = (T0 - T1 p) / n.p, grad_p = -T1 n / n.p; a plane through the origin (n.p == 0) has no valid
 // sample and gets zeros.
+template <bool kFrames = false>
 __global__ __launch_bounds__(kPatchThreads) void patch_correlation_backward_kernel(PatchArgs a, const float* __restrict__ stats, const float* __restrict__ upstream,
                                                                                    float* __restrict__ grad_positions, float* __restrict__ grad_normals) {
     __shared__ PatchShared sh;
     __shared__ float adjoint[kPatchMaxViews * kPatchMaxViews];   // S
     __shared__ float partial[kPatchWaves][4];
+    if (kFrames) {
+        const long long shift = patch_of_frame(a);
+        VSRD_OF_FRAME_NONNULL(stats, shift); VSRD_OF_FRAME_NONNULL(upstream, shift); VSRD_OF_FRAME_NONNULL(grad_positions, shift);
+        VSRD_OF_FRAME_NONNULL(grad_normals, shift);
+    }
     const int ray = static_cast<int>(blockIdx.x), thread = static_cast<int>(threadIdx.x), lane = lane_id(), wave = wave_in_block();
     const int V = a.num_views, P = a.patch_width * a.patch_height;
-    if (a.converged[ray] == 0) {
+    if (a.converged[ray] == 0 || !patch_served<kFrames>(a)) {
         if (thread < 3) { grad_positions[3 * ray + thread] = 0.0f; grad_normals[3 * ray + thread] = 0.0f; }
         return;
     }

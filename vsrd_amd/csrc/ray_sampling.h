@@ -439,4 +439,13 @@ __global__ __launch_bounds__(kTableThreads) void sample_table_kernel(RayTableHea
     sample_table_body(table, count, k, seed, step, device_step, remap, indices);
 }
 
+// The same draw for a batch of frames (wave.h): frame blockIdx.y draws from its own table, keyed by its own step counter, into its own
+// indices -- the three lie frame_stride bytes apart per frame.
+__global__ __launch_bounds__(kTableThreads) void sample_table_frames_kernel(RayTableHeader* table, long long count, int k, unsigned long long seed,
+                                                                            const unsigned long long* __restrict__ device_step,
+                                                                            long long* __restrict__ indices, long long frame_stride) {
+    const long long shift = frame_shift(frame_stride, blockIdx.y);
+    sample_table_body(of_frame_nonnull(table, shift), count, k, seed, 0ull, of_frame_nonnull(device_step, shift), nullptr, of_frame_nonnull(indices, shift));
+}
+
 }  // namespace vsrd

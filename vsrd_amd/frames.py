@@ -51,6 +51,8 @@ class FramePack:
     label_extrinsic_matrices: Optional[np.ndarray] = None   # [L,4,4] float32, relative to the rectified target like extrinsic_matrices
     label_boxes_2d: Optional[np.ndarray] = None             # [L,N,4] float32 (xmin, ymin, xmax, ymax) in the target's instance order, zeros where invisible
     label_visible: Optional[np.ndarray] = None              # [L,N] uint8
+    # the views' colour images, for the photometric term (optimization.FrameInputs.images); written only when present
+    images: Optional[np.ndarray] = None                     # [V,3,H,W] uint8; on the device float32 x / 255 (pack_images)
 
     @property
     def num_label_views(self):
@@ -82,7 +84,8 @@ def _normalised(pack):
                      np.ascontiguousarray(pack.polygon_offsets, dtype=np.int64), np.ascontiguousarray(pack.polygon_vertices, dtype=np.int32),
                      np.ascontiguousarray(pack.inside, dtype=np.uint8),
                      *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=np.float32) for field in _OPTIONAL],
-                     *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=dtype) for field, dtype in _GROUP])
+                     *[None if getattr(pack, field) is None else np.ascontiguousarray(getattr(pack, field), dtype=dtype) for field, dtype in _GROUP],
+                     images=None if pack.images is None else np.ascontiguousarray(pack.images))
 
 
 def validate(pack, name="frame pack"):
@@ -155,6 +158,11 @@ def validate(pack, name="frame pack"):
         for field, shape in shapes.items():
             if group[field].shape != shape:
                 bad(f"{field} of shape {group[field].shape}, expected {shape}")
+    if pack.images is not None:
+        if not isinstance(pack.images, np.ndarray) or pack.images.dtype != np.uint8:
+            bad(f"images is not a uint8 array (dtype {getattr(pack.images, 'dtype', type(pack.images))})")
+        if pack.images.shape != (views, 3, height, width):
+            bad(f"images of shape {pack.images.shape}, expected {(views, 3, height, width)}")
     return pack
 
 
@@ -164,7 +172,7 @@ def save_pack(path, pack):
     staged = f"{path}.tmp.{os.getpid()}"
     try:
         with open(staged, "wb") as handle:
-            members = _FIELDS + _OPTIONAL + tuple(field for field, _ in _GROUP)
+            members = _FIELDS + _OPTIONAL + tuple(field for field, _ in _GROUP) + ("images",)
             np.savez(handle, **{field: np.asarray(getattr(pack, field)) for field in members if getattr(pack, field) is not None})
         os.replace(staged, path)
     finally:
@@ -192,7 +200,7 @@ def load_pack(path):
     """Read and validate a pack; ValueError naming the file when it is malformed."""
     with _open(path) as data:
         arrays = {field: _member(data, path, field) for field in _FIELDS}
-        arrays.update({field: _member(data, path, field) for field in _OPTIONAL + tuple(f for f, _ in _GROUP) if field in data.files})
+        arrays.update({field: _member(data, path, field) for field in _OPTIONAL + tuple(f for f, _ in _GROUP) + ("images",) if field in data.files})
     if arrays["image_size"].size != 2:
         raise ValueError(f"{path}: malformed frame pack: image_size of shape {arrays['image_size'].shape}")
     for field in arrays:
@@ -220,6 +228,20 @@ def pack_label_views(path):
     if label_ids.ndim != 1:
         raise ValueError(f"{path}: malformed frame pack: label_frame_ids of shape {label_ids.shape}")
     return len(label_ids)
+
+
+def pack_has_images(path):
+    """Whether the pack at `path` carries the views' images, without loading anything."""
+    with _open(path) as data:
+        return "images" in data.files
+
+
+def pack_images(pack, device):
+    """The pack's images on `device` as FrameInputs.images defines them -- [V,3,H,W] float32, x / 255 -- or None for a pack without them.
+    The ONE conversion: frames.ingest and a row's reset(FramePack) both come through here, so the two routes give the same gray planes."""
+    if pack.images is None:
+        return None
+    return torch.from_numpy(pack.images).to(device).to(torch.float32) / 255.0
 
 
 def collate_tables(pack):
@@ -298,4 +320,4 @@ def ingest(pack, device, temperature=TEMPERATURE):
     ingest_into(pack, device, instances, soft_masks=soft, gt_boxes=boxes, visible=visible, temperature=temperature)
     intrinsics, extrinsics = camera_matrices(pack, device)
     return FrameInputs((height, width), intrinsics, extrinsics, soft, boxes.reshape(views, instances, 2, 2), visible.bool(),
-                       *ground_truth_3d(pack, device), **group_tables(pack, device))
+                       *ground_truth_3d(pack, device), **group_tables(pack, device), images=pack_images(pack, device))

@@ -205,11 +205,12 @@ def run_frames(frames, optimise: Callable, checkpoint_path: Callable[[object], s
 #   python -m vsrd_amd.launcher --gpus N --frames K      (or under torchrun; `python bench.py --native --gpus N ...` forwards here)
 # ---------------------------------------------------------------------------------------------------------------------------------
 
-def synthetic_frame_inputs(device, frame, views, instances, height=376, width=1408, label_views=0):
+def synthetic_frame_inputs(device, frame, views, instances, height=376, width=1408, label_views=0, images=False):
     """FrameInputs of synthetic frame number `frame` (synthetic.synthetic_frame(seed = frame): KITTI-360 intrinsics, boxes in the
     reference's ranges): soft masks rendered from the true boxes at the sharp end of the schedule, ground-truth 2-D boxes projected
     from them, every instance visible in every view; the true boxes' corners are the frame's 3-D ground truth (boxes_3d).
-    ``label_views`` L > 0: the frame also carries a group of L label views (synthetic.synthetic_group)."""
+    ``label_views`` L > 0: the frame also carries a group of L label views (synthetic.synthetic_group).  ``images``: it carries the views'
+    colour images (synthetic.synthetic_images, x / 255), which the photometric term needs."""
     from . import fields, models, operations, optimization, rendering, synthetic
     K, E, raw_loc, raw_dim, raw_ori = synthetic.synthetic_frame(int(frame), views, height, width, instances)
     K, E = K.to(device), E.to(device)
@@ -226,7 +227,8 @@ def synthetic_frame_inputs(device, frame, views, instances, height=376, width=14
     group = {key: value.to(device) for key, value in synthetic.synthetic_group(frame, height, width, label_views, out["boxes_3d"][0].cpu()).items()} \
         if label_views else {}
     return optimization.FrameInputs((height, width), K, E, soft, gt_boxes, torch.ones(views, instances, dtype=torch.bool, device=device),
-                                    boxes_3d=out["boxes_3d"][0].contiguous(), **group)
+                                    boxes_3d=out["boxes_3d"][0].contiguous(), **group,
+                                    images=synthetic.synthetic_images(frame, views, height, width).to(device).to(torch.float32) / 255.0 if images else None)
 
 
 def scan_frames_dir(folder, limit=0):
@@ -275,6 +277,19 @@ def scan_label_views(files):
         if counts[-1] > frames.MAX_LABEL_VIEWS:
             raise SystemExit(f"--frames-dir: {path} has {counts[-1]} label views, 1..{frames.MAX_LABEL_VIEWS}")
     return counts
+
+
+def scan_images(files):
+    """--photometric with --frames-dir: every pack must carry the views' images (frames.FramePack.images); the first one without is named."""
+    from . import frames
+    for path in files:
+        try:
+            present = frames.pack_has_images(path)
+        except ValueError as error:
+            raise SystemExit(f"--frames-dir: {error}")
+        if not present:
+            raise SystemExit(f"--photometric: the frame pack {path} carries no images (the optional member `images`, [V,3,H,W] uint8: "
+                             "tools/make_frame_packs.py --images writes it)")
 
 
 def _newest_change(folder):
@@ -377,6 +392,12 @@ class _RenderWork:
         self.logs = self.scalar_interval > 0 or self.ckpt_interval > 0
         if self.logs:
             self.config.update(scalar_interval=self.scalar_interval, checkpoint_interval=self.ckpt_interval)
+        # --photometric W: the photometric term in every loop and every batch row of the job (FrameBatch(..., photometric=True))
+        self.photometric = float(getattr(args, "photometric", 0.0) or 0.0)
+        self.photometric_losses = {}
+        if self.photometric:
+            from . import losses
+            self.config.update(loss_weights={**losses.LOSS_WEIGHTS, "photometric_loss": self.photometric})
 
     def path_of(self, frame):
         return os.path.join(self.manifest["out"], f"frame_{int(frame):06d}", f"step_{self.args.num_steps - 1}.pt")
@@ -397,7 +418,7 @@ class _RenderWork:
             from . import frames
             return frames.load_pack(self.manifest["packs"][int(frame)])
         return synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts), instances_of(frame, args.instance_counts), args.height, args.width,
-                                      args.label_views)
+                                      args.label_views, images=bool(self.photometric))
 
     def materialised(self, inputs):
         """`inputs` as a FrameInputs on the device: what founds a slot or a batch, and what a loop of its own is built on."""
@@ -430,7 +451,8 @@ class _RenderWork:
         # (frame packs are NOT made resident: a directory holds any number of them, 9 MB each at the reference's size.  A pack is read when its
         #  frame is taken -- inside the clock, under phase_seconds["inputs"] -- and dropped once its row is reset)
         self.inputs = {} if args.frames_dir else {frame: synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts),
-                                                                                instances_of(frame, args.instance_counts), args.height, args.width, args.label_views) for frame in mine}
+                                                                                instances_of(frame, args.instance_counts), args.height, args.width, args.label_views,
+                                                                                images=bool(self.photometric)) for frame in mine}
         self.slots, self.batch = queue.Queue(), None
         self.setup_seconds, self.graphs_per_slot, self.unsuitable_founders = 0.0, 0, []
         # the frames a slot or batch may be founded on: this rank's own (static), or the head of the job's queue (dynamic: built here, once)
@@ -446,7 +468,7 @@ class _RenderWork:
                     self.batch = optimization.FrameBatch(founders, self.optimization_config(), self.device,
                                                          max_instances=max(args.instance_counts) if mixed else None,
                                                          max_views=max(args.view_counts) if mixed_views else None,
-                                                         max_label_views=args.label_view_capacity)
+                                                         max_label_views=args.label_view_capacity, photometric=bool(self.photometric))
                     if self.logs:                # (before the captures: the buffers the log reads exist in every row)
                         self.batch.log_outputs(metrics=args.metrics, masks=args.masks)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
@@ -485,6 +507,11 @@ class _RenderWork:
         self._write_outputs(pending)
         return loss, payload
 
+    def _note_photometric(self, frame, record):
+        """--photometric: the frame's final photometric_loss, where its last step had the term (a residual step)."""
+        if self.photometric and "photometric_loss" in record:
+            self.photometric_losses[int(frame)] = float(record["photometric_loss"])
+
     def _finish_alone(self, frame, loop, record, health=None):
         """The end of a frame that ran alone, in a slot or in a loop of its own, `record` its last step's: its loss, the sampler's `health`
         where the caller reads it, its checkpoint payload and its outputs -> (loss, payload, pending file writes)."""
@@ -492,6 +519,7 @@ class _RenderWork:
         with optimization.exclusive_device_access():       # (host synchronisations and copies: refused now and then while another frame's thread captures)
             torch.cuda.current_stream().synchronize()
             loss = float(record["loss"])
+            self._note_photometric(frame, record)
             if health is not None:
                 health(frame, loop)
             payload = formats.checkpoint_payload(loop, step=self.args.num_steps - 1, metrics={}, host=True)
@@ -632,7 +660,8 @@ class _RenderWork:
                     gate_capture_seconds=optimization.exclusive_device_access().capture_seconds - self.captures_before,
                     slot_setup_seconds=self.setup_seconds, graphs_per_slot=self.graphs_per_slot, final_losses={int(f): losses[f] for f in sorted(losses)},
                     frames_outside_slots=sorted(fallbacks), unsuitable_founders=self.unsuitable_founders, frames_with_unhealthy_draws=sorted(unhealthy),
-                    phase_seconds=self.phase_seconds, **({"frame_metrics": self.frame_metrics} if args.metrics else {}))
+                    phase_seconds=self.phase_seconds, final_photometric_losses=dict(sorted(self.photometric_losses.items())),
+                    **({"frame_metrics": self.frame_metrics} if args.metrics else {}))
 
     def _run_batches(self, losses, fallbacks, health):
         """Groups of --frame-batch frames through the FrameBatch: reset row by row, ONE graph replay per (four) step(s) for the whole group,
@@ -664,6 +693,7 @@ class _RenderWork:
                     payloads = []
                     for row, (frame, path) in enumerate(rows):
                         losses[frame] = float(batch.outputs(row)["loss"])
+                        self._note_photometric(frame, batch.outputs(row))
                         health(frame, batch.frames[row])
                         payloads.append(formats.checkpoint_payload(batch.frames[row], step=args.num_steps - 1, metrics={}, host=True))
                     t2 = time.perf_counter()
@@ -822,6 +852,10 @@ def main(argv=None):
                         help="OptimizationConfig.mlp_adjoint_item_slots (vsrd_render_config::adjoint_slots_per_item): 0 = planned (4 for one frame of 1000 rays; "
                              "a batch picks FrameBatch.item_slots).  A frame's trajectory is bit-identical alone and in a batch for equal numbers")
     parser.add_argument("--fp32-mlp", action="store_true", help="the residual MLP's products on the exact-fp32 matrix instruction instead of split bf16")
+    parser.add_argument("--photometric", type=float, default=0.0, metavar="W",
+                        help="loss_weights['photometric_loss'] = W (default 0: the term is off): the multi-view patch-correlation term in every residual "
+                             "step, in frame batches too (optimization.FrameBatch(..., photometric=True)).  Synthetic frames then carry images "
+                             "(synthetic.synthetic_images); --frames-dir packs must carry the member `images` (tools/make_frame_packs.py --images)")
     parser.add_argument("--frames-dir", default="",
                         help="optimise the frame packs of this directory (vsrd_amd/frames.py; tools/make_frame_packs.py writes synthetic ones) instead of "
                              "synthetic frames: frame j is the j-th of its sorted *.npz files, --frames defaults to all of them, views / image size / "
@@ -913,6 +947,10 @@ def main(argv=None):
             raise SystemExit(f"{flag} logs optimised frames; --selftest optimises none: drop one of --selftest, {flag}")
         if value and not args.out:
             raise SystemExit(f"{flag} writes history.json, step_*.pt and model.pt next to every frame's checkpoint: it needs --out")
+    if args.photometric and args.selftest:
+        raise SystemExit("--photometric is a term of optimised frames' loss; --selftest optimises none: drop one of --selftest, --photometric")
+    if not (args.photometric >= 0.0 and args.photometric < float("inf")):
+        raise SystemExit(f"--photometric: a finite weight >= 0 (0: off), got {args.photometric}")
     if args.scalar_interval < 0 or args.ckpt_interval < 0:
         raise SystemExit("--scalar-interval and --ckpt-interval must be at least 0 (0: off)")
     try:
@@ -943,6 +981,8 @@ def main(argv=None):
             files, _ = scan_frames_dir(args.frames_dir, args.frames)
             if args.group_predictions:
                 scan_label_views(files)
+            if args.photometric:
+                scan_images(files)
     args.height, args.width = (default if value is None else value for value, default in ((args.height, 376), (args.width, 1408)))
     args.view_counts = parse_views("17" if args.views is None else args.views)
     args.views = args.view_counts[0] if len(args.view_counts) == 1 else ",".join(str(v) for v in args.view_counts)
@@ -1118,6 +1158,10 @@ def _rank_main(args):
                 "mlp_products": "exact fp32 (v_mfma_f32_16x16x4_f32)" if args.fp32_mlp else "split bf16 (v_mfma_f32_16x16x32_bf16 on hi/lo parts, fp32 accumulation)",
                 "per_rank_seconds": [r["own_seconds"] for r in gathered], "per_rank_frames": [r["frames"] for r in gathered],
                 "seconds_per_frame_per_rank": [r["own_seconds"] / r["frames"] if r["frames"] else None for r in gathered],
+                # --photometric: the term's weight (0: off) and the mean of the frames' final photometric_loss (None: no frame ended in a residual step)
+                "photometric_weight": args.photometric,
+                "mean_final_photometric_loss": (lambda values: sum(values) / len(values) if values else None)(
+                    [v for r in gathered for v in r.get("final_photometric_losses", {}).values()]),
                 "mean_final_loss": [r["mean_final_loss"] for r in gathered], "data": "frame packs" if args.frames_dir else "synthetic", "dtype": "f32",
                 "final_loss_per_frame": {str(f): v for r in gathered for f, v in r["final_losses"].items()},
                 # host time per frame spent capturing hipGraphs (optimization._CaptureGate): what the other frames in flight wait for

@@ -812,6 +812,20 @@ def photometric_weight(config):
     return float(config.loss_weights.get("photometric_loss", 0.0) or 0.0)
 
 
+def _photometric_buffers(V, N, H, W, config, fused=True):
+    """The photometric term's (csrc/frame_photometric.h): the gray planes, the target view's hard-mask union as the weights of the term's
+    draw, the drawn rays, and -- `fused`: the fused glue -- the workspace and the outputs of vsrd_frame_photometric.  (The ray table over
+    the hard-mask weights, vsrd_ray_table_bytes(H W), follows them in graph mode.)"""
+    f32, rays = torch.float32, int(config.surface_num_rays)
+    pw, ph = (int(x) for x in config.surface_patch_size)
+    declared = [("gray", (V, H, W), f32, 0.0), ("hard_weights", (H * W,), f32, 0.0), ("ray_indices", (rays,), torch.int64, 0)]
+    if fused:
+        declared += [("workspace", (_lib.load().vsrd_frame_photometric_workspace_bytes(N, 1, V, rays, pw * ph),), torch.uint8, None),
+                     ("loss", (1,), f32, 0.0), ("stats", (2,), f32, 0.0), ("grad_instances", (N, 16), f32, 0.0),
+                     ("grad_mlp", (N, _lib.MLP_WEIGHTS), f32, 0.0)]
+    return declared
+
+
 def _check_loss_weights(config):
     """ValueError for a loss weight the loops do not know: a term that nothing applies would otherwise be dropped without a word."""
     unknown = sorted(set(config.loss_weights) - set(losses.LOSS_WEIGHTS))
@@ -840,10 +854,13 @@ def _check_photometric(inputs, config, num_views, num_instances):
         raise ValueError(f"the photometric term serves 1..{_lib.MAX_INSTANCES} instances, got {N}")
     images = getattr(inputs, "images", None)
     if images is None:
-        raise ValueError("loss_weights['photometric_loss'] is non-zero: the frame needs its images (FrameInputs.images [V,3,H,W]; frame packs carry none)")
+        raise ValueError("loss_weights['photometric_loss'] is non-zero: the frame needs its images (FrameInputs.images [V,3,H,W]; a frame pack's "
+                         "optional member `images`)")
     H, W = (int(x) for x in inputs.image_size)
     if tuple(int(x) for x in images.shape) != (V, 3, H, W):
         raise ValueError(f"images of shape {tuple(images.shape)} for a frame of {V} views of {H} x {W}: expected {(V, 3, H, W)}")
+    if isinstance(inputs, frames.FramePack):
+        return      # (a pack's soft masks exist on the device only: reset() counts the hard pixels once vsrd_frame_ingest has written them)
     hard = int((inputs.soft_masks[0].amax(dim=-1) > 0.5).sum())
     if hard < rays:
         raise ValueError(f"only {hard} pixels of the target view lie in a hard mask, fewer than surface_num_rays = {rays} "
@@ -1087,18 +1104,9 @@ class FrameOptimizer:
         """The term's buffers, at construction and only when it is live (a loop without it has none of them): the gray planes, the target
         view's hard-mask union as sampling weights with its ray table (graph mode), the drawn rays, and for the fused glue the workspace and
         outputs of vsrd_frame_photometric -- all by the one placement rule (`_new`)."""
-        cfg, new, lib = self.config, self._new, _lib.load()
         H, W = (int(x) for x in self.inputs.image_size)
-        N, rays = self.capacity, int(cfg.surface_num_rays)
         p = self._photometric = dict(table=None)
-        p["gray"] = new((self.view_capacity, H, W), fill=0.0)
-        p["hard_weights"] = new(H * W, fill=0.0)
-        p["ray_indices"] = new(rays, torch.int64, fill=0)
-        if self.fused_glue:
-            pw, ph = (int(x) for x in cfg.surface_patch_size)
-            p["workspace"] = new(lib.vsrd_frame_photometric_workspace_bytes(N, 1, self.view_capacity, rays, pw * ph), torch.uint8)
-            p["loss"], p["stats"] = new(1, fill=0.0), new(2, fill=0.0)
-            p["grad_instances"], p["grad_mlp"] = new((N, 16), fill=0.0), new((N, _lib.MLP_WEIGHTS), fill=0.0)
+        p.update(self._buffers(_photometric_buffers(self.view_capacity, self.capacity, H, W, self.config, self.fused_glue)))
         if not self._write_photometric():
             raise UnsuitableFrameError("the hard masks of this frame's target view do not suit the table sampler (rendering.RayTable.suits): it "
                                        "cannot found a frame slot -- optimise it in a loop of its own (persistent=False)")
@@ -1113,6 +1121,10 @@ class FrameOptimizer:
         images = self.inputs.images.to(device=self.device, dtype=torch.float32).contiguous()
         _lib.check(_lib.load().vsrd_grayscale_images(_lib.ptr(images), V, H, W, _lib.ptr(p["gray"]), _lib.stream()))
         p["hard_weights"].copy_(self.flat_masks[:H * W, :N].amax(dim=-1) > 0.5)
+        if self.persistent and int(p["hard_weights"].sum()) < int(cfg.surface_num_rays):
+            # (a frame from a pack, whose hard pixels _check_photometric could not count: a draw would be padded with -1.  The caller
+            #  optimises it in a loop of its own, whose construction says why it cannot be)
+            return False
         if not (self.graph and self.device.type == "cuda"):
             return True
         had_table = p["table"] is not None
@@ -1155,16 +1167,35 @@ class FrameOptimizer:
         return losses.patch_correlation_loss(p["gray"][:V], self.inputs.intrinsic_matrices.to(self.device), self.inputs.extrinsic_matrices.to(self.device),
                                              indices, positions, normals, converged, tuple(cfg.surface_patch_size), int(cfg.surface_top_k))
 
-    def _launch_photometric(self, field, surface_ray_indices, stream):
-        """vsrd_frame_photometric on the step's field, after the render launch has written grad_instances / grad_mlp and before anything reads them."""
+    def _launch_photometric(self, field, surface_ray_indices, stream, frames=None, header=None):
+        """vsrd_frame_photometric on the step's field, after the render launch has written grad_instances / grad_mlp and before anything reads them.
+        ``frames = (B, stride)``: this loop is frame 0 of a batch -- the batched draw (every frame from its own table, keyed by its own step
+        counter) and vsrd_frame_photometric_with_header with the batch's `header`, each ONE call for the B frames."""
         cfg, b, p, lib = self.config, self._glue, self._photometric, _lib.load()
         H, W = (int(x) for x in self.inputs.image_size)
+        weights = cfg.loss_weights
+        pw, ph = (int(x) for x in cfg.surface_patch_size)
+        if frames is not None:
+            if surface_ray_indices is not None or p["table"] is None:
+                raise RuntimeError("a batch of frames draws the photometric term's rays from the frames' hard-mask tables")
+            rays, table = int(cfg.surface_num_rays), p["table"]
+            _lib.check(lib.vsrd_sample_rays_table_frames(table.table.data_ptr(), table.count, rays, (cfg.seed + 2) & 0xFFFFFFFFFFFFFFFF,
+                                                         self.step_tensor.data_ptr(), p["ray_indices"].data_ptr(), int(frames[0]), int(frames[1]), stream))
+            # (under a header the by-value counts are the capacities; the frames' own are in their headers)
+            patch = _lib.PatchCorrelationConfig(self.view_capacity if header is not None else self.num_views, rays, H, W, pw, ph, int(cfg.surface_top_k), 0,
+                                                1.0e-6, 1.0e-12)
+            config = _lib.FramePhotometricConfig(int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria), float(cfg.surface_bounding_radius),
+                                                 photometric_weight(cfg) / float(weights["silhouette_loss"]), int(frames[0]), int(frames[1]))
+            _lib.check(lib.vsrd_frame_photometric_with_header(
+                config, patch, field, _lib.ptr(self.camera_positions), _lib.ptr(self.ray_directions), _lib.ptr(p["gray"]), _lib.ptr(b["intrinsics"]),
+                _lib.ptr(b["extrinsics"]), p["ray_indices"].data_ptr(), p["workspace"].data_ptr(), p["workspace"].numel(), _lib.ptr(p["loss"]),
+                _lib.ptr(p["stats"]), _lib.ptr(p["grad_instances"]), _lib.ptr(p["grad_mlp"]), _lib.ptr(b["grad_instances"]), _lib.ptr(b["grad_mlp"]),
+                None, None, None, header, stream))
+            return
         indices = self._surface_rays(surface_ray_indices)
         rays = int(indices.numel())
         if rays != int(cfg.surface_num_rays):
             raise ValueError(f"surface_ray_indices: config.surface_num_rays = {cfg.surface_num_rays} rays (the term's buffers are laid out for them), got {rays}")
-        weights = cfg.loss_weights
-        pw, ph = (int(x) for x in cfg.surface_patch_size)
         patch = _lib.PatchCorrelationConfig(self.num_views, rays, H, W, pw, ph, int(cfg.surface_top_k), 0, 1.0e-6, 1.0e-12)
         config = _lib.FramePhotometricConfig(int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria), float(cfg.surface_bounding_radius),
                                              photometric_weight(cfg) / float(weights["silhouette_loss"]), 1, 0)
@@ -1452,11 +1483,9 @@ class FrameOptimizer:
                                                                    _lib.ptr(b["grad_instances"]), None, header, stream))
         photometric = residual and self._photometric is not None
         if photometric:
-            if batch[0] > 1:
-                raise RuntimeError("the photometric term is not batched over frames (vsrd_frame_photometric: one frame per call)")
             # on the step's own stream: the call ends in the accumulation into grad_instances / grad_mlp, which the render launch has just
             # written and which the hypernetwork's backward and the epilogue read next -- no stretch of it is free of both
-            self._launch_photometric(field, surface_ray_indices, stream)
+            self._launch_photometric(field, surface_ray_indices, stream, frames=None if frames is None else batch, header=header)
         if fused_net:     # branch: backward through the hypernetwork, Adam on it and on the embeddings, both rates decayed (next to the epilogue)
             net_branch.wait_stream(main)
             with torch.cuda.stream(net_branch):
@@ -1472,7 +1501,11 @@ class FrameOptimizer:
         _lib.check(lib.vsrd_frame_epilogue_with_header(*epilogue_args, header, stream))
         if photometric:   # record[4], which the epilogue has just written, gains the term
             p = self._photometric
-            _lib.check(lib.vsrd_frame_photometric_finish(_lib.ptr(p["loss"]), _lib.ptr(p["stats"]), photometric_weight(cfg), _lib.ptr(b["record"]), stream))
+            if frames is None:
+                _lib.check(lib.vsrd_frame_photometric_finish(_lib.ptr(p["loss"]), _lib.ptr(p["stats"]), photometric_weight(cfg), _lib.ptr(b["record"]), stream))
+            else:
+                _lib.check(lib.vsrd_frame_photometric_finish_with_header(_lib.ptr(p["loss"]), _lib.ptr(p["stats"]), photometric_weight(cfg),
+                                                                         _lib.ptr(b["record"]), *batch, stream))
         if residual and not fused_net:    # autograd + torch.optim.Adam (the box tensors have no .grad: skipped)
             mlp_weights.backward(b["grad_mlp"] * weights["silhouette_loss"])
             self.optimizer.step()
@@ -1691,7 +1724,8 @@ class FrameOptimizer:
         intrinsics, extrinsics = frames.camera_matrices(pack, self.device)
         return FrameInputs((H, W), intrinsics, extrinsics, self.flat_masks.view(V, H, W, stride)[..., :N],
                            b["gt_boxes"][:, :N].unflatten(-1, (2, 2)), b["visible"][:, :N].bool(), *frames.ground_truth_3d(pack, self.device),
-                           **frames.group_tables(pack, self.device))
+                           **frames.group_tables(pack, self.device),
+                           images=frames.pack_images(pack, self.device) if self._photometric is not None else None)
 
     def reset(self, inputs: FrameInputs, init_seed=None):
         """Start ANOTHER frame of the same shape in this loop, in place: the new frame's matrices, boxes and soft masks are copied into
@@ -1769,7 +1803,9 @@ class FrameOptimizer:
                 self._write_log_table()
             suits = self._prepare_sampler(cfg)
             if self._photometric is not None:    # (the new frame's gray planes and hard masks, in the buffers the graphs read)
-                for name in ("loss", "stats", "grad_instances", "grad_mlp"):
+                # (ray_indices too: the draw overwrites them before use, but a slot then holds what a fresh loop -- or a batch's row -- holds
+                #  in the box-only steps, which is what a state comparison between the two looks at)
+                for name in ("loss", "stats", "grad_instances", "grad_mlp", "ray_indices"):
                     self._photometric[name].zero_()
                 suits = self._write_photometric() and suits
             main.synchronize()
@@ -1977,7 +2013,7 @@ class FrameBatch:
     Like a frame slot, a batch is built and captured once (``capture_all``) and then serves group after group of frames through
     ``reset(f, inputs, init_seed)``; a last group of fewer than B frames runs with ``active < B`` (the first ``active`` rows)."""
 
-    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None, max_label_views=None):
+    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None, max_label_views=None, photometric=False):
         """``max_instances`` and ``max_views`` None: every frame has ONE shape (views, height, width, instances).  ``max_instances`` an
         integer: a MIXED batch -- the frames have 1..max_instances instances each; every row is laid out for ``max_instances`` (the capacity)
         and carries its frame's own count in a header (include/vsrd_hip.h, vsrd_frame_header), and frame f still walks, bit for bit, the
@@ -1985,14 +2021,26 @@ class FrameBatch:
         1..max_views views each and every row is laid out for ``max_views`` views (ABI 12).  The two combine; giving either one gives every
         row a header, and the axis without a capacity stays uniform.  The frames always share (height, width).  ``max_label_views``: the
         label-view capacity of every row (``group_labels``; the frames' groups may differ in size whatever the other capacities are, their
-        count lives in the row) -- None: the largest L of the frames given, 0: no groups."""
+        count lives in the row) -- None: the largest L of the frames given, 0: no groups.
+        ``photometric``: with a non-zero loss_weights["photometric_loss"], carry the photometric term in the batch -- every row gains the gray
+        planes of its views ([view capacity, H, W] floats: 36 MB at 17 x 376 x 1408), the hard-mask weights of its target view with their
+        ray table, and the workspace of vsrd_frame_photometric, and every residual step issues the batched draw,
+        vsrd_frame_photometric_with_header and the batched finish (the term's field evaluations run the exact-fp32 MLP).  Every frame then
+        needs its images and at least surface_top_k views.  The default refuses such a config; with weight 0 the keyword changes nothing."""
         inputs = list(inputs)
         if not inputs:
             raise ValueError("FrameBatch needs at least one frame")
         _check_loss_weights(config)
-        if photometric_weight(config) != 0.0:
-            raise ValueError("loss_weights['photometric_loss'] is non-zero: the photometric term is not batched over frames yet "
-                             "(vsrd_frame_photometric serves one frame per call) -- optimise such frames in FrameOptimizer loops")
+        self.photometric = bool(photometric) and photometric_weight(config) != 0.0
+        if photometric_weight(config) != 0.0 and not photometric:
+            raise ValueError("loss_weights['photometric_loss'] is non-zero: the photometric term is not batched over frames unless asked for "
+                             "-- FrameBatch(..., photometric=True) gives every row the term's buffers (gray planes, hard-mask table, workspace); "
+                             "or optimise such frames in FrameOptimizer loops")
+        for position, frame_inputs in enumerate(inputs):        # (before any device work: a frame without images, or with fewer views than top_k)
+            try:
+                _check_photometric(frame_inputs, config, frame_inputs.soft_masks.shape[0], frame_inputs.soft_masks.shape[-1])
+            except ValueError as error:
+                raise ValueError(f"frame {position} of the batch: {error}") from None
         largest = max(label_view_count(i) for i in inputs)
         self.max_label_views = largest if max_label_views is None else int(max_label_views)
         if not 0 <= self.max_label_views <= _lib.MAX_LABEL_VIEWS:
@@ -2030,7 +2078,8 @@ class FrameBatch:
             config = dataclasses.replace(config, mlp_adjoint_item_slots=self.item_slots(self.size, config, shape[-1]))
         self.config, self.device = config, _indexed(device)
         with _capture_lock:
-            self.arena = FrameArena(self.size, self._row_bytes(shape, config, self.max_label_views, headed=capacities != (None, None)), self.device)
+            self.arena = FrameArena(self.size, self._row_bytes(shape, config, self.max_label_views, headed=capacities != (None, None),
+                                                               photometric=self.photometric), self.device)
         # A row is FOUNDED on a frame that suits the table sampler its graphs will draw from (the frames a row later serves come through reset(),
         # which says so when one does not suit).  A founder that does not suit is replaced by the first one that does -- the shape is what a
         # row needs from its founder -- and listed in `unsuitable_founders`; no suitable founder at all: UnsuitableFrameError.
@@ -2077,10 +2126,11 @@ class FrameBatch:
         return slots
 
     @staticmethod
-    def _row_bytes(shape, config, label_views=0, headed=False):
+    def _row_bytes(shape, config, label_views=0, headed=False, photometric=False):
         """Bytes of one frame's row: the aligned sizes of everything a FrameOptimizer(row=...) creates there, summed over the declarations it
         allocates from and the regions the library sizes, in the order of allocation (Adam's state, declared with the parameters, comes
-        amid the glue) -- every output included, so a row is exactly full once each has been asked for.  `headed`: rows with a header."""
+        amid the glue) -- every output included, so a row is exactly full once each has been asked for.  `headed`: rows with a header;
+        `photometric`: rows that carry the photometric term (nothing is added while its weight is 0)."""
         V, H, W, N = (int(x) for x in shape)
         def sizes(declared):
             return [_buffer_bytes(shape, dtype) for _, shape, dtype, _ in declared]
@@ -2090,6 +2140,8 @@ class FrameBatch:
         parts += sizes(_glue_buffers(V, N, config, headed))
         if config.scalar_interval > 0 or config.checkpoint_interval > 0:
             parts += sizes(_log_buffers(N, config))
+        if photometric and photometric_weight(config) != 0.0:
+            parts += sizes(_photometric_buffers(V, N, H, W, config)) + [_lib.load().vsrd_ray_table_bytes(H * W)]
         for output in _OUTPUTS.values():
             parts += sizes(output.buffers(V, N, H, W))
         if label_views > 0:

@@ -76,3 +76,18 @@ def synthetic_frame(seed, num_views, height, width, num_instances):
     raw_dim = torch.randn(1, num_instances, 3, generator=g) * 0.5
     raw_ori = torch.nn.functional.normalize(torch.randn(1, num_instances, 2, generator=g), dim=-1)
     return K, E, raw_loc, raw_dim, raw_ori
+
+
+def synthetic_images(frame, views, height, width):
+    """Smooth deterministic colour images of synthetic frame number `frame` for the photometric term: per view and channel a sum of six
+    sinusoids of period 24-64 px (texture a patch correlation can hold on to), quantised as image files are -- [V,3,H,W] uint8.  On the
+    device they are x / 255 (optimization.FrameInputs.images; frames.pack_images for a pack that carries them)."""
+    g = torch.Generator().manual_seed(7919 * int(frame) + 13)
+    y, x = torch.meshgrid(torch.arange(height, dtype=torch.float32), torch.arange(width, dtype=torch.float32), indexing="ij")
+    images = torch.zeros(views, 3, height, width)
+    for _ in range(6):
+        period = torch.empty(views, 3, 1, 1).uniform_(24.0, 64.0, generator=g)
+        angle = torch.empty(views, 3, 1, 1).uniform_(0.0, 2.0 * math.pi, generator=g)
+        phase = torch.empty(views, 3, 1, 1).uniform_(0.0, 2.0 * math.pi, generator=g)
+        images += torch.sin(2.0 * math.pi * (x * torch.cos(angle) + y * torch.sin(angle)) / period + phase)
+    return ((images / 12.0 + 0.5).clamp(0.0, 1.0) * 255.0).round().to(torch.uint8)
