@@ -687,6 +687,79 @@ int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* conf
                          uint8_t* mask_bits /* [N,H,ceil(W/8)] */, float* soft /* [H*W,N] or NULL */, int32_t* counts /* [N,3] or NULL */,
                          const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
 
+/* Frame surface (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): the dense
+ * surface render of ONE view of a frame -- the surface of the field in a camera view with range, normal, owning instance, shadow and a
+ * shaded image laid over the photograph: sphere_tracing, surface_normal, shadow_rendering and phong_shading (vsrd/rendering/renderers.py:21-174)
+ * as the dense logging branch of scripts/main.py:1028-1041 composes them -- in ONE launch for all frames of a batch, no host synchronisation,
+ * no allocation, capturable.  A wave owns a run of 64 pixels of an image row, one lane each; everything behind the primary trace is done
+ * only in runs where some pixel converged.
+ * Conventions as for vsrd_frame_masks: field->num_instances is the capacity N (1..VSRD_MAX_INSTANCES) and the stride of every instance axis
+ * (palette); config->num_frames / frame_stride batch the call (every pointer addresses frame 0, frame f lies f * frame_stride bytes behind
+ * it); frame_header (may be NULL: every frame has N instances) carries the frame's own n_f, clamped to [1, N]; instances n_f .. N-1 are
+ * neither read nor written.  Of config the call reads num_frames, frame_stride and device_schedule (its temperature, as in the step
+ * kernels) and nothing else.  The residual form evaluates the MLPs with the exact-fp32 products.
+ * Pixel p = y W + x of view `view`: origin o = camera_positions[view], direction r = ray_directions[view H W + p];
+ *   1. primary trace   what vsrd_sphere_trace computes with foreground = NULL, initialise = 0 and hard_union = (flags & VSRD_SURFACE_HARD_UNION)
+ *                      -> position, converged.  Which union to trace is the caller's choice;
+ *   2. surface point   (converged pixels) one evaluation of the union with its analytic gradient g, as vsrd_field_eval:
+ *                      normal = g / max(|g|, 1e-12); instance = the first member with the smallest distance (the arg-min of the hard
+ *                      union, the arg-max label of the soft one); range = |position - o|;
+ *   3. shadow trace    (light != NULL and flags & VSRD_SURFACE_SHADOWS) the same march -- same union, iteration count, criteria and
+ *                      bounding radius, no initialisation -- from position + normal * shadow_offset (product and sum rounded on their
+ *                      own) along -light; shadow = converged AND this trace's converged: shadow_rendering with foreground_masks = the
+ *                      primary convergence.  Without it shadow = 0;
+ *   4. shade           phong_shading (renderers.py:116-146) with view = r, the normal and the light all normalised:
+ *                      reflected = l - 2 n (l.n), diffuse = relu(-l.n), specular = relu(-reflected.view)^shininess,
+ *                      colour = clamp(material_emission + material_ambient light_ambient
+ *                                     + (1 - shadow) (palette[instance] light_diffuse diffuse + material_specular light_specular specular), 0, 1);
+ *                      a converged pixel is alpha colour + (1 - alpha) background / 255, any other the background pixel itself (or
+ *                      background_color when background is NULL); stored as (int)(255 c + 0.5).
+ * Stated deviations from the reference:
+ *   - the reference defines no way to combine shadow and shading; the (1 - shadow) factor on the diffuse and specular terms is this
+ *     project's choice;
+ *   - shadow_offset is a field of its own where the reference offsets by convergence_criteria c: with c a point at d(p) = delta < 0 starts
+ *     its shadow ray at about delta + c < c, converges at once and reads as shadowed.  Callers should pass 2 c (the launcher's default):
+ *     because d(p) > -c, d(start) ~ d(p) + 2 c > c for a field with unit gradient;
+ *   - FrameOptimizer.surface() traces the hard union by default; the reference's logging trace uses the soft union (hard = False).
+ * Outputs, each may be NULL and is then skipped:
+ *   converged_bits, shadow_bits [H, ceil(W/8)]  numpy.packbits along W: most significant bit first, pad bits 0 (the `inside` layout);
+ *   instance [H W] uint8                        255 where not converged;
+ *   range [H W] float32                         exactly 0 where not converged;
+ *   colors [H W,3] uint8                        needs light and palette;
+ *   positions [H W,3] float32                   where not converged the position the trace ended at, as vsrd_sphere_trace writes;
+ *   normals [H W,3] float32                     exactly 0 where not converged.
+ * No floating-point atomics; no output depends on the grid or on where a pixel sits in the launch.
+ * VSRD_E_INVALID_ARGUMENT before any launch, nothing written: a NULL field, config, surface, camera_positions or ray_directions; N outside
+ * 1..VSRD_MAX_INSTANCES; view outside 0..num_views-1; height, width < 1 or num_iterations < 0; colors without light or without palette;
+ * a background whose background_pixels is not H W. */
+#define VSRD_SURFACE_HARD_UNION 1u
+#define VSRD_SURFACE_SHADOWS 2u
+typedef struct vsrd_frame_surface_config {
+    int32_t view;               /* which view of the row, 0 = target                                              */
+    int32_t num_views;          /* V (the view capacity of the row): rows of camera_positions, views of ray_directions */
+    int32_t height, width;
+    int32_t num_iterations;     /* sphere_tracing, initialization=False: both traces                              */
+    float convergence_criteria;
+    float bounding_radius;      /* <= 0: none                                                                     */
+    float shadow_offset;        /* the shadow ray starts at position + normal * shadow_offset                     */
+    uint32_t flags;             /* VSRD_SURFACE_*                                                                 */
+    int32_t background_pixels;  /* H W of the `background` image; must be H W when background is given            */
+    float alpha;                /* weight of the shaded colour over the background                                */
+    float shininess;
+    float background_color[3];  /* where nothing converged and background is NULL                                 */
+    float light_ambient[3], light_diffuse[3], light_specular[3];
+    float material_ambient[3], material_specular[3], material_emission[3];
+} vsrd_frame_surface_config;
+
+int32_t vsrd_frame_surface(const vsrd_field* field, const vsrd_render_config* config, const vsrd_frame_surface_config* surface,
+                           const float* camera_positions /* [V,3] */, const float* ray_directions /* [V*H*W,3] */,
+                           const float* light /* [3] device: the direction the light travels, or NULL */,
+                           const float* palette /* [N,3] device: the instances' diffuse colours, or NULL */,
+                           const uint8_t* background /* [H*W,3] or NULL */,
+                           uint8_t* converged_bits, uint8_t* shadow_bits, uint8_t* instance, float* range, uint8_t* colors,
+                           float* positions, float* normals,
+                           const vsrd_frame_header* frame_header /* may be NULL */, void* stream);
+
 /* Frame metrics (added within ABI 12; probe for the symbol -- VSRD_ABI_VERSION is unchanged, no existing struct has a new field): a frame's
  * evaluation against its 3-D ground truth -- what the reference logs every `scalar_intervals` steps (scripts/main.py:870-924) -- in ONE
  * launch, one wave per frame, no host synchronisation, no allocation, capturable.  Lane k handles the matched pair

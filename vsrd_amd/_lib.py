@@ -167,6 +167,36 @@ class FrameMasksConfig(ctypes.Structure):
     ]
 
 
+FRAME_SURFACE_HARD_UNION = 1   # VSRD_SURFACE_*: flags of a vsrd_frame_surface call
+FRAME_SURFACE_SHADOWS = 2
+
+
+class FrameSurfaceConfig(ctypes.Structure):
+    """include/vsrd_hip.h::vsrd_frame_surface_config (added within ABI 12): the view, the image size, the sphere-tracing constants, the shadow
+    ray's offset, the blend and the light and material colours of one vsrd_frame_surface call."""
+    _fields_ = [
+        ("view", ctypes.c_int32),
+        ("num_views", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("num_iterations", ctypes.c_int32),
+        ("convergence_criteria", ctypes.c_float),
+        ("bounding_radius", ctypes.c_float),
+        ("shadow_offset", ctypes.c_float),
+        ("flags", ctypes.c_uint32),
+        ("background_pixels", ctypes.c_int32),
+        ("alpha", ctypes.c_float),
+        ("shininess", ctypes.c_float),
+        ("background_color", ctypes.c_float * 3),
+        ("light_ambient", ctypes.c_float * 3),
+        ("light_diffuse", ctypes.c_float * 3),
+        ("light_specular", ctypes.c_float * 3),
+        ("material_ambient", ctypes.c_float * 3),
+        ("material_specular", ctypes.c_float * 3),
+        ("material_emission", ctypes.c_float * 3),
+    ]
+
+
 class LogSegment(ctypes.Structure):
     """include/vsrd_hip.h::vsrd_log_segment (device memory): `count` 32-bit words from `source` to word `offset` of a snapshot slot."""
     _fields_ = [
@@ -246,7 +276,8 @@ _SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ct
 _RETURNS = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
 # host structures, passed as const T*; every other pointer is device memory (vsrd_frame_header too) or the stream, and travels as an integer
 _HOST_STRUCTS = {"vsrd_field": Field, "vsrd_render_config": RenderConfig, "vsrd_frame_config": FrameConfig, "vsrd_adam_tensors": AdamTensors,
-                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig, "vsrd_frame_log_config": FrameLogConfig,
+                 "vsrd_hypernetwork": Hypernetwork, "vsrd_frame_masks_config": FrameMasksConfig, "vsrd_frame_surface_config": FrameSurfaceConfig,
+                 "vsrd_frame_log_config": FrameLogConfig,
                  "vsrd_patch_correlation_config": PatchCorrelationConfig, "vsrd_frame_photometric_config": FramePhotometricConfig}
 _DEVICE_POINTEES = {"void", "float", "uint8_t", "int32_t", "int64_t", "uint64_t", "vsrd_frame_header"}
 

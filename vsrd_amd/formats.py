@@ -236,6 +236,65 @@ def load_frame_masks(path):
                     mask_iou=data["mask_iou"])
 
 
+def png_bytes(image):
+    """An 8-bit RGB image [H,W,3] uint8 as the bytes of a PNG file: the signature, IHDR, one IDAT (every row with filter 0, deflated by the
+    standard library's zlib) and IEND.  Nothing but the standard library: the project grows no imaging dependency for one picture."""
+    import struct
+    import zlib
+    import numpy as np
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f"an RGB image is [H,W,3], got {image.shape}")
+    height, width = int(image.shape[0]), int(image.shape[1])
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+    rows = np.concatenate([np.zeros((height, 1), dtype=np.uint8), image.reshape(height, width * 3)], axis=1)       # (filter type 0 in front of every row)
+    header = struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)                 # bit depth 8, colour type 2 (RGB), deflate, adaptive filtering, no interlace
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", header) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b"")
+
+
+def save_frame_surface(folder, surface, view=0):
+    """One view's dense surface render as files.  ``surface``: the dictionary of ``FrameOptimizer.surface()`` (host or device tensors) --
+    converged_bits / shadow_bits [H,ceil(W/8)] uint8, instance [H,W] uint8, range [H,W], colors [H,W,3] uint8, light [3], shape.  Writes
+    ``folder/surface/view_VV.npz`` with `converged_bits` and `shadow_bits` (numpy.packbits along W, most significant bit first:
+    frames.unpack_masks reads them), `instance` (255: none), `range`, `shape` and `light`, and ``folder/surface/view_VV.png``, the colour
+    image (png_bytes); each under a temporary name and renamed.  Returns the two paths."""
+    import numpy as np
+    arrays = {key: torch.as_tensor(surface[key]).detach().cpu().numpy() for key in ("converged_bits", "shadow_bits", "instance", "range", "colors", "light")}
+    height, width = (int(x) for x in surface["shape"])
+    for key in ("converged_bits", "shadow_bits"):
+        if arrays[key].shape != (height, (width + 7) // 8):
+            raise ValueError(f"{key} of shape {arrays[key].shape} does not hold {height} x {width} pixels")
+    if arrays["instance"].shape != (height, width) or arrays["range"].shape != (height, width) or arrays["colors"].shape != (height, width, 3):
+        raise ValueError(f"instance, range and colors of shapes {arrays['instance'].shape}, {arrays['range'].shape}, {arrays['colors'].shape} "
+                         f"for an image of {height} x {width} pixels")
+    stem = os.path.join(folder, "surface", f"view_{int(view):02d}")
+
+    def write_arrays(name):
+        with open(name, "wb") as file:         # (a file object: numpy appends no suffix to the temporary name)
+            np.savez(file, converged_bits=arrays["converged_bits"].astype(np.uint8), shadow_bits=arrays["shadow_bits"].astype(np.uint8),
+                     instance=arrays["instance"].astype(np.uint8), range=arrays["range"].astype(np.float32),
+                     shape=np.asarray([height, width], dtype=np.int64), light=arrays["light"].astype(np.float32).reshape(3))
+
+    def write_image(name):
+        with open(name, "wb") as file:
+            file.write(png_bytes(arrays["colors"]))
+    _atomic_write(stem + ".npz", write_arrays)
+    _atomic_write(stem + ".png", write_image)
+    return stem + ".npz", stem + ".png"
+
+
+def load_frame_surface(path):
+    """What save_frame_surface wrote in its npz (a folder: its surface/view_00.npz): a dictionary of numpy arrays, `shape` as a tuple (H, W)."""
+    import numpy as np
+    if os.path.isdir(path):
+        path = os.path.join(path, "surface", "view_00.npz")
+    with np.load(path) as data:
+        return dict(converged_bits=data["converged_bits"], shadow_bits=data["shadow_bits"], instance=data["instance"], range=data["range"],
+                    shape=tuple(int(x) for x in data["shape"]), light=data["light"])
+
+
 # ---- the per-frame log: scalar history and step snapshots (optimization.FrameOptimizer.history / snapshots, vsrd_frame_log) ---------------
 HISTORY_LOSSES = ("iou_projection_loss", "l1_projection_loss", "silhouette_loss", "eikonal_loss", "loss")
 # config.optimization.param_group_names of the reference's configs, the order of the optimiser's groups (scripts/main.py:929-933)

@@ -279,6 +279,21 @@ def scan_label_views(files):
     return counts
 
 
+def parse_light(text):
+    """--surface-light "X,Y,Z" -> (x, y, z), None for the empty string (the default light); ValueError for anything that is not three finite
+    numbers with a direction (not all zero)."""
+    if not text:
+        return None
+    import math
+    try:
+        light = tuple(float(part) for part in text.split(","))
+    except ValueError:
+        light = ()
+    if len(light) != 3 or not all(math.isfinite(x) for x in light) or not any(light):
+        raise ValueError(f"--surface-light: three finite numbers X,Y,Z, not all zero, got {text!r}")
+    return light
+
+
 def scan_images(files):
     """--photometric with --frames-dir: every pack must carry the views' images (frames.FramePack.images); the first one without is named."""
     from . import frames
@@ -395,6 +410,7 @@ class _RenderWork:
         # --photometric W: the photometric term in every loop and every batch row of the job (FrameBatch(..., photometric=True))
         self.photometric = float(getattr(args, "photometric", 0.0) or 0.0)
         self.photometric_losses = {}
+        self.backgrounds = {}            # --surface: frame -> uint8 [H,W,3] (_note_background)
         if self.photometric:
             from . import losses
             self.config.update(loss_weights={**losses.LOSS_WEIGHTS, "photometric_loss": self.photometric})
@@ -412,13 +428,24 @@ class _RenderWork:
         loop's); a dynamic queue's are built when the frame is taken -- inside the clock, like the reference's loader -- and dropped after.
         Frame packs (--frames-dir) are always read when the frame is taken and never kept."""
         if frame in self.inputs:
-            return self.inputs[frame]
+            return self._note_background(frame, self.inputs[frame])
         args = self.args
         if args.frames_dir:          # a frame pack (frames.py), host side: slots and batch rows reset from it, vsrd_frame_ingest fills the row
             from . import frames
-            return frames.load_pack(self.manifest["packs"][int(frame)])
-        return synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts), instances_of(frame, args.instance_counts), args.height, args.width,
-                                      args.label_views, images=bool(self.photometric))
+            return self._note_background(frame, frames.load_pack(self.manifest["packs"][int(frame)]))
+        return self._note_background(frame, synthetic_frame_inputs(self.device, frame, views_of(frame, args.view_counts), instances_of(frame, args.instance_counts),
+                                                                   args.height, args.width, args.label_views, images=bool(self.photometric)))
+
+    def _note_background(self, frame, inputs):
+        """--surface: the target view's photograph of a frame that carries its images (a pack's member `images`, FrameInputs.images), as the
+        uint8 [H,W,3] image the surface render is laid over -- kept from the moment the frame is taken until its outputs are collected."""
+        images = getattr(inputs, "images", None) if getattr(self.args, "surface", False) else None
+        if images is not None:
+            first = torch.as_tensor(images[0])
+            if first.dtype != torch.uint8:
+                first = (first.to(torch.float32) * 255.0 + 0.5).clamp(0.0, 255.0).to(torch.uint8)
+            self.backgrounds[int(frame)] = first.permute(1, 2, 0).contiguous()
+        return inputs
 
     def materialised(self, inputs):
         """`inputs` as a FrameInputs on the device: what founds a slot or a batch, and what a loop of its own is built on."""
@@ -468,7 +495,8 @@ class _RenderWork:
                     self.batch = optimization.FrameBatch(founders, self.optimization_config(), self.device,
                                                          max_instances=max(args.instance_counts) if mixed else None,
                                                          max_views=max(args.view_counts) if mixed_views else None,
-                                                         max_label_views=args.label_view_capacity, photometric=bool(self.photometric))
+                                                         max_label_views=args.label_view_capacity, photometric=bool(self.photometric),
+                                                         surface=bool(getattr(args, "surface", False)))
                     if self.logs:                # (before the captures: the buffers the log reads exist in every row)
                         self.batch.log_outputs(metrics=args.metrics, masks=args.masks)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
@@ -531,7 +559,8 @@ class _RenderWork:
         clock) and the rank's report of per-frame metrics."""
         args = self.args
         keys = [key for wanted, keys in ((args.predictions, ("labels", "labels_write")), (getattr(args, "group_predictions", False), ("group_labels", "group_labels_write")),
-                                         (args.masks, ("masks", "masks_write")), (args.metrics, ("metrics",)))
+                                         (args.masks, ("masks", "masks_write")), (getattr(args, "surface", False), ("surface", "surface_write")),
+                                         (args.metrics, ("metrics",)))
                 if wanted for key in keys]
         keys += ["log", "log_write"] if self.logs else []
         self.phase_seconds, self.frame_metrics = dict.fromkeys(keys, 0.0) or None, {}
@@ -576,7 +605,8 @@ class _RenderWork:
         loop of ONE frame, or the batch whose first `active` rows hold the `frames` = [(frame, checkpoint path)].  In this order, each ONE
         vsrd_frame_* call for the group and its copies to the host: --predictions, the labels; --group-predictions, the labels in every
         frame's own group; --masks, the target view's predicted masks,
-        and every payload's metric mask_iou (the mean over its instances); --metrics, the reference's six metrics into the payload's
+        and every payload's metric mask_iou (the mean over its instances); --surface, the target view's dense surface render, laid over the
+        frame's photograph when every frame of the group carries one; --metrics, the reference's six metrics into the payload's
         `metrics` and the rank's report, for every frame that had 3-D ground truth (a loop without it is not asked; a batch is, and its
         frames without come back with count 0 and are skipped).  Returns the pending file writes for `_write_outputs`."""
         import time
@@ -594,6 +624,16 @@ class _RenderWork:
             payload["metrics"] = dict(payload.get("metrics") or {}, mask_iou=float(host["mask_iou"].mean()))
             pending.append(("masks_write", formats.save_frame_masks, (folder, host, host["shape"])))
 
+        def surface(frame, folder, entry, payload):
+            pending.append(("surface_write", formats.save_frame_surface, (folder, formats.to_host(entry))))
+
+        def ask_surface():
+            photographs = [self.backgrounds.pop(int(frame), None) for frame, _ in frames]
+            light = getattr(args, "surface_light", None)
+            if active is None:
+                return source.surface(light=light, background=photographs[0])
+            return source.surface(active=active, light=light, background=photographs if all(p is not None for p in photographs) else None)
+
         def metrics(frame, folder, entry, payload):
             named = formats.frame_metrics(entry["summary"])
             if named:
@@ -601,10 +641,14 @@ class _RenderWork:
                 self.frame_metrics[int(frame)] = named
 
         for key, wanted, each in (("labels", args.predictions, labels), ("group_labels", getattr(args, "group_predictions", False), group_labels), ("masks", args.masks, masks),
+                                  ("surface", getattr(args, "surface", False), surface),
                                   ("metrics", args.metrics and (active is not None or source.inputs.boxes_3d is not None), metrics)):
             if wanted:
                 t0 = time.perf_counter()
-                entries = getattr(source, key)() if active is None else getattr(source, key)(active=active)
+                if key == "surface":
+                    entries = ask_surface()
+                else:
+                    entries = getattr(source, key)() if active is None else getattr(source, key)(active=active)
                 for (frame, path), entry, payload in zip(frames, entries if isinstance(entries, list) else [entries], payloads):
                     each(frame, os.path.dirname(path), entry, payload)
                 self.phase_seconds[key] += time.perf_counter() - t0
@@ -895,6 +939,14 @@ def main(argv=None):
                              "to the frame's checkpoint and store their mean IoU against the masks the frame was fitted to as the checkpoint's "
                              "metric `mask_iou`; with --ckpt-interval every step_*.pt carries it too, and --select mask_iou:max picks among "
                              "them.  Needs --out; not with --selftest")
+    parser.add_argument("--surface", action="store_true",
+                        help="after a frame's steps, render the target view's dense surface -- range, owning instance, shadow and a shaded colour image "
+                             "of the fitted field, laid over the frame's photograph when the frame carries its images (scripts/main.py:1028-1041) -- "
+                             "vsrd_frame_surface, one launch per group of frames -- and write surface/view_00.npz and surface/view_00.png next to the "
+                             "frame's checkpoint.  Needs --out; not with --selftest")
+    parser.add_argument("--surface-light", default="",
+                        help="X,Y,Z: the direction the light of --surface travels, in the rectified camera frame (x right, y down, z forward).  "
+                             "Default 0.3,1,0.6: from above and behind the camera, a little from the left")
     parser.add_argument("--metrics", action="store_true",
                         help="after a frame's steps, evaluate its boxes against the frame's 3-D ground truth (FrameInputs.boxes_3d / a frame pack's "
                              "boxes_3d; synthetic frames carry their true boxes) -- vsrd_frame_metrics, one launch per group of frames -- and store the "
@@ -940,6 +992,16 @@ def main(argv=None):
         raise SystemExit("--predictions writes the labels of optimised frames; --selftest optimises none: drop one of --selftest, --predictions")
     if args.masks and args.selftest:
         raise SystemExit("--masks renders the masks of optimised frames; --selftest optimises none: drop one of --selftest, --masks")
+    if args.surface and args.selftest:
+        raise SystemExit("--surface renders the surface of optimised frames; --selftest optimises none: drop one of --selftest, --surface")
+    if args.surface and not args.out:
+        raise SystemExit("--surface writes surface/view_00.npz and surface/view_00.png next to every frame's checkpoint: it needs --out")
+    try:
+        args.surface_light = parse_light(args.surface_light)
+    except ValueError as error:
+        raise SystemExit(str(error))
+    if args.surface_light is not None and not args.surface:
+        raise SystemExit("--surface-light sets the light of --surface: add --surface or drop it")
     if args.metrics and args.selftest:
         raise SystemExit("--metrics evaluates the boxes of optimised frames; --selftest optimises none: drop one of --selftest, --metrics")
     for flag, value in (("--scalar-interval", args.scalar_interval), ("--ckpt-interval", args.ckpt_interval), ("--select", args.select)):
@@ -1174,7 +1236,8 @@ def _rank_main(args):
                 "phase_seconds": [r.get("phase_seconds") for r in gathered],
                 **({"predictions": True} if args.predictions else {}),
                 **({"group_predictions": True} if args.group_predictions else {}),
-                **({"masks": True} if args.masks else {}),      # (--predictions: label files next to every checkpoint)
+                **({"masks": True} if args.masks else {}),
+                **({"surface": True} if args.surface else {}),      # (--predictions: label files next to every checkpoint)
                 **({"frame_log": {"scalar_interval": args.scalar_interval, "ckpt_interval": args.ckpt_interval, "select": args.select}}
                    if args.scalar_interval or args.ckpt_interval or args.select else {}),
                 **(mean_frame_metrics(gathered) if args.metrics else {}),

@@ -736,8 +736,49 @@ _OUTPUTS = dict(
 _LABEL_VIEW_OUTPUTS = dict(group_labels=_FrameOutput(_group_buffers, _launch_group_labels, _group_views))     # csrc/frame_group_labels.h
 
 
+def _surface_buffers(V, N, H, W):
+    """What the caller hands over (the light, the instances' diffuse colours, the photograph), then vsrd_frame_surface's compact outputs.
+    Positions and normals, the call's per-pixel float triples, are not kept (rendering.surface_render returns them)."""
+    u8, f32 = torch.uint8, torch.float32
+    return [("light", (3,), f32, 0.0), ("palette", (N, 3), f32, 0.0), ("background", (H * W, 3), u8, 0), ("converged_bits", (H, (W + 7) // 8), u8, 0),
+            ("shadow_bits", (H, (W + 7) // 8), u8, 0), ("instance", (H * W,), u8, 255), ("range", (H * W,), f32, 0.0), ("colors", (H * W, 3), u8, 0)]
+
+
+def _launch_surface(loop, state, frame, header, view=0, hard=True, shadows=True, background=False, alpha=None):
+    cfg, b = loop.config, loop._glue
+    H, W = (int(x) for x in loop.inputs.image_size)
+    from .rendering import renderers
+    # the field the last step rendered, by the rule of _launch_masks: its instance block, and in the residual phase its (centred) MLP weights
+    residual = loop.step_index - 1 >= cfg.warmup_steps
+    if residual and not loop.fused_hypernetwork:
+        raise RuntimeError("surface() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
+    field = _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
+    config = _lib.make_config(0, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, schedule=loop.schedule, frames=(frame.num_frames, frame.frame_stride))
+    blend = (0.6 if background else 1.0) if alpha is None else float(alpha)
+    surface = renderers.surface_config(view, loop.view_capacity, H, W, cfg.surface_num_iterations, cfg.surface_convergence_criteria,
+                                       cfg.surface_bounding_radius, None, hard=hard, shadows=shadows, background=background, alpha=blend)
+    return _lib.load().vsrd_frame_surface(
+        field, config, surface, _lib.ptr(loop.camera_positions), _lib.ptr(loop.ray_directions), _lib.ptr(state["light"]), _lib.ptr(state["palette"]),
+        state["background"].data_ptr() if background else None, state["converged_bits"].data_ptr(), state["shadow_bits"].data_ptr(),
+        state["instance"].data_ptr(), _lib.ptr(state["range"]), state["colors"].data_ptr(), None, None, header, _lib.stream())
+
+
+def _surface_views(loop, state, view=0, hard=True, shadows=True, background=False, alpha=None):
+    H, W = (int(x) for x in loop.inputs.image_size)
+    return dict(converged_bits=state["converged_bits"], shadow_bits=state["shadow_bits"], instance=state["instance"].view(H, W),
+                range=state["range"].view(H, W), colors=state["colors"].view(H, W, 3), light=state["light"], shape=(H, W), view=int(view), hard=bool(hard))
+
+
+# ... and the output whose buffers are whole images per row (5.7 MB at 376 x 1408): a fourth entry on the same path, in a table of its own
+# because a batch's rows hold them only when the batch was built for it (FrameBatch(..., surface=True)) -- `_row_bytes` counts them then
+_IMAGE_OUTPUTS = dict(surface=_FrameOutput(_surface_buffers, _launch_surface, _surface_views, last_step="field block"))       # csrc/frame_surface.h
+
+
 def _output(name):
-    return _OUTPUTS[name] if name in _OUTPUTS else _LABEL_VIEW_OUTPUTS[name]
+    for table in (_OUTPUTS, _LABEL_VIEW_OUTPUTS, _IMAGE_OUTPUTS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 # ---- what a graph-mode loop keeps besides its outputs, declared as they are: plain functions of the capacities and the config ->
@@ -1908,6 +1949,36 @@ class FrameOptimizer:
             raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
         return self._ask("masks", view=view, threshold=threshold, soft=soft)
 
+    def _write_surface(self, light, background):
+        """The row's light, palette and photograph for the next surface launch (host values: outside any capture)."""
+        from .rendering import renderers
+        state = self._output_state("surface")
+        H, W = (int(x) for x in self.inputs.image_size)
+        with torch.no_grad():
+            state["light"].copy_(torch.as_tensor(renderers.SURFACE_LIGHT if light is None else light, dtype=torch.float32).reshape(3))
+            state["palette"].copy_(renderers.surface_palette(self.capacity))
+            if background is not None:
+                if tuple(background.shape) != (H, W, 3) or background.dtype != torch.uint8:
+                    raise ValueError(f"background must be uint8 [H,W,3] = {(H, W, 3)}, got {background.dtype} {tuple(background.shape)}")
+                state["background"].copy_(background.reshape(H * W, 3))
+
+    def surface(self, view=0, hard=True, light=None, shadows=True, background=None, alpha=None):
+        """The dense surface render of view ``view`` (0: the target view) -- the surface of the fitted field with range, owning instance,
+        shadow and a shaded image, what the dense logging branch of scripts/main.py:1028-1041 composes from sphere_tracing, surface_normal,
+        shadow_rendering and phong_shading -- by one vsrd_frame_surface launch on the current stream, no host synchronisation.  It renders
+        the field the LAST STEP rendered, by the rule of ``masks()``.  ``hard``: trace the hard union (the default; the reference's logging
+        trace uses the soft one, ``hard=False``); ``light`` [3]: the direction the light travels (None: rendering.SURFACE_LIGHT);
+        ``background`` [H,W,3] uint8: the photograph the shaded colours are laid over with weight ``alpha`` (None: 0.6 over a background,
+        else 1).  RuntimeError when no step has run since construction or ``reset()``.  A dictionary of device tensors: converged_bits /
+        shadow_bits [H, ceil(W/8)] uint8 (numpy.packbits along W), instance [H,W] uint8 (255: none), range [H,W], colors [H,W,3] uint8,
+        light [3], shape, view.  They are views of buffers the next call overwrites (formats.save_frame_surface)."""
+        if not 0 <= int(view) < self.num_views:
+            raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
+        _check_asked("surface", [self])
+        with _capture_lock:
+            self._write_surface(light, background)
+        return self._ask("surface", view=view, hard=hard, shadows=shadows, background=background is not None, alpha=alpha)
+
     def _write_ground_truth(self, n):
         """The row's ground-truth corners and rectification matrix from `self.inputs`: NaN (no annotation) in every slot the frame does not
         fill -- all of them when the frame has no boxes_3d -- and the identity without a rectification matrix."""
@@ -2013,7 +2084,8 @@ class FrameBatch:
     Like a frame slot, a batch is built and captured once (``capture_all``) and then serves group after group of frames through
     ``reset(f, inputs, init_seed)``; a last group of fewer than B frames runs with ``active < B`` (the first ``active`` rows)."""
 
-    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None, max_label_views=None, photometric=False):
+    def __init__(self, inputs, config, device, init_seeds=None, max_instances=None, max_views=None, max_label_views=None, photometric=False,
+                 surface=False):
         """``max_instances`` and ``max_views`` None: every frame has ONE shape (views, height, width, instances).  ``max_instances`` an
         integer: a MIXED batch -- the frames have 1..max_instances instances each; every row is laid out for ``max_instances`` (the capacity)
         and carries its frame's own count in a header (include/vsrd_hip.h, vsrd_frame_header), and frame f still walks, bit for bit, the
@@ -2026,8 +2098,10 @@ class FrameBatch:
         planes of its views ([view capacity, H, W] floats: 36 MB at 17 x 376 x 1408), the hard-mask weights of its target view with their
         ray table, and the workspace of vsrd_frame_photometric, and every residual step issues the batched draw,
         vsrd_frame_photometric_with_header and the batched finish (the term's field evaluations run the exact-fp32 MLP).  Every frame then
-        needs its images and at least surface_top_k views.  The default refuses such a config; with weight 0 the keyword changes nothing."""
+        needs its images and at least surface_top_k views.  The default refuses such a config; with weight 0 the keyword changes nothing.
+        ``surface``: lay every row out for the buffers of ``surface()`` as well (whole images: 5.7 MB per row at 376 x 1408)."""
         inputs = list(inputs)
+        self.surface_rows = bool(surface)
         if not inputs:
             raise ValueError("FrameBatch needs at least one frame")
         _check_loss_weights(config)
@@ -2079,7 +2153,7 @@ class FrameBatch:
         self.config, self.device = config, _indexed(device)
         with _capture_lock:
             self.arena = FrameArena(self.size, self._row_bytes(shape, config, self.max_label_views, headed=capacities != (None, None),
-                                                               photometric=self.photometric), self.device)
+                                                               photometric=self.photometric, surface=self.surface_rows), self.device)
         # A row is FOUNDED on a frame that suits the table sampler its graphs will draw from (the frames a row later serves come through reset(),
         # which says so when one does not suit).  A founder that does not suit is replaced by the first one that does -- the shape is what a
         # row needs from its founder -- and listed in `unsuitable_founders`; no suitable founder at all: UnsuitableFrameError.
@@ -2126,11 +2200,12 @@ class FrameBatch:
         return slots
 
     @staticmethod
-    def _row_bytes(shape, config, label_views=0, headed=False, photometric=False):
+    def _row_bytes(shape, config, label_views=0, headed=False, photometric=False, surface=False):
         """Bytes of one frame's row: the aligned sizes of everything a FrameOptimizer(row=...) creates there, summed over the declarations it
         allocates from and the regions the library sizes, in the order of allocation (Adam's state, declared with the parameters, comes
         amid the glue) -- every output included, so a row is exactly full once each has been asked for.  `headed`: rows with a header;
-        `photometric`: rows that carry the photometric term (nothing is added while its weight is 0)."""
+        `photometric`: rows that carry the photometric term (nothing is added while its weight is 0); `surface`: rows that hold the
+        buffers of surface() (_IMAGE_OUTPUTS)."""
         V, H, W, N = (int(x) for x in shape)
         def sizes(declared):
             return [_buffer_bytes(shape, dtype) for _, shape, dtype, _ in declared]
@@ -2147,6 +2222,9 @@ class FrameBatch:
         if label_views > 0:
             for output in _LABEL_VIEW_OUTPUTS.values():
                 parts += sizes(output.buffers(int(label_views), N, H, W))
+        if surface:
+            for output in _IMAGE_OUTPUTS.values():
+                parts += sizes(output.buffers(V, N, H, W))
         return sum(FrameArena.aligned(nbytes) for nbytes in parts)
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
@@ -2208,6 +2286,25 @@ class FrameBatch:
         if any(not 0 <= int(view) < m.num_views for m in self._members(active)[1]):
             raise ValueError(f"view {view} does not exist in every active frame")
         return self._ask("masks", active, view=view, threshold=threshold, soft=soft)
+
+    def surface(self, active=None, view=0, hard=True, light=None, shadows=True, background=None, alpha=None):
+        """The dense surface renders of the first ``active`` frames (``FrameOptimizer.surface``) by ONE vsrd_frame_surface call for all of
+        them: a list of dictionaries of device tensors.  ``view`` must exist in every active frame; ``background``: None, or one
+        [H,W,3] uint8 image per active frame.  The batch must have been built with ``surface=True`` (its rows hold the images)."""
+        if not self.surface_rows:
+            raise RuntimeError("surface(): this batch's rows were laid out without the surface buffers -- FrameBatch(..., surface=True)")
+        active, members = self._members(active)
+        if any(not 0 <= int(view) < m.num_views for m in members):
+            raise ValueError(f"view {view} does not exist in every active frame")
+        if background is not None and len(background) != active:
+            raise ValueError(f"background: one image per active frame ({active}), got {len(background)}")
+        _check_asked("surface", members)
+        with _capture_lock:
+            for m in self.frames:
+                m._output_state("surface")
+            for k, m in enumerate(members):
+                m._write_surface(light, None if background is None else background[k])
+        return self._ask("surface", active, view=view, hard=hard, shadows=shadows, background=background is not None, alpha=alpha)
 
     def metrics(self, active=None):
         """The 3-D / BEV IoU metrics of the first ``active`` frames (``FrameOptimizer.metrics``) by ONE vsrd_frame_metrics call for all of

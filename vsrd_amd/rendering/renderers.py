@@ -15,6 +15,7 @@ Two ways in:
 Gradients reach the field parameters through ``torch.autograd.Function``s whose backward is the
 hand-derived adjoint kernel (``vsrd_render_backward``); there is no PyTorch-op fallback.
 """
+import ctypes
 import os
 import threading
 
@@ -620,6 +621,84 @@ def surface_normal(distance_field, surface_positions, finite_difference_epsilon=
         out = evaluate_field(distance_field, surface_positions, with_gradients=True, with_labels=False)
         normals = out[-1] if isinstance(out, tuple) else out
     return torch.nn.functional.normalize(normals, dim=-1)
+
+
+# The default light of a surface render, as the direction the light travels in the rectified camera frame (x right, y down, z forward): from
+# above and behind the camera, a little from the left -- it falls forwards and downwards onto what the camera looks at.
+SURFACE_LIGHT = (0.3, 1.0, 0.6)
+# The instances' diffuse colours when the caller names none: twelve well-separated hues, repeated.
+_SURFACE_PALETTE = ((0.90, 0.10, 0.10), (0.10, 0.60, 0.90), (0.20, 0.75, 0.20), (0.95, 0.65, 0.05), (0.60, 0.25, 0.80), (0.10, 0.80, 0.75),
+                    (0.95, 0.40, 0.65), (0.55, 0.55, 0.10), (0.35, 0.35, 0.95), (0.95, 0.85, 0.25), (0.50, 0.30, 0.15), (0.60, 0.60, 0.60))
+
+
+def surface_palette(num_instances, device=None):
+    """The default diffuse colours [N,3] float32 of a surface render's instances."""
+    rows = [_SURFACE_PALETTE[n % len(_SURFACE_PALETTE)] for n in range(int(num_instances))]
+    return torch.tensor(rows, dtype=torch.float32, device=device).reshape(int(num_instances), 3)
+
+
+def surface_config(view, num_views, height, width, num_iterations, convergence_criteria, bounding_radius=None, shadow_offset=None, hard=True,
+                   shadows=True, background=False, alpha=1.0, shininess=32.0, background_color=(0.0, 0.0, 0.0), light_ambient=(1.0, 1.0, 1.0),
+                   light_diffuse=(1.0, 1.0, 1.0), light_specular=(1.0, 1.0, 1.0), material_ambient=(0.1, 0.1, 0.1),
+                   material_specular=(0.3, 0.3, 0.3), material_emission=(0.0, 0.0, 0.0)):
+    """include/vsrd_hip.h::vsrd_frame_surface_config.  ``shadow_offset`` None: twice the convergence criteria (the header says why);
+    ``background``: the call gets a background image of height x width pixels."""
+    triple = lambda values: (ctypes.c_float * 3)(*(float(x) for x in values))
+    offset = 2.0 * float(convergence_criteria) if shadow_offset is None else float(shadow_offset)
+    flags = (_lib.FRAME_SURFACE_HARD_UNION if hard else 0) | (_lib.FRAME_SURFACE_SHADOWS if shadows else 0)
+    return _lib.FrameSurfaceConfig(int(view), int(num_views), int(height), int(width), int(num_iterations), float(convergence_criteria),
+                                   float(bounding_radius or 0.0), offset, flags, int(height) * int(width) if background else 0, float(alpha),
+                                   float(shininess), triple(background_color), triple(light_ambient), triple(light_diffuse), triple(light_specular),
+                                   triple(material_ambient), triple(material_specular), triple(material_emission))
+
+
+def surface_render(distance_field, camera_position, ray_directions, num_iterations, convergence_criteria, bounding_radius=None, light=None,
+                   shadows=True, shadow_offset=None, palette=None, background=None, colors=True, **shading):
+    """The dense surface render of one view by ONE vsrd_frame_surface launch: sphere_tracing(initialization=False), surface_normal,
+    shadow_rendering and phong_shading composed per pixel (include/vsrd_hip.h says how, and where the composition is this project's own).
+    ``distance_field``: any field the recogniser flattens; the union traced is the block's own (``hard``), as in sphere_tracing.
+    ``camera_position`` [3], ``ray_directions`` [H,W,3]; ``light`` [3]: the direction the light travels (None: no shadows, no colours);
+    ``palette`` [N,3]: the instances' diffuse colours (None: surface_palette); ``background`` [H,W,3] uint8 or None; ``shading``: the
+    blend and the colours of surface_config (alpha, shininess, background_color, light_* and material_*).
+    Returns a dictionary: converged_bits / shadow_bits [H, ceil(W/8)] uint8 (frames.unpack reads them), instance [H,W] uint8 (255: none),
+    range [H,W], positions / normals [H,W,3] and, with a light and ``colors``, colors [H,W,3] uint8."""
+    lib = _lib.load()
+    if not hasattr(lib, "vsrd_frame_surface"):
+        raise _lib.VsrdHipError("libvsrd_hip has no vsrd_frame_surface: this build cannot render surfaces")
+    block = flatten(distance_field)
+    if ray_directions.dim() != 3 or ray_directions.shape[-1] != 3:
+        raise ValueError(f"ray_directions must be [H,W,3], got {tuple(ray_directions.shape)}")
+    H, W = int(ray_directions.shape[0]), int(ray_directions.shape[1])
+    dev = ray_directions.device
+    directions = ray_directions.reshape(-1, 3).to(torch.float32).contiguous()
+    origin = camera_position.reshape(1, 3).to(device=dev, dtype=torch.float32).contiguous()
+    N = block.num_instances
+    u8, f32 = torch.uint8, torch.float32
+    out = dict(converged_bits=torch.empty(H, (W + 7) // 8, dtype=u8, device=dev), shadow_bits=torch.empty(H, (W + 7) // 8, dtype=u8, device=dev),
+               instance=torch.empty(H, W, dtype=u8, device=dev), range=torch.empty(H, W, dtype=f32, device=dev),
+               positions=torch.empty(H, W, 3, dtype=f32, device=dev), normals=torch.empty(H, W, 3, dtype=f32, device=dev))
+    light_tensor = palette_tensor = None
+    if light is not None:
+        light_tensor = torch.as_tensor(light, dtype=f32).reshape(3).to(dev).contiguous()
+        palette_tensor = (surface_palette(N, dev) if palette is None else torch.as_tensor(palette).to(device=dev, dtype=f32)).reshape(N, 3).contiguous()
+        if colors:
+            out["colors"] = torch.empty(H, W, 3, dtype=u8, device=dev)
+    if background is not None:
+        if tuple(background.shape) != (H, W, 3) or background.dtype != u8:
+            raise ValueError(f"background must be uint8 [H,W,3] = {(H, W, 3)}, got {background.dtype} {tuple(background.shape)}")
+        background = background.to(dev).contiguous()
+    mlp = None if block.mlp_weights is None else block.mlp_weights.detach().contiguous()
+    field = _lib.make_field(block.instances.detach().contiguous(), block.temperature, mlp)
+    config = _lib.make_config(0, 2, (0.0, 1.0), 1.0, 1.0, 1.0e-6, 3)
+    surface = surface_config(0, 1, H, W, num_iterations, convergence_criteria, bounding_radius, shadow_offset, hard=bool(block.hard), shadows=shadows,
+                             background=background is not None, **shading)
+    address = lambda t: None if t is None else t.data_ptr()
+    with profiling.timed("vsrd_frame_surface"):
+        _lib.check(lib.vsrd_frame_surface(field, config, surface, _lib.ptr(origin), _lib.ptr(directions), _lib.ptr(light_tensor), _lib.ptr(palette_tensor),
+                                          address(background), out["converged_bits"].data_ptr(), out["shadow_bits"].data_ptr(), out["instance"].data_ptr(),
+                                          _lib.ptr(out["range"]), address(out.get("colors")), _lib.ptr(out["positions"]), _lib.ptr(out["normals"]),
+                                          None, _lib.stream()))
+    return out
 
 
 class _SilhouetteStep(torch.autograd.Function):
