@@ -295,3 +295,81 @@ def test_outputs_asked_in_any_order_equal_each_frame_alone(dev):
     assert sorted(nbytes for _, nbytes in tail_a) == sorted(nbytes for _, nbytes in tail_b)
     for other in (record_b, record_c):
         assert all(torch.equal(x, y) for mine, theirs in zip(record_a, other) for x, y in zip(mine, theirs))
+
+
+def test_all_five_outputs_of_a_batch_equal_each_frame_alone(dev):
+    """The one table's five outputs at the smallest shape that can still go wrong -- 2 views of 16 x 72 (two runs per image row, the second a
+    tail of 8 pixels), 3 and 2 instances in rows of capacity 3 with 2 label views, surface=True, one step into the residual phase: the batch
+    asked in the table's order and each frame alone, in a slot of its own, asked in the reverse order give the same tensors bit for bit.
+    (Every loop starts from the boxes its frame was made of: from a fresh draw -- every box at 50 m, a pixel of this image -- four steps
+    leave nothing for the dense outputs to show.)"""
+    import dataclasses
+    from vsrd_amd import launcher, optimization, synthetic
+    config = optimization.OptimizationConfig(num_samples=40, num_rays=64, warmup_steps=3, num_steps=4, seed=3, mlp_adjoint_item_slots=8,
+                                             surface_num_iterations=64)
+    order = list(optimization._OUTPUTS)
+    assert order == ["labels", "masks", "metrics", "group_labels", "surface"]
+    photographs = [torch.arange(16 * 72 * 3, device=dev).mul(7 + k).remainder(251).to(torch.uint8).view(16, 72, 3) for k in range(2)]
+
+    def ask(source, name, background, **batch):
+        arguments = dict(masks=dict(soft=True), surface=dict(light=(0.2, 1.0, 0.4), background=background))
+        return getattr(source, name)(**batch, **arguments.get(name, {}))
+
+    def start_at_the_truth(loop, number):
+        _, _, location, dimension, orientation = synthetic.synthetic_frame(number, 2, 16, 72, loop.num_instances)
+        with torch.no_grad():
+            loop.detector.locations.copy_(location); loop.detector.dimensions.copy_(dimension); loop.detector.orientations.copy_(orientation)
+
+    def bits(tensor):        # (float32 as its bits: NaN equals NaN)
+        return tensor.contiguous().view(torch.int32) if tensor.dtype == torch.float32 else tensor
+
+    def snapshot(result):
+        return {key: value.clone() if isinstance(value, torch.Tensor) else value for key, value in result.items()}
+
+    inputs, numbers, alone, number = [], [], [], 3
+    for k, n in enumerate((3, 2)):
+        while True:          # (frames whose soft masks do not suit the table sampler are skipped)
+            frame = launcher.synthetic_frame_inputs(dev, number, 2, n, height=16, width=72, label_views=2)
+            number += 1
+            try:
+                loop = optimization.FrameOptimizer(frame, dataclasses.replace(config, init_seed=70 + k), dev, graph=True, persistent=True, max_label_views=2)
+            except optimization.UnsuitableFrameError:
+                assert number < 40
+                continue
+            break
+        numbers.append(number - 1)
+        start_at_the_truth(loop, numbers[-1])
+        loop.run(config.num_steps, steps_per_graph=1)
+        alone.append({name: snapshot(ask(loop, name, photographs[k])) for name in reversed(order)})
+        assert list(loop._outputs) == order[::-1]
+        torch.cuda.synchronize()
+        loop.close()
+        inputs.append(frame)
+
+    batch = optimization.FrameBatch(inputs, config, dev, init_seeds=[70, 71], max_instances=3, max_label_views=2, surface=True)
+    assert batch.unsuitable_founders == [] and [m.num_instances for m in batch.frames] == [3, 2]
+    for member, made_of in zip(batch.frames, numbers):
+        start_at_the_truth(member, made_of)
+    batch.run(config.num_steps, steps_per_graph=1)
+    assert all(m.step_index - 1 >= config.warmup_steps for m in batch.frames)          # (the last step was a residual one)
+    got = {name: [snapshot(entry) for entry in ask(batch, name, photographs, active=2)] for name in order}
+    torch.cuda.synchronize()
+    assert list(batch.frames[0]._outputs) == order and all(row.layout == batch.arena.rows[0].layout for row in batch.arena.rows)
+    compared = 0
+    for name in order:
+        for f in range(2):
+            mine, theirs = got[name][f], alone[f][name]
+            assert mine.keys() == theirs.keys(), (name, f)
+            for key, value in theirs.items():
+                if isinstance(value, torch.Tensor):
+                    assert mine[key].shape == value.shape and mine[key].dtype == value.dtype, (name, f, key)
+                    assert torch.equal(bits(mine[key]), bits(value)), (name, f, key)
+                    compared += 1
+                else:
+                    assert mine[key] == value, (name, f, key)
+    assert compared >= 2 * (5 + 4 + 4 + 6 + 6)
+    owned = [int((entry["instance"] != 255).sum()) for entry in got["surface"]]
+    inside = [int(entry["counts"][:, 0].sum()) for entry in got["masks"]]
+    print("pixels of", 16 * 72, "that own an instance in the surface render:", owned, "and that lie inside a predicted mask:", inside)
+    assert 0 < sum(owned) < 2 * 16 * 72 and sum(inside) > 0          # (the dense outputs show something, and not everything)
+    batch.close()

@@ -174,6 +174,7 @@ def test_frames_of_different_view_counts_walk_their_own_trajectories(dev, split_
 
 ROWS = [  # (shapes (views, instances) of the two frames, width, label views of each frame's group, log, the batch's capacities)
     pytest.param([(2, 2), (3, 3)], 128, 2, True, dict(max_instances=4, max_views=3, max_label_views=2), id="capacities_group_log"),
+    pytest.param([(2, 2), (3, 3)], 128, 2, True, dict(max_instances=4, max_views=3, max_label_views=2, surface=True), id="all_five_outputs"),
     pytest.param([(3, 3), (3, 3)], 128, 0, False, {}, id="one_shape"),
     pytest.param([(3, 3), (3, 3)], 100, 0, False, {}, id="width_100"),         # (the bit-packed masks round the width up to 13 bytes)
 ]
@@ -200,13 +201,15 @@ def test_a_row_is_exactly_as_large_as_planned(dev, shapes, width, label_views, l
         pytest.fail("no frame that suits the table sampler")
     if log:
         batch.log_outputs(metrics=True, masks=True)
-    names = ["labels", "masks", "metrics"] + (["group_labels"] if label_views else [])
+    founder = batch.frames[0]
+    switches = dict(label_views=batch.max_label_views, headed=founder._headed, photometric=False, surface=batch.surface_rows)
+    assert switches["headed"] == bool(capacities) and switches["surface"] == capacities.get("surface", False)
+    names = [name for name, output in optimization._OUTPUTS.items() if output.held(switches)]       # (the table and its row switches say what a row holds)
+    assert names == ["labels", "masks", "metrics"] + (["group_labels"] if label_views else []) + (["surface"] if switches["surface"] else [])
     for member in batch.frames:
         for name in names:
             member._output_state(name)
-    founder = batch.frames[0]
-    planned = optimization.FrameBatch._row_bytes((founder.view_capacity, 128, width, founder.capacity), batch.config, batch.max_label_views,
-                                                 headed=bool(capacities))
+    planned = optimization.FrameBatch._row_bytes((founder.view_capacity, 128, width, founder.capacity), batch.config, **switches)
     assert batch.arena.stride == optimization.FrameArena.aligned(planned)
     for row in batch.arena.rows:
         print(f"row {row.index}: cursor {row.cursor}, planned {planned}, {len(row.layout)} buffers")

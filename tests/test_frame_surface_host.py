@@ -132,23 +132,29 @@ def test_surface_files_round_trip_and_the_png_decodes(tmp_path):
 
 
 def test_row_declaration_and_planning():
-    """surface() is a fourth _FrameOutput on the path of the others, in a table of its own: a batch's rows count its buffers only when the
-    batch was built for them, so rows without are as large as before."""
+    """surface() is the fifth _FrameOutput of the one table, on the path of the others: a batch's rows count its buffers only when the
+    batch was built for them (its row switch), so rows without are as large as before."""
     from vsrd_amd import optimization
     V, N, H, W = 3, 5, 6, 20
-    got = optimization._IMAGE_OUTPUTS["surface"].buffers(V, N, H, W)
+    got = optimization._OUTPUTS["surface"].buffers(V, N, H, W)
     u8, f32 = torch.uint8, torch.float32
     assert [(key, tuple(shape), dtype, fill) for key, shape, dtype, fill in got] == [
         ("light", (3,), f32, 0.0), ("palette", (N, 3), f32, 0.0), ("background", (H * W, 3), u8, 0), ("converged_bits", (H, 3), u8, 0), ("shadow_bits", (H, 3), u8, 0),
         ("instance", (H * W,), u8, 255), ("range", (H * W,), f32, 0.0), ("colors", (H * W, 3), u8, 0)]
-    assert optimization._output("surface") is optimization._IMAGE_OUTPUTS["surface"] and optimization._output("surface").last_step == "field block"
-    assert optimization._output("masks") is optimization._OUTPUTS["masks"] and list(optimization._OUTPUTS) == ["labels", "masks", "metrics"]
+    assert optimization._OUTPUTS["surface"].last_step == "field block" and optimization._OUTPUTS["surface"].leading == "view_capacity"
+    assert list(optimization._OUTPUTS) == ["labels", "masks", "metrics", "group_labels", "surface"]
     aligned = optimization.FrameArena.aligned
     extra = sum(aligned(optimization._buffer_bytes(shape, dtype)) for _, shape, dtype, _ in got)
     import inspect
     assert inspect.signature(optimization.FrameBatch._row_bytes).parameters["surface"].default is False
     assert inspect.signature(optimization.FrameBatch.__init__).parameters["surface"].default is False
     assert extra == sum(aligned(n) for n in (12, N * 12, H * W * 3, H * 3, H * 3, H * W, H * W * 4, H * W * 3))
+    # the row switch: counted with surface=True and only then, whatever the other switches say
+    config = optimization.OptimizationConfig()
+    for label_views in (0, 2):
+        for headed in (False, True):
+            sizes = [optimization.FrameBatch._row_bytes((V, H, W, N), config, label_views, headed=headed, surface=surface) for surface in (False, True)]
+            assert sizes[0] == optimization.FrameBatch._row_bytes((V, H, W, N), config, label_views, headed=headed) and sizes[1] - sizes[0] == extra
 
 
 def _launcher(*arguments, timeout=300):

@@ -183,7 +183,7 @@ def test_workspace_sizes_are_the_parents(lib, monkeypatch):
 def test_constants_match_the_header():
     """The literal constants of the binding against the header's #defines, both ways round: every integer VSRD_<X> the binding has a name <X>
     for has that value, and every constant of the binding's families is defined in the header.  MAX_VIEWS, which the header does not
-    define, against the frame glue's own limit."""
+    define, against the frame glue's own limit: the ONE definition, in the header of the host checks, which the glue's header takes over."""
     from vsrd_amd import _lib
     header = open(os.path.join(ROOT, "include", "vsrd_hip.h")).read()
     defines = {name: int(value.rstrip("u"), 0) for name, value in re.findall(r"^#define VSRD_(\w+) \(?(-?(?:0x[0-9a-fA-F]+|\d+)u?)\)?(?:\s|$)", header, flags=re.M)}
@@ -194,8 +194,9 @@ def test_constants_match_the_header():
     family = re.compile(r"(FLAG_|E_)\w+|MAX_INSTANCES|MAX_SAMPLES|MAX_LABEL_VIEWS|INSTANCE_STRIDE|MLP_WEIGHTS|HYPER_LAYERS|FRAME_HEADER_HAS_VIEWS|ABI_VERSION")
     named = [name for name in vars(_lib) if family.fullmatch(name)]
     assert sorted(named) == sorted(shared) and len(named) == 24
-    glue = open(os.path.join(ROOT, "vsrd_amd", "csrc", "frame_step.h")).read()
-    assert _lib.MAX_VIEWS == int(re.search(r"constexpr int kFrameMaxViews = (\d+)", glue).group(1))
+    checks, glue = (open(os.path.join(ROOT, "vsrd_amd", "csrc", name)).read() for name in ("host_checks.h", "frame_step.h"))
+    assert _lib.MAX_VIEWS == int(re.search(r"constexpr int kFrameMaxViews = (\d+)", checks).group(1))
+    assert "using vsrd_host::kFrameMaxViews;" in glue and "kFrameMaxViews =" not in glue
 
 
 STRUCTS = {"Field": "vsrd_field", "RenderConfig": "vsrd_render_config", "FrameConfig": "vsrd_frame_config", "AdamTensors": "vsrd_adam_tensors",
@@ -813,24 +814,40 @@ def test_reset_admits_the_loops_shape_or_up_to_its_capacities():
 
 
 def test_frame_output_buffer_lists_and_their_rows():
-    """The buffers labels() / masks() / metrics() create at first use (optimization._OUTPUTS[...].buffers: plain functions of the capacities
-    and the image size), against literals: names, shapes, dtypes, fills and order; and the rows they give in an arena, in two orders of
-    first use -- equal in both rows, at the offsets 256-byte alignment gives."""
+    """The buffers the five outputs create at first use (optimization._OUTPUTS[...].buffers: plain functions of the capacities and the image
+    size; `V`: the view capacity, for group_labels the label-view capacity), against literals: names, shapes, dtypes, fills and order; what
+    the ONE table says of each beyond them; and the rows they give in an arena, in two orders of first use -- equal in both rows, at the
+    offsets 256-byte alignment gives."""
     from vsrd_amd import optimization
     V, N, H, W = 3, 5, 6, 9
-    f32, nan = torch.float32, float("nan")
+    f32, u8, nan = torch.float32, torch.uint8, float("nan")
     want = dict(labels=[("camera_corners", (V, N, 8, 3), f32, 0.0), ("boxes_2d", (V, N, 4), f32, 0.0), ("mean_iou", (N, N), f32, 0.0),
                         ("matched_gt", (N,), torch.int64, 0), ("confidences", (N,), f32, 0.0)],
                 masks=[("inside", (N, H, 2), torch.uint8, 0), ("soft", (H * W, N), f32, 0.0), ("counts", (N, 3), torch.int32, 0)],
                 metrics=[("gt_boxes_3d", (N, 8, 3), f32, nan), ("rectification", (3, 3), f32, 0.0), ("corners", (N, 8, 3), f32, 0.0),
-                         ("ious", (N, 2), f32, nan), ("summary", (8,), f32, 0.0)])
-    assert list(optimization._OUTPUTS) == ["labels", "masks", "metrics"]
+                         ("ious", (N, 2), f32, nan), ("summary", (8,), f32, 0.0)],
+                group_labels=[("count", (1,), torch.int32, 1), ("frame_ids", (V,), torch.int64, -1), ("extrinsics", (V, 16), f32, 0.0),
+                              ("intrinsics", (V, 9), f32, 0.0), ("gt_boxes", (V, N, 4), f32, 0.0), ("visible", (V, N), u8, 0),
+                              ("camera_corners", (V, N, 8, 3), f32, 0.0), ("boxes_2d", (V, N, 4), f32, 0.0), ("mean_iou", (N, N), f32, 0.0),
+                              ("matched_gt", (N,), torch.int64, 0), ("confidences", (N,), f32, 0.0)],
+                surface=[("light", (3,), f32, 0.0), ("palette", (N, 3), f32, 0.0), ("background", (H * W, 3), u8, 0), ("converged_bits", (H, 2), u8, 0),
+                         ("shadow_bits", (H, 2), u8, 0), ("instance", (H * W,), u8, 255), ("range", (H * W,), f32, 0.0), ("colors", (H * W, 3), u8, 0)])
+    assert list(optimization._OUTPUTS) == ["labels", "masks", "metrics", "group_labels", "surface"] == list(want)
+    assert not any(hasattr(optimization, gone) for gone in ("_LABEL_VIEW_OUTPUTS", "_IMAGE_OUTPUTS", "_output"))
+    # what differs between them, as data: what they read of the last step, which capacity leads their buffers, which rows hold them
+    table = optimization._OUTPUTS
+    assert [table[name].last_step for name in want] == [None, "field block", "matching", None, "field block"]
+    assert [table[name].leading for name in want] == ["view_capacity"] * 3 + ["label_view_capacity", "view_capacity"]
+    for label_views in (0, 1, 7):
+        for surface in (False, True):
+            switches = dict(label_views=label_views, headed=False, photometric=False, surface=surface)
+            assert [bool(table[name].held(switches)) for name in want] == [True, True, True, label_views > 0, surface]
     for name, buffers in want.items():
         got = optimization._OUTPUTS[name].buffers(V, N, H, W)
         assert [(key, tuple(shape), dtype) for key, shape, dtype, _ in got] == [(key, shape, dtype) for key, shape, dtype, _ in buffers], name
         assert all(fill == expected or fill != fill and expected != expected for (*_, fill), (*_, expected) in zip(got, buffers)), name
     item = {f32: 4, torch.int64: 8, torch.int32: 4, torch.uint8: 1}
-    for order in (("labels", "masks", "metrics"), ("metrics", "masks", "labels")):
+    for order in (("labels", "masks", "metrics"), ("metrics", "masks", "labels"), tuple(want), tuple(want)[::-1]):
         arena = optimization.FrameArena(2, 20_000, "cpu")
         layout, cursor = [], 0
         for name in order:
@@ -847,24 +864,100 @@ def test_frame_output_buffer_lists_and_their_rows():
         assert arena.rows[0].layout == arena.rows[1].layout == layout, order
 
 
+ROW_SHAPES = ((2, 16, 72, 3), (17, 376, 1408, 8))
+# FrameBatch._row_bytes as recorded BEFORE the outputs shared one table, per shape over label_views in (0, 2) x headed x photometric x surface x log
+# (itertools.product, each off then on): the defaults of OptimizationConfig with loss_weights["photometric_loss"] = 0.1, the log at intervals 50 / 500
+ROW_BYTES = (
+    230352384, 246781440, 230366464, 246795520, 451705344, 468134400, 451719424, 468148480,
+    230352640, 246781696, 230366720, 246795776, 451705600, 468134656, 451719680, 468148736,
+    230355712, 246784768, 230369792, 246798848, 451708672, 468137728, 451722752, 468151808,
+    230355968, 246785024, 230370048, 246799104, 451708928, 468137984, 451723008, 468152064,
+    1188851200, 1205312000, 1194807808, 1211268608, 1825562112, 1842022912, 1831518720, 1847979520,
+    1188851456, 1205312256, 1194808064, 1211268864, 1825562368, 1842023168, 1831518976, 1847979776,
+    1188855296, 1205316096, 1194811904, 1211272704, 1825566208, 1842027008, 1831522816, 1847983616,
+    1188855552, 1205316352, 1194812160, 1211272960, 1825566464, 1842027264, 1831523072, 1847983872)
+
+
+def _row_grid():
+    import dataclasses
+    import itertools
+    from vsrd_amd import losses, optimization
+    base = optimization.OptimizationConfig(loss_weights={**losses.LOSS_WEIGHTS, "photometric_loss": 0.1})
+    logged = dataclasses.replace(base, scalar_interval=50, checkpoint_interval=500)
+    for shape in ROW_SHAPES:
+        for label_views, headed, photometric, surface, log in itertools.product((0, 2), (False, True), (False, True), (False, True), (False, True)):
+            yield shape, logged if log else base, dict(label_views=label_views, headed=headed, photometric=photometric, surface=surface)
+
+
+def test_row_sizes_are_what_they_were_before_the_one_table(lib):
+    """FrameBatch._row_bytes over the grid of its switches, against the values recorded on the commit before: one loop over one table counts
+    what three loops over three tables counted."""
+    from vsrd_amd import optimization
+    got = [optimization.FrameBatch._row_bytes(shape, config, **switches) for shape, config, switches in _row_grid()]
+    assert len(got) == len(ROW_BYTES) == 64 and tuple(got) == ROW_BYTES
+    # rows without surface=True, and rows without label views, are as large as they were: the switch alone moves the size, by the buffers' own
+    aligned = optimization.FrameArena.aligned
+    for (shape, config, switches), size in zip(_row_grid(), got):
+        V, H, W, N = shape
+        for name, off in (("surface", dict(surface=False)), ("group_labels", dict(label_views=0))):
+            leading = switches["label_views"] if name == "group_labels" else V
+            own = sum(aligned(optimization._buffer_bytes(s, d)) for _, s, d, _ in optimization._OUTPUTS[name].buffers(leading, N, H, W))
+            held = switches["surface"] if name == "surface" else switches["label_views"] > 0
+            assert size - optimization.FrameBatch._row_bytes(shape, config, **dict(switches, **off)) == (own if held else 0), (shape, switches, name)
+
+
+def test_a_sixth_output_is_counted_under_its_own_row_switch(lib, monkeypatch):
+    """An entry put into the table with a row switch of its own: FrameBatch._row_bytes counts its buffers exactly under that switch, laid out
+    for the capacity it names -- no line of FrameOptimizer or FrameBatch knows its name."""
+    import dataclasses
+    from vsrd_amd import optimization
+
+    def buffers(V, N, H, W):
+        return [("planes", (V, H, W), torch.float32, 0.0), ("flags", (N, 3), torch.uint8, 0)]
+
+    stand_in = dataclasses.replace(optimization._OUTPUTS["labels"], buffers=buffers, leading="label_view_capacity",
+                                   held=lambda switches: switches["headed"] and not switches["surface"])
+    plain = {case: optimization.FrameBatch._row_bytes(shape, config, **switches) for case, (shape, config, switches) in enumerate(_row_grid())}
+    monkeypatch.setitem(optimization._OUTPUTS, "stand_in", stand_in)
+    assert list(optimization._OUTPUTS)[-1] == "stand_in" and len(optimization._OUTPUTS) == 6
+    aligned, counted = optimization.FrameArena.aligned, 0
+    for case, (shape, config, switches) in enumerate(_row_grid()):
+        V, H, W, N = shape
+        extra = aligned(switches["label_views"] * H * W * 4) + aligned(N * 3) if switches["headed"] and not switches["surface"] else 0
+        assert optimization.FrameBatch._row_bytes(shape, config, **switches) - plain[case] == extra, (shape, switches)
+        counted += extra > 0
+    assert counted == 16             # (headed, no surface: a quarter of the grid; with label_views = 0 the planes are empty and the flags remain)
+
+
 class _StandInSource:
-    """What the launcher's `_collect` asks of a loop (`active` None) or a batch: labels / masks / metrics of the documented shapes, on the host."""
+    """What the launcher's `_collect` asks of a loop (`active` None) or a batch: labels / group_labels / masks / surface / metrics of the
+    documented shapes, on the host; `surface_calls`: what surface() was asked with."""
 
     def __init__(self, counts, summaries, boxes_3d="given"):
-        self.counts, self.summaries, self.asked = counts, summaries, []
+        self.counts, self.summaries, self.asked, self.surface_calls = counts, summaries, [], []
         self.inputs = type("Inputs", (), dict(boxes_3d=None if boxes_3d is None else torch.zeros(counts[0], 8, 3)))()
 
     def _answer(self, name, active, make):
         self.asked.append(name)
         return make(0) if active is None else [make(f) for f in range(active)]
 
+    def _labels_of(self, f):
+        n = self.counts[f]
+        corners = torch.tensor([[0., 0, 0], [1, 0, 0], [1, 0, 2], [0, 0, 2], [0, 1, 0], [1, 1, 0], [1, 1, 2], [0, 1, 2]]) + torch.tensor([0.0, 0.0, 10.0 + f])
+        return dict(boxes_3d=corners.expand(1, n, 8, 3).clone(), boxes_2d=torch.tensor([[10.0, 20.0], [30.0, 40.0]]).expand(1, n, 2, 2).clone(),
+                    confidences=torch.full((n,), 0.5), matched_gt=torch.arange(n), mean_iou=torch.eye(n))
+
     def labels(self, active=None):
-        def make(f):
-            n = self.counts[f]
-            corners = torch.tensor([[0., 0, 0], [1, 0, 0], [1, 0, 2], [0, 0, 2], [0, 1, 0], [1, 1, 0], [1, 1, 2], [0, 1, 2]]) + torch.tensor([0.0, 0.0, 10.0 + f])
-            return dict(boxes_3d=corners.expand(1, n, 8, 3).clone(), boxes_2d=torch.tensor([[10.0, 20.0], [30.0, 40.0]]).expand(1, n, 2, 2).clone(),
-                        confidences=torch.full((n,), 0.5), matched_gt=torch.arange(n), mean_iou=torch.eye(n))
-        return self._answer("labels", active, make)
+        return self._answer("labels", active, self._labels_of)
+
+    def group_labels(self, active=None):       # (a group of one frame, id 40 + f)
+        return self._answer("group_labels", active, lambda f: dict(self._labels_of(f), frame_ids=torch.tensor([40 + f])))
+
+    def surface(self, active=None, light=None, background=None):
+        self.surface_calls.append(dict(active=active, light=light, background=background))
+        return self._answer("surface", active, lambda f: dict(
+            converged_bits=torch.zeros(4, 2, dtype=torch.uint8), shadow_bits=torch.zeros(4, 2, dtype=torch.uint8), instance=torch.full((4, 9), 255, dtype=torch.uint8),
+            range=torch.zeros(4, 9), colors=torch.full((4, 9, 3), 10 * (f + 1), dtype=torch.uint8), light=torch.tensor([0.0, 1.0, 0.0]), shape=(4, 9), view=0, hard=True))
 
     def masks(self, active=None):
         def make(f):
@@ -936,3 +1029,35 @@ def test_launcher_collects_and_writes_a_frames_outputs_in_one_place(tmp_path):
     pending = work._collect(nothing, [(0, work.path_of(0))], payloads)
     work._write_outputs(pending)
     assert work.phase_seconds is None and nothing.asked == [] and pending == [] and payloads == [dict(metrics={})] and not os.path.exists(tmp_path / "none")
+    # ---- all five flags: the order of asking, the clock's keys, and what surface() is asked with ----
+    every = dict(predictions=True, group_predictions=True, masks=True, surface=True, metrics=True)
+    order = ["labels", "group_labels", "masks", "surface", "metrics"]
+    more = ("group/predictions/0000000040.json", "group/labels/0000000040.txt", "surface/view_00.npz", "surface/view_00.png")
+    work = _render_work(tmp_path / "every", surface_light=(0.0, 0.0, 1.0), **every)
+    assert list(work.phase_seconds) == ["labels", "labels_write", "group_labels", "group_labels_write", "masks", "masks_write", "surface", "surface_write", "metrics"]
+    photograph = torch.full((4, 9, 3), 7, dtype=torch.uint8)
+    work.backgrounds[7] = photograph
+    loop, payloads = _StandInSource([3], [summary]), [dict(metrics={})]
+    pending = work._collect(loop, [(7, work.path_of(7))], payloads)
+    assert loop.asked == order and [key for key, *_ in pending] == ["labels_write", "group_labels_write", "masks_write", "surface_write"]
+    assert len(loop.surface_calls) == 1 and loop.surface_calls[0]["active"] is None and loop.surface_calls[0]["light"] == (0.0, 0.0, 1.0)
+    assert loop.surface_calls[0]["background"] is photograph and work.backgrounds == {}
+    work._write_outputs(pending)
+    assert all(os.path.exists(os.path.join(folder(work, 7), name)) for name in files + more) and all(value > 0.0 for value in work.phase_seconds.values())
+    assert set(payloads[0]["metrics"]) == {"mask_iou", *formats.FRAME_METRIC_NAMES}
+    # a loop without a photograph, and one without a light: asked with None
+    loop = _StandInSource([3], [summary])
+    _render_work(tmp_path / "dark", **every)._collect(loop, [(7, work.path_of(7))], [dict(metrics={})])
+    assert loop.asked == order and loop.surface_calls == [dict(active=None, light=None, background=None)]
+    # a batch: its frames' photographs in order -- or, when not EVERY frame of the group carries one, none at all (and none is left behind)
+    for carried, expected in (((4, 9), "both"), ((9,), None), ((), None)):
+        work = _render_work(tmp_path / f"batch_{len(carried)}", **every)
+        work.backgrounds.update({frame: torch.full((4, 9, 3), frame, dtype=torch.uint8) for frame in carried})
+        kept = dict(work.backgrounds)
+        batch, payloads = _StandInSource([3, 5], [empty, summary], boxes_3d=None), [dict(metrics={}), dict(metrics={})]
+        pending = work._collect(batch, rows, payloads, active=2)
+        assert batch.asked == order and len(batch.surface_calls) == 1 and batch.surface_calls[0]["active"] == 2 and work.backgrounds == {}
+        background = batch.surface_calls[0]["background"]
+        assert background is None if expected is None else len(background) == 2 and background[0] is kept[4] and background[1] is kept[9]
+        assert [key for key, *_ in pending] == ["labels_write"] * 2 + ["group_labels_write"] * 2 + ["masks_write"] * 2 + ["surface_write"] * 2
+        assert set(work.phase_seconds) == {"labels", "labels_write", "group_labels", "group_labels_write", "masks", "masks_write", "surface", "surface_write", "metrics"}

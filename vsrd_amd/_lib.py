@@ -267,7 +267,7 @@ PATCH_RAYS = 65535             # VSRD_PATCH_MAX_RAYS
 FRAME_LOG_COLUMNS = 22        # VSRD_LOG_SCALARS: (step | record 5 | learning rates 5 | schedule 3 | metrics summary 8) of a history row
 FRAME_LOG_SEGMENTS = 32        # VSRD_LOG_MAX_SEGMENTS: entries of a frame's snapshot table
 FRAME_HEADER_HAS_VIEWS = 0x10000
-MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h: kFrameMaxViews)
+MAX_VIEWS = 32                 # the frame glue's limit (csrc/host_checks.h: kFrameMaxViews)
 MAX_LABEL_VIEWS = 4096         # VSRD_MAX_LABEL_VIEWS: the label views (a frame's group) of vsrd_frame_group_labels
 
 

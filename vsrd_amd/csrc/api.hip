@@ -1,9 +1,7 @@
 // C ABI of libvsrd_hip (include/vsrd_hip.h): argument validation, launch geometry, dispatch on the
 // number of 64-sample rounds.  No torch types, no allocation, and no state beyond the experiment switches below, which are read from
 // the environment ONCE (first call) and frozen: no entry point calls getenv per launch.
-#include <cstdio>
-#include <cstdlib>
-#include "../../include/vsrd_hip.h"
+#include "host_checks.h"
 #include "aux_kernels.h"
 #include "quad_step.h"
 #include "matching.h"
@@ -24,14 +22,12 @@
 namespace {
 
 using namespace vsrd;
-
-constexpr int kMaxBlocks = 16384;             // 256 CUs x 8 workgroups: many more workgroups than are resident: rays differ a lot in cost and the dispatcher is the load balancer (r01: 2048 -> 16384 workgroups = -12 % time); also sizes the partial buffer
+using namespace vsrd_host;       // (kMaxBlocks, kMaxFrames, Frames / frames_of, valid_field, launch_status and the image checks: shared with frame_surface.hip)
 
 // Experiment / A-B switches of the library, all of them: read once, then constants of the process.
 struct Switches {
     int grid_blocks;          // VSRD_GRID_BLOCKS=<n> (<= kMaxBlocks): cap of the render grids
     bool cap_to_residency;    // VSRD_CAP_TO_RESIDENCY=1: fit_to_residency really caps
-    bool debug;               // VSRD_DEBUG: failed launches / LDS opt-ins are reported on stderr
     int split_max_rays;       // VSRD_SPLIT_MAX_RAYS: box-only step, launches of at most this many rays split every ray over two waves (0: never)
     bool no_full_shape;       // VSRD_NO_FULL_SHAPE: the step keeps the run-time-shape kernels (quad_step.h: kFull)
     int pair_max_rays;        // VSRD_PAIR_MAX_RAYS: residual step, 0 turns the pair kernel off for two-round launches
@@ -45,7 +41,6 @@ const Switches& switches() {
         w.grid_blocks = (blocks > 0 && blocks <= kMaxBlocks) ? blocks : kMaxBlocks;
         const char* cap = getenv("VSRD_CAP_TO_RESIDENCY");
         w.cap_to_residency = cap != nullptr && cap[0] == '1';
-        w.debug = getenv("VSRD_DEBUG") != nullptr;
         w.split_max_rays = number("VSRD_SPLIT_MAX_RAYS", 2048);
         w.no_full_shape = getenv("VSRD_NO_FULL_SHAPE") != nullptr;
         w.pair_max_rays = number("VSRD_PAIR_MAX_RAYS", 2048);
@@ -99,35 +94,9 @@ void fit_to_residency(Kernel kernel, Geometry* g) {
 
 template <typename Kernel>
 int opt_in_lds(Kernel kernel, size_t bytes) {
-    return opt_in(kernel, bytes, switches().debug) ? VSRD_OK : VSRD_E_LAUNCH;
+    return opt_in(kernel, bytes, debug()) ? VSRD_OK : VSRD_E_LAUNCH;
 }
 
-int launch_status() {
-    const hipError_t error = hipGetLastError();
-    if (error == hipSuccess) return VSRD_OK;
-    if (switches().debug) fprintf(stderr, "libvsrd_hip: launch failed: %s\n", hipGetErrorString(error));
-    return VSRD_E_LAUNCH;
-}
-
-bool valid_field(const vsrd_field* f) {
-    return f != nullptr && f->instances != nullptr && f->num_instances >= 1 && f->num_instances <= VSRD_MAX_INSTANCES &&
-           f->temperature > 0.0f;
-}
-
-// Frame batches (include/vsrd_hip.h, ABI 8): B copies of the one-frame grid along blockIdx.y, every pointer moved by frame_stride bytes per frame.
-constexpr int kMaxFrames = 1024;
-struct Frames {
-    int count;              // B (1: one frame)
-    long long stride;       // bytes; 0 for one frame (the kernels test this, not the count)
-};
-bool frames_of(int32_t num_frames, int64_t frame_stride, Frames* f) {
-    f->count = num_frames <= 1 ? 1 : num_frames;
-    f->stride = 0;
-    if (f->count == 1) return true;
-    if (f->count > kMaxFrames || frame_stride <= 0 || (frame_stride & 255) != 0) return false;
-    f->stride = frame_stride;
-    return true;
-}
 // one fill for every frame's copy of a scratch region (masks, counters)
 bool clear_frames(void* first, size_t bytes, const Frames& frames, hipStream_t s) {
     if (frames.count == 1) return hipMemsetAsync(first, 0, bytes, s) == hipSuccess;
@@ -1151,7 +1120,7 @@ int32_t vsrd_render_residual_step_with_header(const vsrd_field* field, const vsr
                                                       instance_weights, loss_scale, eikonal_scale, eikonal_norm, labels, w.box_partials, w.jets, w.loss_partials, w.seeds,
                                                       w.masks, p.slots_per_instance, first, rays, chunk_index > 0 ? 1 : 0, p.pair, p.rounds, p.front_blocks, p.front_lds,
                                                       wants_samples(config), frames.count, frame_header};
-        const int code = split ? vsrd_split_front::launch_front(launch, s, switches().debug) : vsrd::launch_front(launch, s, switches().debug);
+        const int code = split ? vsrd_split_front::launch_front(launch, s, debug()) : vsrd::launch_front(launch, s, debug());
         if (code != vsrd_split_front::kOk) return code == vsrd_split_front::kUnsupported ? VSRD_E_UNSUPPORTED : VSRD_E_LAUNCH;
         const int32_t status = launch_adjoint_tail(field, split ? w.images : nullptr, config->flags, p, w, rays, chunk_index > 0, grad_mlp_weights, frames, header, s);
         if (status != VSRD_OK) return status;
@@ -1355,22 +1324,20 @@ int32_t vsrd_frame_masks(const vsrd_field* field, const vsrd_render_config* conf
     vsrd_render_config own = *config;
     own.num_rays = 0;                                            // (ignored: the ray count is H W)
     if (!valid_config(&own)) return VSRD_E_INVALID_ARGUMENT;     // (rejects ray_indices, target_columns and out_* inside the config)
-    if (masks->num_views < 1 || masks->num_views > kFrameMaxViews || masks->view < 0 || masks->view >= masks->num_views || masks->height < 1 ||
-        masks->width < 1 || masks->num_iterations < 0)
-        return VSRD_E_INVALID_ARGUMENT;
+    const int32_t image = image_view_status(masks->num_views, masks->view, masks->height, masks->width, masks->num_iterations);
+    if (image == VSRD_E_INVALID_ARGUMENT) return VSRD_E_INVALID_ARGUMENT;
     if ((targets != nullptr) != (counts != nullptr)) return VSRD_E_INVALID_ARGUMENT;
     const int N = field->num_instances, S = config->num_samples;
     if (targets != nullptr && masks->target_stride < (target_columns ? 1 : N)) return VSRD_E_INVALID_ARGUMENT;
     const bool residual = field->mlp_weights != nullptr;
     const int rounds = rounds_for(2 * S - 1);
     if (rounds == 0 || (residual && rounds > 4)) return VSRD_E_INVALID_ARGUMENT;
-    const int64_t pixels = static_cast<int64_t>(masks->height) * masks->width;
-    if (pixels >= (int64_t{1} << 30)) return VSRD_E_UNSUPPORTED;
+    if (image != VSRD_OK) return image;
     Frames frames;
     if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
-    const int num_runs = masks->height * ((masks->width + kWave - 1) / kWave);
+    static_assert(kRunPixels == kWave, "a run is one wave's pixels");
     Geometry g;
-    if (!plan(num_runs, static_cast<size_t>(hierarchical_lds_floats(S, N, residual)), &g)) return VSRD_E_UNSUPPORTED;
+    if (!plan(image_runs(masks->height, masks->width), static_cast<size_t>(hierarchical_lds_floats(S, N, residual)), &g)) return VSRD_E_UNSUPPORTED;
     const FieldArgs f = field_args(field);
     RenderArgs c = render_args(config);
     c.sh.inv_t = f.inv_t;

@@ -20,12 +20,13 @@
 #include "matching.h"
 #include "projection.h"
 #include "box_decode.h"
+#include "host_checks.h"
 
 namespace vsrd {
 
 constexpr int kFrameThreads = 256;
 constexpr int kFrameMaxBoxes = 64;
-constexpr int kFrameMaxViews = 32;
+using vsrd_host::kFrameMaxViews;         // (host_checks.h: the entry points outside this unit check against it too)
 constexpr int kBoxEdges = 12;
 
 struct FrameStepArgs {

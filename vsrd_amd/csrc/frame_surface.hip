@@ -1,21 +1,13 @@
-// Fourth translation unit of libvsrd_hip: vsrd_frame_surface (include/vsrd_hip.h), its argument checks and its kernel
-// (frame_surface.h).  A unit of its own so that api.hip's code object is what it was without the surface render; the headers' namespace
+// Fourth translation unit of libvsrd_hip: vsrd_frame_surface (include/vsrd_hip.h) and its kernel (frame_surface.h); its argument checks
+// are api.hip's (host_checks.h).  A unit of its own so that api.hip's code object is what it was without the surface render; the headers' namespace
 // is renamed, as in split_front.hip, so that this unit's copies of the kernels they define do not collide with api.hip's at link time.
-#include <cstdio>
-#include <cstdlib>
-#include "../../include/vsrd_hip.h"
+#include "host_checks.h"
 #define vsrd vsrd_surface
 #include "frame_surface.h"
 #undef vsrd
 
-namespace {
-
 using namespace vsrd_surface;
-
-constexpr int kSurfaceMaxBlocks = 16384;      // (api.hip: kMaxBlocks -- many more workgroups than are resident, the dispatcher balances the runs)
-constexpr int kSurfaceMaxFrames = 1024, kSurfaceMaxViews = 32;      // (api.hip: kMaxFrames; frame_step.h: kFrameMaxViews)
-
-}  // namespace
+using namespace vsrd_host;
 
 extern "C" int32_t vsrd_frame_surface(const vsrd_field* field, const vsrd_render_config* config, const vsrd_frame_surface_config* surface,
                                       const float* camera_positions, const float* ray_directions, const float* light, const float* palette,
@@ -23,22 +15,14 @@ extern "C" int32_t vsrd_frame_surface(const vsrd_field* field, const vsrd_render
                                       uint8_t* colors, float* positions, float* normals, const vsrd_frame_header* frame_header, void* stream) {
     static_assert(kSurfaceHardUnion == VSRD_SURFACE_HARD_UNION && kSurfaceShadows == VSRD_SURFACE_SHADOWS, "frame_surface.h and the ABI agree on the flags");
     static_assert(sizeof(vsrd_frame_header) == sizeof(FrameHeader), "wave.h: FrameHeader is vsrd_frame_header");
-    if (!field || !field->instances || field->num_instances < 1 || field->num_instances > VSRD_MAX_INSTANCES || !(field->temperature > 0.0f))
-        return VSRD_E_INVALID_ARGUMENT;
-    if (!config || !surface || !camera_positions || !ray_directions) return VSRD_E_INVALID_ARGUMENT;
-    if (surface->num_views < 1 || surface->num_views > kSurfaceMaxViews || surface->view < 0 || surface->view >= surface->num_views || surface->height < 1 ||
-        surface->width < 1 || surface->num_iterations < 0)
-        return VSRD_E_INVALID_ARGUMENT;
-    if (colors != nullptr && (light == nullptr || palette == nullptr)) return VSRD_E_INVALID_ARGUMENT;
-    const int64_t pixels = static_cast<int64_t>(surface->height) * surface->width;
-    if (pixels >= (int64_t{1} << 30)) return VSRD_E_UNSUPPORTED;
-    if (background != nullptr && surface->background_pixels != pixels) return VSRD_E_INVALID_ARGUMENT;
-    const int frames = config->num_frames <= 1 ? 1 : config->num_frames;
-    long long frame_stride = 0;
-    if (frames > 1) {
-        if (frames > kSurfaceMaxFrames || config->frame_stride <= 0 || (config->frame_stride & 255) != 0) return VSRD_E_INVALID_ARGUMENT;
-        frame_stride = config->frame_stride;
-    }
+    static_assert(kRunPixels == kWave, "a run is one wave's pixels");
+    if (!valid_field(field) || !config || !surface || !camera_positions || !ray_directions) return VSRD_E_INVALID_ARGUMENT;
+    const int32_t image = image_view_status(surface->num_views, surface->view, surface->height, surface->width, surface->num_iterations);
+    if (image == VSRD_E_INVALID_ARGUMENT || (colors != nullptr && (light == nullptr || palette == nullptr))) return VSRD_E_INVALID_ARGUMENT;
+    if (image != VSRD_OK) return image;
+    if (background != nullptr && surface->background_pixels != static_cast<int64_t>(surface->height) * surface->width) return VSRD_E_INVALID_ARGUMENT;
+    Frames frames;
+    if (!frames_of(config->num_frames, config->frame_stride, &frames)) return VSRD_E_INVALID_ARGUMENT;
     FieldArgs f;
     f.num_instances = field->num_instances;
     f.inv_t = 1.0f / field->temperature;
@@ -57,18 +41,15 @@ extern "C" int32_t vsrd_frame_surface(const vsrd_field* field, const vsrd_render
     b.converged_bits = converged_bits; b.shadow_bits = shadow_bits; b.instance = instance; b.range = range; b.colors = colors;
     b.positions = positions; b.normals = normals;
     const int waves = kSurfaceThreads / kWave;
-    const int num_runs = surface->height * ((surface->width + kWave - 1) / kWave);
-    const int want = (num_runs + waves - 1) / waves;
-    const int blocks = want > kSurfaceMaxBlocks ? kSurfaceMaxBlocks : want;
+    const int want = (image_runs(surface->height, surface->width) + waves - 1) / waves;
+    const int blocks = want > kMaxBlocks ? kMaxBlocks : want;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const FrameHeader* header = reinterpret_cast<const FrameHeader*>(frame_header);
     if (field->mlp_weights != nullptr)
-        hipLaunchKernelGGL(frame_surface_kernel<true>, dim3(blocks, frames), dim3(kSurfaceThreads), 0, s, f, field->instances, field->mlp_weights,
-                           config->device_schedule, a, b, frame_stride, header);
+        hipLaunchKernelGGL(frame_surface_kernel<true>, dim3(blocks, frames.count), dim3(kSurfaceThreads), 0, s, f, field->instances, field->mlp_weights,
+                           config->device_schedule, a, b, frames.stride, header);
     else
-        hipLaunchKernelGGL(frame_surface_kernel<false>, dim3(blocks, frames), dim3(kSurfaceThreads), 0, s, f, field->instances, field->mlp_weights,
-                           config->device_schedule, a, b, frame_stride, header);
-    const hipError_t error = hipGetLastError();
-    if (error != hipSuccess && getenv("VSRD_DEBUG") != nullptr) fprintf(stderr, "libvsrd_hip: launch failed: %s\n", hipGetErrorString(error));
-    return error == hipSuccess ? VSRD_OK : VSRD_E_LAUNCH;
+        hipLaunchKernelGGL(frame_surface_kernel<false>, dim3(blocks, frames.count), dim3(kSurfaceThreads), 0, s, f, field->instances, field->mlp_weights,
+                           config->device_schedule, a, b, frames.stride, header);
+    return launch_status();
 }

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 
-MAX_VIEWS = 32                 # the frame glue's limit (csrc/frame_step.h)
+MAX_VIEWS = 32                 # the frame glue's limit (csrc/host_checks.h: kFrameMaxViews)
 TEMPERATURE = 10.0             # SoftRasterizer's default (geometric_transforms.py:235)
 
 _FIELDS = ("image_size", "intrinsic_matrices", "extrinsic_matrices", "view_offsets", "instance_ids", "polygon_offsets", "polygon_vertices",

@@ -393,6 +393,44 @@ def _supervise(argv, args):
     return abs(failed[1]) or 1
 
 
+# ---- what the flags ask of a group of finished frames, in the order of asking: ONE list for the clock's keys (_RenderWork._begin_outputs) and
+# for the collection (_RenderWork._collect).  `each(work, pending, frame, folder, entry, payload)`: what one frame's entry adds to the pending
+# file writes and to its payload; `how(work, source, frames, active)`: the keyword arguments to ask with (None: this source is not asked)
+def _to_file(key, save):
+    from . import formats
+    return lambda work, pending, frame, folder, entry, payload: pending.append((key, getattr(formats, save), (folder, formats.to_host(entry))))
+
+
+def _masks_to_file(work, pending, frame, folder, entry, payload):
+    from . import formats
+    host = formats.to_host({key: value for key, value in entry.items() if key != "soft"})
+    payload["metrics"] = dict(payload.get("metrics") or {}, mask_iou=float(host["mask_iou"].mean()))
+    pending.append(("masks_write", formats.save_frame_masks, (folder, host, host["shape"])))
+
+
+def _metrics_to_report(work, pending, frame, folder, entry, payload):
+    from . import formats
+    named = formats.frame_metrics(entry["summary"])
+    if named:
+        payload["metrics"] = dict(payload.get("metrics") or {}, **named)
+        work.frame_metrics[int(frame)] = named
+
+
+def _with_light(work, source, frames, active):      # (--surface: laid over the frames' photographs when every frame of the group carries one)
+    photographs = [work.backgrounds.pop(int(frame), None) for frame, _ in frames]
+    return dict(light=work.surface_light, background=photographs[0] if active is None else (photographs if all(p is not None for p in photographs) else None))
+
+
+_plainly = lambda work, source, frames, active: {}
+_OUTPUTS = [        # (flag, method of a FrameOptimizer / a FrameBatch, the clock's keys, each, how)
+    ("predictions", "labels", ("labels", "labels_write"), _to_file("labels_write", "save_frame_labels"), _plainly),
+    ("group_predictions", "group_labels", ("group_labels", "group_labels_write"), _to_file("group_labels_write", "save_frame_group_labels"), _plainly),
+    ("masks", "masks", ("masks", "masks_write"), _masks_to_file, _plainly),
+    ("surface", "surface", ("surface", "surface_write"), _to_file("surface_write", "save_frame_surface"), _with_light),
+    # (a loop without 3-D ground truth is not asked; a batch is, and its frames without come back with count 0 and are skipped)
+    ("metrics", "metrics", ("metrics",), _metrics_to_report, lambda work, source, frames, active: {} if active is not None or source.inputs.boxes_3d is not None else None)]
+
+
 class _RenderWork:
     """What ONE PROCESS does with the frames it takes from the queue on its GPU: frame slots / the frame batch (and, with a static queue,
     the inputs) before the clock, then the frames."""
@@ -411,6 +449,8 @@ class _RenderWork:
         self.photometric = float(getattr(args, "photometric", 0.0) or 0.0)
         self.photometric_losses = {}
         self.backgrounds = {}            # --surface: frame -> uint8 [H,W,3] (_note_background)
+        self.wanted = {flag: bool(getattr(args, flag, False)) for flag, *_ in _OUTPUTS}      # (the output flags, read HERE only: bare arguments may lack the newer ones)
+        self.surface_light = getattr(args, "surface_light", None)
         if self.photometric:
             from . import losses
             self.config.update(loss_weights={**losses.LOSS_WEIGHTS, "photometric_loss": self.photometric})
@@ -439,8 +479,8 @@ class _RenderWork:
     def _note_background(self, frame, inputs):
         """--surface: the target view's photograph of a frame that carries its images (a pack's member `images`, FrameInputs.images), as the
         uint8 [H,W,3] image the surface render is laid over -- kept from the moment the frame is taken until its outputs are collected."""
-        images = getattr(inputs, "images", None) if getattr(self.args, "surface", False) else None
-        if images is not None:
+        images = getattr(inputs, "images", None)
+        if self.wanted["surface"] and images is not None:
             first = torch.as_tensor(images[0])
             if first.dtype != torch.uint8:
                 first = (first.to(torch.float32) * 255.0 + 0.5).clamp(0.0, 255.0).to(torch.uint8)
@@ -496,7 +536,7 @@ class _RenderWork:
                                                          max_instances=max(args.instance_counts) if mixed else None,
                                                          max_views=max(args.view_counts) if mixed_views else None,
                                                          max_label_views=args.label_view_capacity, photometric=bool(self.photometric),
-                                                         surface=bool(getattr(args, "surface", False)))
+                                                         surface=self.wanted["surface"])
                     if self.logs:                # (before the captures: the buffers the log reads exist in every row)
                         self.batch.log_outputs(metrics=args.metrics, masks=args.masks)
                     self.unsuitable_founders += [int(candidates[min(f, len(candidates) - 1)]) for f in self.batch.unsuitable_founders]
@@ -557,11 +597,7 @@ class _RenderWork:
     def _begin_outputs(self):
         """The clock's keys of --predictions / --masks / --metrics (None without any of them: outside the batch path such a job has no
         clock) and the rank's report of per-frame metrics."""
-        args = self.args
-        keys = [key for wanted, keys in ((args.predictions, ("labels", "labels_write")), (getattr(args, "group_predictions", False), ("group_labels", "group_labels_write")),
-                                         (args.masks, ("masks", "masks_write")), (getattr(args, "surface", False), ("surface", "surface_write")),
-                                         (args.metrics, ("metrics",)))
-                if wanted for key in keys]
+        keys = [key for flag, _, keys, *_ in _OUTPUTS if self.wanted[flag] for key in keys]
         keys += ["log", "log_write"] if self.logs else []
         self.phase_seconds, self.frame_metrics = dict.fromkeys(keys, 0.0) or None, {}
 
@@ -602,56 +638,20 @@ class _RenderWork:
 
     def _collect(self, source, frames, payloads, active=None):
         """What the flags ask of a group of finished frames, inside the section that copies their checkpoint `payloads`: `source` is the
-        loop of ONE frame, or the batch whose first `active` rows hold the `frames` = [(frame, checkpoint path)].  In this order, each ONE
-        vsrd_frame_* call for the group and its copies to the host: --predictions, the labels; --group-predictions, the labels in every
-        frame's own group; --masks, the target view's predicted masks,
-        and every payload's metric mask_iou (the mean over its instances); --surface, the target view's dense surface render, laid over the
-        frame's photograph when every frame of the group carries one; --metrics, the reference's six metrics into the payload's
-        `metrics` and the rank's report, for every frame that had 3-D ground truth (a loop without it is not asked; a batch is, and its
-        frames without come back with count 0 and are skipped).  Returns the pending file writes for `_write_outputs`."""
+        loop of ONE frame, or the batch whose first `active` rows hold the `frames` = [(frame, checkpoint path)].  In the order of `_OUTPUTS`,
+        each ONE vsrd_frame_* call for the group and its copies to the host: --predictions, the labels; --group-predictions, the labels in
+        every frame's own group; --masks, the target view's predicted masks, and every payload's metric mask_iou (the mean over its
+        instances); --surface, the target view's dense surface render; --metrics, the reference's six metrics into the payload's `metrics`
+        and the rank's report, for every frame that had 3-D ground truth.  Returns the pending file writes for `_write_outputs`."""
         import time
-        from . import formats
-        args, pending = self.args, []
-
-        def labels(frame, folder, entry, payload):
-            pending.append(("labels_write", formats.save_frame_labels, (folder, formats.to_host(entry))))
-
-        def group_labels(frame, folder, entry, payload):
-            pending.append(("group_labels_write", formats.save_frame_group_labels, (folder, formats.to_host(entry))))
-
-        def masks(frame, folder, entry, payload):
-            host = formats.to_host({key: value for key, value in entry.items() if key != "soft"})
-            payload["metrics"] = dict(payload.get("metrics") or {}, mask_iou=float(host["mask_iou"].mean()))
-            pending.append(("masks_write", formats.save_frame_masks, (folder, host, host["shape"])))
-
-        def surface(frame, folder, entry, payload):
-            pending.append(("surface_write", formats.save_frame_surface, (folder, formats.to_host(entry))))
-
-        def ask_surface():
-            photographs = [self.backgrounds.pop(int(frame), None) for frame, _ in frames]
-            light = getattr(args, "surface_light", None)
-            if active is None:
-                return source.surface(light=light, background=photographs[0])
-            return source.surface(active=active, light=light, background=photographs if all(p is not None for p in photographs) else None)
-
-        def metrics(frame, folder, entry, payload):
-            named = formats.frame_metrics(entry["summary"])
-            if named:
-                payload["metrics"] = dict(payload.get("metrics") or {}, **named)
-                self.frame_metrics[int(frame)] = named
-
-        for key, wanted, each in (("labels", args.predictions, labels), ("group_labels", getattr(args, "group_predictions", False), group_labels), ("masks", args.masks, masks),
-                                  ("surface", getattr(args, "surface", False), surface),
-                                  ("metrics", args.metrics and (active is not None or source.inputs.boxes_3d is not None), metrics)):
-            if wanted:
-                t0 = time.perf_counter()
-                if key == "surface":
-                    entries = ask_surface()
-                else:
-                    entries = getattr(source, key)() if active is None else getattr(source, key)(active=active)
-                for (frame, path), entry, payload in zip(frames, entries if isinstance(entries, list) else [entries], payloads):
-                    each(frame, os.path.dirname(path), entry, payload)
-                self.phase_seconds[key] += time.perf_counter() - t0
+        pending = []
+        for flag, name, _, each, how in _OUTPUTS:
+            t0, arguments = time.perf_counter(), how(self, source, frames, active) if self.wanted[flag] else None
+            if arguments is not None:
+                entries = [getattr(source, name)(**arguments)] if active is None else getattr(source, name)(active=active, **arguments)
+                for (frame, path), entry, payload in zip(frames, entries, payloads):
+                    each(self, pending, frame, os.path.dirname(path), entry, payload)
+                self.phase_seconds[name] += time.perf_counter() - t0
         return pending
 
     def _write_outputs(self, pending):

@@ -578,7 +578,7 @@ def mask_iou(counts):
     return torch.where(union > 0, inter / union.clamp(min=1.0), torch.zeros_like(union))
 
 
-# ---- what a frame can be asked for after its steps: labels(), masks(), metrics() --------------------------------------------------------
+# ---- what a frame can be asked for after its steps: labels(), masks(), metrics(), group_labels(), surface() ----------------------------
 @dataclass(frozen=True)
 class _FrameOutput:
     """What differs between the outputs; `FrameOptimizer._output_state` / `_launch_output` / `_ask` and `FrameBatch._ask` are the ONE path all take."""
@@ -586,16 +586,44 @@ class _FrameOutput:
     launch: object                   # (loop, state, frame, header, **arguments) -> the status of the ONE vsrd_frame_* call; `frame`: the call's own frame config
     views: object                    # (loop, state, **arguments) -> the caller's dictionary: the buffers sliced to the frame's own V views / n instances
     last_step: Optional[str] = None  # what the output reads of the LAST STEP in the fused glue's tensors (it needs the glue AND a step to have run: the two needs coincide in today's outputs, one that had only one of them would split this field)
+    leading: str = "view_capacity"   # the loop's capacity that is `V`, the buffers' leading dimension: "view_capacity" or "label_view_capacity"
+    held: object = lambda switches: True             # (switches) -> whether a batch's row holds the buffers; `switches`: the keywords of FrameBatch._row_bytes, by name
+    # an output that keeps INPUTS in its state has hooks for them, all run inside the capture gate under no_grad but `check`:
+    check: object = lambda loop, inputs, n: None     # (loop, inputs, n): ValueError unless the frame `inputs` of n instances suits -- before anything is created, and by reset() before anything is overwritten
+    write: object = lambda loop, state, n: None      # (loop, state, n): what the state keeps of the frame `loop.inputs` -- at creation and by every reset()
+    take: object = lambda loop, state, **inputs: None        # (loop, state, **inputs): what the state keeps of ONE CALL's own inputs -- once per call, before its launch
 
 
 def _check_asked(name, members):
     """RuntimeError unless the loops `members` -- one loop, or the active frames of a batch -- can be asked for output `name` now."""
-    reads = _output(name).last_step
+    reads = _OUTPUTS[name].last_step
     if reads and not members[0].fused_glue:
         raise RuntimeError(f"{name}() reads the {reads} the fused glue keeps on the device (graph=True)")
     if reads and any(m.step_index < 1 or m.step_index != members[0].step_index for m in members):
         raise RuntimeError(f"{name}() reads the {reads} of the last step: no step has run since the loop was built or reset() (or, in a "
                            "batch, the frames are not in step)")
+
+
+def _check_view(view, members, alone=False):
+    """ValueError unless every one of the loops `members` has view `view`; `alone`: one loop's wording, which names its views."""
+    if any(not 0 <= int(view) < m.num_views for m in members):
+        raise ValueError(f"view: 0..{members[0].num_views - 1}, got {view}" if alone else f"view {view} does not exist in every active frame")
+
+
+def _last_step_field(loop, asked):
+    """(residual, field): whether the LAST STEP was a residual one, and the field it rendered -- the loop's instance block and, in the residual
+    phase, its (centred) MLP weights -- for `asked`, the public method that renders it again: RuntimeError where a residual step left no weights."""
+    residual = loop.step_index - 1 >= loop.config.warmup_steps
+    if residual and not loop.fused_hypernetwork:
+        raise RuntimeError(f"{asked}() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
+    b = loop._glue
+    return residual, _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
+
+
+def _write_label_tables(loop, state, n):
+    """A loop without the fused glue has no tables on the device: float32 copies of its inputs' tables, kept in the state."""
+    if not loop.fused_glue:
+        state["tables"] = loop._input_tables()
 
 
 def _label_buffers(V, N, H, W):
@@ -605,7 +633,7 @@ def _label_buffers(V, N, H, W):
 
 
 def _launch_labels(loop, state, frame, header):
-    # (a loop without the fused glue keeps float32 copies of its inputs' tables in the state: FrameOptimizer.labels)
+    # (a loop without the fused glue keeps float32 copies of its inputs' tables in the state: _write_label_tables)
     det, t = loop.detector, loop._glue if loop.fused_glue else state["tables"]
     return _lib.load().vsrd_frame_labels(
         frame, _lib.ptr(det.locations.data), _lib.ptr(det.dimensions.data), _lib.ptr(det.orientations.data), _lib.ptr(t["extrinsics"]),
@@ -627,16 +655,12 @@ def _launch_masks(loop, state, frame, header, view=0, threshold=0.5, soft=False)
     cfg, b = loop.config, loop._glue
     H, W = (int(x) for x in loop.inputs.image_size)
     from .rendering import renderers
-    # the field the last step rendered: its instance block, and in the residual phase its (centred) MLP weights, exact-fp32 products
-    residual = loop.step_index - 1 >= cfg.warmup_steps
-    flags = renderers._base_flags() & ~_lib.FLAG_MLP_SPLIT_BF16
+    residual, field = _last_step_field(loop, "masks")
+    flags = renderers._base_flags() & ~_lib.FLAG_MLP_SPLIT_BF16      # (exact-fp32 products)
     if residual:
-        if not loop.fused_hypernetwork:
-            raise RuntimeError("masks() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
         flags |= _lib.FLAG_MLP_WEIGHTS_CENTRED
     elif cfg.skip_exact_misses:
         flags |= _lib.FLAG_SKIP_EXACT_MISSES
-    field = _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
     config = _lib.make_config(0, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, seed=cfg.seed, stream_offset=loop.step_tensor, flags=flags,
                               schedule=loop.schedule, frames=(frame.num_frames, frame.frame_stride))
     masks = _lib.FrameMasksConfig(int(view), loop.view_capacity, H, W, int(cfg.surface_num_iterations), float(cfg.surface_convergence_criteria),
@@ -662,6 +686,16 @@ def _metric_buffers(V, N, H, W):
     f32, nan = torch.float32, float("nan")
     return [("gt_boxes_3d", (N, 8, 3), f32, nan), ("rectification", (3, 3), f32, 0.0), ("corners", (N, 8, 3), f32, 0.0), ("ious", (N, 2), f32, nan),
             ("summary", (8,), f32, 0.0)]
+
+
+def _write_ground_truth(loop, state, n):
+    """The row's ground-truth corners and rectification matrix from `loop.inputs`: NaN (no annotation) in every slot the frame does not
+    fill -- all of them when the frame has no boxes_3d -- and the identity without a rectification matrix."""
+    inp = loop.inputs
+    state["gt_boxes_3d"].fill_(float("nan"))
+    if inp.boxes_3d is not None:
+        state["gt_boxes_3d"][:int(n)].copy_(inp.boxes_3d)
+    state["rectification"].copy_(torch.eye(3) if inp.rectification_matrix is None else inp.rectification_matrix)
 
 
 def _launch_metrics(loop, state, frame, header):
@@ -702,6 +736,21 @@ def _check_group(inputs, num_instances, capacity):
                              f"instances: expected {shape}")
 
 
+def _write_group(loop, state, n):
+    """The row's label-view tables and count from `loop.inputs`; a frame without a group leaves the count at 1 (group_labels() refuses it)."""
+    inp = loop.inputs
+    count = label_view_count(inp)
+    state["count"].fill_(max(count, 1))
+    state["frame_ids"].fill_(-1)
+    if count:
+        n = int(n)
+        state["frame_ids"][:count].copy_(inp.label_frame_ids)
+        state["extrinsics"][:count].copy_(inp.label_extrinsic_matrices.reshape(count, 16))
+        state["intrinsics"][:count].copy_(inp.label_intrinsic_matrices.reshape(count, 9))
+        state["gt_boxes"][:count, :n].copy_(inp.label_boxes_2d.reshape(count, n, 4))
+        state["visible"][:count, :n].copy_(inp.label_visible.reshape(count, n))
+
+
 def _group_buffers(L, N, H, W):
     """`L`: the label-view capacity.  The group's tables and the frame's own count (read), then vsrd_frame_group_labels' five outputs."""
     f32 = torch.float32
@@ -725,17 +774,6 @@ def _group_views(loop, state):
                 matched_gt=state["matched_gt"][:n], mean_iou=state["mean_iou"][:n, :n], frame_ids=state["frame_ids"][:l])
 
 
-_OUTPUTS = dict(
-    labels=_FrameOutput(_label_buffers, _launch_labels, _label_views),                                        # csrc/frame_labels.h
-    masks=_FrameOutput(_mask_buffers, _launch_masks, _mask_views, last_step="field block"),                   # csrc/frame_masks.h
-    metrics=_FrameOutput(_metric_buffers, _launch_metrics, _metric_views, last_step="matching"))              # csrc/frame_metrics.h
-
-
-# ... and the outputs whose buffers are laid out for the LABEL-view capacity (max_label_views) instead of the row's views: a fourth entry on
-# the same path (`_output` finds either kind), in a table of its own because that one difference is all `_output_state` needs to know
-_LABEL_VIEW_OUTPUTS = dict(group_labels=_FrameOutput(_group_buffers, _launch_group_labels, _group_views))     # csrc/frame_group_labels.h
-
-
 def _surface_buffers(V, N, H, W):
     """What the caller hands over (the light, the instances' diffuse colours, the photograph), then vsrd_frame_surface's compact outputs.
     Positions and normals, the call's per-pixel float triples, are not kept (rendering.surface_render returns them)."""
@@ -744,15 +782,23 @@ def _surface_buffers(V, N, H, W):
             ("shadow_bits", (H, (W + 7) // 8), u8, 0), ("instance", (H * W,), u8, 255), ("range", (H * W,), f32, 0.0), ("colors", (H * W, 3), u8, 0)]
 
 
+def _write_surface(loop, state, light=None, background=None):
+    """The row's light, palette and photograph for the call's surface launch (host values: outside any capture)."""
+    from .rendering import renderers
+    H, W = (int(x) for x in loop.inputs.image_size)
+    state["light"].copy_(torch.as_tensor(renderers.SURFACE_LIGHT if light is None else light, dtype=torch.float32).reshape(3))
+    state["palette"].copy_(renderers.surface_palette(loop.capacity))
+    if background is not None:
+        if tuple(background.shape) != (H, W, 3) or background.dtype != torch.uint8:
+            raise ValueError(f"background must be uint8 [H,W,3] = {(H, W, 3)}, got {background.dtype} {tuple(background.shape)}")
+        state["background"].copy_(background.reshape(H * W, 3))
+
+
 def _launch_surface(loop, state, frame, header, view=0, hard=True, shadows=True, background=False, alpha=None):
-    cfg, b = loop.config, loop._glue
+    cfg = loop.config
     H, W = (int(x) for x in loop.inputs.image_size)
     from .rendering import renderers
-    # the field the last step rendered, by the rule of _launch_masks: its instance block, and in the residual phase its (centred) MLP weights
-    residual = loop.step_index - 1 >= cfg.warmup_steps
-    if residual and not loop.fused_hypernetwork:
-        raise RuntimeError("surface() in the residual phase reads the MLP weights csrc/hypernetwork.h leaves on the device")
-    field = _lib.make_field(b["instances"], 1.0, b["mlp_centred"] if residual else None)      # (the temperature comes from the device schedule)
+    _, field = _last_step_field(loop, "surface")
     config = _lib.make_config(0, cfg.num_samples, cfg.distance_range, 1.0, 1.0, 1.0e-6, 3, schedule=loop.schedule, frames=(frame.num_frames, frame.frame_stride))
     blend = (0.6 if background else 1.0) if alpha is None else float(alpha)
     surface = renderers.surface_config(view, loop.view_capacity, H, W, cfg.surface_num_iterations, cfg.surface_convergence_criteria,
@@ -769,16 +815,18 @@ def _surface_views(loop, state, view=0, hard=True, shadows=True, background=Fals
                 range=state["range"].view(H, W), colors=state["colors"].view(H, W, 3), light=state["light"], shape=(H, W), view=int(view), hard=bool(hard))
 
 
-# ... and the output whose buffers are whole images per row (5.7 MB at 376 x 1408): a fourth entry on the same path, in a table of its own
-# because a batch's rows hold them only when the batch was built for it (FrameBatch(..., surface=True)) -- `_row_bytes` counts them then
-_IMAGE_OUTPUTS = dict(surface=_FrameOutput(_surface_buffers, _launch_surface, _surface_views, last_step="field block"))       # csrc/frame_surface.h
-
-
-def _output(name):
-    for table in (_OUTPUTS, _LABEL_VIEW_OUTPUTS, _IMAGE_OUTPUTS):
-        if name in table:
-            return table[name]
-    raise KeyError(name)
+# THE table of the outputs, in the order a row holds them.  group_labels: laid out for the LABEL-view capacity, in the rows of a batch that
+# has one (max_label_views); surface: whole images per row (5.7 MB at 376 x 1408), in the rows of a batch built for it (surface=True)
+_OUTPUTS = dict(
+    labels=_FrameOutput(_label_buffers, _launch_labels, _label_views, write=_write_label_tables),             # csrc/frame_labels.h
+    masks=_FrameOutput(_mask_buffers, _launch_masks, _mask_views, last_step="field block"),                   # csrc/frame_masks.h
+    metrics=_FrameOutput(_metric_buffers, _launch_metrics, _metric_views, last_step="matching",               # csrc/frame_metrics.h
+                         check=lambda loop, inputs, n: _check_ground_truth(inputs, n), write=_write_ground_truth),
+    group_labels=_FrameOutput(_group_buffers, _launch_group_labels, _group_views, leading="label_view_capacity",          # csrc/frame_group_labels.h
+                              held=lambda switches: switches["label_views"] > 0,
+                              check=lambda loop, inputs, n: _check_group(inputs, n, loop.label_view_capacity), write=_write_group),
+    surface=_FrameOutput(_surface_buffers, _launch_surface, _surface_views, last_step="field block",          # csrc/frame_surface.h
+                         held=lambda switches: switches["surface"], take=_write_surface))
 
 
 # ---- what a graph-mode loop keeps besides its outputs, declared as they are: plain functions of the capacities and the config ->
@@ -1782,8 +1830,8 @@ class FrameOptimizer:
         # views and 1..capacity instances, any other loop: with its own counts
         V, H, W, N = _incoming_shape(inputs, (self.num_views, *self.inputs.image_size, self.num_instances),
                                      (self.view_capacity, self.capacity) if self._headed else None)
-        _check_ground_truth(inputs, N)           # (before anything of the row is overwritten)
-        _check_group(inputs, N, self.label_view_capacity)
+        for output in _OUTPUTS.values():         # (before anything of the row is overwritten: the 3-D ground truth, the group)
+            output.check(self, inputs, N)
         _check_photometric(inputs, cfg, V, N)
         with _capture_lock, torch.no_grad():
             main = torch.cuda.current_stream(dev)
@@ -1802,10 +1850,8 @@ class FrameOptimizer:
             self.camera_positions.copy_(cam)
             self.ray_directions.copy_(dirs.reshape(-1, 3))
             self.inputs = inputs
-            if "metrics" in self._outputs:
-                self._write_ground_truth(N)      # (the row's 3-D ground truth becomes the new frame's, or none)
-            if "group_labels" in self._outputs:
-                self._write_group(N)             # (likewise the row's group)
+            for name, state in self._outputs.items():
+                _OUTPUTS[name].write(self, state, N)         # (the row's 3-D ground truth, its group: the new frame's, or none)
             if N != self.num_instances:
                 # the detector's parameters and their moments become the first N instances of their [1, capacity, ...] buffers (same
                 # addresses: the pointer blocks and the captured graphs stay valid)
@@ -1858,22 +1904,16 @@ class FrameOptimizer:
 
     # ---- what a frame can be asked for after its steps (_OUTPUTS) ------------------------------------------------------------------
     def _output_state(self, name):
-        """The buffers of output `name` (_output(name).buffers), created at first use -- in the frame's row when there is one (a
-        FrameBatch creates them in every row at once: equal offsets) -- and laid out for the capacities.  metrics() keeps the frame's 3-D
-        ground truth among them: checked before anything is created, written here and by every reset()."""
+        """The buffers of output `name` (_OUTPUTS[name].buffers), created at first use -- in the frame's row when there is one (a
+        FrameBatch creates them in every row at once: equal offsets) -- and laid out for the capacities.  What an output keeps of the
+        frame among them (metrics(): its 3-D ground truth) is checked before anything is created, written here and by every reset()."""
         if name not in self._outputs:
+            output = _OUTPUTS[name]
             H, W = (int(x) for x in self.inputs.image_size)
-            if name == "metrics":      # (by name, like reset(): the outputs with inputs in their state; a hook for the two would be an extension point)
-                _check_ground_truth(self.inputs, self.num_instances)
-            if name == "group_labels":
-                _check_group(self.inputs, self.num_instances, self.label_view_capacity)
-            views = self.label_view_capacity if name in _LABEL_VIEW_OUTPUTS else self.view_capacity      # (the group's buffers: label views along dimension 0)
+            output.check(self, self.inputs, self.num_instances)
             with _capture_lock, torch.no_grad():
-                self._outputs[name] = self._buffers(_output(name).buffers(views, self.capacity, H, W))
-                if name == "metrics":
-                    self._write_ground_truth(self.num_instances)
-                if name == "group_labels":
-                    self._write_group(self.num_instances)
+                state = self._outputs[name] = self._buffers(output.buffers(getattr(self, output.leading), self.capacity, H, W))
+                output.write(self, state, self.num_instances)
         return self._outputs[name]
 
     def _launch_output(self, name, frames=None, **arguments):
@@ -1885,38 +1925,28 @@ class FrameOptimizer:
         frame.num_frames, frame.frame_stride = (1, 0) if frames is None else (int(frames[0]), int(frames[1]))
         header = self._glue.get("header") if self.fused_glue else None
         with _capture_lock:
-            _lib.check(_output(name).launch(self, state, frame, None if header is None else header.data_ptr(), **arguments))
+            _lib.check(_OUTPUTS[name].launch(self, state, frame, None if header is None else header.data_ptr(), **arguments))
         return state
 
-    def _ask(self, name, **arguments):
-        """Output `name` (_OUTPUTS) of this loop: the preconditions, ONE launch on the current stream, the frame's own views."""
+    def _take(self, name, inputs):
+        """One call's own `inputs` of output `name` into its state (first use creates it), as host values: outside any capture."""
+        with _capture_lock, torch.no_grad():
+            _OUTPUTS[name].take(self, self._output_state(name), **inputs)
+
+    def _ask(self, name, inputs={}, **arguments):
+        """Output `name` (_OUTPUTS) of this loop: the preconditions, the call's own `inputs` (_FrameOutput.take), ONE launch on the current
+        stream, the frame's own views."""
         _check_asked(name, [self])
+        self._take(name, inputs)
         state = self._launch_output(name, **arguments)
-        return _output(name).views(self, state, **arguments)
+        return _OUTPUTS[name].views(self, state, **arguments)
 
     def labels(self):
         """The frame's pseudo-labels from its CURRENT parameters (tools/kitti_360/make_predictions.py:61-192), by one vsrd_frame_labels
         launch on the current stream, no host synchronisation: a dictionary of device tensors sliced to the frame's own V views and n instances --
         boxes_3d [V,n,8,3] (camera-frame corners in every view), boxes_2d [V,n,2,2] (clipped), confidences [n] (the matched mean IoU),
         matched_gt [n], mean_iou [n,n].  They are views of buffers the next call overwrites (formats.save_frame_labels writes them out)."""
-        if not self.fused_glue and "labels" not in self._outputs:
-            with _capture_lock, torch.no_grad():       # (a loop without the fused glue: float32 copies of its inputs' tables and a frame config)
-                self._output_state("labels").update(tables=self._input_tables(), frame=self._frame_config())
         return self._ask("labels")
-
-    def _write_group(self, n):
-        """The row's label-view tables and count from `self.inputs`; a frame without a group leaves the count at 1 (group_labels() refuses it)."""
-        state, inp = self._outputs["group_labels"], self.inputs
-        count = label_view_count(inp)
-        state["count"].fill_(max(count, 1))
-        state["frame_ids"].fill_(-1)
-        if count:
-            n = int(n)
-            state["frame_ids"][:count].copy_(inp.label_frame_ids)
-            state["extrinsics"][:count].copy_(inp.label_extrinsic_matrices.reshape(count, 16))
-            state["intrinsics"][:count].copy_(inp.label_intrinsic_matrices.reshape(count, 9))
-            state["gt_boxes"][:count, :n].copy_(inp.label_boxes_2d.reshape(count, n, 4))
-            state["visible"][:count, :n].copy_(inp.label_visible.reshape(count, n))
 
     def _check_has_group(self):
         if label_view_count(self.inputs) == 0:
@@ -1945,22 +1975,8 @@ class FrameOptimizer:
         instances: inside [n,H,ceil(W/8)] uint8 (numpy.packbits along W, the frame packs' mask format), counts [n,3] int32 (#pred,
         #target, #both against the soft masks the frame was fitted to, through the last step's assignment), mask_iou [n], and with
         ``soft`` the values themselves, soft [H,W,n].  They are views of buffers the next call overwrites (formats.save_frame_masks)."""
-        if not 0 <= int(view) < self.num_views:
-            raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
+        _check_view(view, [self], alone=True)
         return self._ask("masks", view=view, threshold=threshold, soft=soft)
-
-    def _write_surface(self, light, background):
-        """The row's light, palette and photograph for the next surface launch (host values: outside any capture)."""
-        from .rendering import renderers
-        state = self._output_state("surface")
-        H, W = (int(x) for x in self.inputs.image_size)
-        with torch.no_grad():
-            state["light"].copy_(torch.as_tensor(renderers.SURFACE_LIGHT if light is None else light, dtype=torch.float32).reshape(3))
-            state["palette"].copy_(renderers.surface_palette(self.capacity))
-            if background is not None:
-                if tuple(background.shape) != (H, W, 3) or background.dtype != torch.uint8:
-                    raise ValueError(f"background must be uint8 [H,W,3] = {(H, W, 3)}, got {background.dtype} {tuple(background.shape)}")
-                state["background"].copy_(background.reshape(H * W, 3))
 
     def surface(self, view=0, hard=True, light=None, shadows=True, background=None, alpha=None):
         """The dense surface render of view ``view`` (0: the target view) -- the surface of the fitted field with range, owning instance,
@@ -1972,21 +1988,8 @@ class FrameOptimizer:
         else 1).  RuntimeError when no step has run since construction or ``reset()``.  A dictionary of device tensors: converged_bits /
         shadow_bits [H, ceil(W/8)] uint8 (numpy.packbits along W), instance [H,W] uint8 (255: none), range [H,W], colors [H,W,3] uint8,
         light [3], shape, view.  They are views of buffers the next call overwrites (formats.save_frame_surface)."""
-        if not 0 <= int(view) < self.num_views:
-            raise ValueError(f"view: 0..{self.num_views - 1}, got {view}")
-        _check_asked("surface", [self])
-        with _capture_lock:
-            self._write_surface(light, background)
-        return self._ask("surface", view=view, hard=hard, shadows=shadows, background=background is not None, alpha=alpha)
-
-    def _write_ground_truth(self, n):
-        """The row's ground-truth corners and rectification matrix from `self.inputs`: NaN (no annotation) in every slot the frame does not
-        fill -- all of them when the frame has no boxes_3d -- and the identity without a rectification matrix."""
-        state, inp = self._outputs["metrics"], self.inputs
-        state["gt_boxes_3d"].fill_(float("nan"))
-        if inp.boxes_3d is not None:
-            state["gt_boxes_3d"][:int(n)].copy_(inp.boxes_3d)
-        state["rectification"].copy_(torch.eye(3) if inp.rectification_matrix is None else inp.rectification_matrix)
+        _check_view(view, [self], alone=True)
+        return self._ask("surface", dict(light=light, background=background), view=view, hard=hard, shadows=shadows, background=background is not None, alpha=alpha)
 
     def metrics(self):
         """The frame's evaluation against its 3-D ground truth (``FrameInputs.boxes_3d``) -- the reference's iou_3d, iou_bev and accuracies
@@ -2205,7 +2208,7 @@ class FrameBatch:
         allocates from and the regions the library sizes, in the order of allocation (Adam's state, declared with the parameters, comes
         amid the glue) -- every output included, so a row is exactly full once each has been asked for.  `headed`: rows with a header;
         `photometric`: rows that carry the photometric term (nothing is added while its weight is 0); `surface`: rows that hold the
-        buffers of surface() (_IMAGE_OUTPUTS)."""
+        buffers of surface().  Which rows hold which output: _FrameOutput.held, over these switches."""
         V, H, W, N = (int(x) for x in shape)
         def sizes(declared):
             return [_buffer_bytes(shape, dtype) for _, shape, dtype, _ in declared]
@@ -2217,14 +2220,11 @@ class FrameBatch:
             parts += sizes(_log_buffers(N, config))
         if photometric and photometric_weight(config) != 0.0:
             parts += sizes(_photometric_buffers(V, N, H, W, config)) + [_lib.load().vsrd_ray_table_bytes(H * W)]
+        switches = dict(label_views=int(label_views), headed=headed, photometric=photometric, surface=surface)
+        leading = dict(view_capacity=V, label_view_capacity=int(label_views))
         for output in _OUTPUTS.values():
-            parts += sizes(output.buffers(V, N, H, W))
-        if label_views > 0:
-            for output in _LABEL_VIEW_OUTPUTS.values():
-                parts += sizes(output.buffers(int(label_views), N, H, W))
-        if surface:
-            for output in _IMAGE_OUTPUTS.values():
-                parts += sizes(output.buffers(V, N, H, W))
+            if output.held(switches):
+                parts += sizes(output.buffers(leading[output.leading], N, H, W))
         return sum(FrameArena.aligned(nbytes) for nbytes in parts)
 
     # ---- one step of the first `active` frames -----------------------------------------------------------------------------------
@@ -2254,17 +2254,20 @@ class FrameBatch:
         # (step_index counts the steps done: the last one had index step_index - 1, and `step_index - 1 >= warmup_steps` is its `residual`)
         return m._step_record(m.step_index > self.config.warmup_steps)
 
-    def _ask(self, name, active, **arguments):
+    def _ask(self, name, active, inputs=(), **arguments):
         """Output `name` (_OUTPUTS) of the first ``active`` frames: first use creates its buffers in EVERY row, so that the rows keep equal
-        offsets; then ONE launch on row 0 covers the first ``active`` rows, and every frame gets its own views."""
+        offsets, and every active frame takes the call's own `inputs` (one dictionary each: _FrameOutput.take); then ONE launch on row 0
+        covers the first ``active`` rows, and every frame gets its own views."""
         active, members = self._members(active)
         _check_asked(name, members)
         for m in self.frames:
             m._output_state(name)
+        for m, own in zip(members, inputs):
+            m._take(name, own)
         if any(row.layout != self.arena.rows[0].layout for row in self.arena.rows[1:]):
             raise RuntimeError(f"the frames of a batch laid their {name} buffers out differently: frame batches need equal offsets in every row")
         self.frames[0]._launch_output(name, frames=(active, self.arena.stride), **arguments)
-        return [_output(name).views(m, m._outputs[name], **arguments) for m in members]
+        return [_OUTPUTS[name].views(m, m._outputs[name], **arguments) for m in members]
 
     def labels(self, active=None):
         """The pseudo-labels of the first ``active`` frames (``FrameOptimizer.labels``) by ONE vsrd_frame_labels call for all of them: a
@@ -2283,8 +2286,7 @@ class FrameBatch:
         """The dense predicted masks of the first ``active`` frames (``FrameOptimizer.masks``) by ONE vsrd_frame_masks call for all of
         them: a list of dictionaries of device tensors, each sliced to its frame's own instance count.  ``view`` must exist in every
         active frame."""
-        if any(not 0 <= int(view) < m.num_views for m in self._members(active)[1]):
-            raise ValueError(f"view {view} does not exist in every active frame")
+        _check_view(view, self._members(active)[1])
         return self._ask("masks", active, view=view, threshold=threshold, soft=soft)
 
     def surface(self, active=None, view=0, hard=True, light=None, shadows=True, background=None, alpha=None):
@@ -2294,17 +2296,11 @@ class FrameBatch:
         if not self.surface_rows:
             raise RuntimeError("surface(): this batch's rows were laid out without the surface buffers -- FrameBatch(..., surface=True)")
         active, members = self._members(active)
-        if any(not 0 <= int(view) < m.num_views for m in members):
-            raise ValueError(f"view {view} does not exist in every active frame")
+        _check_view(view, members)
         if background is not None and len(background) != active:
             raise ValueError(f"background: one image per active frame ({active}), got {len(background)}")
-        _check_asked("surface", members)
-        with _capture_lock:
-            for m in self.frames:
-                m._output_state("surface")
-            for k, m in enumerate(members):
-                m._write_surface(light, None if background is None else background[k])
-        return self._ask("surface", active, view=view, hard=hard, shadows=shadows, background=background is not None, alpha=alpha)
+        inputs = [dict(light=light, background=None if background is None else background[k]) for k in range(active)]
+        return self._ask("surface", active, inputs, view=view, hard=hard, shadows=shadows, background=background is not None, alpha=alpha)
 
     def metrics(self, active=None):
         """The 3-D / BEV IoU metrics of the first ``active`` frames (``FrameOptimizer.metrics``) by ONE vsrd_frame_metrics call for all of
